@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the pangene graph-construction path (stages A+B+C) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...)
 
 Workload (BASELINE.json): configs[1] = synthetic bacterial pangenome, 100 genomes x 5000 proteins (~1 M PAF
@@ -14,7 +14,13 @@ A step = one full pass of the hot path over the shard that is already resident i
 pg_post_process (stage A: both orders and the per-hit records per genome in LDS, filters + interval sweeps; stage B) +
 pg_graph_gen (vertex selection, 17 arc rounds, 15 branch rounds) + the final per-hit state download.
 
-Two rates, both in the line, each named for what it is:
+A plain run (no --full) does only what its headline figure needs: inputs, the tiny warm-up set below, the first pass, W warm-up
+and K timed passes, then the line (metric, value, unit, higher_is_better, dtype, ms_per_step = milliseconds per timed pass).
+--dump-outputs DIR writes what the last timed pass computed -- the graph's segment and arc tables, one field per file -- as
+DIR/<table>_<field>.npy in float64 (a fixed, seeded sample of rows above 64 MB in all).  Same arguments, same inputs.
+--full adds everything else below: the upload-inclusive series, the legs, rooflines, K2, the copy-kernel peak and the GFA md5s.
+
+Two rates, both in the line under --full, each named for what it is:
   value / ms_per_step  the RESIDENT rate: the bench contract's definition ("inputs already resident in HBM when the timed region
                        starts"; a PCIe-inclusive figure is never `value`), K timed passes between barriers;
   upload_inclusive     SURVEY 8(d)'s metric as the survey words it ("device upload included"): ONE pass over a data set the
@@ -24,7 +30,7 @@ Two rates, both in the line, each named for what it is:
                        process (which also pays the driver's hipMalloc of the two arenas: 0.4-40 ms on this pool).
 A tiny data set is run first so that kernel code objects are loaded.
 
-Legs of the default run (N = 1 only; each brings its own data set and context, one context at a time):
+Legs of a --full run (N = 1 only; each brings its own data set and context, one context at a time):
   roofline / big_shard  K1 = the stage-A interval-dominance sweep, and all of stage A, on a shard past the 256 MiB Infinity
                         Cache (1250 x 5 k = the per-GPU shard of configs[3], ~12 M hits; SURVEY 8d asks for >= 10 M hits)
   human_shard           the same on a human-shaped shard (multi-exon hits, fragmented contigs: the k_sweep<3, true> flavour)
@@ -88,6 +94,47 @@ def _k2_pmc(hits):
         return {}
 
 
+class _pg_graph_t(C.Structure):  # include/pangene_amd.h: pg_graph_t
+    _fields_ = [("d", C.c_void_p), ("g2s", C.c_void_p), ("n_seg", C.c_int32), ("m_seg", C.c_int32), ("seg", C.c_void_p),
+                ("n_arc", C.c_int32), ("m_arc", C.c_int32), ("arc", C.c_void_p), ("idx", C.c_void_p)]
+
+
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(g, out_dir):
+    """What the caller of pg_graph_gen receives, the segment table (pg_seg_t, 32 B) and the arc table (pg_arc_t, 32 B), one field a
+    file: DIR/seg_<field>.npy and DIR/arc_<field>.npy in float64 (every field is an integer below 2^53).  A table whose rows would take
+    the files past 64 MB in all keeps a fixed, seeded sample of rows (ascending), named in DIR/<table>_row.npy."""
+    import numpy as np
+    seg_dt = np.dtype([("gid", "<i4"), ("n_dom", "<i4"), ("n_sub", "<i4"), ("n_genome", "<i4"), ("tot_cnt", "<i4"), ("bits", "<u4"), ("n_dist_loci", "<i4", (2,))])
+    arc_dt = np.dtype([("x", "<u8"), ("n_genome", "<i4"), ("tot_cnt", "<i4"), ("avg_dist", "<i4"), ("s1", "<i4"), ("s2", "<i4"), ("bits", "<u4")])
+    assert seg_dt.itemsize == 32 and arc_dt.itemsize == 32
+    q = C.cast(g, C.POINTER(_pg_graph_t)).contents
+
+    def table(ptr, n, dt):
+        if n <= 0 or not ptr:
+            return np.zeros(0, dtype=dt)
+        return np.frombuffer((C.c_uint8 * (n * dt.itemsize)).from_address(ptr), dtype=dt).copy()
+
+    seg, arc = table(q.seg, q.n_seg, seg_dt), table(q.arc, q.n_arc, arc_dt)
+    out = {"seg": {"gid": seg["gid"], "n_dom": seg["n_dom"], "n_sub": seg["n_sub"], "n_genome": seg["n_genome"], "tot_cnt": seg["tot_cnt"],
+                   "del": seg["bits"] & 1, "n_dist_loci": seg["n_dist_loci"]},
+           "arc": {"v": arc["x"] >> np.uint64(32), "w": arc["x"] & np.uint64(0xffffffff), "n_genome": arc["n_genome"], "tot_cnt": arc["tot_cnt"],
+                   "avg_dist": arc["avg_dist"], "s1": arc["s1"], "s2": arc["s2"], "del": arc["bits"] & 1, "weak_br": (arc["bits"] >> 1) & 3}}
+    row_bytes = sum(8 * (int(np.prod(v.shape[1:])) if v.ndim > 1 else 1) for t in out.values() for v in t.values())
+    cap_rows = max(1, DUMP_CAP_BYTES // row_bytes)  # rows a table may keep so that both together stay under the cap
+    os.makedirs(out_dir, exist_ok=True)
+    for name, fields in out.items():
+        n = len(next(iter(fields.values())))
+        rows = None
+        if n > cap_rows:
+            rows = np.sort(np.random.default_rng(12345).choice(n, cap_rows, replace=False))
+            np.save(os.path.join(out_dir, "%s_row.npy" % name), rows.astype(np.float64))
+        for field, v in fields.items():
+            np.save(os.path.join(out_dir, "%s_%s.npy" % (name, field)), (v if rows is None else v[rows]).astype(np.float64))
+
+
 def _gen_range(args):
     kind, base, a, b, G, proteins, seed = args
     from pangene_amd import synth
@@ -107,7 +154,8 @@ def _gen(kind, base, lo, hi, G, proteins, seed):
     todo = [j for j in range(lo, hi) if not os.path.exists(os.path.join(base, "g%05d.paf.done" % j))]
     if not todo:
         return
-    nproc = max(1, min(len(todo), min(os.cpu_count() or 1, 96)))
+    from pangene_amd import synth
+    nproc = max(1, min(len(todo), min(synth._cpu_budget(), 96)))  # the cores this process is granted, not the ones the host shows
     per = max(1, (len(todo) + 4 * nproc - 1) // (4 * nproc))
     jobs = []
     i = 0
@@ -145,8 +193,15 @@ def main():
     ap.add_argument("--human-genomes", type=int, default=500, help="size of the human-shaped shard (x 20 k genes) of the human leg (0 = no such leg)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra-legs", action="store_true", help="skip the exchange-overhead and command-line legs")
+    ap.add_argument("--full", action="store_true", help="also the legs, the upload-inclusive series, rooflines and checks (off: only the timed steps and the line)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (float64)")
     ap.add_argument("--leg", default="", help=argparse.SUPPRESS)  # internal: "steps-only" prints {"ms_per_step": ...} for the exchange-overhead leg
     a = ap.parse_args()
+    if a.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    if not a.full and a.leg == "":  # a plain run: the timed steps and the line, no leg and no extra series
+        a.no_extra_legs = a.no_cpu_baseline = True
+        a.roofline_genomes = a.human_genomes = a.cold_sets = 0
     full = {"config3": ("bact", 10000, 5000, 1.0, [], "bact10000x5k", ""), "config4": ("human", 200, 20000, 5.5, ["-p0", "-a1"], "human200x20k_iso5.5", "-p0 -a1")}.get(a.workload)
     if full:  # one leg of its own (full_size_leg): the bench workload in front of it is the default one, with no other leg
         a.no_extra_legs = a.no_cpu_baseline = True
@@ -314,7 +369,7 @@ def main():
     nh, ne = C.c_int64(), C.c_int64()
     lib.pg_shard_counts(d, C.byref(nh), C.byref(ne))
     t_write = []
-    gfa = gfa_of(g, t_write)
+    gfa = gfa_of(g, t_write) if a.full or a.leg else None
     lib.pg_graph_destroy(g)
     for _ in range(max(0, a.warmup)):
         lib.pg_graph_destroy(one_pass(d, False))
@@ -325,8 +380,13 @@ def main():
     path_sec = 0.0
     phases = None
     attempts = 0
-    for _ in range(a.steps):
-        lib.pg_graph_destroy(one_pass(d, False))
+    g_last = None
+    for i in range(a.steps):
+        g = one_pass(d, False)
+        if a.dump_outputs and i == a.steps - 1:
+            g_last = g  # read after the clock stops
+        else:
+            lib.pg_graph_destroy(g)
         path_sec += lib.pg_last_path_seconds()
         attempts += lib.pg_last_attempts()
         ph = (C.c_double * 16)()
@@ -335,6 +395,10 @@ def main():
         phases = cur if phases is None else [x + y for x, y in zip(phases, cur)]
     sync()
     dt = time.time() - t0
+    if g_last is not None:
+        if rank == 0:
+            dump_outputs(g_last, a.dump_outputs)
+        lib.pg_graph_destroy(g_last)
     coll_per_step = (lib.pg_collective_count() - n_coll0) / a.steps
     waits_per_step = k_timing(d, 4)[1] / a.steps  # times the host waited for the stream
     if a.leg == "steps-only":  # the exchange-overhead leg of another bench.py: its own line, nothing else
@@ -352,11 +416,12 @@ def main():
         h = torch.tensor([n_hits], dtype=torch.int64, device=xdev)
         dist.all_reduce(h)
         tot_hits = int(h.item())
-        # every rank must have built the same graph: the S/L lines' md5 of all ranks against rank 0's
-        m = torch.tensor(list(bytes.fromhex(sl_md5(gfa))), dtype=torch.int64, device=xdev)
-        lo_, hi_ = m.clone(), m.clone()
-        dist.all_reduce(lo_, op=dist.ReduceOp.MIN); dist.all_reduce(hi_, op=dist.ReduceOp.MAX)
-        ranks_agree = bool(torch.equal(lo_, hi_))
+        ranks_agree = None
+        if gfa is not None:  # every rank must have built the same graph: the S/L lines' md5 of all ranks against rank 0's
+            m = torch.tensor(list(bytes.fromhex(sl_md5(gfa))), dtype=torch.int64, device=xdev)
+            lo_, hi_ = m.clone(), m.clone()
+            dist.all_reduce(lo_, op=dist.ReduceOp.MIN); dist.all_reduce(hi_, op=dist.ReduceOp.MAX)
+            ranks_agree = bool(torch.equal(lo_, hi_))
     else:
         tot_hits, t_cold_all = n_hits, t_cold + t_pack
         ranks_agree = None
@@ -441,7 +506,7 @@ def main():
                 out["frac_by_counters"] = round(tot / (ev[5][0] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
         return out
 
-    roof = roofline_of(d, nh.value, ne.value, "the bench workload itself (fits the 256 MiB Infinity Cache: an L3 figure)")
+    roof = roofline_of(d, nh.value, ne.value, "the bench workload itself (fits the 256 MiB Infinity Cache: an L3 figure)") if a.full else None
     lib.pg_data_destroy(d)  # one context (and one HIP stream) at a time: the legs below bring their own
     d = None
 
@@ -476,16 +541,17 @@ def main():
 
     # the box's host link, as this process sees it (measured AFTER the timed passes: torch's allocations must not sit between the warm-up set and the cold pass)
     link_gbps = None
-    try:
-        hb = torch.empty(64 << 20, dtype=torch.uint8).pin_memory()
-        db_ = torch.empty(64 << 20, dtype=torch.uint8, device=dev)
-        db_.copy_(hb, non_blocking=True); torch.cuda.synchronize(dev)
-        t0 = time.time()
-        db_.copy_(hb, non_blocking=True); torch.cuda.synchronize(dev)
-        link_gbps = round((64 << 20) / (time.time() - t0) / 1e9, 1)
-        del hb, db_
-    except Exception:
-        pass
+    if a.full:
+        try:
+            hb = torch.empty(64 << 20, dtype=torch.uint8).pin_memory()
+            db_ = torch.empty(64 << 20, dtype=torch.uint8, device=dev)
+            db_.copy_(hb, non_blocking=True); torch.cuda.synchronize(dev)
+            t0 = time.time()
+            db_.copy_(hb, non_blocking=True); torch.cuda.synchronize(dev)
+            link_gbps = round((64 << 20) / (time.time() - t0) / 1e9, 1)
+            del hb, db_
+        except Exception:
+            pass
 
 
     def shard_leg(dirname, n_genomes, what, n_pass=3, more_dirs=()):
@@ -602,7 +668,7 @@ def main():
 
     # HBM bandwidth of a plain copy kernel in this very process ("calibrate with a copy kernel in the same run")
     peak_meas = None
-    if rank == 0:
+    if rank == 0 and a.full:
         try:
             lib.pg_trim_host_cache(0)  # (the cached device blocks of the legs go back first)
             gb = lib.pg_device_copy_gbps(1 << 30, 5)
@@ -700,10 +766,10 @@ def main():
                                       % (t_pack * 1e3, t_upload * 1e3),
                           "upload_MB": round((44 * nh.value + 8 * ne.value) / 1e6, 1), "host_to_device_GBps_of_this_box": link_gbps},
             "roofline": roof, "cpu_baseline": cpu, "big_shard": big, "human_shard": human, "exchange_overhead": xo, "cli": cli,
-            "gfa_md5": hashlib.md5(gfa).hexdigest() if world == 1 else None,
-            "gfa_sl_md5": sl_md5(gfa), "gfa_sl_lines_same_on_all_ranks": ranks_agree,
+            "gfa_md5": hashlib.md5(gfa).hexdigest() if world == 1 and gfa is not None else None,
+            "gfa_sl_md5": sl_md5(gfa) if gfa is not None else None, "gfa_sl_lines_same_on_all_ranks": ranks_agree,
             "gfa_identical_to_reference": (hashlib.md5(gfa).hexdigest() == ref_md5) if ref_md5 else None,
-            "not_timed": {"paf_generate_s": round(t_gen, 2), "paf_parse_and_pack_s": round(t_parse, 3), "gfa_write_s": round(t_write[0], 4), "path_only_ms_per_step": round(path_sec / a.steps * 1e3, 3)},
+            "not_timed": {"paf_generate_s": round(t_gen, 2), "paf_parse_and_pack_s": round(t_parse, 3), "gfa_write_s": round(t_write[0], 4) if t_write else None, "path_only_ms_per_step": round(path_sec / a.steps * 1e3, 3)},
             "host_waits_per_step": waits_per_step, "collectives_per_step": coll_per_step,
             "host_phases_ms_per_step": {lib.pg_phase_name(i).decode(): round(v / a.steps * 1e3, 3) for i, v in enumerate(phases or [])},
         }

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""HBM bytes per launch of K1 (k_sweep<3, *>) from the two PMC passes of `python bench.py --no-cpu-baseline --no-extra-legs`, per
+"""HBM bytes per launch of K1 (k_sweep<3, *>) from the two PMC passes of `python bench.py --full --no-cpu-baseline --no-extra-legs`, per
 kernel flavour and shard size.  rocprofv3 reports FETCH_SIZE / WRITE_SIZE in KB (1 unit = 1024 B); on gfx950 FETCH_SIZE tallies
 64 B per request where a wide coalesced read moves 128 B, so it is doubled (MI355X_MICROARCH.md, HBM section).  The bench launches
 k_sweep<3, false> on three shard sizes (the tiny warm-up set, the bench workload, the past-L3 shard of the roofline leg) and
@@ -52,6 +52,6 @@ for flavour, sizes in want.items():
         tot = int((2 * fk + wk) * 1024)
         ent.append({"kernel": KNAME[flavour], "flavour": flavour, "k_sweep_sha16": sha, "hits_per_launch": hits, "fetch_kb_raw": round(fk, 1), "write_kb": round(wk, 1),
                     "bytes_per_launch": tot, "bytes_per_hit": round(tot / hits, 1), "dispatches": [nf[-1 - k], nw[-1 - k]],
-                    "note": "FETCH_SIZE x2 (gfx950 correction), separate --pmc passes of `python bench.py --no-cpu-baseline --no-extra-legs --steps 2 --warmup 0`"})
+                    "note": "FETCH_SIZE x2 (gfx950 correction), separate --pmc passes of `python bench.py --full --no-cpu-baseline --no-extra-legs --steps 2 --warmup 0`"})
     out += ent[::-1]
 print(json.dumps(out, indent=1))

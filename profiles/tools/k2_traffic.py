@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """HBM bytes per launch of the arc round's kernels (k_walk, k_gene_arcs_big, k_gene_arcs_wave, k_sweep<0, and k_rep_fill of the branch step) on the
-12 M-hit shard, from the two PMC passes of `python bench.py ... --genomes-per-gpu 1250 --steps 1 --warmup 0` (FETCH_SIZE doubled: gfx950, see
+12 M-hit shard, from the two PMC passes of `python bench.py --full ... --genomes-per-gpu 1250 --steps 1 --warmup 0` (FETCH_SIZE doubled: gfx950, see
 k1_traffic.py).  The launches of the shard are told from those of the small warm-up sets by their counter values (within a factor 8 of the
 largest); the mean over them is what bench.py's K2 figures are averages over as well (live lists shrink the later rounds' launches).
 Every entry carries the sha256 of k_genes.hpp: bench.py reports `frac_by_counters` only while the source is the same.

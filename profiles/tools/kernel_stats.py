@@ -5,7 +5,7 @@ db = sorted(glob.glob(os.path.join(sys.argv[1], "**", "*.db"), recursive=True))[
 cur = sqlite3.connect(db).cursor()
 rows = cur.execute("SELECT name, COUNT(*), SUM(duration), AVG(duration), MIN(duration), MAX(duration) FROM kernels GROUP BY name ORDER BY SUM(duration) DESC").fetchall()
 tot = sum(r[2] for r in rows)
-print("# rocprofv3 --kernel-trace --stats -- python bench.py --no-cpu-baseline   (first pass + warm-up + timed steps)")
+print("# rocprofv3 --kernel-trace --stats -- python bench.py --full --no-cpu-baseline  (first pass + warm-up + timed steps)")
 print("# total kernel time %.3f ms in %d launches" % (tot / 1e6, sum(r[1] for r in rows)))
 print("# %-88s %7s %12s %10s %10s %10s %6s" % ("kernel", "calls", "total_us", "avg_us", "min_us", "max_us", "%"))
 for r in rows:

@@ -53,3 +53,27 @@ def all_cases():
     with open(os.path.join(GOLD, "expected.json")) as f:
         exp = json.load(f)
     return [(s, v) for s in sorted(exp) for v in sorted(exp[s])]
+
+
+REF_BIN = os.path.join(ROOT, "oracle", "_ref", "pangene_ref")
+_REF_OUT = None
+
+
+def reference_output(key, argv, files):
+    """{"md5", "bytes"} of what the untouched reference prints for `files` with options `argv`, as recorded in
+    tests/golden/reference_outputs.json under `key` (tests/golden/make_reference_outputs.py).  Where oracle/_ref/pangene_ref was
+    built it is run as well, and must print what was recorded."""
+    global _REF_OUT
+    if _REF_OUT is None:
+        with open(os.path.join(GOLD, "reference_outputs.json")) as f:
+            _REF_OUT = json.load(f)
+    rec = _REF_OUT.get(key)
+    if os.path.exists(REF_BIN):
+        import hashlib
+        import subprocess
+        out = subprocess.run([REF_BIN] + list(argv) + list(files), stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, check=True).stdout
+        live = {"md5": hashlib.md5(out).hexdigest(), "bytes": len(out)}
+        assert rec is None or rec == live, "the reference binary no longer prints what was recorded for " + key
+        return live
+    assert rec is not None, "no recorded reference output for " + key
+    return rec

@@ -10,7 +10,7 @@ import sys
 import numpy as np
 import pytest
 
-from conftest import ROOT, all_cases, golden_files
+from conftest import ROOT, all_cases, golden_files, reference_output
 import oracle_host  # tests/oracle_host.py: the checker build of the host driver
 from pangene_amd import capi, synth
 
@@ -302,18 +302,14 @@ def _expected_large(name, variant):
 
 
 def test_config1_full_size_against_reference(hip, tmp_path):
-    """BASELINE configs[1]: bact(100, 5000), ~1 M hits: GFA bit-identical to the reference binary (run here when it was shipped,
-    explicit skip of that half otherwise); rerun on the HBM-resident shard is idempotent."""
+    """BASELINE configs[1]: bact(100, 5000), ~1 M hits: GFA bit-identical to the reference's (recorded in
+    tests/golden/reference_outputs.json; the binary runs too where it was shipped); rerun on the HBM-resident shard is idempotent."""
     files = synth.write_files_parallel("bact", str(tmp_path / "c2"), G=100, P=5000, seed=1)
     hip.pg_set_exact_mode(1)
     a = capi.run(hip, files, [])
     b = capi.run(hip, files, [])
-    ref = os.path.join(ROOT, "oracle", "_ref", "pangene_ref")
-    if not os.path.exists(ref):
-        assert a == b
-        pytest.skip("oracle/_ref/pangene_ref not shipped: the reference comparison did not run (idempotence did)")
-    want = subprocess.run([ref] + files, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, check=True).stdout
-    assert a == want
+    want = reference_output("config1|", [], files)
+    assert (hashlib.md5(a).hexdigest(), len(a)) == (want["md5"], want["bytes"])
     assert a == b
     s = sum(1 for l in a.split(b"\n") if l[:1] == b"S")
     assert 4000 < s <= 5000

@@ -13,7 +13,7 @@ import subprocess
 
 import pytest
 
-from conftest import ROOT, all_cases, golden_files
+from conftest import ROOT, all_cases, golden_files, reference_output
 import oracle_host  # tests/oracle_host.py: the checker build of the host driver
 from pangene_amd import capi, synth
 
@@ -57,18 +57,15 @@ def test_c4_md5_is_the_surveyed_one(expected):
 
 @pytest.mark.parametrize("seed", [11, 12, 13])
 def test_live_against_reference_binary(ora, tmp_path, seed):
-    """Fresh seeds straight against oracle/_ref (skipped where the binary was not built)."""
-    ref = os.path.join(ROOT, "oracle", "_ref", "pangene_ref")
-    if not os.path.exists(ref):
-        pytest.skip("oracle/_ref/pangene_ref not built")
+    """Fresh seeds against the reference's output (recorded in tests/golden/reference_outputs.json; oracle/_ref runs too where built)."""
     files = synth.write_files(synth.bact(12, 400, seed=seed), str(tmp_path / "b"))
     files2 = synth.write_files(synth.fuzz(seed, harsh=bool(seed & 1)), str(tmp_path / "f"))
-    for fs in (files, files2):
+    for tag, fs in (("b", files), ("f", files2)):
         for mode, args in ((2, []), (2, ["--bed=flag"]), (1, []), (1, ["-S"])):
             ora.pg_set_exact_mode(mode)
             mine = capi.run(ora, fs, args)
-            want = subprocess.run([ref] + args + fs, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, check=True).stdout
-            assert mine == want
+            want = reference_output("live:%s%d|%s" % (tag, seed, " ".join(args)), args, fs)
+            assert (_md5(mine), len(mine)) == (want["md5"], want["bytes"])
 
 
 @pytest.mark.parametrize("first,n,shapes,variants", [
@@ -78,25 +75,20 @@ def test_live_against_reference_binary(ora, tmp_path, seed):
 def test_fuzz_sweep_default_mode_against_reference_binary(built, first, n, shapes, variants):
     """tests/fuzz_oracle_vs_ref.py as a test: the DEFAULT tie-order mode (auto) must print the reference's bytes on > 300 fresh fuzz
     seeds, including the variants that put pg_n_local's local_dist / local_count boundary inside the fuzz shapes (H2b)."""
-    if not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "pangene_ref")):
-        pytest.skip("oracle/_ref/pangene_ref not built")
     import fuzz_oracle_vs_ref as fz
     vs = [v for v in fz.VARIANTS if "-D" in v] if variants == "dc" else fz.VARIANTS
-    tot, bad = fz.sweep(first, n, modes=(1,), variants=vs, shapes=shapes, verbose=False)
+    tot, bad = fz.sweep(first, n, modes=(1,), variants=vs, shapes=shapes, verbose=False, reference=reference_output)
     assert tot == n * len(shapes) * len(vs) and not bad, bad[:10]
 
 
 def test_dense_shape_against_reference_binary(ora, tmp_path):
-    """giant spanning hit + pile-ups (the shape the GPU sweep sends through its slow list), host driver + oracle vs oracle/_ref"""
-    ref = os.path.join(ROOT, "oracle", "_ref", "pangene_ref")
-    if not os.path.exists(ref):
-        pytest.skip("oracle/_ref/pangene_ref not built")
-    for fs in (synth.write_files(synth.dense(3), str(tmp_path / "d")), synth.write_files(synth.many_doms(2), str(tmp_path / "m"))):
+    """giant spanning hit + pile-ups (the shape the GPU sweep sends through its slow list), host driver + oracle vs the reference's output"""
+    for tag, fs in (("dense3", synth.write_files(synth.dense(3), str(tmp_path / "d"))), ("manydoms2", synth.write_files(synth.many_doms(2), str(tmp_path / "m")))):
         for mode, args in ((2, []), (2, ["-p0", "-a1"]), (1, []), (1, ["-S"]), (1, ["-G"])):
             ora.pg_set_exact_mode(mode)
             mine = capi.run(ora, fs, args)
-            want = subprocess.run([ref] + args + fs, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, check=True).stdout
-            assert mine == want and len(want) > 1000
+            want = reference_output("%s|%s" % (tag, " ".join(args)), args, fs)
+            assert (_md5(mine), len(mine)) == (want["md5"], want["bytes"]) and want["bytes"] > 1000
 
 
 @pytest.mark.parametrize("name", ["C4", "bact20", "human8f", "fuzz3"])
@@ -109,15 +101,22 @@ def test_batch_reader_equals_sequential_reader(built, name):
 
 
 def test_ksort_exact_reproduces_the_reference_radix_sort(tmp_path):
-    """pangene_amd/csrc/host/ksort_exact.hpp against the reference's own KRADIX_SORT_INIT instance (header used where it lies):
-    the same permutation, ties included, on ~1000 random arrays of 1 .. 100 k elements."""
-    ref_hdr = "/root/reference/ksort.h"
-    if not os.path.exists(ref_hdr):
-        pytest.skip("reference sources not present (GPU box)")
+    """pangene_amd/csrc/host/ksort_exact.hpp against the reference's own KRADIX_SORT_INIT instance: the same permutation, ties
+    included, on ~1000 random arrays of 1 .. 100 k elements -- against digests of the reference's permutations
+    (tests/golden/ksort_reference_digests.txt, `ksort_check record`), and directly where the reference's header is present."""
     sup = os.path.join(ROOT, "tests", "support")
-    obj, exe = str(tmp_path / "stub.o"), str(tmp_path / "ksort_check")
-    subprocess.run(["gcc", "-std=c99", "-O2", "-I/root/reference", "-c", os.path.join(sup, "ksort_ref_stub.c"), "-o", obj], check=True)
-    subprocess.run(["g++", "-std=c++17", "-O2", "-I" + os.path.join(ROOT, "pangene_amd", "csrc", "host"), os.path.join(sup, "ksort_check.cpp"), obj, "-o", exe], check=True)
-    r = subprocess.run([exe], stdout=subprocess.PIPE)
+    host = "-I" + os.path.join(ROOT, "pangene_amd", "csrc", "host")
+    exe = str(tmp_path / "ksort_check")
+    subprocess.run(["g++", "-std=c++17", "-O2", host, os.path.join(sup, "ksort_check.cpp"), "-o", exe], check=True)
+    r = subprocess.run([exe, "check", os.path.join(ROOT, "tests", "golden", "ksort_reference_digests.txt")], stdout=subprocess.PIPE)
     assert r.returncode == 0, r.stdout.decode()[-1000:]
     assert b" 0 mismatches" in r.stdout
+    import re
+    ref_dir = re.search(r"^REF\s*\?=\s*(\S+)", open(os.path.join(ROOT, "oracle", "Makefile")).read(), re.M).group(1)  # where oracle/Makefile finds the reference
+    if os.path.exists(os.path.join(ref_dir, "ksort.h")):
+        obj, exe = str(tmp_path / "stub.o"), str(tmp_path / "ksort_check_ref")
+        subprocess.run(["gcc", "-std=c99", "-O2", "-I" + ref_dir, "-c", os.path.join(sup, "ksort_ref_stub.c"), "-o", obj], check=True)
+        subprocess.run(["g++", "-std=c++17", "-O2", "-DKSORT_REF", host, os.path.join(sup, "ksort_check.cpp"), obj, "-o", exe], check=True)
+        r = subprocess.run([exe], stdout=subprocess.PIPE)
+        assert r.returncode == 0, r.stdout.decode()[-1000:]
+        assert b" 0 mismatches" in r.stdout
