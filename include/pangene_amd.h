@@ -173,6 +173,24 @@ long       pg_peakrss(void);    /* bytes */
 void pg_write_matrix(pg_graph_t *g, int32_t copy_number);
 int  pg_gfa2matrix_file(const char *gfa_fn, int32_t copy_number, const char *clstr_fn, int32_t print_cd);
 
+/* pangene.js `call` (pangene.js:93-392, 440-980; version 1.1-r231), bubble calling with the alleles the walks take through each
+ * bubble, byte for byte.  The options are the script's: max_ext (-m, default 100; <0 never happens there, INT32_MAX stands for
+ * its NaN), ignore_walk -w, use_pst -p, add_super -s, ref -r (NULL: none), and the outputs -b (Bandage CSV), -e (cycle
+ * equivalence), -d (DFS); with none of the three the bubble report ("CC" header, FB / BB / AL lines) is printed.  The walk side
+ * (which walks pass a bubble, alleles, genes) runs on the backend (pga_call_bubbles).
+ * pg_call_file reads a GFA file, plain or gzipped, as the script does; it returns 0, -1 when the file cannot be opened, -2 when
+ * the script would have stopped with an error ("Wrong!" for a GFA that lists links in one direction only, "DFS bug"): one line
+ * on stderr then and nothing on the output.  pg_write_call does the same for the graph in memory after pg_graph_gen: the
+ * segments, links and walks pg_write_graph / pg_write_walk would print, taken from the arrays behind them. */
+typedef struct {
+	int32_t max_ext, ignore_walk, use_pst, add_super;
+	int32_t print_bandage, print_cec, print_dfs;
+	const char *ref;
+} pg_call_opt_t;
+void pg_call_opt_init(pg_call_opt_t *o);
+int  pg_call_file(const char *gfa_fn, const pg_call_opt_t *o);
+void pg_write_call(pg_graph_t *g, const pg_call_opt_t *o);
+
 /* Last error of the path (0 = none).  The reference aborts on invariant violations; this library
  * records a status instead, prints one line to stderr, and leaves the graph empty. */
 int         pg_last_error(void);

@@ -94,7 +94,7 @@ typedef struct {
  * Device layout limits (PGA_ERR_RANGE otherwise): coordinates inside a block < 2^31 (contigs beyond that arrive as virtual contigs,
  * see pga_genome_block_t; what remains out of reach is a single cluster of overlapping hits spanning 2^30 bp), < 2^30 hits and < 2^31
  * exons per shard, < 2^20 genes, < 2^24 genomes. */
-#define PGA_ABI_VERSION 5u  /* bumped whenever a struct of this header or the order of pga_backend_t changes; pga_create refuses another */
+#define PGA_ABI_VERSION 6u  /* bumped whenever a struct of this header or the order of pga_backend_t changes; pga_create refuses another */
 typedef struct {
 	uint32_t abi_version;        /* = PGA_ABI_VERSION of the header the caller was compiled against (PGA_ERR_ARG otherwise) */
 	int32_t n_genome;            /* genomes in this shard (may include genomes with 0 hits) */
@@ -284,6 +284,29 @@ typedef struct {
 
 PGA_DECLARE(pga)
 
+/* pangene.js `call` (pangene.js:812-862), the walk side of bubble calling: which walks pass through which bubble, and the alleles
+ * and genes they carry.  Context-free (no shard): the walks and bubbles come from the host, the results go back to it.
+ * In:  walks as one array of oriented segments (vertex = segment * 2 + reverse), walk w = step[walk_off[w] .. walk_off[w+1]);
+ *      bubble b runs from vertex bub_vs[b] to bub_ve[b] (bub_vs[b] < 0: no bubble, nothing is recorded for it).
+ * Out: rec[n_rec], every (bubble, orientation) passage of every walk: a start vertex at st_off followed in the same walk by the
+ *      end vertex at en_off (orientation +: vs .. ve; -: ve^1 .. vs^1), ALL earlier starts for each end (the script's quirk), sorted
+ *      by (bubble, walk, en_off, st_off, orientation);
+ *      rep[r] = the first record of r's bubble whose oriented path (vs .. ve as vertices) equals r's; cnt[r] = how many records have
+ *      rep r (0 when r is not a first record);
+ *      gene_*[n_gene]: every (bubble, interior segment) once, with the position of its first appearance (interior steps numbered
+ *      in record order, st_off+1 .. en_off-1 inside a record), sorted by (bubble, segment).
+ * The output arrays belong to the backend and stay valid until its next call_bubbles. */
+typedef struct { int32_t bo, walk, st_off, en_off; } pga_call_rec_t; /* bo = bubble * 2 + (orientation < 0) */
+typedef struct {
+	const int32_t *step; const int64_t *walk_off; int32_t n_walk; int32_t n_seg;
+	const int32_t *bub_vs, *bub_ve; int32_t n_bub;
+} pga_call_in_t;
+typedef struct {
+	int64_t n_rec; const pga_call_rec_t *rec; const int32_t *rep, *cnt;
+	int64_t n_gene; const int32_t *gene_bub, *gene_seg; const int64_t *gene_first;
+} pga_call_out_t;
+int pga_call_bubbles(const pga_call_in_t *in, pga_call_out_t *out);
+
 /* the same ABI as a table, so the host driver is written once */
 struct pga_branch_par_s; struct pga_loop_xchg_s;
 typedef struct {
@@ -339,6 +362,7 @@ typedef struct {
 	int  (*reserve)(int64_t, int64_t, int32_t, int32_t, int32_t, int64_t); /* may be NULL */
 	int  (*stage)(const void *, size_t); /* may be NULL */
 	void (*stage_drop)(const void *);    /* may be NULL */
+	int  (*call_bubbles)(const pga_call_in_t *, pga_call_out_t *); /* may be NULL: the host driver then runs the same step itself */
 } pga_backend_t;
 
 const pga_backend_t *pga_backend(void);

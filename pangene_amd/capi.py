@@ -37,6 +37,26 @@ class pg_exchange_t(C.Structure):
     _fields_ = [("rank", C.c_int32), ("world", C.c_int32), ("user", C.c_void_p), ("allreduce", ALLREDUCE_CB), ("allgather", ALLGATHER_CB), ("stream_ordered", C.c_int32)]
 
 
+class pg_call_opt_t(C.Structure):
+    """pangene.js call options (include/pangene_amd.h)."""
+    _fields_ = [("max_ext", C.c_int32), ("ignore_walk", C.c_int32), ("use_pst", C.c_int32), ("add_super", C.c_int32),
+                ("print_bandage", C.c_int32), ("print_cec", C.c_int32), ("print_dfs", C.c_int32), ("ref", C.c_char_p)]
+
+
+def call_opt(lib: C.CDLL, argv: Sequence[str] = ()) -> pg_call_opt_t:
+    """The option letters of `pangene.js call` (-m INT -w -b -e -d -p -s -r STR)."""
+    o = pg_call_opt_t()
+    lib.pg_call_opt_init(C.byref(o))
+    it = iter(argv)
+    for a in it:
+        if a == "-m": o.max_ext = int(next(it))
+        elif a == "-r": o.ref = next(it).encode()
+        else:
+            for ch in a[1:]:
+                setattr(o, {"w": "ignore_walk", "p": "use_pst", "s": "add_super", "b": "print_bandage", "e": "print_cec", "d": "print_dfs"}[ch], 1)
+    return o
+
+
 _API = {
     "pg_opt_init": (None, [C.POINTER(pg_opt_t)]),
     "pg_data_init": (C.c_void_p, []),
@@ -53,6 +73,9 @@ _API = {
     "pg_write_walk": (None, [C.c_void_p]),
     "pg_write_matrix": (None, [C.c_void_p, C.c_int32]),
     "pg_gfa2matrix_file": (C.c_int, [C.c_char_p, C.c_int32, C.c_char_p, C.c_int32]),
+    "pg_call_opt_init": (None, [C.c_void_p]),
+    "pg_call_file": (C.c_int, [C.c_char_p, C.c_void_p]),
+    "pg_write_call": (None, [C.c_void_p, C.c_void_p]),
     "pg_read_list_dict": (C.c_void_p, [C.c_char_p]),
     "pg_dict_destroy": (None, [C.c_void_p]),
     "pg_last_error": (C.c_int, []),
@@ -118,7 +141,7 @@ def parse_args(lib: C.CDLL, argv: Sequence[str]) -> pg_opt_t:
         elif a in ("--bed", "--bed=walk"): opt.flag |= PG_F_WRITE_BED_WALK
         elif a == "--bed=raw": opt.flag |= PG_F_WRITE_BED_RAW
         elif a == "--bed=flag": opt.flag |= PG_F_WRITE_BED_FLAG
-        elif a in ("--matrix", "--matrix=presence", "--matrix=count"): pass  # handled by run()
+        elif a in ("--matrix", "--matrix=presence", "--matrix=count", "--call"): pass  # handled by run()
         elif a[:2] in ("-p", "-a", "-f", "-c", "-g", "-r", "-b", "-B", "-y", "-T", "-D", "-C", "-e", "-l", "-m", "-d", "-X", "-I", "-P"):
             v = a[2:] if len(a) > 2 else next(it)
             k = a[1]
@@ -180,6 +203,12 @@ def run(lib: C.CDLL, files: Sequence[str], argv: Sequence[str] = (), scan_only: 
             if lib.pg_last_error():
                 raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
             if any(x.startswith("--matrix") for x in argv): lib.pg_write_matrix(g, 1 if "--matrix=count" in argv else 0)
+            elif "--call" in argv:
+                co = pg_call_opt_t()
+                lib.pg_call_opt_init(C.byref(co))
+                lib.pg_write_call(g, C.byref(co))
+                if lib.pg_last_error():
+                    raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
             elif opt.flag & PG_F_WRITE_BED_WALK: lib.pg_write_bed(d, 1)
             elif opt.flag & PG_F_WRITE_BED_FLAG: lib.pg_write_bed(d, 0)
             else:

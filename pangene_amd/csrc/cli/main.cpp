@@ -8,6 +8,8 @@
 #include <sys/stat.h>
 #include <sys/wait.h>
 #include <unistd.h>
+#include <cctype>
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -49,7 +51,9 @@ static int usage(FILE *fp, const pg_opt_t *opt)
 	std::fprintf(fp, "    --matrix[=STR] output the gene x assembly matrix of pangene.js gfa2matrix, STR presence or count [presence]\n");
 	std::fprintf(fp, "    --gpus=INT    shard the genomes over INT GPUs of this node: one process per device, RCCL over xGMI [1]\n");
 	std::fprintf(fp, "    --version     print version number\n");
+	std::fprintf(fp, "    --call        output the bubbles and alleles of pangene.js call (default options) instead of the graph\n");
 	std::fprintf(fp, "  Also: pangene gfa2matrix [-c] [-d FILE] [-p] <in.gfa>   (pangene.js gfa2matrix on a GFA file)\n");
+	std::fprintf(fp, "        pangene call [-m INT] [-w] [-b] [-e] [-d] [-p] [-s] [-r STR] <in.gfa>   (pangene.js call on a GFA file)\n");
 	return fp == stdout ? 0 : 1;
 }
 
@@ -79,6 +83,43 @@ static int main_gfa2matrix(int argc, char *argv[]) // pangene.js:1168-1183
 	return pg_gfa2matrix_file(argv[optind], copy_number, clstr, print_cd) == 0 ? 0 : 1;
 }
 
+// `pangene call` = pangene.js call (pangene.js:941-980): bubbles of a GFA and the alleles its walks take through them
+static int32_t js_int(const char *s) // parseInt; its NaN behaves like a limit nothing exceeds
+{
+	while (*s && std::isspace((unsigned char)*s)) ++s;
+	const char *p = s + (*s == '+' || *s == '-');
+	if (*p < '0' || *p > '9') return INT32_MAX;
+	const double x = std::strtod(std::string(s, (size_t)(p - s) + std::strspn(p, "0123456789")).c_str(), nullptr);
+	return x > INT32_MAX ? INT32_MAX : x < INT32_MIN ? INT32_MIN : (int32_t)x;
+}
+
+static int main_call(int argc, char *argv[])
+{
+	pg_call_opt_t o;
+	pg_call_opt_init(&o);
+	int c;
+	while ((c = getopt(argc, argv, "bedpm:wr:s")) >= 0) {
+		if (c == 'b') o.print_bandage = 1;
+		else if (c == 'e') o.print_cec = 1;
+		else if (c == 'd') o.print_dfs = 1;
+		else if (c == 'm') o.max_ext = js_int(optarg);
+		else if (c == 'w') o.ignore_walk = 1;
+		else if (c == 'r') o.ref = optarg;
+		else if (c == 'p') o.use_pst = 1;
+		else if (c == 's') o.add_super = 1;
+	}
+	if (argc - optind < 1) {
+		std::printf("Usage: pangene call [options] <in.gfa>\nOptions:\n  General:\n    -m INT   don't output gene lists longer than INT [%d]\n"
+		            "    -w       ignore walks\n    -b       output equivalent classes for Bandage visualization\n  Use PST:\n"
+		            "    -p       use program structure tree (PST) to find bubbles\n"
+		            "    -s       add a super node (preferred and only effectively with -p)\n"
+		            "    -r INT   reference assembly for additional edges to the super node []\n"
+		            "  Debugging:\n    -d       output DFS traversal\n    -e       output cycle equivalent class\n", o.max_ext);
+		return 0;
+	}
+	return pg_call_file(argv[optind], &o) == 0 ? 0 : 1;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // `pangene --gpus N`: main.c:117-142 for N devices of one node.  The command forks N - 1 workers BEFORE anything touches the GPU;
 // rank r takes device r and the r-th contiguous block of the PAF files (so that the ranks' W / BED lines, concatenated in rank
@@ -87,7 +128,7 @@ static int main_gfa2matrix(int argc, char *argv[]) // pangene.js:1168-1183
 // tests) it is a shared-memory region mapped before the fork.  Rank 0 prints the graph; every rank writes the lines of its own
 // genomes to a temporary file that rank 0 copies to stdout in rank order.
 // ---------------------------------------------------------------------------------------------------------------
-struct Output { int matrix = 0; };
+struct Output { int matrix = 0; bool call = false; };
 
 static int run_path(pg_opt_t &opt, int n_files, char **files, const uint8_t *ids_only, const Output &o, bool graph_lines, bool own_lines, int device = -1)
 {
@@ -117,6 +158,7 @@ static int run_path(pg_opt_t &opt, int n_files, char **files, const uint8_t *ids
 		t4 = pg_realtime();
 		if (pg_last_error()) rc = 2;
 		else if (o.matrix) pg_write_matrix(g, o.matrix == 2);
+		else if (o.call) { pg_call_opt_t co; pg_call_opt_init(&co); pg_write_call(g, &co); if (pg_last_error()) rc = 2; }
 		else if (opt.flag & PG_F_WRITE_BED_WALK) { if (own_lines) pg_write_bed(d, 1); }
 		else if (opt.flag & PG_F_WRITE_BED_FLAG) { if (own_lines) pg_write_bed(d, 0); }
 		else {
@@ -175,6 +217,7 @@ static std::vector<int> partition_files(int W, int n_files, char **files)
 static int run_sharded(pg_opt_t &opt, int W, int n_files, char **files, const Output &o)
 {
 	if (o.matrix) { std::fprintf(stderr, "ERROR: --matrix needs every genome in one process; run it without --gpus\n"); return 1; }
+	if (o.call) { std::fprintf(stderr, "ERROR: --call needs every genome in one process; run it without --gpus\n"); return 1; }
 	const bool dev = pg_backend_is_device() != 0;
 	typedef int (*uid_fn)(void *); typedef int (*init_fn)(int32_t, int32_t, const void *); typedef int (*fin_fn)(void);
 	uid_fn rccl_uid = nullptr; init_fn rccl_init = nullptr; fin_fn rccl_fin = nullptr;
@@ -315,9 +358,11 @@ static int run_sharded(pg_opt_t &opt, int W, int n_files, char **files, const Ou
 int main(int argc, char *argv[])
 {
 	if (argc >= 2 && std::strcmp(argv[1], "gfa2matrix") == 0) return main_gfa2matrix(argc - 1, argv + 1);
+	if (argc >= 2 && std::strcmp(argv[1], "call") == 0) return main_call(argc - 1, argv + 1);
 	int matrix = 0, n_gpus = 1; // matrix: 1 presence, 2 counts
+	bool call = false;
 	static const struct option lopts[] = {
-		{ "bed", optional_argument, nullptr, 301 }, { "ori-sc", no_argument, nullptr, 302 }, { "matrix", optional_argument, nullptr, 303 },
+		{ "bed", optional_argument, nullptr, 301 }, { "ori-sc", no_argument, nullptr, 302 }, { "matrix", optional_argument, nullptr, 303 }, { "call", no_argument, nullptr, 305 },
 		{ "gpus", required_argument, nullptr, 304 }, { "procs", required_argument, nullptr, 304 },
 		{ "version", no_argument, nullptr, 401 }, { nullptr, 0, nullptr, 0 } };
 	pg_opt_t opt;
@@ -361,6 +406,7 @@ int main(int argc, char *argv[])
 		case 302: opt.flag |= PG_F_ORI_FOR_BRANCH; break;
 		case 303: matrix = (optarg && std::strcmp(optarg, "count") == 0) ? 2 : 1; break;
 		case 304: n_gpus = std::atoi(optarg); break;
+		case 305: call = true; break;
 		case 401: std::puts(PG_VERSION); return 0;
 		default: break;
 		}
@@ -368,6 +414,7 @@ int main(int argc, char *argv[])
 	if (argc - optind < 1) return usage(stderr, &opt);
 	Output o;
 	o.matrix = matrix;
+	o.call = call;
 	int rc;
 	if (n_gpus > 1) {
 		rc = run_sharded(opt, n_gpus, argc - optind, argv + optind, o);

@@ -68,7 +68,7 @@ static int32_t parse_sample(std::string &sample, const char *name)
 }
 
 // every line of a plain or gzipped text file (without the line terminators)
-static int read_lines(const char *fn, std::vector<std::string> &out)
+int read_lines(const char *fn, std::vector<std::string> &out)
 {
 	gzFile fp = (fn && std::strcmp(fn, "-") != 0) ? gzopen(fn, "r") : gzdopen(0, "r");
 	if (fp == nullptr) return -1;
@@ -253,6 +253,86 @@ void pg_write_walk(pg_graph_t *q)
 	}
 	std::fflush(fp);
 }
+
+} // extern "C"
+
+namespace pgx {
+// The walks pg_write_walk prints, as the bubble caller reads them back (call.cpp): per W-line its "sample#hap" and its steps as
+// oriented segments (segment * 2 + reverse); a step whose gene has no segment is left out, as a reader of the GFA would.
+int walk_lists(pg_graph_t *q, std::vector<std::string> &asm_name, std::vector<int32_t> &step, std::vector<int64_t> &walk_off)
+{
+	pg_data_t *d = q->d;
+	asm_name.clear(), step.clear(), walk_off.assign(1, 0);
+	if (sync_host(d, false) != 0) return -1;
+	DataExt *ext = ext_of(d, false);
+	if (ext == nullptr || ext->ctx == nullptr) { set_error(PGA_ERR_ARG, "pg_write_call: pg_graph_gen has not run on this data set"); return -1; }
+	std::vector<int64_t> goff_of((size_t)d->n_genome, -1);
+	for (size_t k = 0; k < ext->local_genomes.size(); ++k) goff_of[(size_t)ext->local_genomes[k]] = ext->hit_off[k];
+	for (int32_t j = 0; j < d->n_genome; ++j) {
+		const pg_genome_t *g = &d->genome[j];
+		if (g->n_hit > 0 && (goff_of[(size_t)j] < 0 || (size_t)j >= ext->y_file.size() || ext->y_file[(size_t)j].size() != (size_t)g->n_hit)) { set_error(PGA_ERR_ARG, "pg_write_call: genome without backend state"); return -1; }
+	}
+	std::vector<int32_t> seg_of((size_t)d->n_gene, -1);
+	for (int32_t i = 0; i < q->n_seg; ++i) seg_of[(size_t)q->seg[i].gid] = i;
+	const uint64_t *fb = ext->flt_bits.data();
+	// genomes are independent: host threads collect them side by side, the lists are joined in genome order
+	struct Part { std::vector<std::string> names; std::vector<int32_t> steps; std::vector<int64_t> lens; };
+	std::vector<Part> part((size_t)d->n_genome);
+	auto collect = [&](int32_t j) {
+		const pg_genome_t *g = &d->genome[j];
+		if (g->n_hit == 0) return;
+		Part &P = part[(size_t)j];
+		const int64_t goff = goff_of[(size_t)j];
+		const int32_t *yf = ext->y_file[(size_t)j].data();
+		const int32_t *hof = ext->hits_sorted[(size_t)j] ? ext->host_of_file[(size_t)j].data() : nullptr;
+		const int32_t *px = ext->pos_x.data() + goff;
+		auto hit_of = [&](int32_t k) -> const pg_hit_t * { const int32_t f = yf[k]; return &g->hit[hof ? hof[f] : f]; };
+		auto is_flt = [&](int32_t k) { const int64_t b = goff + px[yf[k]]; return (fb[b >> 6] >> (b & 63) & 1) != 0; };
+		std::string sample;
+		for (int32_t i0 = 0, i = 1; i <= g->n_hit; ++i) {
+			if (i != g->n_hit && hit_of(i)->cid == hit_of(i0)->cid) continue;
+			int32_t n = 0;
+			const size_t at = P.steps.size();
+			for (int32_t k = i0; k < i; ++k) {
+				if (is_flt(k)) continue;
+				const pg_hit_t *a = hit_of(k);
+				const int32_t s = seg_of[(size_t)d->prot[a->pid].gid];
+				if (s >= 0) P.steps.push_back(s * 2 + (a->rev ? 1 : 0));
+				++n;
+			}
+			if (n > 0) {
+				const int32_t hap = parse_sample(sample, g->ctg[hit_of(i0)->cid].name);
+				if (hap >= 0) P.names.push_back(sample + "#" + std::to_string(hap));
+				else if (g->label) P.names.push_back(std::string(g->label) + "#0");
+				else P.names.push_back(std::to_string(j) + "#0");
+				P.lens.push_back((int64_t)(P.steps.size() - at));
+			}
+			i0 = i;
+		}
+	};
+	unsigned nt = ext->n_hit_local > 200000 ? host_threads(32u) : 1u;
+	if (nt > (unsigned)d->n_genome) nt = (unsigned)std::max(1, d->n_genome);
+	if (nt <= 1) for (int32_t j = 0; j < d->n_genome; ++j) collect(j);
+	else {
+		std::atomic<int32_t> next{0};
+		std::vector<std::thread> th;
+		for (unsigned t = 0; t < nt; ++t)
+			th.emplace_back([&]() { for (;;) { const int32_t j = next.fetch_add(1); if (j >= d->n_genome) break; collect(j); } });
+		for (auto &x : th) x.join();
+	}
+	size_t n_step = 0;
+	for (const Part &P : part) n_step += P.steps.size();
+	step.reserve(n_step);
+	for (Part &P : part) {
+		step.insert(step.end(), P.steps.begin(), P.steps.end());
+		for (size_t w = 0; w < P.lens.size(); ++w) asm_name.push_back(std::move(P.names[w])), walk_off.push_back(walk_off.back() + P.lens[w]);
+	}
+	return 0;
+}
+
+} // namespace pgx
+
+extern "C" {
 
 // pangene.js gfa2matrix (pangene.js:1168-1247) straight from the graph in memory: rows = segments in S-line order, columns =
 // sample#haplotype in the order the W-lines would introduce them, entry = presence (or, copy_number != 0, the number of

@@ -219,6 +219,7 @@ extern pg_exchange_t g_xchg; extern bool g_has_xchg;
 void set_error(int code, const char *where);
 
 FILE *out_stream();
+int read_lines(const char *fn, std::vector<std::string> &out); // every line of a plain or gzipped text file, terminators removed
 
 double now_sec();
 const char *stamp();
