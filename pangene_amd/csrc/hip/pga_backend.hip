@@ -106,7 +106,6 @@ extern "C" const char *pga_strerror(int code)
 #include "k_ingest.hpp"
 #include "k_sweep.hpp"
 #include "k_segsort.hpp"
-#include "k_segsort2.hpp"
 #include "k_stage_b.hpp"
 #include "k_vertex.hpp"
 #include "k_arcs.hpp"

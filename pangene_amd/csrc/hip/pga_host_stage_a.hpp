@@ -132,37 +132,33 @@ static int create_impl(pga_ctx *c, const pga_shard_t *sh)
 	c->any_multi = multi, c->density_known = false, c->lists_in_lds = true;
 	c->ctg_bits = bits_for((uint32_t)(max_ctg - 1));
 	c->gs_np = std::max(64, (max_hit + 63) & ~63);
-	c->gs_ok = c->gs_np <= GS_NP_MAX && getenv("PANGENE_GLOBAL_SORT") == nullptr; // (plane 15 holds a 32-bit comparison key either way: rk_shift < 0 = its dense rank, made below)
-	c->gs2 = 0;
-	if (c->gs_ok && c->gs_np <= GS2_NP_BIG) {
-		c->gs2 = 1;
-		std::vector<int32_t> small, big;
-		int np_small = 64;
+	c->gs_ok = c->gs_np <= GS2_NP_WIDE && getenv("PANGENE_GLOBAL_SORT") == nullptr; // (plane 15 holds a 32-bit comparison key either way: rk_shift < 0 = its dense rank, made below)
+	if (c->gs_ok) { // the genomes by size class (k_segsort.hpp), a launch each in pga_begin
+		std::vector<int32_t> cls[3];
 		for (int g = 0; g < GL; ++g) {
 			const int nh = sh->block[g].n_hit;
-			if (nh <= GS2_NP_MAX && c->gs2 == 1) small.push_back(g), np_small = std::max(np_small, (nh + 63) & ~63);
-			else big.push_back(g);
+			cls[nh <= GS2_NP_MAX ? 0 : nh <= GS2_NP_BIG ? 1 : 2].push_back(g);
 		}
 		// (a) a shard that cannot even fill the CUs once gains nothing from two workgroups per CU, and two half-empty launches in a row
-		// cost more than one: everything by the 14-items form then; (b) the largest genomes first: the tail of a launch is then made
-		// of the short ones
-		if ((int)small.size() < 2 * c->n_cu) { big.insert(big.end(), small.begin(), small.end()); small.clear(); np_small = 64; }
+		// cost more than one: its small genomes then go to the 14-items form; (b) the largest genomes first: the tail of a launch is then
+		// made of the short ones
+		if ((int)cls[0].size() < 2 * c->n_cu) { cls[1].insert(cls[1].end(), cls[0].begin(), cls[0].end()); cls[0].clear(); }
 		auto by_size = [&](int32_t x, int32_t y) { return sh->block[x].n_hit != sh->block[y].n_hit ? sh->block[x].n_hit > sh->block[y].n_hit : x < y; };
-		std::sort(small.begin(), small.end(), by_size), std::sort(big.begin(), big.end(), by_size);
-		c->gs2_n_small = (int)small.size(), c->gs2_n_big = (int)big.size(), c->gs2_np_small = np_small;
-		small.insert(small.end(), big.begin(), big.end());
-		if (c->gs2 && hipFuncSetAttribute(reinterpret_cast<const void *>(k_genome_sort2), hipFuncAttributeMaxDynamicSharedMemorySize, (int)gs2_lds_bytes(GS2_NP_MAX)) != hipSuccess) { (void)hipGetLastError(); c->gs2 = 0; }
-		if (c->gs2 && hipFuncSetAttribute(reinterpret_cast<const void *>(k_genome_sort2d), hipFuncAttributeMaxDynamicSharedMemorySize, (int)gs2_lds_bytes(GS2_NP_BIG)) != hipSuccess) { (void)hipGetLastError(); c->gs2 = 0; }
-		if (c->gs2) {
-			c->gs2_list = (int32_t *)c->pool.get(S_GS2LIST, sizeof(int32_t) * (size_t)std::max(1, GL));
-			if (!c->gs2_list) return PGA_ERR_NOMEM;
-			if (GL) HIPCHK(hipMemcpyAsync(c->gs2_list, small.data(), sizeof(int32_t) * (size_t)GL, hipMemcpyHostToDevice, c->st));
+		const void *const kf[3] = { reinterpret_cast<const void *>(k_genome_sort2), reinterpret_cast<const void *>(k_genome_sort2d), reinterpret_cast<const void *>(k_genome_sort2w) };
+		const int np_max[3] = { GS2_NP_MAX, GS2_NP_BIG, GS2_NP_WIDE };
+		std::vector<int32_t> list;
+		for (int k = 0; k < 3; ++k) {
+			std::sort(cls[k].begin(), cls[k].end(), by_size);
+			c->gs_n[k] = (int)cls[k].size(), c->gs_np_of[k] = cls[k].empty() ? 64 : std::max(64, (sh->block[cls[k][0]].n_hit + 63) & ~63);
+			list.insert(list.end(), cls[k].begin(), cls[k].end());
+			if (c->gs_n[k] && hipFuncSetAttribute(kf[k], hipFuncAttributeMaxDynamicSharedMemorySize, (int)gs2_lds_bytes(np_max[k])) != hipSuccess) { (void)hipGetLastError(); c->gs_ok = false; }
+		}
+		if (c->gs_ok) {
+			c->gs_list = (int32_t *)c->pool.get(S_GSLIST, sizeof(int32_t) * (size_t)std::max(1, GL));
+			if (!c->gs_list) return PGA_ERR_NOMEM;
+			if (GL) HIPCHK(hipMemcpyAsync(c->gs_list, list.data(), sizeof(int32_t) * (size_t)GL, hipMemcpyHostToDevice, c->st));
 			HIPCHK(hipStreamSynchronize(c->st)); // (the list is a local)
 		}
-	}
-	if (c->gs_ok) {
-		const void *kf = c->gs_np <= GS_K_SMALL * GS_T ? reinterpret_cast<const void *>(k_genome_sort) : reinterpret_cast<const void *>(k_genome_sort_big);
-		if (hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gs_lds_bytes(c->gs_np)) != hipSuccess) { (void)hipGetLastError(); c->gs_ok = false; }
 	}
 
 	c->gf_pos_bits = bits_for((uint32_t)std::max(1, max_hit - 1));
@@ -313,7 +309,7 @@ static int create_impl(pga_ctx *c, const pga_shard_t *sh)
 	return rc;
 }
 
-static int y_fixup_on() { static const int on = [] { const char *e = getenv("PANGENE_Y_FIXUP"); return (e && *e == '0') ? 0 : 1; }(); return on; } // (k_segsort2.hpp: the cm order out of the cs order by transpositions; 0 = by radix passes, as rounds 3-5)
+static int y_fixup_on() { static const int on = [] { const char *e = getenv("PANGENE_Y_FIXUP"); return (e && *e == '0') ? 0 : 1; }(); return on; } // (k_segsort.hpp: the cm order out of the cs order by transpositions; 0 = by radix passes, as rounds 3-5)
 // per-hit constants in file order, X order (sort + gather), running max of ce, Y order; resets all state
 extern "C" int pga_begin(pga_ctx_t *c)
 {
@@ -343,37 +339,23 @@ extern "C" int pga_begin(pga_ctx_t *c)
 	if (c->bin_on) { // contig bins (k_segsort.hpp): both orders, every per-hit constant, the packed records -- a workgroup per bin, its keys in LDS
 		HitArrays o = { c->fidx, c->gnm, c->seg, c->pid, c->gid, c->cs, c->ce, c->cm, c->cds, c->nex, c->offx, c->sori, c->sadj, c->rank, c->sdom, c->pdom, c->pdom0, c->rk, c->flags };
 		GenomeSort gs = { c->up_grouped, (int64_t)N, c->goff, c->ctg_base, c->cs_bits, c->cm_bits, c->bin_ctg_bits, c->bin_np_small, GL,
-		                  o, c->yperm, c->headpos, c->recA, c->recB, c->recC, nullptr, nullptr, c->bins, y_fixup_on() };
+		                  o, c->yperm, c->headpos, c->recA, c->recB, c->recC, nullptr, c->bins, y_fixup_on() };
 		if (c->bin_n_small) hipLaunchKernelGGL(k_genome_sort2, dim3((unsigned)c->bin_n_small), dim3(GS2_T), gs2_lds_bytes(c->bin_np_small), c->st, gs);
 		if (c->bin_n_big) { GenomeSort g2 = gs; g2.bins = c->bins + c->bin_n_small, g2.np = c->bin_np_big; hipLaunchKernelGGL(k_genome_sort2d, dim3((unsigned)c->bin_n_big), dim3(GS2_T), gs2_lds_bytes(c->bin_np_big), c->st, g2); }
 		HIPCHK(hipMemcpyAsync(c->headpos, c->goff, sizeof(int32_t) * ((size_t)GL + 1), hipMemcpyDeviceToDevice, c->st));
 		c->inv_valid = false;
 		return 0;
 	}
-	if (c->gs_ok) { // one launch: both orders, every per-hit constant, the packed records (k_segsort.hpp)
+	if (c->gs_ok) { // a launch per size class over the genome list: both orders, every per-hit constant, the packed records (k_segsort.hpp)
 		HitArrays o = { c->fidx, c->gnm, c->seg, c->pid, c->gid, c->cs, c->ce, c->cm, c->cds, c->nex, c->offx, c->sori, c->sadj, c->rank, c->sdom, c->pdom, c->pdom0, c->rk, c->flags };
 		GenomeSort gs = { up, (int64_t)N, c->goff, c->ctg_base, c->cs_bits, c->cm_bits, c->ctg_bits, c->gs_np, GL,
-		                  o, c->yperm, c->headpos, c->recA, c->recB, c->recC, nullptr, nullptr, nullptr, y_fixup_on() };
-		static const bool gs_prof = getenv("PANGENE_GS_PROF") != nullptr;
-		if (gs_prof) { gs.prof = (long long *)c->pool.get(S_SCRATCH, sizeof(long long) * 32 * (size_t)GL); if (gs.prof) HIPCHK(hipMemsetAsync(gs.prof, 0, sizeof(long long) * 32 * (size_t)GL, c->st)); }
-		if (c->gs2 && !gs_prof) {
-			if (c->gs2_n_small) { GenomeSort g1 = gs; g1.glist = c->gs2_list, g1.np = c->gs2_np_small; hipLaunchKernelGGL(k_genome_sort2, dim3((unsigned)c->gs2_n_small), dim3(GS2_T), gs2_lds_bytes(c->gs2_np_small), c->st, g1); }
-			if (c->gs2_n_big) { GenomeSort g2 = gs; g2.glist = c->gs2_list + c->gs2_n_small; hipLaunchKernelGGL(k_genome_sort2d, dim3((unsigned)c->gs2_n_big), dim3(GS2_T), gs2_lds_bytes(c->gs_np), c->st, g2); }
+		                  o, c->yperm, c->headpos, c->recA, c->recB, c->recC, c->gs_list, nullptr, y_fixup_on() };
+		void (*const kf[3])(GenomeSort) = { k_genome_sort2, k_genome_sort2d, k_genome_sort2w };
+		for (int k = 0; k < 3; ++k) {
+			if (c->gs_n[k]) { GenomeSort g = gs; g.np = c->gs_np_of[k]; hipLaunchKernelGGL(kf[k], dim3((unsigned)c->gs_n[k]), dim3(GS2_T), gs2_lds_bytes(g.np), c->st, g); }
+			gs.glist += c->gs_n[k];
 		}
-		else if (c->gs_np <= GS_K_SMALL * GS_T) hipLaunchKernelGGL(k_genome_sort, dim3((unsigned)GL), dim3(GS_T), gs_lds_bytes(c->gs_np), c->st, gs);
-		else hipLaunchKernelGGL(k_genome_sort_big, dim3((unsigned)GL), dim3(GS_T), gs_lds_bytes(c->gs_np), c->st, gs);
 		c->inv_valid = false;
-		if (gs.prof) { // mean cycles per phase over the workgroups (100 MHz constant counter: 10 ns per tick)
-			std::vector<long long> hp((size_t)32 * GL);
-			HIPCHK(hipStreamSynchronize(c->st));
-			HIPCHK(hipMemcpy(hp.data(), gs.prof, hp.size() * sizeof(long long), hipMemcpyDeviceToHost));
-			double d[20] = { 0 }; long long t_min = INT64_MAX, t_max = 0;
-			for (int g2 = 0; g2 < GL; ++g2) { for (int k = 1; k <= 12; ++k) d[k] += (double)(hp[(size_t)g2 * 32 + k] - hp[(size_t)g2 * 32 + k - 1]); for (int k = 17; k <= 21; ++k) d[k - 4] += (double)(hp[(size_t)g2 * 32 + k] - hp[(size_t)g2 * 32 + k - 1]); d[0] += (double)(hp[(size_t)g2 * 32 + 16] - hp[(size_t)g2 * 32]); t_min = std::min(t_min, hp[(size_t)g2 * 32]), t_max = std::max(t_max, hp[(size_t)g2 * 32 + 12]); }
-			fprintf(stderr, "[k_genome_sort profile, np %d, ticks/workgroup]", c->gs_np);
-			for (int k = 1; k <= 12; ++k) fprintf(stderr, " %d:%.0f", k, d[k] / GL);
-			fprintf(stderr, " | first radix pass: until the byte plane is staged %.0f, histogram %.0f (wave 0) + %.0f (barrier), scan %.0f, scatter %.0f (wave 0) + %.0f (barrier)", d[0] / GL, d[13] / GL, d[14] / GL, d[15] / GL, d[16] / GL, d[17] / GL);
-			fprintf(stderr, " | kernel span %lld ticks\n", t_max - t_min);
-		}
 		return 0;
 	}
 	// (the per-hit constants -- genome, segment, gene, CDS length, static flag bits and, when it fits 32 bits, the comparison key -- were

@@ -24,7 +24,7 @@ except Exception as ex:
 # idle time is distributed (launch gaps vs host waits); the last `--steps` passes are delimited by the k_prepare launches
 try:
     ev = cur.execute("SELECT name, start, end FROM kernels ORDER BY start").fetchall()
-    # first big kernel of pga_begin: k_genome_sort* (stage A's orders may take two launches: k_genome_sort2 + k_genome_sort2d) or, for
+    # first big kernel of pga_begin: k_genome_sort* (stage A's orders may take up to three launches: k_genome_sort2 / 2d / 2w) or, for
     # genomes beyond the per-genome sorts (the 110 k-hit assemblies of configs[4]), k_prepare in front of the multi-workgroup radix sort
     # (round 5: k_prepare runs once per upload; the multi-workgroup path of pga_begin now opens with k_score_key -- 64-bit score keys -- or k_xkey)
     def first_of_begin(i):

@@ -124,8 +124,8 @@ def test_arc_round_paths_agree(hip, expected, tmp_path, name, variant, env):
     (the general route of a branch round: sharded runs, log lines, rounds repeated on the sort path) -- and with a four-entry table
     the queued branch rounds (pga_branch_loop, the default) give up on their sticky flag, so the run is repeated with host-driven
     rounds (RC_REDO).  Fourth setting: host-driven rounds from the start (one wait per round, verdicts of pg_flt_high_occ fetched as
-    bytes: the default of round 2) and stage A's orders by the multi-workgroup radix sort instead of k_genome_sort (the path of
-    genomes with more than 25 600 hits), and read.c:249-256 by the four kernels with their tables in HBM instead of k_genome_filters (the
+    bytes: the default of round 2) and stage A's orders by the multi-workgroup radix sort instead of the per-genome LDS sort (the path
+    of genomes with more than 25 600 hits), and read.c:249-256 by the four kernels with their tables in HBM instead of k_genome_filters (the
     path of shards whose P + 8 Q bytes do not fit the LDS).  Fifth setting: the last branch round and the arc round of the graph that is written driven by the
     host behind the queued rounds (the default queues them too and renumbers segments and arcs on the host at the end); and every exon-list
     merge of the sweeps by the reference's literal steps (cds_inter_ref) instead of the shortcuts of cds_inter_t.  Sixth setting: the 4-byte `best`
@@ -139,6 +139,39 @@ def test_arc_round_paths_agree(hip, expected, tmp_path, name, variant, env):
     instead of transpositions."""
     out = _run_with_env(tmp_path, env, 2, variant, golden_files(name))
     assert hashlib.md5(out).hexdigest() == expected[name][variant]["md5"]
+
+
+_GS_BANDS = (10240, 14336, 25600)  # hits a genome: k_genome_sort2 / 2d / 2w (one workgroup per genome, keys in LDS); beyond, the multi-workgroup radix
+_GS_SHARDS = {  # single-contig bacterial shards (contig bins never apply): bact(P, seed 3) genome sets [first, last)
+    "lean": [(3000, 0, 2)], "mid": [(5000, 0, 2)], "wide": [(10500, 0, 2)], "global": [(16000, 0, 2)],
+    "mixed": [(3000, 0, 2), (5000, 2, 3), (10500, 3, 5)],
+}
+
+
+@pytest.mark.parametrize("shard,bands", [("lean", {0}), ("mid", {0, 1}), ("wide", {2}), ("global", {2, 3}), ("mixed", {0, 1, 2})])
+def test_genome_sort_bands(hip, ora, tmp_path, shard, bands):
+    """Stage A's orders by genome size: each band of the per-genome LDS sort (<= 10 240, <= 14 336, <= 25 600 hits) and the global
+    radix beyond, alone and in one shard (a launch per class over one list of genomes; with so few genomes the small ones go to the
+    14-items form), HIP == oracle byte for byte in both modes"""
+    import fuzz_hip_vs_oracle as fz
+    from test_reader import Data
+    files = []
+    for P, first, last in _GS_SHARDS[shard]:
+        files += synth.write_files(synth.bact(5, P, seed=3, first=first, last=last), str(tmp_path / shard))
+    opt, d = capi.parse_args(ora, []), ora.pg_data_init()
+    try:
+        assert capi.read_files(ora, opt, d, files) == 0
+        D = C.cast(d, C.POINTER(Data)).contents
+        n_hit = [D.genome[j].n_hit for j in range(D.n_genome)]
+    finally:
+        ora.pg_data_destroy(d)
+    assert len(n_hit) == len(files) and {sum(n > b for b in _GS_BANDS) for n in n_hit} == bands, n_hit  # bands of the hit counts as read
+    for v in (fz.VARIANTS[0], fz.VARIANTS[1], fz.VARIANTS[2], fz.VARIANTS[8]):  # default, -p0 -a1, -S, -D 300 -C 2
+        for mode in (1, 2):
+            hip.pg_set_exact_mode(mode); ora.pg_set_exact_mode(mode)
+            a, b = capi.run(hip, files, v), capi.run(ora, files, v)
+            assert a == b and len(a) > 1000, (v, mode)
+    hip.pg_set_exact_mode(1); ora.pg_set_exact_mode(1)
 
 
 def test_cross_shard_arc_merge(hip):
@@ -342,8 +375,8 @@ def test_config3_per_gpu_shard_full_size_md5(hip, tmp_path):
 
 def test_config4_per_gpu_shard_full_size_md5(hip, tmp_path):
     """the per-GPU shard of BASELINE configs[4] (200 assemblies x ~110 k all-isoform proteins over 8 GPUs, -p0 -a1): 25 human-shaped
-    haplotypes x 20 k genes x 5.5 isoforms (~110 k proteins, ~2.8 M hits, genomes of ~110 k hits: beyond k_genome_sort's LDS budget,
-    so stage A's orders take the multi-workgroup radix sort): md5 of the GFA equal to the untouched reference's"""
+    haplotypes x 20 k genes x 5.5 isoforms (~110 k proteins, ~2.8 M hits, genomes of ~110 k hits: beyond the per-genome LDS sort's 25 600,
+    so stage A's orders take contig bins): md5 of the GFA equal to the untouched reference's"""
     e = _expected_large("human25x20k_iso5.5", "-p0 -a1")
     files = synth.write_files_parallel("human", str(tmp_path / "c4"), G=25, Q=20000, iso=5.5, seed=1, frag=True)
     hip.pg_set_exact_mode(1)
