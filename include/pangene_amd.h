@@ -191,6 +191,24 @@ void pg_call_opt_init(pg_call_opt_t *o);
 int  pg_call_file(const char *gfa_fn, const pg_call_opt_t *o);
 void pg_write_call(pg_graph_t *g, const pg_call_opt_t *o);
 
+/* Pangenome accumulation (rarefaction) curves: pan, core, new and unique genes as the assemblies are added in n_perm orders.  Genes
+ * are the rows and assemblies the columns of the gfa2matrix matrix, a gene counts as present where its entry is > 0.  Order 0 is
+ * the column order; order p >= 1 is a Fisher-Yates shuffle driven by splitmix64 seeded with (seed << 32) | p (README).  For the
+ * first k columns of an order: pan = genes present in at least one, core = in all, new = in the k-th and none before, unique = in
+ * exactly one.  The counting runs on the backend (pga_pan_curves).  Output: "Stat<TAB>Perm<TAB>1 ... n_asm", then one line
+ * "stat<TAB>p<TAB>v1 ..." per statistic and order: all pan lines (p = 0 .. n_perm-1), then core, new and unique.
+ * pg_write_curves: the graph in memory after pg_graph_gen (the matrix pg_write_matrix prints); pg_curves_file: a GFA file, plain or
+ * gzipped (returns 0, -1 when the file cannot be opened); pg_pan_curves: any presence matrix, row-major uint8 [n_gene][n_asm],
+ * out = int32 [4][n_perm][n_asm] (pan, core, new, unique); returns 0 or a PGA_ERR_* code. */
+typedef struct {
+	int32_t n_perm; /* orders, the input order first [10] */
+	uint32_t seed;  /* [11] */
+} pg_curves_opt_t;
+void pg_curves_opt_init(pg_curves_opt_t *o);
+void pg_write_curves(pg_graph_t *g, const pg_curves_opt_t *o);
+int  pg_curves_file(const char *gfa_fn, const pg_curves_opt_t *o);
+int  pg_pan_curves(const uint8_t *presence, int32_t n_gene, int32_t n_asm, const pg_curves_opt_t *o, int32_t *out);
+
 /* Last error of the path (0 = none).  The reference aborts on invariant violations; this library
  * records a status instead, prints one line to stderr, and leaves the graph empty. */
 int         pg_last_error(void);

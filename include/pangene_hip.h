@@ -94,7 +94,7 @@ typedef struct {
  * Device layout limits (PGA_ERR_RANGE otherwise): coordinates inside a block < 2^31 (contigs beyond that arrive as virtual contigs,
  * see pga_genome_block_t; what remains out of reach is a single cluster of overlapping hits spanning 2^30 bp), < 2^30 hits and < 2^31
  * exons per shard, < 2^20 genes, < 2^24 genomes. */
-#define PGA_ABI_VERSION 6u  /* bumped whenever a struct of this header or the order of pga_backend_t changes; pga_create refuses another */
+#define PGA_ABI_VERSION 7u  /* bumped whenever a struct of this header or the order of pga_backend_t changes; pga_create refuses another */
 typedef struct {
 	uint32_t abi_version;        /* = PGA_ABI_VERSION of the header the caller was compiled against (PGA_ERR_ARG otherwise) */
 	int32_t n_genome;            /* genomes in this shard (may include genomes with 0 hits) */
@@ -307,6 +307,19 @@ typedef struct {
 } pga_call_out_t;
 int pga_call_bubbles(const pga_call_in_t *in, pga_call_out_t *out);
 
+/* Pangenome accumulation curves (include/pangene_amd.h pg_pan_curves) over a gene x assembly presence matrix.  Context-free, like
+ * call_bubbles.  In:  bits[n_gene][(n_asm + 31) / 32], bit (a & 31) of word a >> 5 of row g = gene g present in column a (bits past
+ *      n_asm are ignored); order[n_perm][n_asm], each row a permutation of the columns, in the order they are added.
+ * Out: count[4][n_perm][n_asm]: for order p and k = 1 .. n_asm at [s][p][k - 1] the genes present in at least one of the first k
+ *      columns (s = 0, pan), in all of them (1, core), in column order[p][k - 1] and none before it (2, new), in exactly one of them
+ *      (3, unique).  The array belongs to the backend and stays valid until its next pan_curves. */
+typedef struct {
+	const uint32_t *bits; const int32_t *order;
+	int32_t n_gene, n_asm, n_perm;
+} pga_curves_in_t;
+typedef struct { const int32_t *count; } pga_curves_out_t;
+int pga_pan_curves(const pga_curves_in_t *in, pga_curves_out_t *out);
+
 /* the same ABI as a table, so the host driver is written once */
 struct pga_branch_par_s; struct pga_loop_xchg_s;
 typedef struct {
@@ -363,6 +376,7 @@ typedef struct {
 	int  (*stage)(const void *, size_t); /* may be NULL */
 	void (*stage_drop)(const void *);    /* may be NULL */
 	int  (*call_bubbles)(const pga_call_in_t *, pga_call_out_t *); /* may be NULL: the host driver then runs the same step itself */
+	int  (*pan_curves)(const pga_curves_in_t *, pga_curves_out_t *); /* may be NULL: the host driver then runs the same step itself */
 } pga_backend_t;
 
 const pga_backend_t *pga_backend(void);

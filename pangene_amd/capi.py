@@ -57,6 +57,50 @@ def call_opt(lib: C.CDLL, argv: Sequence[str] = ()) -> pg_call_opt_t:
     return o
 
 
+class pg_curves_opt_t(C.Structure):
+    """Accumulation-curve options (include/pangene_amd.h): orders (the input order first) and their seed."""
+    _fields_ = [("n_perm", C.c_int32), ("seed", C.c_uint32)]
+
+
+CURVE_STATS = ("pan", "core", "new", "unique")
+
+
+def curves_opt(lib: C.CDLL, n_perm: int | None = None, seed: int | None = None) -> pg_curves_opt_t:
+    o = pg_curves_opt_t()
+    lib.pg_curves_opt_init(C.byref(o))
+    if n_perm is not None: o.n_perm = n_perm
+    if seed is not None: o.seed = seed
+    return o
+
+
+def pan_curves(lib: C.CDLL, presence, n_perm: int = 10, seed: int = 11):
+    """Accumulation curves of a gene x assembly presence matrix (bool numpy array or torch tensor, shape (G, A)) through
+    pg_pan_curves: an int32 array (4, n_perm, A) of pan, core, new and unique genes after k = 1 .. A assemblies, per order."""
+    import numpy as np
+    if hasattr(presence, "detach"):  # torch tensor, on any device
+        presence = presence.detach().cpu().numpy()
+    p = np.ascontiguousarray(np.asarray(presence) != 0, dtype=np.uint8)
+    if p.ndim != 2:
+        raise ValueError("presence must be 2-D (genes x assemblies)")
+    G, A = p.shape
+    out = np.zeros((4, n_perm, A), dtype=np.int32)
+    o = curves_opt(lib, n_perm, seed)
+    rc = lib.pg_pan_curves(p.ctypes.data_as(C.POINTER(C.c_uint8)), G, A, C.byref(o), out.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc != 0:
+        raise RuntimeError("pg_pan_curves: status %d" % rc)
+    return out
+
+
+def _curves_args(argv: Sequence[str]):
+    """(orders, seed) of --curves[=INT] / --curves-seed=INT in argv; orders = 0 without --curves."""
+    n, seed = 0, 11
+    for a in argv:
+        if a == "--curves": n = 10
+        elif a.startswith("--curves="): n = int(a.split("=", 1)[1])
+        elif a.startswith("--curves-seed="): seed = int(a.split("=", 1)[1])
+    return n, seed
+
+
 _API = {
     "pg_opt_init": (None, [C.POINTER(pg_opt_t)]),
     "pg_data_init": (C.c_void_p, []),
@@ -76,6 +120,10 @@ _API = {
     "pg_call_opt_init": (None, [C.c_void_p]),
     "pg_call_file": (C.c_int, [C.c_char_p, C.c_void_p]),
     "pg_write_call": (None, [C.c_void_p, C.c_void_p]),
+    "pg_curves_opt_init": (None, [C.c_void_p]),
+    "pg_curves_file": (C.c_int, [C.c_char_p, C.c_void_p]),
+    "pg_write_curves": (None, [C.c_void_p, C.c_void_p]),
+    "pg_pan_curves": (C.c_int, [C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]),
     "pg_read_list_dict": (C.c_void_p, [C.c_char_p]),
     "pg_dict_destroy": (None, [C.c_void_p]),
     "pg_last_error": (C.c_int, []),
@@ -141,7 +189,7 @@ def parse_args(lib: C.CDLL, argv: Sequence[str]) -> pg_opt_t:
         elif a in ("--bed", "--bed=walk"): opt.flag |= PG_F_WRITE_BED_WALK
         elif a == "--bed=raw": opt.flag |= PG_F_WRITE_BED_RAW
         elif a == "--bed=flag": opt.flag |= PG_F_WRITE_BED_FLAG
-        elif a in ("--matrix", "--matrix=presence", "--matrix=count", "--call"): pass  # handled by run()
+        elif a in ("--matrix", "--matrix=presence", "--matrix=count", "--call") or a.startswith("--curves"): pass  # handled by run()
         elif a[:2] in ("-p", "-a", "-f", "-c", "-g", "-r", "-b", "-B", "-y", "-T", "-D", "-C", "-e", "-l", "-m", "-d", "-X", "-I", "-P"):
             v = a[2:] if len(a) > 2 else next(it)
             k = a[1]
@@ -186,6 +234,9 @@ def read_files(lib: C.CDLL, opt, d, files: Sequence[str], scan_only: Sequence[bo
 def run(lib: C.CDLL, files: Sequence[str], argv: Sequence[str] = (), scan_only: Sequence[bool] | None = None, batch: bool = True) -> bytes:
     """main.c:117-142 in-process: returns what the command line would print to stdout."""
     opt = parse_args(lib, argv)
+    n_curves, curves_seed = _curves_args(argv)
+    if n_curves and (any(x.startswith("--matrix") for x in argv) or "--call" in argv):
+        raise ValueError("--curves cannot be combined with --matrix or --call")
     fd, out = tempfile.mkstemp(prefix="pangene_", suffix=".out")
     os.close(fd)
     lib.pg_set_output(out.encode())
@@ -207,6 +258,10 @@ def run(lib: C.CDLL, files: Sequence[str], argv: Sequence[str] = (), scan_only: 
                 co = pg_call_opt_t()
                 lib.pg_call_opt_init(C.byref(co))
                 lib.pg_write_call(g, C.byref(co))
+                if lib.pg_last_error():
+                    raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
+            elif n_curves:
+                lib.pg_write_curves(g, C.byref(curves_opt(lib, n_curves, curves_seed)))
                 if lib.pg_last_error():
                     raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
             elif opt.flag & PG_F_WRITE_BED_WALK: lib.pg_write_bed(d, 1)

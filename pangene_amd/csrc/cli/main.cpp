@@ -52,8 +52,11 @@ static int usage(FILE *fp, const pg_opt_t *opt)
 	std::fprintf(fp, "    --gpus=INT    shard the genomes over INT GPUs of this node: one process per device, RCCL over xGMI [1]\n");
 	std::fprintf(fp, "    --version     print version number\n");
 	std::fprintf(fp, "    --call        output the bubbles and alleles of pangene.js call (default options) instead of the graph\n");
+	std::fprintf(fp, "    --curves[=INT] output pan/core/new/unique accumulation curves over INT orders of the assemblies [10]\n");
+	std::fprintf(fp, "    --curves-seed=INT  seed of the orders of --curves [11]\n");
 	std::fprintf(fp, "  Also: pangene gfa2matrix [-c] [-d FILE] [-p] <in.gfa>   (pangene.js gfa2matrix on a GFA file)\n");
 	std::fprintf(fp, "        pangene call [-m INT] [-w] [-b] [-e] [-d] [-p] [-s] [-r STR] <in.gfa>   (pangene.js call on a GFA file)\n");
+	std::fprintf(fp, "        pangene curves [-n INT] [-s INT] <in.gfa>   (accumulation curves of the gfa2matrix matrix of a GFA file)\n");
 	return fp == stdout ? 0 : 1;
 }
 
@@ -120,6 +123,26 @@ static int main_call(int argc, char *argv[])
 	return pg_call_file(argv[optind], &o) == 0 ? 0 : 1;
 }
 
+// `pangene curves`: pan / core / new / unique accumulation curves of the matrix `pangene gfa2matrix` prints for the same GFA
+static int main_curves(int argc, char *argv[])
+{
+	pg_curves_opt_t o;
+	pg_curves_opt_init(&o);
+	int c;
+	while ((c = getopt(argc, argv, "n:s:")) >= 0) {
+		if (c == 'n') o.n_perm = std::atoi(optarg);
+		else if (c == 's') o.seed = (uint32_t)std::strtoul(optarg, nullptr, 10);
+		else return 1;
+	}
+	if (o.n_perm < 1) { std::fprintf(stderr, "ERROR: -n must be at least 1\n"); return 1; }
+	if (argc - optind < 1) {
+		std::printf("Usage: pangene curves [options] <in.gfa>\nOptions:\n  -n INT   orders of the assemblies, the input order first [%d]\n"
+		            "  -s INT   seed of the random orders [%u]\n", o.n_perm, o.seed);
+		return 0;
+	}
+	return pg_curves_file(argv[optind], &o) == 0 ? 0 : 1;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // `pangene --gpus N`: main.c:117-142 for N devices of one node.  The command forks N - 1 workers BEFORE anything touches the GPU;
 // rank r takes device r and the r-th contiguous block of the PAF files (so that the ranks' W / BED lines, concatenated in rank
@@ -128,7 +151,7 @@ static int main_call(int argc, char *argv[])
 // tests) it is a shared-memory region mapped before the fork.  Rank 0 prints the graph; every rank writes the lines of its own
 // genomes to a temporary file that rank 0 copies to stdout in rank order.
 // ---------------------------------------------------------------------------------------------------------------
-struct Output { int matrix = 0; bool call = false; };
+struct Output { int matrix = 0; bool call = false; int curves = 0; uint32_t curves_seed = 11; }; // curves: orders (0: none)
 
 static int run_path(pg_opt_t &opt, int n_files, char **files, const uint8_t *ids_only, const Output &o, bool graph_lines, bool own_lines, int device = -1)
 {
@@ -159,6 +182,13 @@ static int run_path(pg_opt_t &opt, int n_files, char **files, const uint8_t *ids
 		if (pg_last_error()) rc = 2;
 		else if (o.matrix) pg_write_matrix(g, o.matrix == 2);
 		else if (o.call) { pg_call_opt_t co; pg_call_opt_init(&co); pg_write_call(g, &co); if (pg_last_error()) rc = 2; }
+		else if (o.curves) {
+			pg_curves_opt_t co;
+			pg_curves_opt_init(&co);
+			co.n_perm = o.curves, co.seed = o.curves_seed;
+			pg_write_curves(g, &co);
+			if (pg_last_error()) rc = 2;
+		}
 		else if (opt.flag & PG_F_WRITE_BED_WALK) { if (own_lines) pg_write_bed(d, 1); }
 		else if (opt.flag & PG_F_WRITE_BED_FLAG) { if (own_lines) pg_write_bed(d, 0); }
 		else {
@@ -218,6 +248,7 @@ static int run_sharded(pg_opt_t &opt, int W, int n_files, char **files, const Ou
 {
 	if (o.matrix) { std::fprintf(stderr, "ERROR: --matrix needs every genome in one process; run it without --gpus\n"); return 1; }
 	if (o.call) { std::fprintf(stderr, "ERROR: --call needs every genome in one process; run it without --gpus\n"); return 1; }
+	if (o.curves) { std::fprintf(stderr, "ERROR: --curves needs every genome in one process; run it without --gpus\n"); return 1; }
 	const bool dev = pg_backend_is_device() != 0;
 	typedef int (*uid_fn)(void *); typedef int (*init_fn)(int32_t, int32_t, const void *); typedef int (*fin_fn)(void);
 	uid_fn rccl_uid = nullptr; init_fn rccl_init = nullptr; fin_fn rccl_fin = nullptr;
@@ -359,10 +390,14 @@ int main(int argc, char *argv[])
 {
 	if (argc >= 2 && std::strcmp(argv[1], "gfa2matrix") == 0) return main_gfa2matrix(argc - 1, argv + 1);
 	if (argc >= 2 && std::strcmp(argv[1], "call") == 0) return main_call(argc - 1, argv + 1);
+	if (argc >= 2 && std::strcmp(argv[1], "curves") == 0) return main_curves(argc - 1, argv + 1);
 	int matrix = 0, n_gpus = 1; // matrix: 1 presence, 2 counts
 	bool call = false;
+	int curves = 0; // orders of --curves (0: not asked for)
+	uint32_t curves_seed = 11;
 	static const struct option lopts[] = {
 		{ "bed", optional_argument, nullptr, 301 }, { "ori-sc", no_argument, nullptr, 302 }, { "matrix", optional_argument, nullptr, 303 }, { "call", no_argument, nullptr, 305 },
+		{ "curves", optional_argument, nullptr, 306 }, { "curves-seed", required_argument, nullptr, 307 },
 		{ "gpus", required_argument, nullptr, 304 }, { "procs", required_argument, nullptr, 304 },
 		{ "version", no_argument, nullptr, 401 }, { nullptr, 0, nullptr, 0 } };
 	pg_opt_t opt;
@@ -407,12 +442,19 @@ int main(int argc, char *argv[])
 		case 303: matrix = (optarg && std::strcmp(optarg, "count") == 0) ? 2 : 1; break;
 		case 304: n_gpus = std::atoi(optarg); break;
 		case 305: call = true; break;
+		case 306:
+			curves = optarg ? std::atoi(optarg) : 10;
+			if (curves < 1) { std::fprintf(stderr, "ERROR: --curves needs at least one order\n"); return 1; }
+			break;
+		case 307: curves_seed = (uint32_t)std::strtoul(optarg, nullptr, 10); break;
 		case 401: std::puts(PG_VERSION); return 0;
 		default: break;
 		}
 	}
 	if (argc - optind < 1) return usage(stderr, &opt);
+	if (curves && (matrix || call)) { std::fprintf(stderr, "ERROR: --curves cannot be combined with --matrix or --call\n"); return 1; }
 	Output o;
+	o.curves = curves, o.curves_seed = curves_seed;
 	o.matrix = matrix;
 	o.call = call;
 	int rc;

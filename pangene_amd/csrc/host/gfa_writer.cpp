@@ -332,22 +332,21 @@ int walk_lists(pg_graph_t *q, std::vector<std::string> &asm_name, std::vector<in
 
 } // namespace pgx
 
-extern "C" {
+namespace pgx {
 
-// pangene.js gfa2matrix (pangene.js:1168-1247) straight from the graph in memory: rows = segments in S-line order, columns =
-// sample#haplotype in the order the W-lines would introduce them, entry = presence (or, copy_number != 0, the number of
-// occurrences) of the segment in the walks of that assembly.  The per-hit reduction runs on the backend (pga_gene_matrix).
-void pg_write_matrix(pg_graph_t *q, int32_t copy_number)
+// the matrix of pg_write_matrix: names[n_asm] = sample#haplotype of the columns, mat[n_seg * n_asm] = occurrences; 0, or -1 with the
+// error recorded
+int graph_matrix(pg_graph_t *q, std::vector<std::string> &names, std::vector<int32_t> &mat)
 {
 	pg_data_t *d = q->d;
 	DataExt *ext = ext_of(d, false);
-	if (ext == nullptr || ext->ctx == nullptr) { set_error(PGA_ERR_ARG, "pg_write_matrix: pg_graph_gen has not run on this data set"); return; }
+	if (ext == nullptr || ext->ctx == nullptr) { set_error(PGA_ERR_ARG, "pg_write_matrix: pg_graph_gen has not run on this data set"); return -1; }
 	// the backend counts per contig AS IT SEES THEM (pieces of virtual contigs, pga_genome_block_t): v_of[] = its numbering
 	size_t n_ctg = 0, n_v = 0;
 	for (size_t k = 0; k < ext->local_genomes.size(); ++k) n_ctg += (size_t)d->genome[ext->local_genomes[k]].n_ctg, n_v += (size_t)(k < ext->n_vctg.size() ? ext->n_vctg[k] : d->genome[ext->local_genomes[k]].n_ctg);
 	std::vector<int32_t> vcnt(n_v + 1, 0), cnt(n_ctg + 1, 0), col(n_ctg + 1, -1), real_of(n_v + 1, 0);
 	int rc = ext->be->ctg_counts(ext->ctx, vcnt.data());
-	if (rc != 0) { set_error(rc, "ctg_counts"); return; }
+	if (rc != 0) { set_error(rc, "ctg_counts"); return -1; }
 	{
 		size_t rb = 0, vb = 0;
 		for (size_t kk = 0; kk < ext->local_genomes.size(); ++kk) {
@@ -357,7 +356,6 @@ void pg_write_matrix(pg_graph_t *q, int32_t copy_number)
 			rb += (size_t)nr, vb += (size_t)nv;
 		}
 	}
-	std::vector<std::string> names;
 	std::unordered_map<std::string, int32_t> idx;
 	std::string sample, key;
 	size_t k = 0;
@@ -376,11 +374,67 @@ void pg_write_matrix(pg_graph_t *q, int32_t copy_number)
 		}
 	}
 	const int32_t n_asm = (int32_t)names.size();
-	std::vector<int32_t> mat((size_t)q->n_seg * (size_t)n_asm + 1, 0);
+	mat.assign((size_t)q->n_seg * (size_t)n_asm + 1, 0);
 	std::vector<int32_t> vcol(n_v + 1, -1); // column of every contig as the backend numbers them
 	for (size_t v = 0; v < n_v; ++v) vcol[v] = col[(size_t)real_of[v]];
 	rc = ext->be->gene_matrix(ext->ctx, vcol.data(), n_asm, q->n_seg, mat.data());
-	if (rc != 0) { set_error(rc, "gene_matrix"); return; }
+	if (rc != 0) { set_error(rc, "gene_matrix"); return -1; }
+	return 0;
+}
+
+// pangene.js gfa2matrix's reading of a GFA (pangene.js:1168-1247 with the parser at 131-197): segments in the order S- and L-lines
+// introduce them, walk steps whose name is not a segment yet are ignored, assemblies = "sample#hap" of the W-lines in first-seen
+// order; mat[seg * n_asm + asm] = occurrences.  Plain or gzipped input.  0, or -1 when the file cannot be opened.
+int gfa_matrix(const char *fn, GfaMatrix &m)
+{
+	std::vector<std::string> lines;
+	if (read_lines(fn, lines) != 0) return -1;
+	std::vector<std::string> &seg = m.seg, &asm_a = m.asm_a;
+	std::unordered_map<std::string, int32_t> &seg_h = m.seg_h, asm_h;
+	std::vector<std::pair<int32_t, int32_t>> walk; // (assembly, segment) of every walk step
+	auto seg_add = [&](const std::string &n) { auto it = seg_h.find(n); if (it == seg_h.end()) it = seg_h.emplace(n, (int32_t)seg.size()).first, seg.push_back(n); return it->second; };
+	auto split = [](const std::string &l, std::vector<std::string> &t) { t.clear(); size_t b = 0; for (;;) { size_t e = l.find('\t', b); t.push_back(l.substr(b, e == std::string::npos ? e : e - b)); if (e == std::string::npos) break; b = e + 1; } };
+	std::vector<std::string> t;
+	for (const std::string &l : lines) {
+		if (l.empty()) continue;
+		if (l[0] == 'S') { split(l, t); if (t.size() >= 3) seg_add(t[1]); }
+		else if (l[0] == 'L') { split(l, t); if (t.size() >= 5 && (t[2] == "+" || t[2] == "-") && (t[4] == "+" || t[4] == "-")) seg_add(t[1]), seg_add(t[3]); }
+		else if (l[0] == 'W') {
+			split(l, t);
+			if (t.size() < 7) continue;
+			const std::string a = t[1] + "#" + t[2];
+			auto it = asm_h.find(a);
+			if (it == asm_h.end()) it = asm_h.emplace(a, (int32_t)asm_a.size()).first, asm_a.push_back(a);
+			const std::string &w = t[6];
+			for (size_t i = 0; i < w.size();) { // ([><])([^\s><]+)
+				if (w[i] != '>' && w[i] != '<') { ++i; continue; }
+				size_t e = i + 1;
+				while (e < w.size() && w[e] != '>' && w[e] != '<' && !std::isspace((unsigned char)w[e])) ++e;
+				if (e > i + 1) { auto sit = seg_h.find(w.substr(i + 1, e - i - 1)); if (sit != seg_h.end()) walk.emplace_back(it->second, sit->second); }
+				i = e;
+			}
+		}
+	}
+	const size_t n_asm = asm_a.size();
+	m.mat.assign(seg.size() * n_asm + 1, 0);
+	for (const auto &st : walk) ++m.mat[(size_t)st.second * n_asm + (size_t)st.first];
+	return 0;
+}
+
+} // namespace pgx
+
+extern "C" {
+
+// pangene.js gfa2matrix (pangene.js:1168-1247) straight from the graph in memory: rows = segments in S-line order, columns =
+// sample#haplotype in the order the W-lines would introduce them, entry = presence (or, copy_number != 0, the number of
+// occurrences) of the segment in the walks of that assembly.  The per-hit reduction runs on the backend (pga_gene_matrix).
+void pg_write_matrix(pg_graph_t *q, int32_t copy_number)
+{
+	std::vector<std::string> names;
+	std::vector<int32_t> mat;
+	if (graph_matrix(q, names, mat) != 0) return;
+	const pg_data_t *d = q->d;
+	const int32_t n_asm = (int32_t)names.size();
 	FILE *fp = out_stream();
 	std::string o = "Gene\t";
 	for (int32_t a = 0; a < n_asm; ++a) { if (a) o += '\t'; o += names[(size_t)a]; }
@@ -407,37 +461,12 @@ void pg_write_matrix(pg_graph_t *q, int32_t copy_number)
 // input.  Returns 0, or -1 when a file cannot be opened.
 int pg_gfa2matrix_file(const char *gfa_fn, int32_t copy_number, const char *clstr_fn, int32_t print_cd)
 {
-	std::vector<std::string> lines;
-	if (read_lines(gfa_fn, lines) != 0) return -1;
-	std::vector<std::string> seg, asm_a;
-	std::unordered_map<std::string, int32_t> seg_h, asm_h;
-	std::vector<std::pair<int32_t, int32_t>> walk; // (assembly, segment) of every walk step
-	auto seg_add = [&](const std::string &n) { auto it = seg_h.find(n); if (it == seg_h.end()) it = seg_h.emplace(n, (int32_t)seg.size()).first, seg.push_back(n); return it->second; };
-	auto split = [](const std::string &l, std::vector<std::string> &t) { t.clear(); size_t b = 0; for (;;) { size_t e = l.find('\t', b); t.push_back(l.substr(b, e == std::string::npos ? e : e - b)); if (e == std::string::npos) break; b = e + 1; } };
-	std::vector<std::string> t;
-	for (const std::string &l : lines) {
-		if (l.empty()) continue;
-		if (l[0] == 'S') { split(l, t); if (t.size() >= 3) seg_add(t[1]); }
-		else if (l[0] == 'L') { split(l, t); if (t.size() >= 5 && (t[2] == "+" || t[2] == "-") && (t[4] == "+" || t[4] == "-")) seg_add(t[1]), seg_add(t[3]); }
-		else if (l[0] == 'W') {
-			split(l, t);
-			if (t.size() < 7) continue;
-			const std::string a = t[1] + "#" + t[2];
-			auto it = asm_h.find(a);
-			if (it == asm_h.end()) it = asm_h.emplace(a, (int32_t)asm_a.size()).first, asm_a.push_back(a);
-			const std::string &w = t[6];
-			for (size_t i = 0; i < w.size();) { // ([><])([^\s><]+)
-				if (w[i] != '>' && w[i] != '<') { ++i; continue; }
-				size_t e = i + 1;
-				while (e < w.size() && w[e] != '>' && w[e] != '<' && !std::isspace((unsigned char)w[e])) ++e;
-				if (e > i + 1) { auto sit = seg_h.find(w.substr(i + 1, e - i - 1)); if (sit != seg_h.end()) walk.emplace_back(it->second, sit->second); }
-				i = e;
-			}
-		}
-	}
+	GfaMatrix m;
+	if (gfa_matrix(gfa_fn, m) != 0) return -1;
+	const std::vector<std::string> &seg = m.seg, &asm_a = m.asm_a;
+	const std::unordered_map<std::string, int32_t> &seg_h = m.seg_h;
+	std::vector<int32_t> &mat = m.mat;
 	const size_t n_asm = asm_a.size();
-	std::vector<int32_t> mat(seg.size() * n_asm + 1, 0);
-	for (const auto &st : walk) ++mat[(size_t)st.second * n_asm + (size_t)st.first];
 	std::unordered_map<std::string, std::string> paralog;
 	std::vector<std::string> paralog_order;
 	FILE *fp = out_stream();

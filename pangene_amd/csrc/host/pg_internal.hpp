@@ -220,6 +220,10 @@ void set_error(int code, const char *where);
 
 FILE *out_stream();
 int read_lines(const char *fn, std::vector<std::string> &out); // every line of a plain or gzipped text file, terminators removed
+// the gene x assembly matrix of gfa2matrix (gfa_writer.cpp): of the graph in memory (pg_write_matrix) and of a GFA file
+int graph_matrix(pg_graph_t *q, std::vector<std::string> &names, std::vector<int32_t> &mat);
+struct GfaMatrix { std::vector<std::string> seg, asm_a; std::unordered_map<std::string, int32_t> seg_h; std::vector<int32_t> mat; };
+int gfa_matrix(const char *fn, GfaMatrix &m);
 
 double now_sec();
 const char *stamp();
