@@ -209,6 +209,28 @@ void pg_write_curves(pg_graph_t *g, const pg_curves_opt_t *o);
 int  pg_curves_file(const char *gfa_fn, const pg_curves_opt_t *o);
 int  pg_pan_curves(const uint8_t *presence, int32_t n_gene, int32_t n_asm, const pg_curves_opt_t *o, int32_t *out);
 
+/* Pairwise distances of the assemblies.  Each assembly is a set of items: its genes (type PG_DIST_GENE: the gfa2matrix entry is > 0)
+ * or the gene adjacencies its walks traverse (PG_DIST_ADJ: consecutive steps (u, v) of one W-line, steps = segment * 2 + reverse,
+ * unknown segments dropped, key min((u, v), (v ^ 1, u ^ 1)) so that >a>b and <b<a are one adjacency).  S[i][j] = items shared by i
+ * and j (the backend's pga_pan_shared); with n_i = S[i][i]: jaccard = 1 - S[i][j] / (n_i + n_j - S[i][j]) (0 when the union is
+ * empty, printed %.6f), shared = S[i][j], diff = n_i + n_j - 2 S[i][j].  Columns in gfa2matrix order and names (sample#hap).
+ * Output, tab-separated: "Asm" and the names, then per assembly its name and its row; phylip: the count on the first line and the
+ * rows without the header.  pg_dist_file: a GFA file, plain or gzipped (0, -1 when it cannot be opened, -2 on a backend error);
+ * pg_write_dist: the graph in memory after pg_graph_gen; pg_pan_shared: any presence matrix, row-major uint8 [n_item][n_asm],
+ * shared = int32 [n_asm][n_asm]; pg_pan_dist: the same, out = double [n_asm][n_asm] of the metric; both return 0 or PGA_ERR_*. */
+enum { PG_DIST_GENE = 0, PG_DIST_ADJ = 1 };
+enum { PG_DIST_JACCARD = 0, PG_DIST_SHARED = 1, PG_DIST_DIFF = 2 };
+typedef struct {
+	int32_t type;   /* PG_DIST_GENE or PG_DIST_ADJ [gene] */
+	int32_t metric; /* PG_DIST_JACCARD, PG_DIST_SHARED or PG_DIST_DIFF [jaccard] */
+	int32_t phylip; /* relaxed PHYLIP layout [0] */
+} pg_dist_opt_t;
+void pg_dist_opt_init(pg_dist_opt_t *o);
+int  pg_dist_file(const char *gfa_fn, const pg_dist_opt_t *o);
+void pg_write_dist(pg_graph_t *g, const pg_dist_opt_t *o);
+int  pg_pan_shared(const uint8_t *presence, int32_t n_item, int32_t n_asm, int32_t *shared);
+int  pg_pan_dist(const uint8_t *presence, int32_t n_item, int32_t n_asm, int32_t metric, double *out);
+
 /* Last error of the path (0 = none).  The reference aborts on invariant violations; this library
  * records a status instead, prints one line to stderr, and leaves the graph empty. */
 int         pg_last_error(void);

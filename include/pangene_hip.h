@@ -94,7 +94,7 @@ typedef struct {
  * Device layout limits (PGA_ERR_RANGE otherwise): coordinates inside a block < 2^31 (contigs beyond that arrive as virtual contigs,
  * see pga_genome_block_t; what remains out of reach is a single cluster of overlapping hits spanning 2^30 bp), < 2^30 hits and < 2^31
  * exons per shard, < 2^20 genes, < 2^24 genomes. */
-#define PGA_ABI_VERSION 7u  /* bumped whenever a struct of this header or the order of pga_backend_t changes; pga_create refuses another */
+#define PGA_ABI_VERSION 8u  /* bumped whenever a struct of this header or the order of pga_backend_t changes; pga_create refuses another */
 typedef struct {
 	uint32_t abi_version;        /* = PGA_ABI_VERSION of the header the caller was compiled against (PGA_ERR_ARG otherwise) */
 	int32_t n_genome;            /* genomes in this shard (may include genomes with 0 hits) */
@@ -320,6 +320,18 @@ typedef struct {
 typedef struct { const int32_t *count; } pga_curves_out_t;
 int pga_pan_curves(const pga_curves_in_t *in, pga_curves_out_t *out);
 
+/* Pairwise shared items of assemblies (include/pangene_amd.h pg_pan_shared, pangene dist).  Context-free, like pan_curves.
+ * In:  bits[n_asm][(n_item + 31) / 32], assembly-major: bit (m & 31) of word m >> 5 of row a = item m is in assembly a; bits past
+ *      n_item are zero (the kernel counts them).
+ * Out: shared[n_asm][n_asm] = popcount(B_i & B_j), full and symmetric, the diagonal = |B_a|.  The array belongs to the backend and
+ *      stays valid until its next pan_shared.  n_asm <= 65 535 (PGA_ERR_RANGE otherwise). */
+typedef struct {
+	const uint32_t *bits;
+	int32_t n_item, n_asm;
+} pga_shared_in_t;
+typedef struct { const int32_t *shared; } pga_shared_out_t;
+int pga_pan_shared(const pga_shared_in_t *in, pga_shared_out_t *out);
+
 /* the same ABI as a table, so the host driver is written once */
 struct pga_branch_par_s; struct pga_loop_xchg_s;
 typedef struct {
@@ -377,6 +389,7 @@ typedef struct {
 	void (*stage_drop)(const void *);    /* may be NULL */
 	int  (*call_bubbles)(const pga_call_in_t *, pga_call_out_t *); /* may be NULL: the host driver then runs the same step itself */
 	int  (*pan_curves)(const pga_curves_in_t *, pga_curves_out_t *); /* may be NULL: the host driver then runs the same step itself */
+	int  (*pan_shared)(const pga_shared_in_t *, pga_shared_out_t *); /* may be NULL: the host driver then runs the same step itself */
 } pga_backend_t;
 
 const pga_backend_t *pga_backend(void);

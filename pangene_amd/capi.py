@@ -101,6 +101,73 @@ def _curves_args(argv: Sequence[str]):
     return n, seed
 
 
+class pg_dist_opt_t(C.Structure):
+    """Distance options (include/pangene_amd.h): items (PG_DIST_GENE / PG_DIST_ADJ), metric, PHYLIP layout."""
+    _fields_ = [("type", C.c_int32), ("metric", C.c_int32), ("phylip", C.c_int32)]
+
+
+DIST_TYPES = ("gene", "adj")
+DIST_METRICS = ("jaccard", "shared", "diff")
+
+
+def dist_opt(lib: C.CDLL, type: str = "gene", metric: str = "jaccard", phylip: bool = False) -> pg_dist_opt_t:
+    o = pg_dist_opt_t()
+    lib.pg_dist_opt_init(C.byref(o))
+    o.type, o.metric, o.phylip = DIST_TYPES.index(type), DIST_METRICS.index(metric), int(bool(phylip))
+    return o
+
+
+def _presence(presence):
+    """(items, assemblies) numpy array or torch tensor -> contiguous uint8 0/1"""
+    import numpy as np
+    if hasattr(presence, "detach"):  # torch tensor, on any device
+        presence = presence.detach().cpu().numpy()
+    p = np.ascontiguousarray(np.asarray(presence) != 0, dtype=np.uint8)
+    if p.ndim != 2:
+        raise ValueError("presence must be 2-D (items x assemblies)")
+    return p
+
+
+def pan_shared(lib: C.CDLL, presence):
+    """Items shared by every pair of assemblies of an item x assembly presence matrix (bool numpy array or torch tensor, shape (M, A))
+    through pg_pan_shared: an int32 array (A, A), the diagonal = the items of each assembly."""
+    import numpy as np
+    p = _presence(presence)
+    M, A = p.shape
+    out = np.zeros((A, A), dtype=np.int32)
+    rc = lib.pg_pan_shared(p.ctypes.data_as(C.POINTER(C.c_uint8)), M, A, out.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc != 0:
+        raise RuntimeError("pg_pan_shared: status %d" % rc)
+    return out
+
+
+def pan_dist(lib: C.CDLL, presence, metric: str = "jaccard"):
+    """Pairwise distances of the assemblies of a presence matrix through pg_pan_dist: (A, A), float64 for jaccard, int64 for shared
+    and diff."""
+    import numpy as np
+    p = _presence(presence)
+    M, A = p.shape
+    out = np.zeros((A, A), dtype=np.float64)
+    rc = lib.pg_pan_dist(p.ctypes.data_as(C.POINTER(C.c_uint8)), M, A, DIST_METRICS.index(metric), out.ctypes.data_as(C.POINTER(C.c_double)))
+    if rc != 0:
+        raise RuntimeError("pg_pan_dist: status %d" % rc)
+    return out if metric == "jaccard" else out.astype(np.int64)
+
+
+def _dist_args(argv: Sequence[str]):
+    """(type, metric) of --dist[=gene|adj] / --dist-metric=STR in argv; type = None without --dist."""
+    t, m = None, "jaccard"
+    for a in argv:
+        if a == "--dist": t = "gene"
+        elif a.startswith("--dist="): t = a.split("=", 1)[1]
+        elif a.startswith("--dist-metric="): m = a.split("=", 1)[1]
+    if t is not None and t not in DIST_TYPES:
+        raise ValueError("--dist must be gene or adj")
+    if m not in DIST_METRICS:
+        raise ValueError("--dist-metric must be jaccard, shared or diff")
+    return t, m
+
+
 _API = {
     "pg_opt_init": (None, [C.POINTER(pg_opt_t)]),
     "pg_data_init": (C.c_void_p, []),
@@ -124,6 +191,11 @@ _API = {
     "pg_curves_file": (C.c_int, [C.c_char_p, C.c_void_p]),
     "pg_write_curves": (None, [C.c_void_p, C.c_void_p]),
     "pg_pan_curves": (C.c_int, [C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]),
+    "pg_dist_opt_init": (None, [C.c_void_p]),
+    "pg_dist_file": (C.c_int, [C.c_char_p, C.c_void_p]),
+    "pg_write_dist": (None, [C.c_void_p, C.c_void_p]),
+    "pg_pan_shared": (C.c_int, [C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    "pg_pan_dist": (C.c_int, [C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double)]),
     "pg_read_list_dict": (C.c_void_p, [C.c_char_p]),
     "pg_dict_destroy": (None, [C.c_void_p]),
     "pg_last_error": (C.c_int, []),
@@ -189,7 +261,7 @@ def parse_args(lib: C.CDLL, argv: Sequence[str]) -> pg_opt_t:
         elif a in ("--bed", "--bed=walk"): opt.flag |= PG_F_WRITE_BED_WALK
         elif a == "--bed=raw": opt.flag |= PG_F_WRITE_BED_RAW
         elif a == "--bed=flag": opt.flag |= PG_F_WRITE_BED_FLAG
-        elif a in ("--matrix", "--matrix=presence", "--matrix=count", "--call") or a.startswith("--curves"): pass  # handled by run()
+        elif a in ("--matrix", "--matrix=presence", "--matrix=count", "--call") or a.startswith("--curves") or a.startswith("--dist"): pass  # handled by run()
         elif a[:2] in ("-p", "-a", "-f", "-c", "-g", "-r", "-b", "-B", "-y", "-T", "-D", "-C", "-e", "-l", "-m", "-d", "-X", "-I", "-P"):
             v = a[2:] if len(a) > 2 else next(it)
             k = a[1]
@@ -237,6 +309,9 @@ def run(lib: C.CDLL, files: Sequence[str], argv: Sequence[str] = (), scan_only: 
     n_curves, curves_seed = _curves_args(argv)
     if n_curves and (any(x.startswith("--matrix") for x in argv) or "--call" in argv):
         raise ValueError("--curves cannot be combined with --matrix or --call")
+    dist_type, dist_metric = _dist_args(argv)
+    if dist_type is not None and (any(x.startswith("--matrix") for x in argv) or "--call" in argv or n_curves):
+        raise ValueError("--dist cannot be combined with --matrix, --call or --curves")
     fd, out = tempfile.mkstemp(prefix="pangene_", suffix=".out")
     os.close(fd)
     lib.pg_set_output(out.encode())
@@ -262,6 +337,10 @@ def run(lib: C.CDLL, files: Sequence[str], argv: Sequence[str] = (), scan_only: 
                     raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
             elif n_curves:
                 lib.pg_write_curves(g, C.byref(curves_opt(lib, n_curves, curves_seed)))
+                if lib.pg_last_error():
+                    raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
+            elif dist_type is not None:
+                lib.pg_write_dist(g, C.byref(dist_opt(lib, dist_type, dist_metric)))
                 if lib.pg_last_error():
                     raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
             elif opt.flag & PG_F_WRITE_BED_WALK: lib.pg_write_bed(d, 1)

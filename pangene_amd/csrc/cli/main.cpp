@@ -54,9 +54,12 @@ static int usage(FILE *fp, const pg_opt_t *opt)
 	std::fprintf(fp, "    --call        output the bubbles and alleles of pangene.js call (default options) instead of the graph\n");
 	std::fprintf(fp, "    --curves[=INT] output pan/core/new/unique accumulation curves over INT orders of the assemblies [10]\n");
 	std::fprintf(fp, "    --curves-seed=INT  seed of the orders of --curves [11]\n");
+	std::fprintf(fp, "    --dist[=STR]  output pairwise distances of the assemblies over gene content (gene) or gene adjacencies (adj) [gene]\n");
+	std::fprintf(fp, "    --dist-metric=STR  metric of --dist: jaccard, shared or diff [jaccard]\n");
 	std::fprintf(fp, "  Also: pangene gfa2matrix [-c] [-d FILE] [-p] <in.gfa>   (pangene.js gfa2matrix on a GFA file)\n");
 	std::fprintf(fp, "        pangene call [-m INT] [-w] [-b] [-e] [-d] [-p] [-s] [-r STR] <in.gfa>   (pangene.js call on a GFA file)\n");
 	std::fprintf(fp, "        pangene curves [-n INT] [-s INT] <in.gfa>   (accumulation curves of the gfa2matrix matrix of a GFA file)\n");
+	std::fprintf(fp, "        pangene dist [-t gene|adj] [-m jaccard|shared|diff] [-p] <in.gfa>   (pairwise distances of the assemblies of a GFA file)\n");
 	return fp == stdout ? 0 : 1;
 }
 
@@ -143,6 +146,32 @@ static int main_curves(int argc, char *argv[])
 	return pg_curves_file(argv[optind], &o) == 0 ? 0 : 1;
 }
 
+static int dist_type(const char *s) { return std::strcmp(s, "gene") == 0 ? PG_DIST_GENE : std::strcmp(s, "adj") == 0 ? PG_DIST_ADJ : -1; }
+static int dist_metric(const char *s)
+{
+	return std::strcmp(s, "jaccard") == 0 ? PG_DIST_JACCARD : std::strcmp(s, "shared") == 0 ? PG_DIST_SHARED : std::strcmp(s, "diff") == 0 ? PG_DIST_DIFF : -1;
+}
+
+// `pangene dist`: pairwise distances of the assemblies of a GFA file over their genes or their gene adjacencies
+static int main_dist(int argc, char *argv[])
+{
+	pg_dist_opt_t o;
+	pg_dist_opt_init(&o);
+	int c;
+	while ((c = getopt(argc, argv, "t:m:p")) >= 0) {
+		if (c == 't') { if ((o.type = dist_type(optarg)) < 0) { std::fprintf(stderr, "ERROR: -t must be gene or adj\n"); return 1; } }
+		else if (c == 'm') { if ((o.metric = dist_metric(optarg)) < 0) { std::fprintf(stderr, "ERROR: -m must be jaccard, shared or diff\n"); return 1; } }
+		else if (c == 'p') o.phylip = 1;
+		else return 1;
+	}
+	if (argc - optind < 1) {
+		std::printf("Usage: pangene dist [options] <in.gfa>\nOptions:\n  -t STR   items: gene (gene content) or adj (gene adjacencies of the walks) [gene]\n"
+		            "  -m STR   metric: jaccard, shared or diff [jaccard]\n  -p       relaxed PHYLIP output\n");
+		return 0;
+	}
+	return pg_dist_file(argv[optind], &o) == 0 ? 0 : 1;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // `pangene --gpus N`: main.c:117-142 for N devices of one node.  The command forks N - 1 workers BEFORE anything touches the GPU;
 // rank r takes device r and the r-th contiguous block of the PAF files (so that the ranks' W / BED lines, concatenated in rank
@@ -151,7 +180,7 @@ static int main_curves(int argc, char *argv[])
 // tests) it is a shared-memory region mapped before the fork.  Rank 0 prints the graph; every rank writes the lines of its own
 // genomes to a temporary file that rank 0 copies to stdout in rank order.
 // ---------------------------------------------------------------------------------------------------------------
-struct Output { int matrix = 0; bool call = false; int curves = 0; uint32_t curves_seed = 11; }; // curves: orders (0: none)
+struct Output { int matrix = 0; bool call = false; int curves = 0; uint32_t curves_seed = 11; int dist = -1, dist_metric = 0; }; // curves: orders (0: none); dist: PG_DIST_* (-1: none)
 
 static int run_path(pg_opt_t &opt, int n_files, char **files, const uint8_t *ids_only, const Output &o, bool graph_lines, bool own_lines, int device = -1)
 {
@@ -187,6 +216,13 @@ static int run_path(pg_opt_t &opt, int n_files, char **files, const uint8_t *ids
 			pg_curves_opt_init(&co);
 			co.n_perm = o.curves, co.seed = o.curves_seed;
 			pg_write_curves(g, &co);
+			if (pg_last_error()) rc = 2;
+		}
+		else if (o.dist >= 0) {
+			pg_dist_opt_t dop;
+			pg_dist_opt_init(&dop);
+			dop.type = o.dist, dop.metric = o.dist_metric;
+			pg_write_dist(g, &dop);
 			if (pg_last_error()) rc = 2;
 		}
 		else if (opt.flag & PG_F_WRITE_BED_WALK) { if (own_lines) pg_write_bed(d, 1); }
@@ -249,6 +285,7 @@ static int run_sharded(pg_opt_t &opt, int W, int n_files, char **files, const Ou
 	if (o.matrix) { std::fprintf(stderr, "ERROR: --matrix needs every genome in one process; run it without --gpus\n"); return 1; }
 	if (o.call) { std::fprintf(stderr, "ERROR: --call needs every genome in one process; run it without --gpus\n"); return 1; }
 	if (o.curves) { std::fprintf(stderr, "ERROR: --curves needs every genome in one process; run it without --gpus\n"); return 1; }
+	if (o.dist >= 0) { std::fprintf(stderr, "ERROR: --dist needs every genome in one process; run it without --gpus\n"); return 1; }
 	const bool dev = pg_backend_is_device() != 0;
 	typedef int (*uid_fn)(void *); typedef int (*init_fn)(int32_t, int32_t, const void *); typedef int (*fin_fn)(void);
 	uid_fn rccl_uid = nullptr; init_fn rccl_init = nullptr; fin_fn rccl_fin = nullptr;
@@ -391,13 +428,16 @@ int main(int argc, char *argv[])
 	if (argc >= 2 && std::strcmp(argv[1], "gfa2matrix") == 0) return main_gfa2matrix(argc - 1, argv + 1);
 	if (argc >= 2 && std::strcmp(argv[1], "call") == 0) return main_call(argc - 1, argv + 1);
 	if (argc >= 2 && std::strcmp(argv[1], "curves") == 0) return main_curves(argc - 1, argv + 1);
+	if (argc >= 2 && std::strcmp(argv[1], "dist") == 0) return main_dist(argc - 1, argv + 1);
 	int matrix = 0, n_gpus = 1; // matrix: 1 presence, 2 counts
 	bool call = false;
 	int curves = 0; // orders of --curves (0: not asked for)
 	uint32_t curves_seed = 11;
+	int dist = -1, dist_metric_v = PG_DIST_JACCARD; // --dist: PG_DIST_* (-1: not asked for)
 	static const struct option lopts[] = {
 		{ "bed", optional_argument, nullptr, 301 }, { "ori-sc", no_argument, nullptr, 302 }, { "matrix", optional_argument, nullptr, 303 }, { "call", no_argument, nullptr, 305 },
 		{ "curves", optional_argument, nullptr, 306 }, { "curves-seed", required_argument, nullptr, 307 },
+		{ "dist", optional_argument, nullptr, 308 }, { "dist-metric", required_argument, nullptr, 309 },
 		{ "gpus", required_argument, nullptr, 304 }, { "procs", required_argument, nullptr, 304 },
 		{ "version", no_argument, nullptr, 401 }, { nullptr, 0, nullptr, 0 } };
 	pg_opt_t opt;
@@ -447,14 +487,24 @@ int main(int argc, char *argv[])
 			if (curves < 1) { std::fprintf(stderr, "ERROR: --curves needs at least one order\n"); return 1; }
 			break;
 		case 307: curves_seed = (uint32_t)std::strtoul(optarg, nullptr, 10); break;
+		case 308:
+			dist = optarg ? dist_type(optarg) : PG_DIST_GENE;
+			if (dist < 0) { std::fprintf(stderr, "ERROR: --dist must be gene or adj\n"); return 1; }
+			break;
+		case 309:
+			dist_metric_v = dist_metric(optarg);
+			if (dist_metric_v < 0) { std::fprintf(stderr, "ERROR: --dist-metric must be jaccard, shared or diff\n"); return 1; }
+			break;
 		case 401: std::puts(PG_VERSION); return 0;
 		default: break;
 		}
 	}
 	if (argc - optind < 1) return usage(stderr, &opt);
 	if (curves && (matrix || call)) { std::fprintf(stderr, "ERROR: --curves cannot be combined with --matrix or --call\n"); return 1; }
+	if (dist >= 0 && (matrix || call || curves)) { std::fprintf(stderr, "ERROR: --dist cannot be combined with --matrix, --call or --curves\n"); return 1; }
 	Output o;
 	o.curves = curves, o.curves_seed = curves_seed;
+	o.dist = dist, o.dist_metric = dist_metric_v;
 	o.matrix = matrix;
 	o.call = call;
 	int rc;

@@ -384,7 +384,8 @@ int graph_matrix(pg_graph_t *q, std::vector<std::string> &names, std::vector<int
 
 // pangene.js gfa2matrix's reading of a GFA (pangene.js:1168-1247 with the parser at 131-197): segments in the order S- and L-lines
 // introduce them, walk steps whose name is not a segment yet are ignored, assemblies = "sample#hap" of the W-lines in first-seen
-// order; mat[seg * n_asm + asm] = occurrences.  Plain or gzipped input.  0, or -1 when the file cannot be opened.
+// order; mat[seg * n_asm + asm] = occurrences, and the oriented steps of every W-line.  Plain or gzipped input.  0, or -1 when the file
+// cannot be opened.
 int gfa_matrix(const char *fn, GfaMatrix &m)
 {
 	std::vector<std::string> lines;
@@ -395,6 +396,7 @@ int gfa_matrix(const char *fn, GfaMatrix &m)
 	auto seg_add = [&](const std::string &n) { auto it = seg_h.find(n); if (it == seg_h.end()) it = seg_h.emplace(n, (int32_t)seg.size()).first, seg.push_back(n); return it->second; };
 	auto split = [](const std::string &l, std::vector<std::string> &t) { t.clear(); size_t b = 0; for (;;) { size_t e = l.find('\t', b); t.push_back(l.substr(b, e == std::string::npos ? e : e - b)); if (e == std::string::npos) break; b = e + 1; } };
 	std::vector<std::string> t;
+	m.step.clear(), m.walk_asm.clear(), m.walk_off.assign(1, 0);
 	for (const std::string &l : lines) {
 		if (l.empty()) continue;
 		if (l[0] == 'S') { split(l, t); if (t.size() >= 3) seg_add(t[1]); }
@@ -410,9 +412,13 @@ int gfa_matrix(const char *fn, GfaMatrix &m)
 				if (w[i] != '>' && w[i] != '<') { ++i; continue; }
 				size_t e = i + 1;
 				while (e < w.size() && w[e] != '>' && w[e] != '<' && !std::isspace((unsigned char)w[e])) ++e;
-				if (e > i + 1) { auto sit = seg_h.find(w.substr(i + 1, e - i - 1)); if (sit != seg_h.end()) walk.emplace_back(it->second, sit->second); }
+				if (e > i + 1) {
+					auto sit = seg_h.find(w.substr(i + 1, e - i - 1));
+					if (sit != seg_h.end()) walk.emplace_back(it->second, sit->second), m.step.push_back(sit->second * 2 + (w[i] == '<'));
+				}
 				i = e;
 			}
+			m.walk_asm.push_back(it->second), m.walk_off.push_back((int64_t)m.step.size());
 		}
 	}
 	const size_t n_asm = asm_a.size();

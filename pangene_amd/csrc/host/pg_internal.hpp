@@ -222,7 +222,11 @@ FILE *out_stream();
 int read_lines(const char *fn, std::vector<std::string> &out); // every line of a plain or gzipped text file, terminators removed
 // the gene x assembly matrix of gfa2matrix (gfa_writer.cpp): of the graph in memory (pg_write_matrix) and of a GFA file
 int graph_matrix(pg_graph_t *q, std::vector<std::string> &names, std::vector<int32_t> &mat);
-struct GfaMatrix { std::vector<std::string> seg, asm_a; std::unordered_map<std::string, int32_t> seg_h; std::vector<int32_t> mat; };
+// the W-lines' known steps too: walk w = step[walk_off[w] .. walk_off[w + 1]) of assembly walk_asm[w], steps = segment * 2 + reverse
+struct GfaMatrix {
+	std::vector<std::string> seg, asm_a; std::unordered_map<std::string, int32_t> seg_h; std::vector<int32_t> mat;
+	std::vector<int32_t> step, walk_asm; std::vector<int64_t> walk_off;
+};
 int gfa_matrix(const char *fn, GfaMatrix &m);
 
 double now_sec();
