@@ -231,6 +231,30 @@ void pg_write_dist(pg_graph_t *g, const pg_dist_opt_t *o);
 int  pg_pan_shared(const uint8_t *presence, int32_t n_item, int32_t n_asm, int32_t *shared);
 int  pg_pan_dist(const uint8_t *presence, int32_t n_item, int32_t n_asm, int32_t metric, double *out);
 
+/* Gene associations: which genes travel together over the assemblies and which exclude each other.  Over the presence matrix of
+ * gfa2matrix (gene g is in assembly a when its entry is > 0; rows in segment order), with A assemblies, a = |B_g|, b = |B_h|,
+ * s = |B_g & B_h|: V_g = a (A - a), D = s A - a b, phi(g, h) = D / sqrt(V_g V_h).  Gene g is eligible when min(a, A - a) >= min_count
+ * (core genes and genes seen nowhere have V = 0; with the default 2 singletons are out too).  min_phi is read as per-mille,
+ * p = floor(1000 min_phi + 0.5), and a pair g < h of eligible genes is selected when 10^6 D^2 >= p^2 V_g V_h -- decided in 128-bit
+ * integers, never in floating point -- and the sign of D is asked for (D = 0 counts as positive).  More than max_pair selected pairs
+ * is an error (PGA_ERR_RANGE; the message names the number that passed).  Output, tab-separated: "GeneA GeneB nA nB nAB phi", then
+ * one line per selected pair in ascending (row of A, row of B); phi = (double)D / sqrt((double)V_g * (double)V_h) as %.4f.
+ * pg_assoc_file: a GFA file, plain or gzipped (0, -1 when it cannot be opened, -2 on a backend error or bad options);
+ * pg_write_assoc: the graph in memory after pg_graph_gen; pg_pan_assoc: any presence matrix, row-major uint8 [n_gene][n_asm]: writes
+ * the first cap selected pairs as pair[.][3] = (g, h, s) and returns the number selected, or a negative PGA_ERR_*.
+ * n_asm <= 16 777 215. */
+enum { PG_ASSOC_BOTH = 0, PG_ASSOC_POS = 1, PG_ASSOC_NEG = 2 };
+typedef struct {
+	double  min_phi;   /* smallest |phi| of a selected pair, in [0, 1], read as per-mille [0.8] */
+	int32_t min_count; /* a gene is eligible when min(a, A - a) >= min_count; >= 1 [2] */
+	int32_t sign;      /* PG_ASSOC_BOTH, PG_ASSOC_POS or PG_ASSOC_NEG [both] */
+	int64_t max_pair;  /* more selected pairs than this is an error [16 777 216] */
+} pg_assoc_opt_t;
+void    pg_assoc_opt_init(pg_assoc_opt_t *o);
+int     pg_assoc_file(const char *gfa_fn, const pg_assoc_opt_t *o);
+void    pg_write_assoc(pg_graph_t *g, const pg_assoc_opt_t *o);
+int64_t pg_pan_assoc(const uint8_t *presence, int32_t n_gene, int32_t n_asm, const pg_assoc_opt_t *o, int32_t *pair, int64_t cap);
+
 /* Last error of the path (0 = none).  The reference aborts on invariant violations; this library
  * records a status instead, prints one line to stderr, and leaves the graph empty. */
 int         pg_last_error(void);

@@ -94,7 +94,7 @@ typedef struct {
  * Device layout limits (PGA_ERR_RANGE otherwise): coordinates inside a block < 2^31 (contigs beyond that arrive as virtual contigs,
  * see pga_genome_block_t; what remains out of reach is a single cluster of overlapping hits spanning 2^30 bp), < 2^30 hits and < 2^31
  * exons per shard, < 2^20 genes, < 2^24 genomes. */
-#define PGA_ABI_VERSION 8u  /* bumped whenever a struct of this header or the order of pga_backend_t changes; pga_create refuses another */
+#define PGA_ABI_VERSION 9u  /* bumped whenever a struct of this header or the order of pga_backend_t changes; pga_create refuses another */
 typedef struct {
 	uint32_t abi_version;        /* = PGA_ABI_VERSION of the header the caller was compiled against (PGA_ERR_ARG otherwise) */
 	int32_t n_genome;            /* genomes in this shard (may include genomes with 0 hits) */
@@ -332,6 +332,31 @@ typedef struct {
 typedef struct { const int32_t *shared; } pga_shared_out_t;
 int pga_pan_shared(const pga_shared_in_t *in, pga_shared_out_t *out);
 
+/* Gene associations (include/pangene_amd.h pg_pan_assoc, pangene assoc): the gene pairs whose presence over the assemblies is
+ * correlated.  Context-free, like pan_shared, of which it is the transpose: an all-pairs popcount over GENE rows that selects on the
+ * device and returns a sparse list instead of the square.  With A = n_asm, a = |B_g|, b = |B_h|, s = |B_g & B_h|, V_g = a (A - a)
+ * and D = s A - a b: gene g is eligible when min(a, A - a) >= min_count, and a pair g < h of eligible genes is selected when
+ * 10^6 D^2 >= r_permille^2 V_g V_h (decided in integers, 128 bits wide) and the sign of D is asked for (sign 0: both, 1: D >= 0,
+ * 2: D < 0).
+ * In:  bits[n_gene][(n_asm + 31) / 32], gene-major: bit (a & 31) of word a >> 5 of row g = gene g is in assembly a; bits past n_asm
+ *      are zero.  min_count >= 1, 0 <= r_permille <= 1000, max_pair >= 0 (PGA_ERR_ARG otherwise).
+ * Out: n_pair selected pairs as pair[n_pair][3] = (g, h, s), g < h, ascending by (g, h), and count[n_gene] = |B_g|.  The arrays
+ *      belong to the backend and stay valid until its next pan_assoc.  More than max_pair selected pairs: PGA_ERR_RANGE with n_pair =
+ *      the number that passed and pair = NULL.
+ * Limits (PGA_ERR_RANGE otherwise): n_asm <= 16 777 215 (both sides of the comparison then stay below 2^112), n_gene <= 16 777 215,
+ * and at most 4 194 304 eligible genes (the upper-triangle tiles of the eligible rows are one 1-D grid with an int32 tile number). */
+typedef struct {
+	const uint32_t *bits;
+	int32_t n_gene, n_asm, min_count, r_permille, sign;
+	int64_t max_pair;
+} pga_assoc_in_t;
+typedef struct {
+	int64_t n_pair;
+	const int32_t *pair;
+	const int32_t *count;
+} pga_assoc_out_t;
+int pga_pan_assoc(const pga_assoc_in_t *in, pga_assoc_out_t *out);
+
 /* the same ABI as a table, so the host driver is written once */
 struct pga_branch_par_s; struct pga_loop_xchg_s;
 typedef struct {
@@ -390,6 +415,7 @@ typedef struct {
 	int  (*call_bubbles)(const pga_call_in_t *, pga_call_out_t *); /* may be NULL: the host driver then runs the same step itself */
 	int  (*pan_curves)(const pga_curves_in_t *, pga_curves_out_t *); /* may be NULL: the host driver then runs the same step itself */
 	int  (*pan_shared)(const pga_shared_in_t *, pga_shared_out_t *); /* may be NULL: the host driver then runs the same step itself */
+	int  (*pan_assoc)(const pga_assoc_in_t *, pga_assoc_out_t *); /* may be NULL: the host driver then runs the same step itself */
 } pga_backend_t;
 
 const pga_backend_t *pga_backend(void);

@@ -168,6 +168,69 @@ def _dist_args(argv: Sequence[str]):
     return t, m
 
 
+class pg_assoc_opt_t(C.Structure):
+    """Association options (include/pangene_amd.h): smallest |phi|, smallest min(a, A - a) of a gene, sign (PG_ASSOC_*), pair limit."""
+    _fields_ = [("min_phi", C.c_double), ("min_count", C.c_int32), ("sign", C.c_int32), ("max_pair", C.c_int64)]
+
+
+ASSOC_SIGNS = ("both", "pos", "neg")
+ASSOC_MAX_PAIR = 16777216
+
+
+def assoc_opt(lib: C.CDLL, min_phi: float = 0.8, min_count: int = 2, sign: str = "both", max_pair: int = ASSOC_MAX_PAIR) -> pg_assoc_opt_t:
+    if not 0.0 <= float(min_phi) <= 1.0:
+        raise ValueError("min_phi must be in [0, 1]")
+    if int(min_count) < 1:
+        raise ValueError("min_count must be at least 1")
+    if sign not in ASSOC_SIGNS:
+        raise ValueError("sign must be pos, neg or both")
+    o = pg_assoc_opt_t()
+    lib.pg_assoc_opt_init(C.byref(o))
+    o.min_phi, o.min_count, o.sign, o.max_pair = float(min_phi), int(min_count), ASSOC_SIGNS.index(sign), int(max_pair)
+    return o
+
+
+def pan_assoc(lib: C.CDLL, presence, min_phi: float = 0.8, min_count: int = 2, sign: str = "both", max_pair: int = ASSOC_MAX_PAIR):
+    """Associated gene pairs of a gene x assembly presence matrix (bool numpy array or torch tensor, shape (G, A)) through pg_pan_assoc:
+    (pairs, phi) with pairs an int32 array (n, 3) of (g, h, |B_g & B_h|), g < h, ascending, and phi a float64 array (n,)."""
+    import numpy as np
+    p = _presence(presence)
+    G, A = p.shape
+    o = assoc_opt(lib, min_phi, min_count, sign, max_pair)
+    cap = 65536
+    while True:  # the call says how many pairs there are; a second one fetches them when the first buffer was too small
+        pairs = np.zeros((cap, 3), dtype=np.int32)
+        n = lib.pg_pan_assoc(p.ctypes.data_as(C.POINTER(C.c_uint8)), G, A, C.byref(o), pairs.ctypes.data_as(C.POINTER(C.c_int32)), cap)
+        if n < 0:
+            raise RuntimeError("pg_pan_assoc: status %d" % n)
+        if n <= cap:
+            break
+        cap = n
+    pairs = pairs[:n].copy()
+    cnt = p.sum(axis=1, dtype=np.int64)
+    a, b, s = cnt[pairs[:, 0]], cnt[pairs[:, 1]], pairs[:, 2].astype(np.int64)
+    D, Vg, Vh = s * A - a * b, a * (A - a), b * (A - b)
+    phi = D.astype(np.float64) / np.sqrt(Vg.astype(np.float64) * Vh.astype(np.float64))
+    return pairs, phi
+
+
+def _assoc_args(argv: Sequence[str]):
+    """(min_phi, min_count, sign) of --assoc[=FLOAT] / --assoc-min-count=INT / --assoc-sign=STR in argv; min_phi = None without --assoc."""
+    r, c, s = None, 2, "both"
+    for a in argv:
+        if a == "--assoc": r = 0.8
+        elif a.startswith("--assoc="): r = float(a.split("=", 1)[1])
+        elif a.startswith("--assoc-min-count="): c = int(a.split("=", 1)[1])
+        elif a.startswith("--assoc-sign="): s = a.split("=", 1)[1]
+    if r is not None and not 0.0 <= r <= 1.0:
+        raise ValueError("--assoc must be in [0, 1]")
+    if c < 1:
+        raise ValueError("--assoc-min-count must be at least 1")
+    if s not in ASSOC_SIGNS:
+        raise ValueError("--assoc-sign must be pos, neg or both")
+    return r, c, s
+
+
 _API = {
     "pg_opt_init": (None, [C.POINTER(pg_opt_t)]),
     "pg_data_init": (C.c_void_p, []),
@@ -196,6 +259,10 @@ _API = {
     "pg_write_dist": (None, [C.c_void_p, C.c_void_p]),
     "pg_pan_shared": (C.c_int, [C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     "pg_pan_dist": (C.c_int, [C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double)]),
+    "pg_assoc_opt_init": (None, [C.c_void_p]),
+    "pg_assoc_file": (C.c_int, [C.c_char_p, C.c_void_p]),
+    "pg_write_assoc": (None, [C.c_void_p, C.c_void_p]),
+    "pg_pan_assoc": (C.c_int64, [C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.c_int64]),
     "pg_read_list_dict": (C.c_void_p, [C.c_char_p]),
     "pg_dict_destroy": (None, [C.c_void_p]),
     "pg_last_error": (C.c_int, []),
@@ -261,7 +328,7 @@ def parse_args(lib: C.CDLL, argv: Sequence[str]) -> pg_opt_t:
         elif a in ("--bed", "--bed=walk"): opt.flag |= PG_F_WRITE_BED_WALK
         elif a == "--bed=raw": opt.flag |= PG_F_WRITE_BED_RAW
         elif a == "--bed=flag": opt.flag |= PG_F_WRITE_BED_FLAG
-        elif a in ("--matrix", "--matrix=presence", "--matrix=count", "--call") or a.startswith("--curves") or a.startswith("--dist"): pass  # handled by run()
+        elif a in ("--matrix", "--matrix=presence", "--matrix=count", "--call") or a.startswith("--curves") or a.startswith("--dist") or a.startswith("--assoc"): pass  # handled by run()
         elif a[:2] in ("-p", "-a", "-f", "-c", "-g", "-r", "-b", "-B", "-y", "-T", "-D", "-C", "-e", "-l", "-m", "-d", "-X", "-I", "-P"):
             v = a[2:] if len(a) > 2 else next(it)
             k = a[1]
@@ -312,6 +379,9 @@ def run(lib: C.CDLL, files: Sequence[str], argv: Sequence[str] = (), scan_only: 
     dist_type, dist_metric = _dist_args(argv)
     if dist_type is not None and (any(x.startswith("--matrix") for x in argv) or "--call" in argv or n_curves):
         raise ValueError("--dist cannot be combined with --matrix, --call or --curves")
+    assoc_phi, assoc_count, assoc_sign = _assoc_args(argv)
+    if assoc_phi is not None and (any(x.startswith("--matrix") for x in argv) or "--call" in argv or n_curves or dist_type is not None):
+        raise ValueError("--assoc cannot be combined with --matrix, --call, --curves or --dist")
     fd, out = tempfile.mkstemp(prefix="pangene_", suffix=".out")
     os.close(fd)
     lib.pg_set_output(out.encode())
@@ -341,6 +411,10 @@ def run(lib: C.CDLL, files: Sequence[str], argv: Sequence[str] = (), scan_only: 
                     raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
             elif dist_type is not None:
                 lib.pg_write_dist(g, C.byref(dist_opt(lib, dist_type, dist_metric)))
+                if lib.pg_last_error():
+                    raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
+            elif assoc_phi is not None:
+                lib.pg_write_assoc(g, C.byref(assoc_opt(lib, assoc_phi, assoc_count, assoc_sign)))
                 if lib.pg_last_error():
                     raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
             elif opt.flag & PG_F_WRITE_BED_WALK: lib.pg_write_bed(d, 1)

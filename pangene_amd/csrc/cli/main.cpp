@@ -56,10 +56,14 @@ static int usage(FILE *fp, const pg_opt_t *opt)
 	std::fprintf(fp, "    --curves-seed=INT  seed of the orders of --curves [11]\n");
 	std::fprintf(fp, "    --dist[=STR]  output pairwise distances of the assemblies over gene content (gene) or gene adjacencies (adj) [gene]\n");
 	std::fprintf(fp, "    --dist-metric=STR  metric of --dist: jaccard, shared or diff [jaccard]\n");
+	std::fprintf(fp, "    --assoc[=FLOAT] output the gene pairs whose presence over the assemblies is correlated, |phi| >= FLOAT [0.8]\n");
+	std::fprintf(fp, "    --assoc-min-count=INT  --assoc: a gene takes part when it is present in >=INT and absent from >=INT assemblies [2]\n");
+	std::fprintf(fp, "    --assoc-sign=STR  --assoc: keep pos (co-occurring), neg (avoiding) or both [both]\n");
 	std::fprintf(fp, "  Also: pangene gfa2matrix [-c] [-d FILE] [-p] <in.gfa>   (pangene.js gfa2matrix on a GFA file)\n");
 	std::fprintf(fp, "        pangene call [-m INT] [-w] [-b] [-e] [-d] [-p] [-s] [-r STR] <in.gfa>   (pangene.js call on a GFA file)\n");
 	std::fprintf(fp, "        pangene curves [-n INT] [-s INT] <in.gfa>   (accumulation curves of the gfa2matrix matrix of a GFA file)\n");
 	std::fprintf(fp, "        pangene dist [-t gene|adj] [-m jaccard|shared|diff] [-p] <in.gfa>   (pairwise distances of the assemblies of a GFA file)\n");
+	std::fprintf(fp, "        pangene assoc [-r FLOAT] [-c INT] [-s pos|neg|both] [-x INT] <in.gfa>   (co-occurring and avoiding gene pairs of a GFA file)\n");
 	return fp == stdout ? 0 : 1;
 }
 
@@ -172,6 +176,37 @@ static int main_dist(int argc, char *argv[])
 	return pg_dist_file(argv[optind], &o) == 0 ? 0 : 1;
 }
 
+static int assoc_sign(const char *s) { return std::strcmp(s, "both") == 0 ? PG_ASSOC_BOTH : std::strcmp(s, "pos") == 0 ? PG_ASSOC_POS : std::strcmp(s, "neg") == 0 ? PG_ASSOC_NEG : -1; }
+static bool assoc_phi(const char *s, double &r) // a number in [0, 1]
+{
+	char *e;
+	r = std::strtod(s, &e);
+	return e != s && *e == 0 && r >= 0.0 && r <= 1.0;
+}
+
+// `pangene assoc`: the gene pairs of a GFA file that travel together over the assemblies or exclude each other
+static int main_assoc(int argc, char *argv[])
+{
+	pg_assoc_opt_t o;
+	pg_assoc_opt_init(&o);
+	int c;
+	while ((c = getopt(argc, argv, "r:c:s:x:")) >= 0) {
+		if (c == 'r') { if (!assoc_phi(optarg, o.min_phi)) { std::fprintf(stderr, "ERROR: -r must be in [0, 1]\n"); return 1; } }
+		else if (c == 'c') { if ((o.min_count = std::atoi(optarg)) < 1) { std::fprintf(stderr, "ERROR: -c must be at least 1\n"); return 1; } }
+		else if (c == 's') { if ((o.sign = assoc_sign(optarg)) < 0) { std::fprintf(stderr, "ERROR: -s must be pos, neg or both\n"); return 1; } }
+		else if (c == 'x') { if ((o.max_pair = std::atoll(optarg)) < 0) { std::fprintf(stderr, "ERROR: -x must not be negative\n"); return 1; } }
+		else return 1;
+	}
+	if (argc - optind < 1) {
+		std::printf("Usage: pangene assoc [options] <in.gfa>\nOptions:\n  -r FLOAT  smallest |phi| of a reported pair, in [0, 1], read as per-mille [%g]\n"
+		            "  -c INT    a gene takes part when it is present in >=INT and absent from >=INT assemblies [%d]\n"
+		            "  -s STR    keep pos (co-occurring), neg (avoiding) or both [both]\n"
+		            "  -x INT    give up when more than INT pairs pass [%lld]\n", o.min_phi, o.min_count, (long long)o.max_pair);
+		return 0;
+	}
+	return pg_assoc_file(argv[optind], &o) == 0 ? 0 : 1;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // `pangene --gpus N`: main.c:117-142 for N devices of one node.  The command forks N - 1 workers BEFORE anything touches the GPU;
 // rank r takes device r and the r-th contiguous block of the PAF files (so that the ranks' W / BED lines, concatenated in rank
@@ -180,7 +215,8 @@ static int main_dist(int argc, char *argv[])
 // tests) it is a shared-memory region mapped before the fork.  Rank 0 prints the graph; every rank writes the lines of its own
 // genomes to a temporary file that rank 0 copies to stdout in rank order.
 // ---------------------------------------------------------------------------------------------------------------
-struct Output { int matrix = 0; bool call = false; int curves = 0; uint32_t curves_seed = 11; int dist = -1, dist_metric = 0; }; // curves: orders (0: none); dist: PG_DIST_* (-1: none)
+struct Output { int matrix = 0; bool call = false; int curves = 0; uint32_t curves_seed = 11; int dist = -1, dist_metric = 0; // curves: orders (0: none); dist: PG_DIST_* (-1: none)
+	bool assoc = false; double assoc_phi = 0.8; int assoc_count = 2, assoc_sign = 0; };
 
 static int run_path(pg_opt_t &opt, int n_files, char **files, const uint8_t *ids_only, const Output &o, bool graph_lines, bool own_lines, int device = -1)
 {
@@ -223,6 +259,13 @@ static int run_path(pg_opt_t &opt, int n_files, char **files, const uint8_t *ids
 			pg_dist_opt_init(&dop);
 			dop.type = o.dist, dop.metric = o.dist_metric;
 			pg_write_dist(g, &dop);
+			if (pg_last_error()) rc = 2;
+		}
+		else if (o.assoc) {
+			pg_assoc_opt_t ao;
+			pg_assoc_opt_init(&ao);
+			ao.min_phi = o.assoc_phi, ao.min_count = o.assoc_count, ao.sign = o.assoc_sign;
+			pg_write_assoc(g, &ao);
 			if (pg_last_error()) rc = 2;
 		}
 		else if (opt.flag & PG_F_WRITE_BED_WALK) { if (own_lines) pg_write_bed(d, 1); }
@@ -286,6 +329,7 @@ static int run_sharded(pg_opt_t &opt, int W, int n_files, char **files, const Ou
 	if (o.call) { std::fprintf(stderr, "ERROR: --call needs every genome in one process; run it without --gpus\n"); return 1; }
 	if (o.curves) { std::fprintf(stderr, "ERROR: --curves needs every genome in one process; run it without --gpus\n"); return 1; }
 	if (o.dist >= 0) { std::fprintf(stderr, "ERROR: --dist needs every genome in one process; run it without --gpus\n"); return 1; }
+	if (o.assoc) { std::fprintf(stderr, "ERROR: --assoc needs every genome in one process; run it without --gpus\n"); return 1; }
 	const bool dev = pg_backend_is_device() != 0;
 	typedef int (*uid_fn)(void *); typedef int (*init_fn)(int32_t, int32_t, const void *); typedef int (*fin_fn)(void);
 	uid_fn rccl_uid = nullptr; init_fn rccl_init = nullptr; fin_fn rccl_fin = nullptr;
@@ -429,15 +473,20 @@ int main(int argc, char *argv[])
 	if (argc >= 2 && std::strcmp(argv[1], "call") == 0) return main_call(argc - 1, argv + 1);
 	if (argc >= 2 && std::strcmp(argv[1], "curves") == 0) return main_curves(argc - 1, argv + 1);
 	if (argc >= 2 && std::strcmp(argv[1], "dist") == 0) return main_dist(argc - 1, argv + 1);
+	if (argc >= 2 && std::strcmp(argv[1], "assoc") == 0) return main_assoc(argc - 1, argv + 1);
 	int matrix = 0, n_gpus = 1; // matrix: 1 presence, 2 counts
 	bool call = false;
 	int curves = 0; // orders of --curves (0: not asked for)
 	uint32_t curves_seed = 11;
 	int dist = -1, dist_metric_v = PG_DIST_JACCARD; // --dist: PG_DIST_* (-1: not asked for)
+	bool assoc = false; // --assoc
+	double assoc_phi_v = 0.8;
+	int assoc_count = 2, assoc_sign_v = PG_ASSOC_BOTH;
 	static const struct option lopts[] = {
 		{ "bed", optional_argument, nullptr, 301 }, { "ori-sc", no_argument, nullptr, 302 }, { "matrix", optional_argument, nullptr, 303 }, { "call", no_argument, nullptr, 305 },
 		{ "curves", optional_argument, nullptr, 306 }, { "curves-seed", required_argument, nullptr, 307 },
 		{ "dist", optional_argument, nullptr, 308 }, { "dist-metric", required_argument, nullptr, 309 },
+		{ "assoc", optional_argument, nullptr, 310 }, { "assoc-min-count", required_argument, nullptr, 311 }, { "assoc-sign", required_argument, nullptr, 312 },
 		{ "gpus", required_argument, nullptr, 304 }, { "procs", required_argument, nullptr, 304 },
 		{ "version", no_argument, nullptr, 401 }, { nullptr, 0, nullptr, 0 } };
 	pg_opt_t opt;
@@ -495,6 +544,16 @@ int main(int argc, char *argv[])
 			dist_metric_v = dist_metric(optarg);
 			if (dist_metric_v < 0) { std::fprintf(stderr, "ERROR: --dist-metric must be jaccard, shared or diff\n"); return 1; }
 			break;
+		case 310:
+			assoc = true;
+			if (optarg && !assoc_phi(optarg, assoc_phi_v)) { std::fprintf(stderr, "ERROR: --assoc must be in [0, 1]\n"); return 1; }
+			break;
+		case 311:
+			if ((assoc_count = std::atoi(optarg)) < 1) { std::fprintf(stderr, "ERROR: --assoc-min-count must be at least 1\n"); return 1; }
+			break;
+		case 312:
+			if ((assoc_sign_v = assoc_sign(optarg)) < 0) { std::fprintf(stderr, "ERROR: --assoc-sign must be pos, neg or both\n"); return 1; }
+			break;
 		case 401: std::puts(PG_VERSION); return 0;
 		default: break;
 		}
@@ -502,7 +561,9 @@ int main(int argc, char *argv[])
 	if (argc - optind < 1) return usage(stderr, &opt);
 	if (curves && (matrix || call)) { std::fprintf(stderr, "ERROR: --curves cannot be combined with --matrix or --call\n"); return 1; }
 	if (dist >= 0 && (matrix || call || curves)) { std::fprintf(stderr, "ERROR: --dist cannot be combined with --matrix, --call or --curves\n"); return 1; }
+	if (assoc && (matrix || call || curves || dist >= 0)) { std::fprintf(stderr, "ERROR: --assoc cannot be combined with --matrix, --call, --curves or --dist\n"); return 1; }
 	Output o;
+	o.assoc = assoc, o.assoc_phi = assoc_phi_v, o.assoc_count = assoc_count, o.assoc_sign = assoc_sign_v;
 	o.curves = curves, o.curves_seed = curves_seed;
 	o.dist = dist, o.dist_metric = dist_metric_v;
 	o.matrix = matrix;

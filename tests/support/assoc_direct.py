@@ -1,0 +1,89 @@
+"""TEST INFRASTRUCTURE: direct pg_pan_assoc cases for tests/test_assoc_gpu.py, run in a child process of their own so that the test can
+bound them with a timeout.  The product library (HIP kernels) runs matrices no GFA fixture reaches; the checker build (host loops) and
+the numpy restatement (exact integers) check every one of them completely: the output is sparse, so the full sorted record arrays
+and the phi arrays are compared, never a sample.  Prints one line per case and "ALL OK" at the end; exits 1 at the first difference.
+
+    python tests/support/assoc_direct.py {large|wide|sizes} [--cpu-only]
+
+--cpu-only runs the checker build against the restatement alone (to see that the cases stay affordable without a GPU)."""
+import os
+import sys
+import time
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import assoc_ref as ar  # noqa: E402
+
+
+def check(libs, P, label, given=None, **kw):
+    """every library in libs against the restatement; given: the matrix as the libraries get it (a tensor)"""
+    from pangene_amd import capi
+    t0 = time.perf_counter()
+    want, cnt = ar.select(P, kw.get("min_phi", 0.8), kw.get("min_count", 2), kw.get("sign", "both"))
+    phi = ar.phi(want, cnt, P.shape[1])
+    t_ref = time.perf_counter() - t0
+    ok, ts = True, []
+    for lib in libs:
+        t0 = time.perf_counter()
+        pairs, f = capi.pan_assoc(lib, P if given is None else given, **kw)
+        ts.append(time.perf_counter() - t0)
+        ok = ok and pairs.shape == want.shape and np.array_equal(pairs, want) and np.array_equal(f, phi)
+    print("%s G=%d A=%d %s: %d pairs, restatement %.1f s, libraries %s s: %s" % (
+        label, P.shape[0], P.shape[1], kw, len(want), t_ref, " ".join("%.2f" % t for t in ts), "ok" if ok else "DIFFERENT"), flush=True)
+    if not ok:
+        sys.exit(1)
+    return len(want)
+
+
+def main():
+    which = sys.argv[1]
+    cpu_only = "--cpu-only" in sys.argv[2:]
+    from pangene_amd import capi
+    import oracle_host
+    ora = oracle_host.load()
+    if cpu_only:
+        hip, libs = None, [ora]
+    else:
+        import torch
+        assert torch.cuda.is_available()
+        torch.cuda.init()
+        hip = capi.load()
+        libs = [hip, ora]
+    if which == "large":
+        P = ar.planted(20003, 1001, 1, n_module=40)  # a U-shaped spectrum: about half of the rows are eligible; 32 words a row, the last partial
+        n = check(libs, P, "large")
+        assert n > 40
+        check(libs, P, "large", min_phi=0.3, min_count=5, sign="neg")
+        if hip is not None:
+            # the second run: a capacity below the number of pairs; the result must be what the unforced run gave
+            os.environ["PANGENE_ASSOC_CAP"] = str(max(1, n // 3))
+            check([hip], P, "large, forced second run")
+            os.environ["PANGENE_ASSOC_CAP"] = "1"
+            check([hip], P, "large, forced second run from 1", min_phi=0.6)
+            del os.environ["PANGENE_ASSOC_CAP"]
+            import torch
+            Q = ar.planted(3000, 500, 3)
+            check([hip], Q, "torch cuda tensor", given=torch.from_numpy(Q).cuda(), min_phi=0.5)
+    elif which == "wide":
+        P = ar.planted(70001, 40, 2, n_module=30)  # more rows than pan_shared takes (65 535), 2 words a row
+        assert check(libs, P, "wide", min_phi=0.9, min_count=3) > 0
+        P = ar.planted(1000003, 12, 5, n_module=10)  # a million rows, few of them eligible at this count
+        check(libs, P, "million rows", min_phi=0.95, min_count=6)
+    else:
+        # the cached device buffers: growing, shrinking and growing again in one process
+        for i, (G, A) in enumerate([(40, 50), (3000, 700), (10, 2), (0, 9), (7, 0), (0, 0), (1, 1), (2, 4), (129, 33), (257, 4097),
+                                    (3000, 700), (1, 64), (100000, 9), (1000, 31)]):
+            check(libs, ar.planted(G, A, 10 + i), "sizes", min_phi=0.7)
+        if hip is not None:
+            hip.pg_trim_host_cache(0)  # gives the buffers back; the next call allocates again
+        check(libs, ar.planted(500, 300, 99), "after trim", min_phi=0.5, min_count=1)
+    print("ALL OK", flush=True)
+
+
+if __name__ == "__main__":
+    main()
