@@ -255,6 +255,37 @@ int     pg_assoc_file(const char *gfa_fn, const pg_assoc_opt_t *o);
 void    pg_write_assoc(pg_graph_t *g, const pg_assoc_opt_t *o);
 int64_t pg_pan_assoc(const uint8_t *presence, int32_t n_gene, int32_t n_asm, const pg_assoc_opt_t *o, int32_t *pair, int64_t cap);
 
+/* Gene-trait association: which genes go with a binary phenotype of the assemblies (the pan-GWAS question).  Presence as for
+ * pg_assoc_*.  The trait file (plain or gzipped) is tab-separated: a header line (any first field, then one trait name per column),
+ * then per line an assembly name as gfa2matrix prints it and per trait 1, 0, or NA / empty (missing); lines starting with '#' after
+ * the header and blank lines are skipped.  An assembly the file does not name is missing for every trait; a name the matrix does not
+ * have, a repeated name, a wrong field count or another value is an error (the line number goes to stderr).  Per trait the columns
+ * with a value are compacted, in matrix order, to N columns with labels y, t = sum y; a trait with t = 0 or t = N prints nothing.
+ * For gene g: a = |B_g|, s = |B_g & y|, D = s N - a t, V_g = a (N - a), V_t = t (N - t); g is eligible when min(a, N - a) >= min_count.
+ * Permutation p = 1 .. n_perm is y_p[r] = y[o_p[r]], o_p = order p of N columns exactly as pg_curves_* define it (seed as there);
+ * s_p = |B_g & y_p|, D_p = s_p N - a t, k_g = #{p : |D_p| >= |D|} -- integers throughout (N <= 16 777 215).
+ * Output, tab-separated: "Trait Gene N nT nG nTG phi p_fisher q_bh n_ge p_perm", one line per eligible gene and trait, traits in
+ * file order, genes in row order: phi = D / sqrt(V_g V_t) as %.4f; p_fisher = the two-sided Fisher exact p (the sum of the
+ * hypergeometric probabilities P(x) <= P(s) (1 + 1e-7), capped at 1) as %.3e; q_bh = Benjamini-Hochberg over the eligible genes of
+ * the trait as %.3e; n_ge = k_g; p_perm = (k_g + 1) / (n_perm + 1) as %.6f (both NA with n_perm = 0).  Only lines with
+ * p_fisher <= max_p are kept (q_bh is over all eligible genes all the same).
+ * pg_trait_file: a GFA file and a trait file (0, -1 when the GFA cannot be opened, -2 on a backend error or bad options, -3 on a bad
+ * trait file); pg_write_trait: the graph in memory after pg_graph_gen (errors: pg_last_error); pg_pan_trait: any presence matrix,
+ * row-major uint8 [n_gene][n_asm], and labels, row-major int8 [n_trait][n_asm] (1, 0, -1 = missing): fills
+ * out[5][n_trait][n_gene] = N, t, a, s, k (a = -1, s = k = 0 for a gene that is not eligible, and for every gene of a trait with
+ * t = 0 or t = N) and returns 0 or a negative PGA_ERR_*. */
+typedef struct {
+	int32_t  n_perm;    /* permutations; 0: none [1000] */
+	uint32_t seed;      /* seed of the orders [11] */
+	int32_t  min_count; /* a gene is eligible when min(a, N - a) >= min_count; >= 1 [1] */
+	int32_t  reserved;
+	double   max_p;     /* keep the lines with p_fisher <= max_p [1: all] */
+} pg_trait_opt_t;
+void pg_trait_opt_init(pg_trait_opt_t *o);
+int  pg_trait_file(const char *gfa_fn, const char *trait_fn, const pg_trait_opt_t *o);
+void pg_write_trait(pg_graph_t *g, const char *trait_fn, const pg_trait_opt_t *o);
+int  pg_pan_trait(const uint8_t *presence, const int8_t *labels, int32_t n_gene, int32_t n_asm, int32_t n_trait, const pg_trait_opt_t *o, int32_t *out);
+
 /* Last error of the path (0 = none).  The reference aborts on invariant violations; this library
  * records a status instead, prints one line to stderr, and leaves the graph empty. */
 int         pg_last_error(void);

@@ -94,7 +94,7 @@ typedef struct {
  * Device layout limits (PGA_ERR_RANGE otherwise): coordinates inside a block < 2^31 (contigs beyond that arrive as virtual contigs,
  * see pga_genome_block_t; what remains out of reach is a single cluster of overlapping hits spanning 2^30 bp), < 2^30 hits and < 2^31
  * exons per shard, < 2^20 genes, < 2^24 genomes. */
-#define PGA_ABI_VERSION 9u  /* bumped whenever a struct of this header or the order of pga_backend_t changes; pga_create refuses another */
+#define PGA_ABI_VERSION 10u  /* bumped whenever a struct of this header or the order of pga_backend_t changes; pga_create refuses another */
 typedef struct {
 	uint32_t abi_version;        /* = PGA_ABI_VERSION of the header the caller was compiled against (PGA_ERR_ARG otherwise) */
 	int32_t n_genome;            /* genomes in this shard (may include genomes with 0 hits) */
@@ -357,6 +357,30 @@ typedef struct {
 } pga_assoc_out_t;
 int pga_pan_assoc(const pga_assoc_in_t *in, pga_assoc_out_t *out);
 
+/* Gene-trait association (include/pangene_amd.h pg_pan_trait, pangene trait): the label-permutation test of one binary trait against
+ * every gene.  Context-free, like pan_assoc.  Over N = n_col columns (the caller has already dropped the columns where the trait is
+ * missing), with y the label row, t = |y|, a = |B_g|, s = |B_g & y|, D = s N - a t: permutation p = 1 .. n_perm of the labels is
+ * y_p[r] = y[o_p[r]] with o_p order p of N columns as pan_curves defines it (Fisher-Yates from the last column down,
+ * j = next() % (i + 1), splitmix64 started from mix((seed << 32) | p)), made on the device from the one label row; s_p = |B_g & y_p|,
+ * D_p = s_p N - a t, and k[g] = #{p : |D_p| >= |D|} for an eligible gene (min(a, N - a) >= min_count), 0 for another.  All integers.
+ * In:  bits[n_gene][(n_col + 31) / 32], gene-major as for pan_assoc, and label[(n_col + 31) / 32] in the same layout; bits past n_col
+ *      are zero in both.  min_count >= 1, n_perm >= 0 (PGA_ERR_ARG otherwise).  perm_rows: NULL, or -- for tests only -- room for
+ *      min(n_perm, pga_trait_batch()) x (n_col + 31) / 32 words that receive the label rows of the first batch of permutations.
+ * Out: a[n_gene], s[n_gene], k[n_gene].  The arrays belong to the backend and stay valid until its next pan_trait.
+ * The permutations go through in batches of pga_trait_batch() rows, so device memory is bounded by n_gene, n_col and the batch.
+ * Limits (PGA_ERR_RANGE otherwise): n_col <= 16 777 215 (every product then stays below 2^48), n_gene <= 16 777 215,
+ * n_perm <= 2^31 - 2. */
+typedef struct {
+	const uint32_t *bits;
+	const uint32_t *label;
+	int32_t n_gene, n_col, min_count, n_perm;
+	uint32_t seed;
+	uint32_t *perm_rows;
+} pga_trait_in_t;
+typedef struct { const int32_t *a, *s, *k; } pga_trait_out_t;
+int pga_pan_trait(const pga_trait_in_t *in, pga_trait_out_t *out);
+int32_t pga_trait_batch(void); /* permutations per batch: 65 536, or PANGENE_TRAIT_BATCH */
+
 /* the same ABI as a table, so the host driver is written once */
 struct pga_branch_par_s; struct pga_loop_xchg_s;
 typedef struct {
@@ -416,6 +440,7 @@ typedef struct {
 	int  (*pan_curves)(const pga_curves_in_t *, pga_curves_out_t *); /* may be NULL: the host driver then runs the same step itself */
 	int  (*pan_shared)(const pga_shared_in_t *, pga_shared_out_t *); /* may be NULL: the host driver then runs the same step itself */
 	int  (*pan_assoc)(const pga_assoc_in_t *, pga_assoc_out_t *); /* may be NULL: the host driver then runs the same step itself */
+	int  (*pan_trait)(const pga_trait_in_t *, pga_trait_out_t *); /* may be NULL: the host driver then runs the same step itself */
 } pga_backend_t;
 
 const pga_backend_t *pga_backend(void);

@@ -231,6 +231,62 @@ def _assoc_args(argv: Sequence[str]):
     return r, c, s
 
 
+class pg_trait_opt_t(C.Structure):
+    """Trait options (include/pangene_amd.h): permutations, their seed, smallest min(a, N - a) of a tested gene, p_fisher cutoff of the lines."""
+    _fields_ = [("n_perm", C.c_int32), ("seed", C.c_uint32), ("min_count", C.c_int32), ("reserved", C.c_int32), ("max_p", C.c_double)]
+
+
+TRAIT_MAX_PERM = 2147483646
+
+
+def trait_opt(lib: C.CDLL, n_perm: int = 1000, seed: int = 11, min_count: int = 1, max_p: float = 1.0) -> pg_trait_opt_t:
+    if not 0 <= int(n_perm) <= TRAIT_MAX_PERM:
+        raise ValueError("n_perm must be in [0, 2^31 - 2]")
+    if int(min_count) < 1:
+        raise ValueError("min_count must be at least 1")
+    o = pg_trait_opt_t()
+    lib.pg_trait_opt_init(C.byref(o))
+    o.n_perm, o.seed, o.min_count, o.max_p = int(n_perm), int(seed) & 0xFFFFFFFF, int(min_count), float(max_p)
+    return o
+
+
+def pan_trait(lib: C.CDLL, presence, labels, n_perm: int = 1000, seed: int = 11, min_count: int = 1):
+    """Gene-trait association of a gene x assembly presence matrix (bool numpy array or torch tensor, shape (G, A)) with binary traits
+    (labels: shape (T, A) or (A,), 1 / 0 and a negative value = missing) through pg_pan_trait: a dict of int32 arrays (T, G): N and t
+    (columns with a value and the 1s among them), a, s (|B_g|, |B_g & y|; a = -1 for a gene that is not tested) and k (the
+    permutations of the labels with |D_p| >= |D|)."""
+    import numpy as np
+    p = _presence(presence)
+    if hasattr(labels, "detach"):  # torch tensor, on any device
+        labels = labels.detach().cpu().numpy()
+    y = np.asarray(labels)
+    if y.ndim == 1:
+        y = y[None, :]
+    G, A = p.shape
+    if y.ndim != 2 or y.shape[1] != A:
+        raise ValueError("labels must be (traits x assemblies) over the assemblies of presence")
+    y = np.ascontiguousarray(np.where(y < 0, -1, np.where(y != 0, 1, 0)), dtype=np.int8)
+    T = y.shape[0]
+    o = trait_opt(lib, n_perm, seed, min_count)
+    out = np.zeros((5, T, G), dtype=np.int32)
+    rc = lib.pg_pan_trait(p.ctypes.data_as(C.POINTER(C.c_uint8)), y.ctypes.data_as(C.POINTER(C.c_int8)), G, A, T, C.byref(o), out.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc != 0:
+        raise RuntimeError("pg_pan_trait: status %d" % rc)
+    return {"N": out[0], "t": out[1], "a": out[2], "s": out[3], "k": out[4]}
+
+
+def _trait_args(argv: Sequence[str]):
+    """(file, permutations, seed) of --trait=FILE / --trait-perm=INT / --trait-seed=INT in argv; file = None without --trait."""
+    f, n, seed = None, 1000, 11
+    for a in argv:
+        if a.startswith("--trait="): f = a.split("=", 1)[1]
+        elif a.startswith("--trait-perm="): n = int(a.split("=", 1)[1])
+        elif a.startswith("--trait-seed="): seed = int(a.split("=", 1)[1])
+    if not 0 <= n <= TRAIT_MAX_PERM:
+        raise ValueError("--trait-perm must be in [0, 2^31 - 2]")
+    return f, n, seed
+
+
 _API = {
     "pg_opt_init": (None, [C.POINTER(pg_opt_t)]),
     "pg_data_init": (C.c_void_p, []),
@@ -263,6 +319,10 @@ _API = {
     "pg_assoc_file": (C.c_int, [C.c_char_p, C.c_void_p]),
     "pg_write_assoc": (None, [C.c_void_p, C.c_void_p]),
     "pg_pan_assoc": (C.c_int64, [C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.c_int64]),
+    "pg_trait_opt_init": (None, [C.c_void_p]),
+    "pg_trait_file": (C.c_int, [C.c_char_p, C.c_char_p, C.c_void_p]),
+    "pg_write_trait": (None, [C.c_void_p, C.c_char_p, C.c_void_p]),
+    "pg_pan_trait": (C.c_int, [C.POINTER(C.c_uint8), C.POINTER(C.c_int8), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]),
     "pg_read_list_dict": (C.c_void_p, [C.c_char_p]),
     "pg_dict_destroy": (None, [C.c_void_p]),
     "pg_last_error": (C.c_int, []),
@@ -328,7 +388,7 @@ def parse_args(lib: C.CDLL, argv: Sequence[str]) -> pg_opt_t:
         elif a in ("--bed", "--bed=walk"): opt.flag |= PG_F_WRITE_BED_WALK
         elif a == "--bed=raw": opt.flag |= PG_F_WRITE_BED_RAW
         elif a == "--bed=flag": opt.flag |= PG_F_WRITE_BED_FLAG
-        elif a in ("--matrix", "--matrix=presence", "--matrix=count", "--call") or a.startswith("--curves") or a.startswith("--dist") or a.startswith("--assoc"): pass  # handled by run()
+        elif a in ("--matrix", "--matrix=presence", "--matrix=count", "--call") or a.startswith("--curves") or a.startswith("--dist") or a.startswith("--assoc") or a.startswith("--trait"): pass  # handled by run()
         elif a[:2] in ("-p", "-a", "-f", "-c", "-g", "-r", "-b", "-B", "-y", "-T", "-D", "-C", "-e", "-l", "-m", "-d", "-X", "-I", "-P"):
             v = a[2:] if len(a) > 2 else next(it)
             k = a[1]
@@ -382,6 +442,9 @@ def run(lib: C.CDLL, files: Sequence[str], argv: Sequence[str] = (), scan_only: 
     assoc_phi, assoc_count, assoc_sign = _assoc_args(argv)
     if assoc_phi is not None and (any(x.startswith("--matrix") for x in argv) or "--call" in argv or n_curves or dist_type is not None):
         raise ValueError("--assoc cannot be combined with --matrix, --call, --curves or --dist")
+    trait_fn, trait_n, trait_seed = _trait_args(argv)
+    if trait_fn is not None and (any(x.startswith("--matrix") for x in argv) or "--call" in argv or n_curves or dist_type is not None or assoc_phi is not None):
+        raise ValueError("--trait cannot be combined with --matrix, --call, --curves, --dist or --assoc")
     fd, out = tempfile.mkstemp(prefix="pangene_", suffix=".out")
     os.close(fd)
     lib.pg_set_output(out.encode())
@@ -415,6 +478,10 @@ def run(lib: C.CDLL, files: Sequence[str], argv: Sequence[str] = (), scan_only: 
                     raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
             elif assoc_phi is not None:
                 lib.pg_write_assoc(g, C.byref(assoc_opt(lib, assoc_phi, assoc_count, assoc_sign)))
+                if lib.pg_last_error():
+                    raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
+            elif trait_fn is not None:
+                lib.pg_write_trait(g, trait_fn.encode(), C.byref(trait_opt(lib, trait_n, trait_seed)))
                 if lib.pg_last_error():
                     raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
             elif opt.flag & PG_F_WRITE_BED_WALK: lib.pg_write_bed(d, 1)

@@ -59,11 +59,15 @@ static int usage(FILE *fp, const pg_opt_t *opt)
 	std::fprintf(fp, "    --assoc[=FLOAT] output the gene pairs whose presence over the assemblies is correlated, |phi| >= FLOAT [0.8]\n");
 	std::fprintf(fp, "    --assoc-min-count=INT  --assoc: a gene takes part when it is present in >=INT and absent from >=INT assemblies [2]\n");
 	std::fprintf(fp, "    --assoc-sign=STR  --assoc: keep pos (co-occurring), neg (avoiding) or both [both]\n");
+	std::fprintf(fp, "    --trait=FILE  output the association of every gene with the binary traits of FILE (assembly, then 1/0/NA per trait)\n");
+	std::fprintf(fp, "    --trait-perm=INT  --trait: label permutations [1000]\n");
+	std::fprintf(fp, "    --trait-seed=INT  --trait: seed of the permutations [11]\n");
 	std::fprintf(fp, "  Also: pangene gfa2matrix [-c] [-d FILE] [-p] <in.gfa>   (pangene.js gfa2matrix on a GFA file)\n");
 	std::fprintf(fp, "        pangene call [-m INT] [-w] [-b] [-e] [-d] [-p] [-s] [-r STR] <in.gfa>   (pangene.js call on a GFA file)\n");
 	std::fprintf(fp, "        pangene curves [-n INT] [-s INT] <in.gfa>   (accumulation curves of the gfa2matrix matrix of a GFA file)\n");
 	std::fprintf(fp, "        pangene dist [-t gene|adj] [-m jaccard|shared|diff] [-p] <in.gfa>   (pairwise distances of the assemblies of a GFA file)\n");
 	std::fprintf(fp, "        pangene assoc [-r FLOAT] [-c INT] [-s pos|neg|both] [-x INT] <in.gfa>   (co-occurring and avoiding gene pairs of a GFA file)\n");
+	std::fprintf(fp, "        pangene trait -t FILE [-n INT] [-s INT] [-c INT] [-p FLOAT] <in.gfa>   (gene-trait association over the matrix of a GFA file)\n");
 	return fp == stdout ? 0 : 1;
 }
 
@@ -207,6 +211,41 @@ static int main_assoc(int argc, char *argv[])
 	return pg_assoc_file(argv[optind], &o) == 0 ? 0 : 1;
 }
 
+static bool trait_perm(const char *s, int32_t &n) // an integer in [0, 2^31 - 2]
+{
+	char *e;
+	const long long v = std::strtoll(s, &e, 10);
+	if (e == s || *e != 0 || v < 0 || v > 2147483646ll) return false;
+	n = (int32_t)v;
+	return true;
+}
+
+// `pangene trait`: the association of every gene of a GFA file with the binary traits of a trait file
+static int main_trait(int argc, char *argv[])
+{
+	pg_trait_opt_t o;
+	pg_trait_opt_init(&o);
+	const char *fn = nullptr;
+	int c;
+	while ((c = getopt(argc, argv, "t:n:s:c:p:")) >= 0) {
+		if (c == 't') fn = optarg;
+		else if (c == 'n') { if (!trait_perm(optarg, o.n_perm)) { std::fprintf(stderr, "ERROR: -n must be in [0, 2147483646]\n"); return 1; } }
+		else if (c == 's') o.seed = (uint32_t)std::strtoul(optarg, nullptr, 10);
+		else if (c == 'c') { if ((o.min_count = std::atoi(optarg)) < 1) { std::fprintf(stderr, "ERROR: -c must be at least 1\n"); return 1; } }
+		else if (c == 'p') { char *e; o.max_p = std::strtod(optarg, &e); if (e == optarg || *e != 0 || !(o.max_p >= 0.0)) { std::fprintf(stderr, "ERROR: -p must be a number >= 0\n"); return 1; } }
+		else return 1;
+	}
+	if (argc - optind < 1) {
+		std::printf("Usage: pangene trait -t FILE [options] <in.gfa>\nOptions:\n  -t FILE   traits: a header line (any first field, one name per trait), then per line an assembly and 1, 0 or NA per trait\n"
+		            "  -n INT    label permutations per trait; 0: none [%d]\n  -s INT    seed of the permutations [%u]\n"
+		            "  -c INT    a gene is tested when it is present in >=INT and absent from >=INT assemblies [%d]\n"
+		            "  -p FLOAT  print the genes with p_fisher <= FLOAT [%g]\n", o.n_perm, o.seed, o.min_count, o.max_p);
+		return 0;
+	}
+	if (fn == nullptr) { std::fprintf(stderr, "ERROR: pangene trait needs -t FILE\n"); return 1; }
+	return pg_trait_file(argv[optind], fn, &o) == 0 ? 0 : 1;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // `pangene --gpus N`: main.c:117-142 for N devices of one node.  The command forks N - 1 workers BEFORE anything touches the GPU;
 // rank r takes device r and the r-th contiguous block of the PAF files (so that the ranks' W / BED lines, concatenated in rank
@@ -216,7 +255,8 @@ static int main_assoc(int argc, char *argv[])
 // genomes to a temporary file that rank 0 copies to stdout in rank order.
 // ---------------------------------------------------------------------------------------------------------------
 struct Output { int matrix = 0; bool call = false; int curves = 0; uint32_t curves_seed = 11; int dist = -1, dist_metric = 0; // curves: orders (0: none); dist: PG_DIST_* (-1: none)
-	bool assoc = false; double assoc_phi = 0.8; int assoc_count = 2, assoc_sign = 0; };
+	bool assoc = false; double assoc_phi = 0.8; int assoc_count = 2, assoc_sign = 0;
+	const char *trait = nullptr; int32_t trait_perm = 1000; uint32_t trait_seed = 11; };
 
 static int run_path(pg_opt_t &opt, int n_files, char **files, const uint8_t *ids_only, const Output &o, bool graph_lines, bool own_lines, int device = -1)
 {
@@ -266,6 +306,13 @@ static int run_path(pg_opt_t &opt, int n_files, char **files, const uint8_t *ids
 			pg_assoc_opt_init(&ao);
 			ao.min_phi = o.assoc_phi, ao.min_count = o.assoc_count, ao.sign = o.assoc_sign;
 			pg_write_assoc(g, &ao);
+			if (pg_last_error()) rc = 2;
+		}
+		else if (o.trait) {
+			pg_trait_opt_t to;
+			pg_trait_opt_init(&to);
+			to.n_perm = o.trait_perm, to.seed = o.trait_seed;
+			pg_write_trait(g, o.trait, &to);
 			if (pg_last_error()) rc = 2;
 		}
 		else if (opt.flag & PG_F_WRITE_BED_WALK) { if (own_lines) pg_write_bed(d, 1); }
@@ -330,6 +377,7 @@ static int run_sharded(pg_opt_t &opt, int W, int n_files, char **files, const Ou
 	if (o.curves) { std::fprintf(stderr, "ERROR: --curves needs every genome in one process; run it without --gpus\n"); return 1; }
 	if (o.dist >= 0) { std::fprintf(stderr, "ERROR: --dist needs every genome in one process; run it without --gpus\n"); return 1; }
 	if (o.assoc) { std::fprintf(stderr, "ERROR: --assoc needs every genome in one process; run it without --gpus\n"); return 1; }
+	if (o.trait) { std::fprintf(stderr, "ERROR: --trait needs every genome in one process; run it without --gpus\n"); return 1; }
 	const bool dev = pg_backend_is_device() != 0;
 	typedef int (*uid_fn)(void *); typedef int (*init_fn)(int32_t, int32_t, const void *); typedef int (*fin_fn)(void);
 	uid_fn rccl_uid = nullptr; init_fn rccl_init = nullptr; fin_fn rccl_fin = nullptr;
@@ -474,6 +522,7 @@ int main(int argc, char *argv[])
 	if (argc >= 2 && std::strcmp(argv[1], "curves") == 0) return main_curves(argc - 1, argv + 1);
 	if (argc >= 2 && std::strcmp(argv[1], "dist") == 0) return main_dist(argc - 1, argv + 1);
 	if (argc >= 2 && std::strcmp(argv[1], "assoc") == 0) return main_assoc(argc - 1, argv + 1);
+	if (argc >= 2 && std::strcmp(argv[1], "trait") == 0) return main_trait(argc - 1, argv + 1);
 	int matrix = 0, n_gpus = 1; // matrix: 1 presence, 2 counts
 	bool call = false;
 	int curves = 0; // orders of --curves (0: not asked for)
@@ -482,11 +531,15 @@ int main(int argc, char *argv[])
 	bool assoc = false; // --assoc
 	double assoc_phi_v = 0.8;
 	int assoc_count = 2, assoc_sign_v = PG_ASSOC_BOTH;
+	const char *trait = nullptr; // --trait=FILE
+	int32_t trait_perm_v = 1000;
+	uint32_t trait_seed = 11;
 	static const struct option lopts[] = {
 		{ "bed", optional_argument, nullptr, 301 }, { "ori-sc", no_argument, nullptr, 302 }, { "matrix", optional_argument, nullptr, 303 }, { "call", no_argument, nullptr, 305 },
 		{ "curves", optional_argument, nullptr, 306 }, { "curves-seed", required_argument, nullptr, 307 },
 		{ "dist", optional_argument, nullptr, 308 }, { "dist-metric", required_argument, nullptr, 309 },
 		{ "assoc", optional_argument, nullptr, 310 }, { "assoc-min-count", required_argument, nullptr, 311 }, { "assoc-sign", required_argument, nullptr, 312 },
+		{ "trait", required_argument, nullptr, 313 }, { "trait-perm", required_argument, nullptr, 314 }, { "trait-seed", required_argument, nullptr, 315 },
 		{ "gpus", required_argument, nullptr, 304 }, { "procs", required_argument, nullptr, 304 },
 		{ "version", no_argument, nullptr, 401 }, { nullptr, 0, nullptr, 0 } };
 	pg_opt_t opt;
@@ -554,6 +607,11 @@ int main(int argc, char *argv[])
 		case 312:
 			if ((assoc_sign_v = assoc_sign(optarg)) < 0) { std::fprintf(stderr, "ERROR: --assoc-sign must be pos, neg or both\n"); return 1; }
 			break;
+		case 313: trait = optarg; break;
+		case 314:
+			if (!trait_perm(optarg, trait_perm_v)) { std::fprintf(stderr, "ERROR: --trait-perm must be in [0, 2147483646]\n"); return 1; }
+			break;
+		case 315: trait_seed = (uint32_t)std::strtoul(optarg, nullptr, 10); break;
 		case 401: std::puts(PG_VERSION); return 0;
 		default: break;
 		}
@@ -562,7 +620,9 @@ int main(int argc, char *argv[])
 	if (curves && (matrix || call)) { std::fprintf(stderr, "ERROR: --curves cannot be combined with --matrix or --call\n"); return 1; }
 	if (dist >= 0 && (matrix || call || curves)) { std::fprintf(stderr, "ERROR: --dist cannot be combined with --matrix, --call or --curves\n"); return 1; }
 	if (assoc && (matrix || call || curves || dist >= 0)) { std::fprintf(stderr, "ERROR: --assoc cannot be combined with --matrix, --call, --curves or --dist\n"); return 1; }
+	if (trait && (matrix || call || curves || dist >= 0 || assoc)) { std::fprintf(stderr, "ERROR: --trait cannot be combined with --matrix, --call, --curves, --dist or --assoc\n"); return 1; }
 	Output o;
+	o.trait = trait, o.trait_perm = trait_perm_v, o.trait_seed = trait_seed;
 	o.assoc = assoc, o.assoc_phi = assoc_phi_v, o.assoc_count = assoc_count, o.assoc_sign = assoc_sign_v;
 	o.curves = curves, o.curves_seed = curves_seed;
 	o.dist = dist, o.dist_metric = dist_metric_v;

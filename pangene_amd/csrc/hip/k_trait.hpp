@@ -1,0 +1,176 @@
+// ------------------------------------------------------------------------------------------------
+// Gene-trait association (pga_pan_trait): the third member of the k_dist.hpp / k_assoc.hpp family -- an all-pairs AND + popcount over
+// bit rows, here GENE rows against PERMUTED COPIES OF ONE LABEL ROW.  With N columns, y the label row, t = |y|, a = |B_g|,
+// s = |B_g & y|, D = s N - a t: permutation p gives s_p = |B_g & y_p|, D_p = s_p N - a t, and k_g counts the p with |D_p| >= |D|.
+// For fixed a, t, N that is s_p <= lo_g or s_p >= hi_g with lo_g = floor((a t - |D|) / N) and hi_g = ceil((a t + |D|) / N).
+//   obs    k_trait_obs: a, s of every row (8 lanes a row, as k_assoc_count), the two thresholds and the eligibility; a row that is not
+//          eligible gets lo = -1 and hi = INT32_MAX, which no count meets.
+//   perm   k_trait_perm: the label rows of one batch of permutations, made here from the one uploaded label row.  One lane per
+//          permutation runs the swap sequence curves pins (Fisher-Yates from the last column down, j = next() % (i + 1), splitmix64
+//          from mix((seed << 32) | p)) over a private bit row: swapping the bits i and j of the row is what applying the order to the
+//          labels gives.  The 64 rows of a wave are lane-interleaved (word k of lane l at k * 64 + l), so a wave's access to "its"
+//          word i >> 5 is one 256-byte line / 64 distinct LDS banks-pairs, and the accesses to the words j >> 5 spread over the banks
+//          by lane.  The rows live in LDS while 64 of them fit 32 KiB (W <= 128, N <= 4 096) and in a global scratch buffer of the
+//          same layout beyond; the finished rows are written row-major for the count kernel.  The 64-bit % is the compiler's: the
+//          same j as the host's for every x.
+//   count  k_trait_count: one workgroup per 128 genes x 128 permutations, the tile scheme of k_dist_shared / k_assoc_pairs (a third
+//          copy of the staging and the micro-tile: sharing it would have meant touching two kernels whose measured numbers are in
+//          DESIGN §8).  Rectangular grid (x: gene tile, y: permutation tile of the batch).  Epilogue: each count against its row's
+//          lo / hi, the hits of a row summed over the 16 lanes that share it, ONE atomicAdd per (tile, row) with a hit into k[g].
+// ------------------------------------------------------------------------------------------------
+constexpr int32_t TRAIT_TILE = DIST_TILE, TRAIT_KC = DIST_KC, TRAIT_LDW = DIST_LDW, TRAIT_SIDE = DIST_SIDE;
+constexpr int32_t TRAIT_LOADS = DIST_LOADS;
+constexpr int32_t TRAIT_ROW_LANES = 8;     // lanes that share one row in k_trait_obs
+constexpr int32_t TRAIT_PERM_LDS_W = 128;  // words of a label row up to which a wave's 64 rows stay in LDS (32 KiB)
+constexpr int32_t TRAIT_NEVER_LO = -1, TRAIT_NEVER_HI = 0x7fffffff;
+
+__global__ __launch_bounds__(BLOCK) void k_trait_obs(const uint32_t *__restrict__ bits, const uint32_t *__restrict__ label, int32_t G, int32_t W, int32_t N,
+                                                     int32_t t_sum, int32_t min_count, int32_t *__restrict__ a_out, int32_t *__restrict__ s_out,
+                                                     int32_t *__restrict__ lo_out, int32_t *__restrict__ hi_out)
+{
+	const int64_t g = (int64_t)blockIdx.x * (BLOCK / TRAIT_ROW_LANES) + (int64_t)(threadIdx.x / TRAIT_ROW_LANES);
+	const int32_t l = (int32_t)threadIdx.x % TRAIT_ROW_LANES;
+	int32_t a = 0, s = 0;
+	if (g < G) {
+		const uint32_t *row = bits + (size_t)g * (size_t)W;
+		for (int32_t k = l; k < W; k += TRAIT_ROW_LANES) {
+			const uint32_t w = row[k];
+			a += __popc(w), s += __popc(w & label[k]);
+		}
+	}
+	a += __shfl_xor(a, 1, WAVE), s += __shfl_xor(s, 1, WAVE);
+	a += __shfl_xor(a, 2, WAVE), s += __shfl_xor(s, 2, WAVE);
+	a += __shfl_xor(a, 4, WAVE), s += __shfl_xor(s, 4, WAVE);
+	if (g < G && l == 0) {
+		int32_t lo = TRAIT_NEVER_LO, hi = TRAIT_NEVER_HI;
+		if (min(a, N - a) >= min_count) {
+			const int64_t c = (int64_t)a * t_sum, d0 = (int64_t)s * N - c, d = d0 < 0 ? -d0 : d0; // all below 2^48
+			lo = c >= d ? (int32_t)((c - d) / N) : -1;
+			hi = (int32_t)((c + d + N - 1) / N);
+		}
+		a_out[g] = a, s_out[g] = s, lo_out[g] = lo, hi_out[g] = hi;
+	}
+}
+
+__device__ __forceinline__ uint64_t trait_mix64(uint64_t z) // splitmix64's output function
+{
+	z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+	z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+	return z ^ (z >> 31);
+}
+
+// the swaps of permutation p over the lane's row: word k of the row at row[k * WAVE]
+template <class P> __device__ __forceinline__ void trait_shuffle(P row, int32_t N, uint32_t seed, uint32_t p)
+{
+	uint64_t x = trait_mix64((uint64_t)seed << 32 | (uint64_t)p);
+	for (int32_t i = N - 1; i >= 1; --i) {
+		x += 0x9E3779B97F4A7C15ull;
+		const int32_t j = (int32_t)(trait_mix64(x) % (uint64_t)(i + 1));
+		const int32_t wi = (i >> 5) * WAVE, wj = (j >> 5) * WAVE;
+		const uint32_t d = ((row[wi] >> (i & 31)) ^ (row[wj] >> (j & 31))) & 1u; // the two labels differ: both flip
+		row[wi] ^= d << (i & 31);
+		row[wj] ^= d << (j & 31); // (read again: wi may be wj)
+	}
+}
+
+// grid: ceil(nb / 64) workgroups of ONE wave; permutation p0 + q of the batch, q < nb, is row q of rows[nb][W].  USE_LDS: the wave's
+// rows in LDS; otherwise in work[workgroup][W][64].  Lanes past nb run a permutation nobody reads and write nothing.
+template <bool USE_LDS>
+__global__ __launch_bounds__(WAVE) void k_trait_perm(const uint32_t *__restrict__ label, int32_t N, int32_t W, uint32_t seed, uint32_t p0, int32_t nb,
+                                                     uint32_t *__restrict__ work, uint32_t *__restrict__ rows)
+{
+	__shared__ uint32_t sh[USE_LDS ? TRAIT_PERM_LDS_W * WAVE : 1];
+	const int32_t l = (int32_t)threadIdx.x;
+	const int64_t q0 = (int64_t)blockIdx.x * WAVE;
+	uint32_t *mine = USE_LDS ? sh : work + (size_t)blockIdx.x * (size_t)W * WAVE;
+	for (int32_t k = 0; k < W; ++k) mine[k * WAVE + l] = label[k];
+	trait_shuffle(mine + l, N, seed, p0 + (uint32_t)(q0 + l));
+	if (USE_LDS) __syncthreads(); // (one wave: orders the lanes' LDS stores before the reads across lanes below)
+	else __threadfence_block();
+	const int32_t n_row = (int32_t)min((int64_t)WAVE, (int64_t)nb - q0);
+	for (int32_t q = 0; q < n_row; ++q) {
+		uint32_t *out = rows + (size_t)(q0 + q) * (size_t)W;
+		for (int32_t k = l; k < W; k += WAVE) out[k] = mine[k * WAVE + q];
+	}
+}
+
+// grid: (ceil(G / 128), ceil(nb / 128)).  bits[G][W], rows[nb][W], lo / hi[G]; k[g] += hits
+__global__ __launch_bounds__(BLOCK, 2) void k_trait_count(const uint32_t *__restrict__ bits, const uint32_t *__restrict__ rows, const int32_t *__restrict__ lo,
+                                                         const int32_t *__restrict__ hi, int32_t G, int32_t nb, int32_t W, int32_t n_chunk,
+                                                         int32_t *__restrict__ k_out)
+{
+	__shared__ uint4 sh4[2 * TRAIT_SIDE / 4];
+	uint32_t *sh = (uint32_t *)sh4;
+	const int32_t t = (int32_t)threadIdx.x, tx = t & 15, ty = t >> 4;
+	const int32_t i0 = (int32_t)blockIdx.x * TRAIT_TILE, j0 = (int32_t)blockIdx.y * TRAIT_TILE;
+
+	uint32_t acc[8][8];
+#pragma unroll
+	for (int32_t ii = 0; ii < 8; ++ii)
+#pragma unroll
+		for (int32_t jj = 0; jj < 8; ++jj) acc[ii][jj] = 0;
+
+	const uint32_t *sa = sh, *sb = sh + TRAIT_SIDE;
+	for (int32_t c = 0; c < n_chunk; ++c) {
+#pragma unroll
+		for (int32_t side = 0; side < 2; ++side) {
+			uint32_t v[TRAIT_LOADS / 2];
+			const int32_t g0 = side ? j0 : i0, n_row = side ? nb : G;
+			const uint32_t *src = side ? rows : bits;
+#pragma unroll
+			for (int32_t r = 0; r < TRAIT_LOADS / 2; ++r) {
+				const int32_t e = t + BLOCK * r, g = g0 + (e >> 5), k = c * TRAIT_KC + (e & 31);
+				v[r] = (g < n_row && k < W) ? src[(size_t)g * (size_t)W + (size_t)k] : 0u;
+			}
+			if (side == 0 && c > 0) __syncthreads(); // everyone is done with the previous chunk
+#pragma unroll
+			for (int32_t r = 0; r < TRAIT_LOADS / 2; ++r) {
+				const int32_t e = t + BLOCK * r;
+				sh[side * TRAIT_SIDE + (e >> 5) * TRAIT_LDW + (e & 31)] = v[r];
+			}
+		}
+		__syncthreads();
+		const int32_t kk_hi = min(TRAIT_KC, (W - c * TRAIT_KC + 3) & ~3); // the words past W are staged as zeros
+#pragma unroll 1
+		for (int32_t kk = 0; kk < kk_hi; kk += 4) {
+			uint4 a[8], b[8];
+#pragma unroll
+			for (int32_t ii = 0; ii < 8; ++ii) a[ii] = *(const uint4 *)(sa + (ty + 16 * ii) * TRAIT_LDW + kk);
+#pragma unroll
+			for (int32_t jj = 0; jj < 8; ++jj) b[jj] = *(const uint4 *)(sb + (tx + 16 * jj) * TRAIT_LDW + kk);
+#pragma unroll
+			for (int32_t ii = 0; ii < 8; ++ii)
+#pragma unroll
+				for (int32_t jj = 0; jj < 8; ++jj) {
+					uint32_t x = acc[ii][jj];
+					x = __popc(a[ii].x & b[jj].x) + x; asm volatile("" : "+v"(x));
+					x = __popc(a[ii].y & b[jj].y) + x; asm volatile("" : "+v"(x));
+					x = __popc(a[ii].z & b[jj].z) + x; asm volatile("" : "+v"(x));
+					x = __popc(a[ii].w & b[jj].w) + x; asm volatile("" : "+v"(x));
+					acc[ii][jj] = x;
+				}
+		}
+	}
+
+	// the epilogue: the thread's 8 columns that exist, then per row its 8 counts against the row's thresholds; the 16 lanes tx = 0..15
+	// of a row are neighbours in the wave, so four shuffles sum the row's hits and lane tx = 0 adds them
+	uint32_t col_ok = 0;
+#pragma unroll
+	for (int32_t jj = 0; jj < 8; ++jj) col_ok |= (uint32_t)(j0 + tx + 16 * jj < nb) << jj;
+#pragma unroll
+	for (int32_t ii = 0; ii < 8; ++ii) {
+		const int32_t g = i0 + ty + 16 * ii;
+		const int32_t l = g < G ? lo[g] : TRAIT_NEVER_LO, h = g < G ? hi[g] : TRAIT_NEVER_HI;
+		int32_t hits = 0;
+#pragma unroll
+		for (int32_t jj = 0; jj < 8; ++jj) {
+			const int32_t s = (int32_t)acc[ii][jj];
+			hits += (int32_t)((col_ok >> jj & 1u) && (s <= l || s >= h));
+		}
+		hits += __shfl_xor(hits, 1, WAVE);
+		hits += __shfl_xor(hits, 2, WAVE);
+		hits += __shfl_xor(hits, 4, WAVE);
+		hits += __shfl_xor(hits, 8, WAVE);
+		if (tx == 0 && hits > 0) atomicAdd(k_out + g, hits);
+	}
+}

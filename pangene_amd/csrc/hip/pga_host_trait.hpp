@@ -1,0 +1,133 @@
+// pga_pan_trait (include/pangene_hip.h): the permutation test of pangene trait on the device (k_trait.hpp).  Context-free: it runs on a
+// stream of its own on the current device.  The device buffers and the page-locked results are kept from call to call and only ever
+// grow; pga_host_trim(0) gives them back.  The results wait in the page-locked buffers until the next call.
+//
+// The permutations go through in batches of pga_trait_batch() label rows (65 536, or PANGENE_TRAIT_BATCH=n up to 4 194 304), so device memory is
+// bounded by G, N and the batch and not by n: per batch k_trait_perm makes the rows and k_trait_count counts them against every gene,
+// one after the other on the one stream.  Nothing is read back between the batches; a, s and k come down once at the end.
+
+constexpr int32_t TRAIT_MAX_COL = 16777215, TRAIT_MAX_GENE = 16777215;
+constexpr int32_t TRAIT_MAX_PERM = 2147483646; // 2^31 - 2
+constexpr int32_t TRAIT_BATCH = 65536;
+
+namespace {
+struct TraitDev {
+	std::mutex mu;
+	hipStream_t st = nullptr;
+	enum { BITS, LABEL, A, S, LO, HI, K, ROWS, WORK, N_BUF };
+	void *p[N_BUF] = {};
+	size_t cap[N_BUF] = {};
+	void *host = nullptr; // page-locked: a, s, k
+	size_t host_cap = 0;
+	template <class T> T *get(int i, size_t n) // at least n elements of T in buffer i (contents not kept)
+	{
+		const size_t bytes = sizeof(T) * (n ? n : 1);
+		if (cap[i] < bytes) {
+			if (p[i]) (void)hipFree(p[i]);
+			p[i] = nullptr, cap[i] = 0;
+			if (hipMalloc(&p[i], bytes) != hipSuccess) { p[i] = nullptr; return nullptr; }
+			cap[i] = bytes;
+		}
+		return (T *)p[i];
+	}
+	int32_t *get_host(size_t n)
+	{
+		const size_t bytes = sizeof(int32_t) * (n ? n : 1);
+		if (host_cap < bytes) {
+			if (host) (void)hipHostFree(host);
+			host = nullptr, host_cap = 0;
+			if (hipHostMalloc(&host, bytes, hipHostMallocDefault) != hipSuccess) { host = nullptr; return nullptr; }
+			host_cap = bytes;
+		}
+		return (int32_t *)host;
+	}
+	void release()
+	{
+		for (int i = 0; i < N_BUF; ++i) { if (p[i]) (void)hipFree(p[i]); p[i] = nullptr, cap[i] = 0; }
+		if (host) (void)hipHostFree(host);
+		host = nullptr, host_cap = 0;
+	}
+};
+TraitDev g_trait;
+}
+
+static void trait_release() { std::lock_guard<std::mutex> lk(g_trait.mu); g_trait.release(); }
+
+extern "C" int32_t pga_trait_batch(void)
+{
+	if (const char *s = getenv("PANGENE_TRAIT_BATCH")) { const long long v = atoll(s); if (v >= 1 && v <= (1 << 22)) return (int32_t)v; }
+	return TRAIT_BATCH;
+}
+
+#define TRAITCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
+	fprintf(stderr, "[E::pga_pan_trait] %s:%d: %s\n", __FILE__, __LINE__, hipGetErrorString(e_)); return PGA_ERR_NO_DEVICE; } } while (0)
+#define TRAITMEM(p) do { if ((p) == nullptr) return PGA_ERR_NOMEM; } while (0)
+
+extern "C" int pga_pan_trait(const pga_trait_in_t *in, pga_trait_out_t *out)
+{
+	if (out == nullptr) return PGA_ERR_ARG;
+	out->a = out->s = out->k = nullptr;
+	if (in == nullptr) return PGA_ERR_ARG;
+	const int32_t G = in->n_gene, N = in->n_col, n = in->n_perm;
+	if (G < 0 || N < 0 || n < 0 || in->min_count < 1) return PGA_ERR_ARG;
+	if (N > TRAIT_MAX_COL || G > TRAIT_MAX_GENE || n > TRAIT_MAX_PERM) return PGA_ERR_RANGE;
+	const int32_t W = (N + 31) / 32;
+	if (W > 0 && ((G > 0 && in->bits == nullptr) || in->label == nullptr)) return PGA_ERR_ARG;
+	std::lock_guard<std::mutex> lk(g_trait.mu);
+	TraitDev &m = g_trait;
+	int32_t *h_res = m.get_host((size_t)G * 3);
+	TRAITMEM(h_res);
+	out->a = h_res, out->s = h_res + G, out->k = h_res + 2 * (size_t)G;
+	memset(h_res, 0, sizeof(int32_t) * 3 * (size_t)G);
+	if (G == 0 && in->perm_rows == nullptr) return 0;
+	if (W == 0) return 0; // no columns: every count is 0
+	int32_t t_sum = 0;
+	for (int32_t k = 0; k < W; ++k) t_sum += __builtin_popcount(in->label[k]);
+	if (m.st == nullptr) TRAITCHK(hipStreamCreateWithFlags(&m.st, hipStreamNonBlocking));
+	hipStream_t st = m.st;
+
+	const size_t n_word = (size_t)G * (size_t)W;
+	const int32_t B = (int32_t)std::min<int64_t>(pga_trait_batch(), std::max<int32_t>(n, 1));
+	const bool lds = W <= TRAIT_PERM_LDS_W;
+	const int64_t perm_blocks = ((int64_t)B + WAVE - 1) / WAVE;
+	uint32_t *d_bits = m.get<uint32_t>(TraitDev::BITS, n_word), *d_label = m.get<uint32_t>(TraitDev::LABEL, (size_t)W);
+	int32_t *d_a = m.get<int32_t>(TraitDev::A, (size_t)G), *d_s = m.get<int32_t>(TraitDev::S, (size_t)G), *d_lo = m.get<int32_t>(TraitDev::LO, (size_t)G);
+	int32_t *d_hi = m.get<int32_t>(TraitDev::HI, (size_t)G), *d_k = m.get<int32_t>(TraitDev::K, (size_t)G);
+	uint32_t *d_rows = m.get<uint32_t>(TraitDev::ROWS, (size_t)B * (size_t)W);
+	uint32_t *d_work = m.get<uint32_t>(TraitDev::WORK, lds ? 1 : (size_t)perm_blocks * (size_t)W * WAVE);
+	TRAITMEM(d_bits); TRAITMEM(d_label); TRAITMEM(d_a); TRAITMEM(d_s); TRAITMEM(d_lo); TRAITMEM(d_hi); TRAITMEM(d_k); TRAITMEM(d_rows); TRAITMEM(d_work);
+	if (n_word) TRAITCHK(hipMemcpyAsync(d_bits, in->bits, sizeof(uint32_t) * n_word, hipMemcpyHostToDevice, st));
+	TRAITCHK(hipMemcpyAsync(d_label, in->label, sizeof(uint32_t) * (size_t)W, hipMemcpyHostToDevice, st));
+	TRAITCHK(hipMemsetAsync(d_k, 0, sizeof(int32_t) * (size_t)(G ? G : 1), st));
+	if (G > 0) {
+		const unsigned row_blocks = (unsigned)(((int64_t)G + BLOCK / TRAIT_ROW_LANES - 1) / (BLOCK / TRAIT_ROW_LANES));
+		hipLaunchKernelGGL(k_trait_obs, dim3(row_blocks), dim3(BLOCK), 0, st, d_bits, d_label, G, W, N, t_sum, in->min_count, d_a, d_s, d_lo, d_hi);
+	}
+	const int32_t n_chunk = (W + TRAIT_KC - 1) / TRAIT_KC;
+	const unsigned gene_tiles = (unsigned)((G + TRAIT_TILE - 1) / TRAIT_TILE);
+	for (int64_t done = 0; done < n; done += B) {
+		const int32_t nb = (int32_t)std::min<int64_t>(B, (int64_t)n - done);
+		const unsigned pb = (unsigned)((nb + WAVE - 1) / WAVE);
+		const uint32_t p0 = (uint32_t)(done + 1); // permutations are numbered from 1
+		if (lds) hipLaunchKernelGGL(k_trait_perm<true>, dim3(pb), dim3(WAVE), 0, st, d_label, N, W, in->seed, p0, nb, d_work, d_rows);
+		else hipLaunchKernelGGL(k_trait_perm<false>, dim3(pb), dim3(WAVE), 0, st, d_label, N, W, in->seed, p0, nb, d_work, d_rows);
+		if (done == 0 && in->perm_rows != nullptr) { // tests only: the label rows of the first batch
+			TRAITCHK(hipGetLastError());
+			TRAITCHK(hipMemcpyAsync(in->perm_rows, d_rows, sizeof(uint32_t) * (size_t)nb * (size_t)W, hipMemcpyDeviceToHost, st));
+			TRAITCHK(hipStreamSynchronize(st));
+		}
+		if (G > 0)
+			hipLaunchKernelGGL(k_trait_count, dim3(gene_tiles, (unsigned)((nb + TRAIT_TILE - 1) / TRAIT_TILE)), dim3(BLOCK), 0, st, d_bits, d_rows, d_lo, d_hi, G, nb, W,
+			                   n_chunk, d_k);
+		TRAITCHK(hipGetLastError());
+	}
+	if (G > 0) {
+		TRAITCHK(hipMemcpyAsync(h_res, d_a, sizeof(int32_t) * (size_t)G, hipMemcpyDeviceToHost, st));
+		TRAITCHK(hipMemcpyAsync(h_res + G, d_s, sizeof(int32_t) * (size_t)G, hipMemcpyDeviceToHost, st));
+		TRAITCHK(hipMemcpyAsync(h_res + 2 * (size_t)G, d_k, sizeof(int32_t) * (size_t)G, hipMemcpyDeviceToHost, st));
+	}
+	TRAITCHK(hipStreamSynchronize(st));
+	return 0;
+}
+#undef TRAITCHK
+#undef TRAITMEM
