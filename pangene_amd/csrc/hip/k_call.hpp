@@ -12,6 +12,9 @@
 // compared element by element with the first of its run -- and, when that differs (a collision), with the records before it in the
 // run -- so that a collision never merges two alleles.  Genes: every interior step as (bubble, segment) -> its position in record
 // order, sorted; the first of each key is the gene's first appearance.
+// Tested directly, without a graph: tests/support/call_direct.py gives pga_call_bubbles walks and bubbles no GFA has (hairpins, shared
+// end vertices, empty walks, R > N and I > R, few hash bits) and compares every output array with the plain restatement of the
+// contract in tests/support/call_ref.py.
 // ------------------------------------------------------------------------------------------------
 
 __device__ __forceinline__ int64_t call_lower_u64(const uint64_t *a, int64_t lo, int64_t hi, uint64_t x)

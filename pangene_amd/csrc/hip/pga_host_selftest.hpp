@@ -4,7 +4,7 @@
 
 
 // ------------------------------------------------------------------------------------------------
-// self-test hooks for the device primitives (tests/test_prims_gpu.py): sort / scan arbitrary host data
+// self-test hooks for the device primitives (tests/test_hip_parity.py: test_device_primitives, test_radix_sort_key_widths): sort / scan arbitrary host data
 // ------------------------------------------------------------------------------------------------
 extern "C" int pga_selftest_sort(uint64_t *keys, uint32_t *vals, int64_t n, int32_t n_bits)
 {

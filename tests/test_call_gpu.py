@@ -14,6 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
 HIP = os.path.join(ROOT, "pangene_amd", "bin", "pangene")
 ORA = os.path.join(ROOT, "tests", "_build", "pangene_oraclehost")
+DIRECT = os.path.join(ROOT, "tests", "support", "call_direct.py")
 sys.path.insert(0, GOLD)
 sys.path.insert(0, ROOT)
 import make_call_outputs as mco  # noqa: E402
@@ -124,3 +125,29 @@ def test_device_equals_host_mutated(built, tmp_path, seed):
     from pangene_amd import synth
     files = synth.write_files(synth.mutate(synth.bact(16, 500, seed=seed), seed=seed), str(tmp_path / "m"))
     _device_vs_host(tmp_path, files)
+
+
+@pytest.mark.parametrize("hash_bits", [None, "1", "8"], ids=["hash32", "hash1", "hash8"])
+@pytest.mark.parametrize("which", ["exhaustive", "edges", "pileup", "graphlike"])
+def test_direct_cases(built, which, hash_bits):
+    """pga_call_bubbles on walks and bubbles no GFA reaches, all six output arrays equal to the plain restatement
+    (tests/support/call_direct.py, call_cases.py, call_ref.py): every walk of 1 .. 4 steps over 4 vertices against every bubble,
+    hairpins (ve == vs ^ 1), duplicated and skipped bubbles among them (exhaustive); 2 n_seg, n_walk, N and n_bub around the steps of
+    the key widths, a radix tile and the scans, empty walks first, last and in the middle, 8 bubbles on one end vertex, inputs
+    without a record, a step or a live bubble (edges); 20 200 records and 1.3 M interior steps from 400 steps, so that the sort
+    buffers grow twice, and 100 alleles a bubble behind a hash of 1 or 8 bits (pileup); 2 000 noisy walks, 3 000 bubbles (graphlike).
+    The expected arrays do not depend on PANGENE_CALL_HASH_BITS."""
+    env = {k: v for k, v in os.environ.items() if k != "PANGENE_CALL_HASH_BITS"}
+    if hash_bits is not None:
+        env["PANGENE_CALL_HASH_BITS"] = hash_bits
+    r = subprocess.run([sys.executable, DIRECT, which], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600, cwd=ROOT, env=env)
+    out = r.stdout.decode(errors="replace")
+    assert r.returncode == 0 and out.rstrip().endswith("ALL OK"), out[-3000:]
+
+
+def test_direct_refusals(built):
+    """a step or a bubble vertex outside [0, 2 n_seg) is PGA_ERR_ARG, a negative n_walk PGA_ERR_RANGE, each found before any device
+    work, and the good call straight afterwards is still right (tests/support/call_direct.py refusals)"""
+    r = subprocess.run([sys.executable, DIRECT, "refusals"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600, cwd=ROOT)
+    out = r.stdout.decode(errors="replace")
+    assert r.returncode == 0 and out.rstrip().endswith("ALL OK"), out[-3000:]

@@ -59,6 +59,29 @@ def test_device_primitives(hip):
             assert np.array_equal(out, exp), (n, mode)
 
 
+@pytest.mark.parametrize("n_bits", [1, 2, 7, 9, 41, 56, 57, 63, 64])
+def test_radix_sort_key_widths(hip, n_bits):
+    """device_radix_sort at the key widths of `pangene call` (pga_host_call.hpp: vb + bits_for(W), bbits, hb + bbits up to 63 bits,
+    bits_for(n_bub * n_seg)): below one digit, just past one, and past 40 bits up to all 64; n one below, at and one above a tile of
+    2 048 keys and 35 tiles with a partial last one.  Keys are uniform below 2^n_bits; a third have the top eight sorted bits all
+    set (at 56 and 64 bits that is the digit 255 of the last pass, the digit of the padding key ~0 of the partial tile), a third keep
+    3 bits only (heavy ties: the sort must be stable).  Keys and values must equal a stable argsort's."""
+    raw = C.CDLL(capi.LIB_HIP)
+    rng = np.random.default_rng(n_bits)
+    top = min(8, n_bits)
+    for n in (2047, 2048, 2049, 70_001):
+        k = rng.integers(0, 1 << n_bits, size=n, dtype=np.uint64)
+        kind = rng.integers(0, 3, size=n)
+        kind[-1], kind[0] = 1, 2  # the last key of the partial tile is a neighbour of the padding
+        k[kind == 1] |= np.uint64(((1 << top) - 1) << (n_bits - top))
+        k[kind == 2] &= np.uint64(7)
+        v = np.arange(n, dtype=np.uint32)
+        k2, v2 = k.copy(), v.copy()
+        assert raw.pga_selftest_sort(k2.ctypes.data_as(C.c_void_p), v2.ctypes.data_as(C.c_void_p), C.c_int64(n), C.c_int32(n_bits)) == 0
+        o = np.argsort(k, kind="stable")
+        assert np.array_equal(k2, k[o]) and np.array_equal(v2, v[o]), n
+
+
 @pytest.mark.parametrize("args", ["", "-p0 -a1", "-S", "-f0.3"])
 def test_sweep_slow_list_and_list_overflow(hip, ora, tmp_path, args):
     """synth.dense: hits with partners hundreds of slots away and waves with > 512 overlapping pairs leave the LDS pair
