@@ -231,6 +231,34 @@ void pg_write_dist(pg_graph_t *g, const pg_dist_opt_t *o);
 int  pg_pan_shared(const uint8_t *presence, int32_t n_item, int32_t n_asm, int32_t *shared);
 int  pg_pan_dist(const uint8_t *presence, int32_t n_item, int32_t n_asm, int32_t metric, double *out);
 
+/* A tree of the assemblies from the distances above (DESIGN.md section 8 "Trees" holds the definition).  The jaccard or diff distances
+ * become integers q = distance * 2^F (jaccard: F = 20, q = ((2^21)(u - s) + u) / (2u) with u = n_i + n_j - s, 0 for an empty union;
+ * diff: q = (n_i + n_j - 2s) << F, F = min(20, 29 - bitlength(largest difference)), PGA_ERR_RANGE when F < 0; shared is not a
+ * distance and is refused).  Neighbour-joining (PG_TREE_NJ) or UPGMA (PG_TREE_UPGMA) then joins slots 0 .. A - 1 in 64-bit integer
+ * arithmetic: ties go to the smallest slot i, then the smallest j, slot i stands for the new node and slot j retires.  A join is one
+ * record of six int64: NJ (i, j, d_ij, R_i, R_j, r), with R the row sums over the r live slots, and at r = 3 the closing record
+ * (x, y, z, d_xy, d_xz, d_yz): A - 2 records; UPGMA (i, j, d_ij, n_i, n_j, r) with n the leaves below a slot: A - 1 records.
+ * A distance that reaches 2^30 in size on the way: PGA_ERR_RANGE.  The records come from the backend's pga_pan_join.
+ * Output: one Newick line; leaves are the gfa2matrix names (sample#hap), single-quoted when they hold one of (),:;[]' or white space;
+ * branch lengths in distance units, %.6f; an NJ tree is unrooted (a trifurcation at the last record) and its negative branch lengths
+ * are printed as they come; a UPGMA tree is rooted and ultrametric up to the integer floors.  One assembly: "(name);", two:
+ * "(a:h,b:h);" with h half their distance, none: ";".
+ * pg_tree_file: a GFA file (0, -1 when it cannot be opened, -2 on a backend or range error); pg_write_tree: the graph in memory after
+ * pg_graph_gen; pg_pan_join: q = int32 [n][n], symmetric with a zero diagonal (PGA_ERR_ARG otherwise), every entry below 2^29 in size
+ * (PGA_ERR_RANGE), 3 <= n <= 65 535, rec = room for n - 2 (NJ) or n - 1 (UPGMA) records; pg_pan_tree: a presence matrix, row-major
+ * uint8 [n_item][n_asm] with n_asm >= 3, through the shared-item counts to the records, *frac_bits = F; both return 0 or PGA_ERR_*. */
+enum { PG_TREE_NJ = 0, PG_TREE_UPGMA = 1 };
+typedef struct {
+	int32_t type;   /* PG_DIST_GENE or PG_DIST_ADJ [gene] */
+	int32_t metric; /* PG_DIST_JACCARD or PG_DIST_DIFF [jaccard] */
+	int32_t method; /* PG_TREE_NJ or PG_TREE_UPGMA [nj] */
+} pg_tree_opt_t;
+void pg_tree_opt_init(pg_tree_opt_t *o);
+int  pg_tree_file(const char *gfa_fn, const pg_tree_opt_t *o);
+void pg_write_tree(pg_graph_t *g, const pg_tree_opt_t *o);
+int  pg_pan_join(const int32_t *q, int32_t n, int32_t method, int64_t *rec);
+int  pg_pan_tree(const uint8_t *presence, int32_t n_item, int32_t n_asm, int32_t metric, int32_t method, int64_t *rec, int32_t *frac_bits);
+
 /* Gene associations: which genes travel together over the assemblies and which exclude each other.  Over the presence matrix of
  * gfa2matrix (gene g is in assembly a when its entry is > 0; rows in segment order), with A assemblies, a = |B_g|, b = |B_h|,
  * s = |B_g & B_h|: V_g = a (A - a), D = s A - a b, phi(g, h) = D / sqrt(V_g V_h).  Gene g is eligible when min(a, A - a) >= min_count

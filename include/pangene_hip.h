@@ -94,7 +94,7 @@ typedef struct {
  * Device layout limits (PGA_ERR_RANGE otherwise): coordinates inside a block < 2^31 (contigs beyond that arrive as virtual contigs,
  * see pga_genome_block_t; what remains out of reach is a single cluster of overlapping hits spanning 2^30 bp), < 2^30 hits and < 2^31
  * exons per shard, < 2^20 genes, < 2^24 genomes. */
-#define PGA_ABI_VERSION 10u  /* bumped whenever a struct of this header or the order of pga_backend_t changes; pga_create refuses another */
+#define PGA_ABI_VERSION 11u  /* bumped whenever a struct of this header or the order of pga_backend_t changes; pga_create refuses another */
 typedef struct {
 	uint32_t abi_version;        /* = PGA_ABI_VERSION of the header the caller was compiled against (PGA_ERR_ARG otherwise) */
 	int32_t n_genome;            /* genomes in this shard (may include genomes with 0 hits) */
@@ -381,6 +381,24 @@ typedef struct { const int32_t *a, *s, *k; } pga_trait_out_t;
 int pga_pan_trait(const pga_trait_in_t *in, pga_trait_out_t *out);
 int32_t pga_trait_batch(void); /* permutations per batch: 65 536, or PANGENE_TRAIT_BATCH */
 
+/* The joins of a tree (include/pangene_amd.h pg_pan_join, pangene tree): neighbour-joining (method 0) or UPGMA (method 1) over a
+ * fixed-point distance matrix, in integers throughout.  Context-free, like pan_shared.  Slots 0 .. n - 1 start live, d = q, r = the
+ * live slots, R[x] = the sum of d[x][y] over live y, n[x] = 1.  A join takes, over live pairs i < j, the smallest
+ * (r - 2) d[i][j] - R[i] - R[j] (NJ) or d[i][j] (UPGMA) in int64, ties to the smallest i and then the smallest j; records
+ * (i, j, d_ij, R_i, R_j, r) or (i, j, d_ij, n_i, n_j, r); sets d[i][k] = d[k][i] = floor((d[i][k] + d[j][k] - d_ij) / 2) or
+ * floor((n_i d[i][k] + n_j d[j][k]) / (n_i + n_j)) for every other live k; n_i += n_j; slot j retires.  NJ stops at r = 3 with the
+ * record (x, y, z, d_xy, d_xz, d_yz) of the live x < y < z; UPGMA at r = 1.
+ * In:  q[n][n], symmetric, zero diagonal, |q| < 2^29 (the caller's promise; an entry that breaks the last part raises the range flag).
+ * Out: rec[n_rec][6], n_rec = n - 2 (NJ) or n - 1 (UPGMA).  The array belongs to the backend and stays valid until its next pan_join.
+ * A distance of 2^30 or more in size on the way: PGA_ERR_RANGE (a flag on the device, read once at the end).
+ * Limits: 3 <= n (PGA_ERR_ARG otherwise), n <= 65 535 (PGA_ERR_RANGE). */
+typedef struct {
+	const int32_t *q;
+	int32_t n, method;
+} pga_join_in_t;
+typedef struct { const int64_t *rec; int32_t n_rec; } pga_join_out_t;
+int pga_pan_join(const pga_join_in_t *in, pga_join_out_t *out);
+
 /* the same ABI as a table, so the host driver is written once */
 struct pga_branch_par_s; struct pga_loop_xchg_s;
 typedef struct {
@@ -441,6 +459,7 @@ typedef struct {
 	int  (*pan_shared)(const pga_shared_in_t *, pga_shared_out_t *); /* may be NULL: the host driver then runs the same step itself */
 	int  (*pan_assoc)(const pga_assoc_in_t *, pga_assoc_out_t *); /* may be NULL: the host driver then runs the same step itself */
 	int  (*pan_trait)(const pga_trait_in_t *, pga_trait_out_t *); /* may be NULL: the host driver then runs the same step itself */
+	int  (*pan_join)(const pga_join_in_t *, pga_join_out_t *); /* may be NULL: the host driver then runs the same step itself */
 } pga_backend_t;
 
 const pga_backend_t *pga_backend(void);

@@ -287,6 +287,77 @@ def _trait_args(argv: Sequence[str]):
     return f, n, seed
 
 
+class pg_tree_opt_t(C.Structure):
+    """Tree options (include/pangene_amd.h): items (PG_DIST_GENE / PG_DIST_ADJ), distance (jaccard or diff), joining method."""
+    _fields_ = [("type", C.c_int32), ("metric", C.c_int32), ("method", C.c_int32)]
+
+
+TREE_METRICS = ("jaccard", "diff")
+TREE_METHODS = ("nj", "upgma")
+
+
+def tree_opt(lib: C.CDLL, type: str = "gene", metric: str = "jaccard", method: str = "nj") -> pg_tree_opt_t:
+    if metric not in TREE_METRICS:
+        raise ValueError("metric must be jaccard or diff (shared is not a distance)")
+    o = pg_tree_opt_t()
+    lib.pg_tree_opt_init(C.byref(o))
+    o.type, o.metric, o.method = DIST_TYPES.index(type), DIST_METRICS.index(metric), TREE_METHODS.index(method)
+    return o
+
+
+def pan_join(lib: C.CDLL, q, method: str = "nj"):
+    """The joins of a fixed-point distance matrix (int32 numpy array or torch tensor, shape (n, n), symmetric, zero diagonal, n >= 3)
+    through pg_pan_join: an int64 array of records, (n - 2, 6) for nj -- (i, j, d_ij, R_i, R_j, r), the last one
+    (x, y, z, d_xy, d_xz, d_yz) -- and (n - 1, 6) for upgma -- (i, j, d_ij, n_i, n_j, r)."""
+    import numpy as np
+    if hasattr(q, "detach"):  # torch tensor, on any device
+        q = q.detach().cpu().numpy()
+    q = np.ascontiguousarray(q, dtype=np.int32)
+    if q.ndim != 2 or q.shape[0] != q.shape[1]:
+        raise ValueError("q must be a square matrix")
+    n = q.shape[0]
+    m = TREE_METHODS.index(method)
+    rec = np.zeros((max(n - 2 + m, 0), 6), dtype=np.int64)
+    rc = lib.pg_pan_join(q.ctypes.data_as(C.POINTER(C.c_int32)), n, m, rec.ctypes.data_as(C.POINTER(C.c_int64)))
+    if rc != 0:
+        raise RuntimeError("pg_pan_join: status %d" % rc)
+    return rec
+
+
+def pan_tree(lib: C.CDLL, presence, metric: str = "jaccard", method: str = "nj"):
+    """The joins of the assemblies of an item x assembly presence matrix (bool numpy array or torch tensor, shape (M, A), A >= 3)
+    through pg_pan_tree: (records as pan_join returns them, F) with distances and row sums in units of 2^-F."""
+    import numpy as np
+    if metric not in TREE_METRICS:
+        raise ValueError("metric must be jaccard or diff (shared is not a distance)")
+    p = _presence(presence)
+    M, A = p.shape
+    m = TREE_METHODS.index(method)
+    rec = np.zeros((max(A - 2 + m, 0), 6), dtype=np.int64)
+    F = C.c_int32(0)
+    rc = lib.pg_pan_tree(p.ctypes.data_as(C.POINTER(C.c_uint8)), M, A, DIST_METRICS.index(metric), m, rec.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(F))
+    if rc != 0:
+        raise RuntimeError("pg_pan_tree: status %d" % rc)
+    return rec, int(F.value)
+
+
+def _tree_args(argv: Sequence[str]):
+    """(type, metric, method) of --tree[=gene|adj] / --tree-metric=STR / --tree-method=STR in argv; type = None without --tree."""
+    t, m, a = None, "jaccard", "nj"
+    for x in argv:
+        if x == "--tree": t = "gene"
+        elif x.startswith("--tree="): t = x.split("=", 1)[1]
+        elif x.startswith("--tree-metric="): m = x.split("=", 1)[1]
+        elif x.startswith("--tree-method="): a = x.split("=", 1)[1]
+    if t is not None and t not in DIST_TYPES:
+        raise ValueError("--tree must be gene or adj")
+    if m not in TREE_METRICS:
+        raise ValueError("--tree-metric must be jaccard or diff")
+    if a not in TREE_METHODS:
+        raise ValueError("--tree-method must be nj or upgma")
+    return t, m, a
+
+
 _API = {
     "pg_opt_init": (None, [C.POINTER(pg_opt_t)]),
     "pg_data_init": (C.c_void_p, []),
@@ -323,6 +394,11 @@ _API = {
     "pg_trait_file": (C.c_int, [C.c_char_p, C.c_char_p, C.c_void_p]),
     "pg_write_trait": (None, [C.c_void_p, C.c_char_p, C.c_void_p]),
     "pg_pan_trait": (C.c_int, [C.POINTER(C.c_uint8), C.POINTER(C.c_int8), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]),
+    "pg_tree_opt_init": (None, [C.c_void_p]),
+    "pg_tree_file": (C.c_int, [C.c_char_p, C.c_void_p]),
+    "pg_write_tree": (None, [C.c_void_p, C.c_void_p]),
+    "pg_pan_join": (C.c_int, [C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "pg_pan_tree": (C.c_int, [C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "pg_read_list_dict": (C.c_void_p, [C.c_char_p]),
     "pg_dict_destroy": (None, [C.c_void_p]),
     "pg_last_error": (C.c_int, []),
@@ -388,7 +464,7 @@ def parse_args(lib: C.CDLL, argv: Sequence[str]) -> pg_opt_t:
         elif a in ("--bed", "--bed=walk"): opt.flag |= PG_F_WRITE_BED_WALK
         elif a == "--bed=raw": opt.flag |= PG_F_WRITE_BED_RAW
         elif a == "--bed=flag": opt.flag |= PG_F_WRITE_BED_FLAG
-        elif a in ("--matrix", "--matrix=presence", "--matrix=count", "--call") or a.startswith("--curves") or a.startswith("--dist") or a.startswith("--assoc") or a.startswith("--trait"): pass  # handled by run()
+        elif a in ("--matrix", "--matrix=presence", "--matrix=count", "--call") or a.startswith("--curves") or a.startswith("--dist") or a.startswith("--assoc") or a.startswith("--trait") or a.startswith("--tree"): pass  # handled by run()
         elif a[:2] in ("-p", "-a", "-f", "-c", "-g", "-r", "-b", "-B", "-y", "-T", "-D", "-C", "-e", "-l", "-m", "-d", "-X", "-I", "-P"):
             v = a[2:] if len(a) > 2 else next(it)
             k = a[1]
@@ -445,6 +521,10 @@ def run(lib: C.CDLL, files: Sequence[str], argv: Sequence[str] = (), scan_only: 
     trait_fn, trait_n, trait_seed = _trait_args(argv)
     if trait_fn is not None and (any(x.startswith("--matrix") for x in argv) or "--call" in argv or n_curves or dist_type is not None or assoc_phi is not None):
         raise ValueError("--trait cannot be combined with --matrix, --call, --curves, --dist or --assoc")
+    tree_type, tree_metric, tree_method = _tree_args(argv)
+    if tree_type is not None and (any(x.startswith("--matrix") for x in argv) or "--call" in argv or n_curves or dist_type is not None or assoc_phi is not None
+                                  or trait_fn is not None):
+        raise ValueError("--tree cannot be combined with --matrix, --call, --curves, --dist, --assoc or --trait")
     fd, out = tempfile.mkstemp(prefix="pangene_", suffix=".out")
     os.close(fd)
     lib.pg_set_output(out.encode())
@@ -482,6 +562,10 @@ def run(lib: C.CDLL, files: Sequence[str], argv: Sequence[str] = (), scan_only: 
                     raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
             elif trait_fn is not None:
                 lib.pg_write_trait(g, trait_fn.encode(), C.byref(trait_opt(lib, trait_n, trait_seed)))
+                if lib.pg_last_error():
+                    raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
+            elif tree_type is not None:
+                lib.pg_write_tree(g, C.byref(tree_opt(lib, tree_type, tree_metric, tree_method)))
                 if lib.pg_last_error():
                     raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
             elif opt.flag & PG_F_WRITE_BED_WALK: lib.pg_write_bed(d, 1)

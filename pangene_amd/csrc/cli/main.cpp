@@ -62,12 +62,16 @@ static int usage(FILE *fp, const pg_opt_t *opt)
 	std::fprintf(fp, "    --trait=FILE  output the association of every gene with the binary traits of FILE (assembly, then 1/0/NA per trait)\n");
 	std::fprintf(fp, "    --trait-perm=INT  --trait: label permutations [1000]\n");
 	std::fprintf(fp, "    --trait-seed=INT  --trait: seed of the permutations [11]\n");
+	std::fprintf(fp, "    --tree[=STR]  output a tree of the assemblies (Newick) from their gene (gene) or gene-adjacency (adj) distances [gene]\n");
+	std::fprintf(fp, "    --tree-metric=STR  distance of --tree: jaccard or diff [jaccard]\n");
+	std::fprintf(fp, "    --tree-method=STR  --tree: nj (neighbour-joining, unrooted; negative branch lengths are printed as they come) or upgma [nj]\n");
 	std::fprintf(fp, "  Also: pangene gfa2matrix [-c] [-d FILE] [-p] <in.gfa>   (pangene.js gfa2matrix on a GFA file)\n");
 	std::fprintf(fp, "        pangene call [-m INT] [-w] [-b] [-e] [-d] [-p] [-s] [-r STR] <in.gfa>   (pangene.js call on a GFA file)\n");
 	std::fprintf(fp, "        pangene curves [-n INT] [-s INT] <in.gfa>   (accumulation curves of the gfa2matrix matrix of a GFA file)\n");
 	std::fprintf(fp, "        pangene dist [-t gene|adj] [-m jaccard|shared|diff] [-p] <in.gfa>   (pairwise distances of the assemblies of a GFA file)\n");
 	std::fprintf(fp, "        pangene assoc [-r FLOAT] [-c INT] [-s pos|neg|both] [-x INT] <in.gfa>   (co-occurring and avoiding gene pairs of a GFA file)\n");
 	std::fprintf(fp, "        pangene trait -t FILE [-n INT] [-s INT] [-c INT] [-p FLOAT] <in.gfa>   (gene-trait association over the matrix of a GFA file)\n");
+	std::fprintf(fp, "        pangene tree [-t gene|adj] [-m jaccard|diff] [-a nj|upgma] <in.gfa>   (neighbour-joining or UPGMA tree of the assemblies of a GFA file)\n");
 	return fp == stdout ? 0 : 1;
 }
 
@@ -180,6 +184,30 @@ static int main_dist(int argc, char *argv[])
 	return pg_dist_file(argv[optind], &o) == 0 ? 0 : 1;
 }
 
+static int tree_metric(const char *s) { return std::strcmp(s, "jaccard") == 0 ? PG_DIST_JACCARD : std::strcmp(s, "diff") == 0 ? PG_DIST_DIFF : -1; }
+static int tree_method(const char *s) { return std::strcmp(s, "nj") == 0 ? PG_TREE_NJ : std::strcmp(s, "upgma") == 0 ? PG_TREE_UPGMA : -1; }
+
+// `pangene tree`: a neighbour-joining or UPGMA tree of the assemblies of a GFA file from the distances `pangene dist` prints
+static int main_tree(int argc, char *argv[])
+{
+	pg_tree_opt_t o;
+	pg_tree_opt_init(&o);
+	int c;
+	while ((c = getopt(argc, argv, "t:m:a:")) >= 0) {
+		if (c == 't') { if ((o.type = dist_type(optarg)) < 0) { std::fprintf(stderr, "ERROR: -t must be gene or adj\n"); return 1; } }
+		else if (c == 'm') { if ((o.metric = tree_metric(optarg)) < 0) { std::fprintf(stderr, "ERROR: -m must be jaccard or diff (shared is not a distance)\n"); return 1; } }
+		else if (c == 'a') { if ((o.method = tree_method(optarg)) < 0) { std::fprintf(stderr, "ERROR: -a must be nj or upgma\n"); return 1; } }
+		else return 1;
+	}
+	if (argc - optind < 1) {
+		std::printf("Usage: pangene tree [options] <in.gfa>\nOptions:\n  -t STR   items: gene (gene content) or adj (gene adjacencies of the walks) [gene]\n"
+		            "  -m STR   distance: jaccard or diff [jaccard]\n"
+		            "  -a STR   nj (neighbour-joining: unrooted, negative branch lengths are printed as they come) or upgma [nj]\n");
+		return 0;
+	}
+	return pg_tree_file(argv[optind], &o) == 0 ? 0 : 1;
+}
+
 static int assoc_sign(const char *s) { return std::strcmp(s, "both") == 0 ? PG_ASSOC_BOTH : std::strcmp(s, "pos") == 0 ? PG_ASSOC_POS : std::strcmp(s, "neg") == 0 ? PG_ASSOC_NEG : -1; }
 static bool assoc_phi(const char *s, double &r) // a number in [0, 1]
 {
@@ -256,7 +284,8 @@ static int main_trait(int argc, char *argv[])
 // ---------------------------------------------------------------------------------------------------------------
 struct Output { int matrix = 0; bool call = false; int curves = 0; uint32_t curves_seed = 11; int dist = -1, dist_metric = 0; // curves: orders (0: none); dist: PG_DIST_* (-1: none)
 	bool assoc = false; double assoc_phi = 0.8; int assoc_count = 2, assoc_sign = 0;
-	const char *trait = nullptr; int32_t trait_perm = 1000; uint32_t trait_seed = 11; };
+	const char *trait = nullptr; int32_t trait_perm = 1000; uint32_t trait_seed = 11;
+	int tree = -1, tree_metric = 0, tree_method = 0; }; // tree: PG_DIST_GENE / PG_DIST_ADJ (-1: none)
 
 static int run_path(pg_opt_t &opt, int n_files, char **files, const uint8_t *ids_only, const Output &o, bool graph_lines, bool own_lines, int device = -1)
 {
@@ -313,6 +342,13 @@ static int run_path(pg_opt_t &opt, int n_files, char **files, const uint8_t *ids
 			pg_trait_opt_init(&to);
 			to.n_perm = o.trait_perm, to.seed = o.trait_seed;
 			pg_write_trait(g, o.trait, &to);
+			if (pg_last_error()) rc = 2;
+		}
+		else if (o.tree >= 0) {
+			pg_tree_opt_t tro;
+			pg_tree_opt_init(&tro);
+			tro.type = o.tree, tro.metric = o.tree_metric, tro.method = o.tree_method;
+			pg_write_tree(g, &tro);
 			if (pg_last_error()) rc = 2;
 		}
 		else if (opt.flag & PG_F_WRITE_BED_WALK) { if (own_lines) pg_write_bed(d, 1); }
@@ -378,6 +414,7 @@ static int run_sharded(pg_opt_t &opt, int W, int n_files, char **files, const Ou
 	if (o.dist >= 0) { std::fprintf(stderr, "ERROR: --dist needs every genome in one process; run it without --gpus\n"); return 1; }
 	if (o.assoc) { std::fprintf(stderr, "ERROR: --assoc needs every genome in one process; run it without --gpus\n"); return 1; }
 	if (o.trait) { std::fprintf(stderr, "ERROR: --trait needs every genome in one process; run it without --gpus\n"); return 1; }
+	if (o.tree >= 0) { std::fprintf(stderr, "ERROR: --tree needs every genome in one process; run it without --gpus\n"); return 1; }
 	const bool dev = pg_backend_is_device() != 0;
 	typedef int (*uid_fn)(void *); typedef int (*init_fn)(int32_t, int32_t, const void *); typedef int (*fin_fn)(void);
 	uid_fn rccl_uid = nullptr; init_fn rccl_init = nullptr; fin_fn rccl_fin = nullptr;
@@ -523,6 +560,7 @@ int main(int argc, char *argv[])
 	if (argc >= 2 && std::strcmp(argv[1], "dist") == 0) return main_dist(argc - 1, argv + 1);
 	if (argc >= 2 && std::strcmp(argv[1], "assoc") == 0) return main_assoc(argc - 1, argv + 1);
 	if (argc >= 2 && std::strcmp(argv[1], "trait") == 0) return main_trait(argc - 1, argv + 1);
+	if (argc >= 2 && std::strcmp(argv[1], "tree") == 0) return main_tree(argc - 1, argv + 1);
 	int matrix = 0, n_gpus = 1; // matrix: 1 presence, 2 counts
 	bool call = false;
 	int curves = 0; // orders of --curves (0: not asked for)
@@ -534,12 +572,14 @@ int main(int argc, char *argv[])
 	const char *trait = nullptr; // --trait=FILE
 	int32_t trait_perm_v = 1000;
 	uint32_t trait_seed = 11;
+	int tree = -1, tree_metric_v = PG_DIST_JACCARD, tree_method_v = PG_TREE_NJ; // --tree: PG_DIST_GENE / PG_DIST_ADJ (-1: not asked for)
 	static const struct option lopts[] = {
 		{ "bed", optional_argument, nullptr, 301 }, { "ori-sc", no_argument, nullptr, 302 }, { "matrix", optional_argument, nullptr, 303 }, { "call", no_argument, nullptr, 305 },
 		{ "curves", optional_argument, nullptr, 306 }, { "curves-seed", required_argument, nullptr, 307 },
 		{ "dist", optional_argument, nullptr, 308 }, { "dist-metric", required_argument, nullptr, 309 },
 		{ "assoc", optional_argument, nullptr, 310 }, { "assoc-min-count", required_argument, nullptr, 311 }, { "assoc-sign", required_argument, nullptr, 312 },
 		{ "trait", required_argument, nullptr, 313 }, { "trait-perm", required_argument, nullptr, 314 }, { "trait-seed", required_argument, nullptr, 315 },
+		{ "tree", optional_argument, nullptr, 316 }, { "tree-metric", required_argument, nullptr, 317 }, { "tree-method", required_argument, nullptr, 318 },
 		{ "gpus", required_argument, nullptr, 304 }, { "procs", required_argument, nullptr, 304 },
 		{ "version", no_argument, nullptr, 401 }, { nullptr, 0, nullptr, 0 } };
 	pg_opt_t opt;
@@ -612,6 +652,16 @@ int main(int argc, char *argv[])
 			if (!trait_perm(optarg, trait_perm_v)) { std::fprintf(stderr, "ERROR: --trait-perm must be in [0, 2147483646]\n"); return 1; }
 			break;
 		case 315: trait_seed = (uint32_t)std::strtoul(optarg, nullptr, 10); break;
+		case 316:
+			tree = optarg ? dist_type(optarg) : PG_DIST_GENE;
+			if (tree < 0) { std::fprintf(stderr, "ERROR: --tree must be gene or adj\n"); return 1; }
+			break;
+		case 317:
+			if ((tree_metric_v = tree_metric(optarg)) < 0) { std::fprintf(stderr, "ERROR: --tree-metric must be jaccard or diff (shared is not a distance)\n"); return 1; }
+			break;
+		case 318:
+			if ((tree_method_v = tree_method(optarg)) < 0) { std::fprintf(stderr, "ERROR: --tree-method must be nj or upgma\n"); return 1; }
+			break;
 		case 401: std::puts(PG_VERSION); return 0;
 		default: break;
 		}
@@ -621,7 +671,9 @@ int main(int argc, char *argv[])
 	if (dist >= 0 && (matrix || call || curves)) { std::fprintf(stderr, "ERROR: --dist cannot be combined with --matrix, --call or --curves\n"); return 1; }
 	if (assoc && (matrix || call || curves || dist >= 0)) { std::fprintf(stderr, "ERROR: --assoc cannot be combined with --matrix, --call, --curves or --dist\n"); return 1; }
 	if (trait && (matrix || call || curves || dist >= 0 || assoc)) { std::fprintf(stderr, "ERROR: --trait cannot be combined with --matrix, --call, --curves, --dist or --assoc\n"); return 1; }
+	if (tree >= 0 && (matrix || call || curves || dist >= 0 || assoc || trait)) { std::fprintf(stderr, "ERROR: --tree cannot be combined with --matrix, --call, --curves, --dist, --assoc or --trait\n"); return 1; }
 	Output o;
+	o.tree = tree, o.tree_metric = tree_metric_v, o.tree_method = tree_method_v;
 	o.trait = trait, o.trait_perm = trait_perm_v, o.trait_seed = trait_seed;
 	o.assoc = assoc, o.assoc_phi = assoc_phi_v, o.assoc_count = assoc_count, o.assoc_sign = assoc_sign_v;
 	o.curves = curves, o.curves_seed = curves_seed;

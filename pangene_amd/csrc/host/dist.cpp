@@ -30,6 +30,8 @@ void shared_host(const uint32_t *bits, int32_t A, int32_t W, int32_t *S)
 
 double t_count = 0; // seconds of the last count step (backend or host loops)
 
+} // namespace
+
 // bits[A][(M + 31) / 32] -> S[A][A]; 0 or a PGA_ERR_* code
 int shared_count(const std::vector<uint32_t> &bits, int32_t M, int32_t A, int32_t *S)
 {
@@ -50,7 +52,7 @@ int shared_count(const std::vector<uint32_t> &bits, int32_t M, int32_t A, int32_
 }
 
 // presence, row-major [M][A] (nonzero = item m in assembly a), -> assembly-major bit rows
-void to_bits(const uint8_t *p, int32_t M, int32_t A, std::vector<uint32_t> &bits)
+void presence_bits(const uint8_t *p, int32_t M, int32_t A, std::vector<uint32_t> &bits)
 {
 	const size_t W = ((size_t)M + 31) / 32;
 	bits.assign((size_t)A * W, 0);
@@ -62,6 +64,8 @@ void to_bits(const uint8_t *p, int32_t M, int32_t A, std::vector<uint32_t> &bits
 			if (row[a]) col[(size_t)a * W] |= bit;
 	}
 }
+
+namespace {
 
 // the gfa2matrix matrix (occurrences, [n_seg][A]): gene g is in assembly a when its entry is > 0
 void gene_bits(const int32_t *mat, int32_t G, int32_t A, std::vector<uint32_t> &bits)
@@ -92,6 +96,48 @@ void adj_bits(const std::vector<int32_t> &step, const std::vector<int64_t> &walk
 	bits.assign((size_t)A * W, 0);
 	for (const auto &h : has) bits[(size_t)h.first * W + (size_t)(h.second >> 5)] |= 1u << (h.second & 31);
 }
+
+} // namespace
+
+// the items of the assemblies of a GFA file as bit rows (0, or -1 when the file cannot be opened), and of the graph in memory
+int dist_items_file(const char *gfa_fn, int32_t type, std::vector<std::string> &names, std::vector<uint32_t> &bits, int32_t &M)
+{
+	GfaMatrix m;
+	if (gfa_matrix(gfa_fn, m) != 0) return -1;
+	const int32_t A = (int32_t)m.asm_a.size();
+	if (type == PG_DIST_ADJ) adj_bits(m.step, m.walk_off, m.walk_asm, A, bits, M);
+	else M = (int32_t)m.seg.size(), gene_bits(m.mat.data(), M, A, bits);
+	names.swap(m.asm_a);
+	return 0;
+}
+
+int dist_items_graph(pg_graph_t *q, int32_t type, std::vector<std::string> &names, std::vector<uint32_t> &bits, int32_t &M)
+{
+	names.clear();
+	if (type == PG_DIST_ADJ) {
+		// the walks pg_write_walk prints; the columns are their sample#hap in first-seen order, as gfa2matrix reads them back
+		std::vector<std::string> walk_name;
+		std::vector<int32_t> step;
+		std::vector<int64_t> walk_off;
+		if (walk_lists(q, walk_name, step, walk_off) != 0) return -1;
+		std::unordered_map<std::string, int32_t> col;
+		std::vector<int32_t> walk_asm(walk_name.size());
+		for (size_t w = 0; w < walk_name.size(); ++w) {
+			auto it = col.emplace(walk_name[w], (int32_t)names.size());
+			if (it.second) names.push_back(walk_name[w]);
+			walk_asm[w] = it.first->second;
+		}
+		adj_bits(step, walk_off, walk_asm, (int32_t)names.size(), bits, M);
+	} else {
+		std::vector<int32_t> mat;
+		if (graph_matrix(q, names, mat) != 0) return -1;
+		M = q->n_seg;
+		gene_bits(mat.data(), M, (int32_t)names.size(), bits);
+	}
+	return 0;
+}
+
+namespace {
 
 double metric_of(int32_t metric, int32_t ni, int32_t nj, int32_t s)
 {
@@ -166,14 +212,11 @@ void pg_dist_opt_init(pg_dist_opt_t *o)
 int pg_dist_file(const char *gfa_fn, const pg_dist_opt_t *o)
 {
 	const double t0 = now_sec();
-	GfaMatrix m;
-	if (gfa_matrix(gfa_fn, m) != 0) { std::fprintf(stderr, "Error: cannot open %s\n", gfa_fn ? gfa_fn : "-"); return -1; }
-	const int32_t A = (int32_t)m.asm_a.size();
+	std::vector<std::string> names;
 	std::vector<uint32_t> bits;
 	int32_t M;
-	if (o->type == PG_DIST_ADJ) adj_bits(m.step, m.walk_off, m.walk_asm, A, bits, M);
-	else M = (int32_t)m.seg.size(), gene_bits(m.mat.data(), M, A, bits);
-	const int rc = dist_run("file", m.asm_a, bits, M, o, t0);
+	if (dist_items_file(gfa_fn, o->type, names, bits, M) != 0) { std::fprintf(stderr, "Error: cannot open %s\n", gfa_fn ? gfa_fn : "-"); return -1; }
+	const int rc = dist_run("file", names, bits, M, o, t0);
 	if (rc != 0) { std::fprintf(stderr, "Error: pan_shared: %s\n", backend_default()->strerror(rc)); return -2; }
 	return 0;
 }
@@ -184,26 +227,7 @@ void pg_write_dist(pg_graph_t *q, const pg_dist_opt_t *o)
 	std::vector<std::string> names;
 	std::vector<uint32_t> bits;
 	int32_t M;
-	if (o->type == PG_DIST_ADJ) {
-		// the walks pg_write_walk prints; the columns are their sample#hap in first-seen order, as gfa2matrix reads them back
-		std::vector<std::string> walk_name;
-		std::vector<int32_t> step;
-		std::vector<int64_t> walk_off;
-		if (walk_lists(q, walk_name, step, walk_off) != 0) return;
-		std::unordered_map<std::string, int32_t> col;
-		std::vector<int32_t> walk_asm(walk_name.size());
-		for (size_t w = 0; w < walk_name.size(); ++w) {
-			auto it = col.emplace(walk_name[w], (int32_t)names.size());
-			if (it.second) names.push_back(walk_name[w]);
-			walk_asm[w] = it.first->second;
-		}
-		adj_bits(step, walk_off, walk_asm, (int32_t)names.size(), bits, M);
-	} else {
-		std::vector<int32_t> mat;
-		if (graph_matrix(q, names, mat) != 0) return;
-		M = q->n_seg;
-		gene_bits(mat.data(), M, (int32_t)names.size(), bits);
-	}
+	if (dist_items_graph(q, o->type, names, bits, M) != 0) return;
 	const int rc = dist_run("memory", names, bits, M, o, t0);
 	if (rc != 0) set_error(rc, "pg_write_dist");
 }
@@ -212,7 +236,7 @@ int pg_pan_shared(const uint8_t *presence, int32_t n_item, int32_t n_asm, int32_
 {
 	if (n_item < 0 || n_asm < 0 || ((size_t)n_item * (size_t)n_asm > 0 && presence == nullptr) || (n_asm > 0 && shared == nullptr)) return PGA_ERR_ARG;
 	std::vector<uint32_t> bits;
-	to_bits(presence, n_item, n_asm, bits);
+	presence_bits(presence, n_item, n_asm, bits);
 	return shared_count(bits, n_item, n_asm, shared);
 }
 
@@ -221,7 +245,7 @@ int pg_pan_dist(const uint8_t *presence, int32_t n_item, int32_t n_asm, int32_t 
 	if (metric < PG_DIST_JACCARD || metric > PG_DIST_DIFF) return PGA_ERR_ARG;
 	if (n_item < 0 || n_asm < 0 || ((size_t)n_item * (size_t)n_asm > 0 && presence == nullptr) || (n_asm > 0 && out == nullptr)) return PGA_ERR_ARG;
 	std::vector<uint32_t> bits;
-	to_bits(presence, n_item, n_asm, bits);
+	presence_bits(presence, n_item, n_asm, bits);
 	const size_t A = (size_t)n_asm;
 	std::vector<int32_t> S(A * A);
 	const int rc = shared_count(bits, n_item, n_asm, S.data());

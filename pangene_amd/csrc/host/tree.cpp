@@ -1,0 +1,274 @@
+// tree.cpp -- a tree of the assemblies from their pairwise distances (pg_tree_file, pg_write_tree, pg_pan_join, pg_pan_tree;
+// include/pangene_amd.h).  The distances of pangene dist become fixed-point integers, neighbour-joining or UPGMA joins them in integer
+// arithmetic (DESIGN.md section 8 "Trees": every sum is an integer sum, ties go to the smallest slot numbers), and only the Newick text
+// is floating point.  The joins run on the backend (pga_pan_join), or as the plain loops below when the backend has no such entry.
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+#include "pg_internal.hpp"
+
+namespace pgx {
+namespace {
+
+constexpr int64_t JOIN_IN_MAX = (int64_t)1 << 29; // an input entry stays below this in size
+constexpr int64_t JOIN_MAX = (int64_t)1 << 30;    // and every distance made on the way below this
+
+inline int64_t floor_div(int64_t a, int64_t b) { const int64_t q = a / b; return (a % b != 0 && ((a < 0) != (b < 0))) ? q - 1 : q; } // b > 0 here
+
+// S[A][A] -> q[A][A] = distance * 2^F; 0, or PGA_ERR_RANGE when the differences leave no fraction bit
+int to_fixed(const int32_t *S, int32_t A, int32_t metric, int32_t *q, int32_t *frac_bits)
+{
+	const size_t n = (size_t)A;
+	int32_t F = 20;
+	if (metric == PG_DIST_DIFF) {
+		int64_t mx = 0;
+		for (size_t i = 0; i < n; ++i)
+			for (size_t j = 0; j < n; ++j) mx = std::max<int64_t>(mx, (int64_t)S[i * n + i] + S[j * n + j] - 2 * (int64_t)S[i * n + j]);
+		int bl = 0;
+		while ((mx >> bl) != 0) ++bl;
+		F = std::min(20, 29 - bl);
+		if (F < 0) return PGA_ERR_RANGE;
+	}
+	for (size_t i = 0; i < n; ++i)
+		for (size_t j = 0; j < n; ++j) {
+			const int64_t ni = S[i * n + i], nj = S[j * n + j], s = S[i * n + j];
+			if (metric == PG_DIST_DIFF) q[i * n + j] = (int32_t)((ni + nj - 2 * s) << F);
+			else {
+				const int64_t u = ni + nj - s;
+				q[i * n + j] = u == 0 ? 0 : (int32_t)((((int64_t)1 << 21) * (u - s) + u) / (2 * u));
+			}
+		}
+	*frac_bits = F;
+	return 0;
+}
+
+// The joins as the definition states them, slot by slot: d[n][n] in place (32-bit storage: a value that passes the range test fits),
+// rec[n_rec][6].  The first distance out of range ends the run, which is what a flag read at the end amounts to.
+int join_host(std::vector<int32_t> &d, int32_t n, int32_t method, int64_t *rec)
+{
+	const size_t N = (size_t)n;
+	std::vector<int32_t> live(N), size(N, 1);
+	std::vector<int64_t> R(N, 0);
+	for (size_t x = 0; x < N; ++x) {
+		live[x] = (int32_t)x;
+		for (size_t y = 0; y < N; ++y) R[x] += d[x * N + y];
+	}
+	const bool nj = method == PG_TREE_NJ;
+	// PANGENE_TREE_STOP_AFTER=k (timing only, tests/run_tree_timing.py): give up after k joins with status 1, so that a large input
+	// can be timed on its first joins
+	const char *stop_s = std::getenv("PANGENE_TREE_STOP_AFTER");
+	const long stop = stop_s ? std::atol(stop_s) : 0;
+	long done = 0;
+	while ((int32_t)live.size() > (nj ? 3 : 1)) {
+		if (stop > 0 && done++ >= stop) return 1;
+		const int64_t r = (int64_t)live.size();
+		int64_t best = 0;
+		size_t bi = 0, bj = 0;
+		bool have = false;
+		for (size_t a = 0; a < live.size(); ++a) {
+			const size_t i = (size_t)live[a];
+			const int32_t *row = d.data() + i * N;
+			for (size_t b = a + 1; b < live.size(); ++b) {
+				const size_t j = (size_t)live[b];
+				const int64_t c = nj ? (r - 2) * (int64_t)row[j] - R[i] - R[j] : (int64_t)row[j];
+				if (!have || c < best) best = c, bi = i, bj = j, have = true;
+			}
+		}
+		const int64_t dij = d[bi * N + bj], ni = size[bi], nn = size[bj];
+		rec[0] = (int64_t)bi, rec[1] = (int64_t)bj, rec[2] = dij, rec[3] = nj ? R[bi] : ni, rec[4] = nj ? R[bj] : nn, rec[5] = r;
+		rec += 6;
+		int64_t sum = 0;
+		for (const int32_t kk : live) {
+			const size_t k = (size_t)kk;
+			if (k == bi || k == bj) continue;
+			const int64_t a = d[bi * N + k], b = d[bj * N + k];
+			const int64_t v = nj ? floor_div(a + b - dij, 2) : floor_div(ni * a + nn * b, ni + nn);
+			if (v >= JOIN_MAX || v <= -JOIN_MAX) return PGA_ERR_RANGE;
+			d[bi * N + k] = d[k * N + bi] = (int32_t)v;
+			R[k] += v - a - b;
+			sum += v;
+		}
+		R[bi] = sum;
+		size[bi] = (int32_t)(ni + nn);
+		live.erase(std::find(live.begin(), live.end(), (int32_t)bj));
+	}
+	if (nj) {
+		const size_t x = (size_t)live[0], y = (size_t)live[1], z = (size_t)live[2];
+		rec[0] = (int64_t)x, rec[1] = (int64_t)y, rec[2] = (int64_t)z, rec[3] = d[x * N + y], rec[4] = d[x * N + z], rec[5] = d[y * N + z];
+	}
+	return 0;
+}
+
+double t_join = 0; // seconds of the last join step (backend or host loops)
+
+// q[n][n] (symmetric, zero diagonal, every entry below 2^29 in size), n >= 3 -> rec; 0 or a PGA_ERR_* code
+int join_run(const int32_t *q, int32_t n, int32_t method, int64_t *rec)
+{
+	if (q == nullptr || rec == nullptr || n < 3 || (method != PG_TREE_NJ && method != PG_TREE_UPGMA)) return PGA_ERR_ARG;
+	if (n > 65535) return PGA_ERR_RANGE;
+	const size_t N = (size_t)n;
+	for (size_t i = 0; i < N; ++i) {
+		if (q[i * N + i] != 0) return PGA_ERR_ARG;
+		for (size_t j = i + 1; j < N; ++j) {
+			if (q[i * N + j] != q[j * N + i]) return PGA_ERR_ARG;
+			if (q[i * N + j] >= JOIN_IN_MAX || q[i * N + j] <= -JOIN_IN_MAX) return PGA_ERR_RANGE;
+		}
+	}
+	const double t0 = now_sec();
+	const pga_backend_t *be = backend_default();
+	int rc;
+	if (be->pan_join != nullptr) {
+		const pga_join_in_t in{q, n, method};
+		pga_join_out_t res{};
+		rc = be->pan_join(&in, &res);
+		if (rc == 0) std::memcpy(rec, res.rec, sizeof(int64_t) * 6 * (size_t)res.n_rec);
+	} else {
+		std::vector<int32_t> d(q, q + N * N);
+		rc = join_host(d, n, method, rec);
+	}
+	t_join = now_sec() - t0;
+	return rc;
+}
+
+std::string quoted(const std::string &s)
+{
+	if (s.find_first_of("(),:;[]' \t\n") == std::string::npos) return s;
+	std::string o = "'";
+	for (const char c : s) { o += c; if (c == '\'') o += c; }
+	return o + "'";
+}
+
+std::string len_text(double fixed, int32_t F)
+{
+	char b[64];
+	std::snprintf(b, sizeof(b), ":%.6f", fixed / (double)((int64_t)1 << F));
+	return b;
+}
+
+// the records of n >= 3 leaves -> one Newick line
+std::string newick(const std::vector<std::string> &names, const int64_t *rec, int32_t method, int32_t F)
+{
+	const size_t n = names.size();
+	std::vector<std::string> sub(n);
+	std::vector<double> height(n, 0.0);
+	for (size_t i = 0; i < n; ++i) sub[i] = quoted(names[i]);
+	if (method == PG_TREE_NJ) {
+		for (size_t s = 0; s + 3 < n; ++s, rec += 6) {
+			const size_t i = (size_t)rec[0], j = (size_t)rec[1];
+			const double li = ((double)rec[2] + (double)(rec[3] - rec[4]) / (double)(rec[5] - 2)) / 2.0, lj = (double)rec[2] - li;
+			sub[i] = "(" + sub[i] + len_text(li, F) + "," + sub[j] + len_text(lj, F) + ")";
+			std::string().swap(sub[j]);
+		}
+		const size_t x = (size_t)rec[0], y = (size_t)rec[1], z = (size_t)rec[2];
+		const double lx = (double)(rec[3] + rec[4] - rec[5]) / 2.0, ly = (double)(rec[3] + rec[5] - rec[4]) / 2.0, lz = (double)(rec[4] + rec[5] - rec[3]) / 2.0;
+		return "(" + sub[x] + len_text(lx, F) + "," + sub[y] + len_text(ly, F) + "," + sub[z] + len_text(lz, F) + ");\n";
+	}
+	size_t root = 0;
+	for (size_t s = 0; s + 1 < n; ++s, rec += 6) {
+		const size_t i = (size_t)rec[0], j = (size_t)rec[1];
+		const double h = (double)rec[2] / 2.0;
+		sub[i] = "(" + sub[i] + len_text(h - height[i], F) + "," + sub[j] + len_text(h - height[j], F) + ")";
+		std::string().swap(sub[j]);
+		height[i] = h, root = i;
+	}
+	return sub[root] + ";\n";
+}
+
+// PANGENE_TREE_TIMING=1: one line on stderr per call
+void report_time(const char *route, int32_t M, int32_t A, double t_prep, double t_write)
+{
+	if (std::getenv("PANGENE_TREE_TIMING") == nullptr) return;
+	std::fprintf(stderr, "[tree-timing] route=%s items=%d assemblies=%d prep_ms=%.3f join_ms=%.3f write_ms=%.3f\n", route, M, A, t_prep * 1e3,
+	             t_join * 1e3, t_write * 1e3);
+}
+
+// bit rows -> S -> q -> rec; A >= 3
+int tree_records(const std::vector<uint32_t> &bits, int32_t M, int32_t A, int32_t metric, int32_t method, std::vector<int32_t> &q, int64_t *rec, int32_t *F)
+{
+	const size_t nn = (size_t)A * (size_t)A;
+	std::vector<int32_t> S(nn);
+	int rc = shared_count(bits, M, A, S.data());
+	if (rc != 0) return rc;
+	q.resize(nn);
+	if ((rc = to_fixed(S.data(), A, metric, q.data(), F)) != 0) return rc;
+	return A >= 3 ? join_run(q.data(), A, method, rec) : 0;
+}
+
+int tree_run(const char *route, const std::vector<std::string> &names, const std::vector<uint32_t> &bits, int32_t M, const pg_tree_opt_t *o, double t_start)
+{
+	if ((o->metric != PG_DIST_JACCARD && o->metric != PG_DIST_DIFF) || (o->method != PG_TREE_NJ && o->method != PG_TREE_UPGMA)) return PGA_ERR_ARG;
+	const int32_t A = (int32_t)names.size();
+	const double t_prep = now_sec() - t_start;
+	std::vector<int32_t> q;
+	std::vector<int64_t> rec((size_t)6 * (size_t)std::max(A, 1));
+	int32_t F = 20;
+	t_join = 0;
+	if (A >= 2) {
+		const int rc = tree_records(bits, M, A, o->metric, o->method, q, rec.data(), &F);
+		if (rc != 0) return rc;
+	}
+	const double t1 = now_sec();
+	std::string s;
+	if (A == 0) s = ";\n";
+	else if (A == 1) s = "(" + quoted(names[0]) + ");\n";
+	else if (A == 2) {
+		const std::string h = len_text((double)q[1] / 2.0, F);
+		s = "(" + quoted(names[0]) + h + "," + quoted(names[1]) + h + ");\n";
+	} else s = newick(names, rec.data(), o->method, F);
+	FILE *fp = out_stream();
+	std::fwrite(s.data(), 1, s.size(), fp);
+	std::fflush(fp);
+	report_time(route, M, A, t_prep, now_sec() - t1);
+	return 0;
+}
+
+} // namespace
+} // namespace pgx
+
+using namespace pgx;
+
+extern "C" {
+
+void pg_tree_opt_init(pg_tree_opt_t *o)
+{
+	std::memset(o, 0, sizeof(*o));
+	o->type = PG_DIST_GENE, o->metric = PG_DIST_JACCARD, o->method = PG_TREE_NJ;
+}
+
+int pg_tree_file(const char *gfa_fn, const pg_tree_opt_t *o)
+{
+	const double t0 = now_sec();
+	std::vector<std::string> names;
+	std::vector<uint32_t> bits;
+	int32_t M;
+	if (dist_items_file(gfa_fn, o->type, names, bits, M) != 0) { std::fprintf(stderr, "Error: cannot open %s\n", gfa_fn ? gfa_fn : "-"); return -1; }
+	const int rc = tree_run("file", names, bits, M, o, t0);
+	if (rc != 0) { std::fprintf(stderr, "Error: pangene tree: %s\n", backend_default()->strerror(rc)); return -2; }
+	return 0;
+}
+
+void pg_write_tree(pg_graph_t *q, const pg_tree_opt_t *o)
+{
+	const double t0 = now_sec();
+	std::vector<std::string> names;
+	std::vector<uint32_t> bits;
+	int32_t M;
+	if (dist_items_graph(q, o->type, names, bits, M) != 0) return;
+	const int rc = tree_run("memory", names, bits, M, o, t0);
+	if (rc != 0) set_error(rc, "pg_write_tree");
+}
+
+int pg_pan_join(const int32_t *q, int32_t n, int32_t method, int64_t *rec) { return join_run(q, n, method, rec); }
+
+int pg_pan_tree(const uint8_t *presence, int32_t n_item, int32_t n_asm, int32_t metric, int32_t method, int64_t *rec, int32_t *frac_bits)
+{
+	if ((metric != PG_DIST_JACCARD && metric != PG_DIST_DIFF) || (method != PG_TREE_NJ && method != PG_TREE_UPGMA)) return PGA_ERR_ARG;
+	if (n_item < 0 || n_asm < 3 || ((size_t)n_item > 0 && presence == nullptr) || rec == nullptr || frac_bits == nullptr) return PGA_ERR_ARG;
+	std::vector<uint32_t> bits;
+	presence_bits(presence, n_item, n_asm, bits);
+	std::vector<int32_t> q;
+	return tree_records(bits, n_item, n_asm, metric, method, q, rec, frac_bits);
+}
+
+} // extern "C"
