@@ -246,18 +246,33 @@ int  pg_pan_dist(const uint8_t *presence, int32_t n_item, int32_t n_asm, int32_t
  * pg_tree_file: a GFA file (0, -1 when it cannot be opened, -2 on a backend or range error); pg_write_tree: the graph in memory after
  * pg_graph_gen; pg_pan_join: q = int32 [n][n], symmetric with a zero diagonal (PGA_ERR_ARG otherwise), every entry below 2^29 in size
  * (PGA_ERR_RANGE), 3 <= n <= 65 535, rec = room for n - 2 (NJ) or n - 1 (UPGMA) records; pg_pan_tree: a presence matrix, row-major
- * uint8 [n_item][n_asm] with n_asm >= 3, through the shared-item counts to the records, *frac_bits = F; both return 0 or PGA_ERR_*. */
+ * uint8 [n_item][n_asm] with n_asm >= 3, through the shared-item counts to the records, *frac_bits = F; both return 0 or PGA_ERR_*.
+ * Bootstrap support (DESIGN.md section 8 "Bootstrap"): replicate b = 1 .. n_boot draws as many items as there are, with replacement --
+ * x0 = mix64((seed << 32) | b) with the mix64 of pg_curves_*, draw t = 0 .. M - 1 is item mix64(x0 + (t + 1) * 0x9E3779B97F4A7C15) % M --
+ * and is joined like the tree itself, distances, F and tie rule included (the backend's pga_pan_boot).  With C(s) the leaves below the
+ * node of join s: an NJ join s < A - 3 is supported by a replicate that has a join with the same leaves or with all the others (the
+ * same split of the unrooted tree), a UPGMA join s < A - 2 by one with the same leaves; count[s] = the supporting replicates, and
+ * n_boot for NJ's closing record and UPGMA's root.  With n_boot > 0 the node of join s is printed "(...,...)P", P = the per cent of
+ * count[s] rounded half up; the trifurcation and the root carry no label; n_boot = 0 prints the plain tree.  A range error in any
+ * replicate is PGA_ERR_RANGE for the whole call.  pg_pan_boot: the records of the tree as pg_pan_tree returns them and count[n_rec];
+ * pg_pan_boot_records: the records of replicates first .. first + n - 1 (first >= 1) as rec_out[n][n_rec][6]. */
 enum { PG_TREE_NJ = 0, PG_TREE_UPGMA = 1 };
 typedef struct {
 	int32_t type;   /* PG_DIST_GENE or PG_DIST_ADJ [gene] */
 	int32_t metric; /* PG_DIST_JACCARD or PG_DIST_DIFF [jaccard] */
 	int32_t method; /* PG_TREE_NJ or PG_TREE_UPGMA [nj] */
+	int32_t n_boot; /* bootstrap replicates; 0: none [0] */
+	uint32_t seed;  /* seed of their draws [0] */
 } pg_tree_opt_t;
 void pg_tree_opt_init(pg_tree_opt_t *o);
 int  pg_tree_file(const char *gfa_fn, const pg_tree_opt_t *o);
 void pg_write_tree(pg_graph_t *g, const pg_tree_opt_t *o);
 int  pg_pan_join(const int32_t *q, int32_t n, int32_t method, int64_t *rec);
 int  pg_pan_tree(const uint8_t *presence, int32_t n_item, int32_t n_asm, int32_t metric, int32_t method, int64_t *rec, int32_t *frac_bits);
+int  pg_pan_boot(const uint8_t *presence, int32_t n_item, int32_t n_asm, int32_t metric, int32_t method, int32_t n_boot, uint32_t seed, int64_t *rec,
+                 int32_t *frac_bits, int32_t *count);
+int  pg_pan_boot_records(const uint8_t *presence, int32_t n_item, int32_t n_asm, int32_t metric, int32_t method, uint32_t seed, int32_t first, int32_t n,
+                         int64_t *rec_out);
 
 /* Gene associations: which genes travel together over the assemblies and which exclude each other.  Over the presence matrix of
  * gfa2matrix (gene g is in assembly a when its entry is > 0; rows in segment order), with A assemblies, a = |B_g|, b = |B_h|,

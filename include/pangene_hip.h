@@ -94,7 +94,7 @@ typedef struct {
  * Device layout limits (PGA_ERR_RANGE otherwise): coordinates inside a block < 2^31 (contigs beyond that arrive as virtual contigs,
  * see pga_genome_block_t; what remains out of reach is a single cluster of overlapping hits spanning 2^30 bp), < 2^30 hits and < 2^31
  * exons per shard, < 2^20 genes, < 2^24 genomes. */
-#define PGA_ABI_VERSION 11u  /* bumped whenever a struct of this header or the order of pga_backend_t changes; pga_create refuses another */
+#define PGA_ABI_VERSION 12u  /* bumped whenever a struct of this header or the order of pga_backend_t changes; pga_create refuses another */
 typedef struct {
 	uint32_t abi_version;        /* = PGA_ABI_VERSION of the header the caller was compiled against (PGA_ERR_ARG otherwise) */
 	int32_t n_genome;            /* genomes in this shard (may include genomes with 0 hits) */
@@ -399,6 +399,34 @@ typedef struct {
 typedef struct { const int64_t *rec; int32_t n_rec; } pga_join_out_t;
 int pga_pan_join(const pga_join_in_t *in, pga_join_out_t *out);
 
+/* Bootstrap replicates of a tree (include/pangene_amd.h pg_pan_boot, pangene tree -b; DESIGN.md section 8 "Bootstrap").  Context-free,
+ * like pan_join.  Replicate b >= 1 draws n_item items with replacement: x0 = mix64((seed << 32) | b) with mix64 splitmix64's output
+ * function, draw t = 0 .. n_item - 1 is m_t = mix64(x0 + (t + 1) * 0x9E3779B97F4A7C15) % n_item; S_b[i][j] = #{t : m_t in B_i & B_j};
+ * q_b = the fixed-point distances of S_b as pangene tree defines them (metric 0 = jaccard, 2 = diff with the replicate's own F);
+ * rec_b = the joins of q_b as pan_join defines them.  Everything from the bit rows to the records happens on the device.
+ * In:  bits[n_asm][(n_item + 31) / 32], assembly-major as for pan_shared; method as for pan_join; replicates first .. first + n_rep - 1
+ *      (first >= 1, n_rep >= 0); draws: NULL, or -- for tests only -- room for n_rep x n_item int32 that receive m_t.
+ * Out: rec[n_rep][n_rec][6], n_rec = n_asm - 2 (NJ) or n_asm - 1 (UPGMA).  The array belongs to the backend and stays valid until its
+ *      next pan_boot.  A range error in any replicate (diff without a fraction bit left, a distance of 2^30 on the way): PGA_ERR_RANGE.
+ * One call takes at most pga_boot_batch(n_asm) replicates (PGA_ERR_ARG otherwise): a device-memory budget of 2 GiB over what a
+ * replicate keeps for the call (its counts, its distances and the joins' small arrays: 66 replicates at n_asm = 2 000, 2 at
+ * 10 000; never more than 1 024), or PANGENE_BOOT_BATCH.  The caller walks its replicates in such chunks.  The function takes n_asm
+ * alone, so the draws and the resampled rows (n_item + n_asm x W words a replicate) are outside that budget: the backend makes them
+ * for groups of replicates of at most 256 MiB (one replicate at least; PANGENE_BOOT_ROWS_WORDS=n, in words, lowers that for tests),
+ * group after group inside the call.  Device memory of a call: at most 2 GiB + the bit rows + 256 MiB, or one replicate's draws and
+ * rows in place of the 256 MiB where those are larger.
+ * Limits: those of pan_shared and pan_join: 3 <= n_asm (PGA_ERR_ARG otherwise), n_asm <= 65 535 (PGA_ERR_RANGE). */
+typedef struct {
+	const uint32_t *bits;
+	int32_t n_item, n_asm, metric, method;
+	uint32_t seed;
+	int32_t first, n_rep;
+	int32_t *draws;
+} pga_boot_in_t;
+typedef struct { const int64_t *rec; int32_t n_rec; } pga_boot_out_t;
+int pga_pan_boot(const pga_boot_in_t *in, pga_boot_out_t *out);
+int32_t pga_boot_batch(int32_t n_asm);
+
 /* the same ABI as a table, so the host driver is written once */
 struct pga_branch_par_s; struct pga_loop_xchg_s;
 typedef struct {
@@ -460,6 +488,7 @@ typedef struct {
 	int  (*pan_assoc)(const pga_assoc_in_t *, pga_assoc_out_t *); /* may be NULL: the host driver then runs the same step itself */
 	int  (*pan_trait)(const pga_trait_in_t *, pga_trait_out_t *); /* may be NULL: the host driver then runs the same step itself */
 	int  (*pan_join)(const pga_join_in_t *, pga_join_out_t *); /* may be NULL: the host driver then runs the same step itself */
+	int  (*pan_boot)(const pga_boot_in_t *, pga_boot_out_t *); /* may be NULL: the host driver then runs the same step itself */
 } pga_backend_t;
 
 const pga_backend_t *pga_backend(void);

@@ -288,20 +288,27 @@ def _trait_args(argv: Sequence[str]):
 
 
 class pg_tree_opt_t(C.Structure):
-    """Tree options (include/pangene_amd.h): items (PG_DIST_GENE / PG_DIST_ADJ), distance (jaccard or diff), joining method."""
-    _fields_ = [("type", C.c_int32), ("metric", C.c_int32), ("method", C.c_int32)]
+    """Tree options (include/pangene_amd.h): items (PG_DIST_GENE / PG_DIST_ADJ), distance (jaccard or diff), joining method, bootstrap
+    replicates and the seed of their draws."""
+    _fields_ = [("type", C.c_int32), ("metric", C.c_int32), ("method", C.c_int32), ("n_boot", C.c_int32), ("seed", C.c_uint32)]
 
 
 TREE_METRICS = ("jaccard", "diff")
 TREE_METHODS = ("nj", "upgma")
 
 
-def tree_opt(lib: C.CDLL, type: str = "gene", metric: str = "jaccard", method: str = "nj") -> pg_tree_opt_t:
+TREE_MAX_BOOT = 2147483647
+
+
+def tree_opt(lib: C.CDLL, type: str = "gene", metric: str = "jaccard", method: str = "nj", n_boot: int = 0, seed: int = 0) -> pg_tree_opt_t:
     if metric not in TREE_METRICS:
         raise ValueError("metric must be jaccard or diff (shared is not a distance)")
+    if not 0 <= int(n_boot) <= TREE_MAX_BOOT:
+        raise ValueError("n_boot must be in [0, 2^31 - 1]")
     o = pg_tree_opt_t()
     lib.pg_tree_opt_init(C.byref(o))
     o.type, o.metric, o.method = DIST_TYPES.index(type), DIST_METRICS.index(metric), TREE_METHODS.index(method)
+    o.n_boot, o.seed = int(n_boot), int(seed) & 0xFFFFFFFF
     return o
 
 
@@ -339,6 +346,59 @@ def pan_tree(lib: C.CDLL, presence, metric: str = "jaccard", method: str = "nj")
     if rc != 0:
         raise RuntimeError("pg_pan_tree: status %d" % rc)
     return rec, int(F.value)
+
+
+def pan_boot(lib: C.CDLL, presence, metric: str = "jaccard", method: str = "nj", n_boot: int = 100, seed: int = 0):
+    """Bootstrap support of the tree of an item x assembly presence matrix (bool numpy array or torch tensor, shape (M, A), A >= 3)
+    through pg_pan_boot: (records, F, count) with the records and F as pan_tree returns them and count an int32 array, one entry per
+    record: the replicates, of n_boot, that have the node of that join (nj: the same split of the leaves); n_boot itself for nj's
+    closing record and upgma's root."""
+    import numpy as np
+    if metric not in TREE_METRICS:
+        raise ValueError("metric must be jaccard or diff (shared is not a distance)")
+    p = _presence(presence)
+    M, A = p.shape
+    m = TREE_METHODS.index(method)
+    rec = np.zeros((max(A - 2 + m, 0), 6), dtype=np.int64)
+    count = np.zeros(max(A - 2 + m, 0), dtype=np.int32)
+    F = C.c_int32(0)
+    rc = lib.pg_pan_boot(p.ctypes.data_as(C.POINTER(C.c_uint8)), M, A, DIST_METRICS.index(metric), m, int(n_boot), int(seed) & 0xFFFFFFFF,
+                         rec.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(F), count.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc != 0:
+        raise RuntimeError("pg_pan_boot: status %d" % rc)
+    return rec, int(F.value), count
+
+
+def pan_boot_records(lib: C.CDLL, presence, metric: str = "jaccard", method: str = "nj", seed: int = 0, first: int = 1, n: int = 1):
+    """The records of bootstrap replicates first .. first + n - 1 (first >= 1) of a presence matrix as pan_boot takes it, through
+    pg_pan_boot_records: an int64 array (n, records, 6), each replicate's records as pan_join returns them."""
+    import numpy as np
+    if metric not in TREE_METRICS:
+        raise ValueError("metric must be jaccard or diff (shared is not a distance)")
+    p = _presence(presence)
+    M, A = p.shape
+    m = TREE_METHODS.index(method)
+    rec = np.zeros((max(int(n), 0), max(A - 2 + m, 0), 6), dtype=np.int64)
+    rc = lib.pg_pan_boot_records(p.ctypes.data_as(C.POINTER(C.c_uint8)), M, A, DIST_METRICS.index(metric), m, int(seed) & 0xFFFFFFFF, int(first), int(n),
+                                 rec.ctypes.data_as(C.POINTER(C.c_int64)))
+    if rc != 0:
+        raise RuntimeError("pg_pan_boot_records: status %d" % rc)
+    return rec
+
+
+def _tree_boot_args(argv: Sequence[str]):
+    """(replicates, seed) of --tree-boot=INT / --tree-seed=INT in argv"""
+    b, seed = 0, 0
+    for x in argv:
+        if x.startswith("--tree-boot="): b = int(x.split("=", 1)[1])
+        elif x.startswith("--tree-seed="):
+            v = x.split("=", 1)[1]
+            if not (v.isascii() and v.isdigit() and int(v) <= 0xFFFFFFFF):  # digits only, as the command line reads it
+                raise ValueError("--tree-seed must be in [0, 2^32 - 1]")
+            seed = int(v)
+    if not 0 <= b <= TREE_MAX_BOOT:
+        raise ValueError("--tree-boot must be in [0, 2^31 - 1]")
+    return b, seed
 
 
 def _tree_args(argv: Sequence[str]):
@@ -399,6 +459,9 @@ _API = {
     "pg_write_tree": (None, [C.c_void_p, C.c_void_p]),
     "pg_pan_join": (C.c_int, [C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "pg_pan_tree": (C.c_int, [C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    "pg_pan_boot": (C.c_int, [C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                              C.POINTER(C.c_int32)]),
+    "pg_pan_boot_records": (C.c_int, [C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "pg_read_list_dict": (C.c_void_p, [C.c_char_p]),
     "pg_dict_destroy": (None, [C.c_void_p]),
     "pg_last_error": (C.c_int, []),
@@ -522,6 +585,7 @@ def run(lib: C.CDLL, files: Sequence[str], argv: Sequence[str] = (), scan_only: 
     if trait_fn is not None and (any(x.startswith("--matrix") for x in argv) or "--call" in argv or n_curves or dist_type is not None or assoc_phi is not None):
         raise ValueError("--trait cannot be combined with --matrix, --call, --curves, --dist or --assoc")
     tree_type, tree_metric, tree_method = _tree_args(argv)
+    tree_boot, tree_seed = _tree_boot_args(argv)
     if tree_type is not None and (any(x.startswith("--matrix") for x in argv) or "--call" in argv or n_curves or dist_type is not None or assoc_phi is not None
                                   or trait_fn is not None):
         raise ValueError("--tree cannot be combined with --matrix, --call, --curves, --dist, --assoc or --trait")
@@ -565,7 +629,7 @@ def run(lib: C.CDLL, files: Sequence[str], argv: Sequence[str] = (), scan_only: 
                 if lib.pg_last_error():
                     raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
             elif tree_type is not None:
-                lib.pg_write_tree(g, C.byref(tree_opt(lib, tree_type, tree_metric, tree_method)))
+                lib.pg_write_tree(g, C.byref(tree_opt(lib, tree_type, tree_metric, tree_method, tree_boot, tree_seed)))
                 if lib.pg_last_error():
                     raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
             elif opt.flag & PG_F_WRITE_BED_WALK: lib.pg_write_bed(d, 1)

@@ -65,13 +65,15 @@ static int usage(FILE *fp, const pg_opt_t *opt)
 	std::fprintf(fp, "    --tree[=STR]  output a tree of the assemblies (Newick) from their gene (gene) or gene-adjacency (adj) distances [gene]\n");
 	std::fprintf(fp, "    --tree-metric=STR  distance of --tree: jaccard or diff [jaccard]\n");
 	std::fprintf(fp, "    --tree-method=STR  --tree: nj (neighbour-joining, unrooted; negative branch lengths are printed as they come) or upgma [nj]\n");
+	std::fprintf(fp, "    --tree-boot=INT    --tree: bootstrap replicates over the items; inner nodes are labelled with their support in per cent [0]\n");
+	std::fprintf(fp, "    --tree-seed=INT    seed of the bootstrap draws [0]\n");
 	std::fprintf(fp, "  Also: pangene gfa2matrix [-c] [-d FILE] [-p] <in.gfa>   (pangene.js gfa2matrix on a GFA file)\n");
 	std::fprintf(fp, "        pangene call [-m INT] [-w] [-b] [-e] [-d] [-p] [-s] [-r STR] <in.gfa>   (pangene.js call on a GFA file)\n");
 	std::fprintf(fp, "        pangene curves [-n INT] [-s INT] <in.gfa>   (accumulation curves of the gfa2matrix matrix of a GFA file)\n");
 	std::fprintf(fp, "        pangene dist [-t gene|adj] [-m jaccard|shared|diff] [-p] <in.gfa>   (pairwise distances of the assemblies of a GFA file)\n");
 	std::fprintf(fp, "        pangene assoc [-r FLOAT] [-c INT] [-s pos|neg|both] [-x INT] <in.gfa>   (co-occurring and avoiding gene pairs of a GFA file)\n");
 	std::fprintf(fp, "        pangene trait -t FILE [-n INT] [-s INT] [-c INT] [-p FLOAT] <in.gfa>   (gene-trait association over the matrix of a GFA file)\n");
-	std::fprintf(fp, "        pangene tree [-t gene|adj] [-m jaccard|diff] [-a nj|upgma] <in.gfa>   (neighbour-joining or UPGMA tree of the assemblies of a GFA file)\n");
+	std::fprintf(fp, "        pangene tree [-t gene|adj] [-m jaccard|diff] [-a nj|upgma] [-b INT] [-s INT] <in.gfa>   (neighbour-joining or UPGMA tree of the assemblies of a GFA file, with bootstrap support)\n");
 	return fp == stdout ? 0 : 1;
 }
 
@@ -186,6 +188,23 @@ static int main_dist(int argc, char *argv[])
 
 static int tree_metric(const char *s) { return std::strcmp(s, "jaccard") == 0 ? PG_DIST_JACCARD : std::strcmp(s, "diff") == 0 ? PG_DIST_DIFF : -1; }
 static int tree_method(const char *s) { return std::strcmp(s, "nj") == 0 ? PG_TREE_NJ : std::strcmp(s, "upgma") == 0 ? PG_TREE_UPGMA : -1; }
+static bool tree_boot(const char *s, int32_t &v) // a whole number of replicates
+{
+	char *end = nullptr;
+	const long long x = std::strtoll(s, &end, 10);
+	if (end == s || *end != 0 || x < 0 || x > 2147483647ll) return false;
+	v = (int32_t)x;
+	return true;
+}
+static bool tree_seed_arg(const char *s, uint32_t &v) // a whole number that fits 32 bits; digits only (strtoull alone would take "-1" and " 7")
+{
+	char *end = nullptr;
+	if (*s < '0' || *s > '9') return false;
+	const unsigned long long x = std::strtoull(s, &end, 10);
+	if (*end != 0 || end - s > 10 || x > 4294967295ull) return false;
+	v = (uint32_t)x;
+	return true;
+}
 
 // `pangene tree`: a neighbour-joining or UPGMA tree of the assemblies of a GFA file from the distances `pangene dist` prints
 static int main_tree(int argc, char *argv[])
@@ -193,16 +212,20 @@ static int main_tree(int argc, char *argv[])
 	pg_tree_opt_t o;
 	pg_tree_opt_init(&o);
 	int c;
-	while ((c = getopt(argc, argv, "t:m:a:")) >= 0) {
+	while ((c = getopt(argc, argv, "t:m:a:b:s:")) >= 0) {
 		if (c == 't') { if ((o.type = dist_type(optarg)) < 0) { std::fprintf(stderr, "ERROR: -t must be gene or adj\n"); return 1; } }
 		else if (c == 'm') { if ((o.metric = tree_metric(optarg)) < 0) { std::fprintf(stderr, "ERROR: -m must be jaccard or diff (shared is not a distance)\n"); return 1; } }
 		else if (c == 'a') { if ((o.method = tree_method(optarg)) < 0) { std::fprintf(stderr, "ERROR: -a must be nj or upgma\n"); return 1; } }
+		else if (c == 'b') { if (!tree_boot(optarg, o.n_boot)) { std::fprintf(stderr, "ERROR: -b must be in [0, 2147483647]\n"); return 1; } }
+		else if (c == 's') { if (!tree_seed_arg(optarg, o.seed)) { std::fprintf(stderr, "ERROR: -s must be in [0, 4294967295]\n"); return 1; } }
 		else return 1;
 	}
 	if (argc - optind < 1) {
 		std::printf("Usage: pangene tree [options] <in.gfa>\nOptions:\n  -t STR   items: gene (gene content) or adj (gene adjacencies of the walks) [gene]\n"
 		            "  -m STR   distance: jaccard or diff [jaccard]\n"
-		            "  -a STR   nj (neighbour-joining: unrooted, negative branch lengths are printed as they come) or upgma [nj]\n");
+		            "  -a STR   nj (neighbour-joining: unrooted, negative branch lengths are printed as they come) or upgma [nj]\n"
+		            "  -b INT   bootstrap replicates over the items: inner nodes are labelled with their support in per cent [0]\n"
+		            "  -s INT   seed of the bootstrap draws [0]\n");
 		return 0;
 	}
 	return pg_tree_file(argv[optind], &o) == 0 ? 0 : 1;
@@ -285,7 +308,7 @@ static int main_trait(int argc, char *argv[])
 struct Output { int matrix = 0; bool call = false; int curves = 0; uint32_t curves_seed = 11; int dist = -1, dist_metric = 0; // curves: orders (0: none); dist: PG_DIST_* (-1: none)
 	bool assoc = false; double assoc_phi = 0.8; int assoc_count = 2, assoc_sign = 0;
 	const char *trait = nullptr; int32_t trait_perm = 1000; uint32_t trait_seed = 11;
-	int tree = -1, tree_metric = 0, tree_method = 0; }; // tree: PG_DIST_GENE / PG_DIST_ADJ (-1: none)
+	int tree = -1, tree_metric = 0, tree_method = 0; int32_t tree_boot = 0; uint32_t tree_seed = 0; }; // tree: PG_DIST_GENE / PG_DIST_ADJ (-1: none)
 
 static int run_path(pg_opt_t &opt, int n_files, char **files, const uint8_t *ids_only, const Output &o, bool graph_lines, bool own_lines, int device = -1)
 {
@@ -347,7 +370,7 @@ static int run_path(pg_opt_t &opt, int n_files, char **files, const uint8_t *ids
 		else if (o.tree >= 0) {
 			pg_tree_opt_t tro;
 			pg_tree_opt_init(&tro);
-			tro.type = o.tree, tro.metric = o.tree_metric, tro.method = o.tree_method;
+			tro.type = o.tree, tro.metric = o.tree_metric, tro.method = o.tree_method, tro.n_boot = o.tree_boot, tro.seed = o.tree_seed;
 			pg_write_tree(g, &tro);
 			if (pg_last_error()) rc = 2;
 		}
@@ -573,6 +596,8 @@ int main(int argc, char *argv[])
 	int32_t trait_perm_v = 1000;
 	uint32_t trait_seed = 11;
 	int tree = -1, tree_metric_v = PG_DIST_JACCARD, tree_method_v = PG_TREE_NJ; // --tree: PG_DIST_GENE / PG_DIST_ADJ (-1: not asked for)
+	int32_t tree_boot_v = 0;
+	uint32_t tree_seed = 0;
 	static const struct option lopts[] = {
 		{ "bed", optional_argument, nullptr, 301 }, { "ori-sc", no_argument, nullptr, 302 }, { "matrix", optional_argument, nullptr, 303 }, { "call", no_argument, nullptr, 305 },
 		{ "curves", optional_argument, nullptr, 306 }, { "curves-seed", required_argument, nullptr, 307 },
@@ -580,6 +605,7 @@ int main(int argc, char *argv[])
 		{ "assoc", optional_argument, nullptr, 310 }, { "assoc-min-count", required_argument, nullptr, 311 }, { "assoc-sign", required_argument, nullptr, 312 },
 		{ "trait", required_argument, nullptr, 313 }, { "trait-perm", required_argument, nullptr, 314 }, { "trait-seed", required_argument, nullptr, 315 },
 		{ "tree", optional_argument, nullptr, 316 }, { "tree-metric", required_argument, nullptr, 317 }, { "tree-method", required_argument, nullptr, 318 },
+		{ "tree-boot", required_argument, nullptr, 319 }, { "tree-seed", required_argument, nullptr, 320 },
 		{ "gpus", required_argument, nullptr, 304 }, { "procs", required_argument, nullptr, 304 },
 		{ "version", no_argument, nullptr, 401 }, { nullptr, 0, nullptr, 0 } };
 	pg_opt_t opt;
@@ -662,6 +688,12 @@ int main(int argc, char *argv[])
 		case 318:
 			if ((tree_method_v = tree_method(optarg)) < 0) { std::fprintf(stderr, "ERROR: --tree-method must be nj or upgma\n"); return 1; }
 			break;
+		case 319:
+			if (!tree_boot(optarg, tree_boot_v)) { std::fprintf(stderr, "ERROR: --tree-boot must be in [0, 2147483647]\n"); return 1; }
+			break;
+		case 320:
+			if (!tree_seed_arg(optarg, tree_seed)) { std::fprintf(stderr, "ERROR: --tree-seed must be in [0, 4294967295]\n"); return 1; }
+			break;
 		case 401: std::puts(PG_VERSION); return 0;
 		default: break;
 		}
@@ -673,7 +705,7 @@ int main(int argc, char *argv[])
 	if (trait && (matrix || call || curves || dist >= 0 || assoc)) { std::fprintf(stderr, "ERROR: --trait cannot be combined with --matrix, --call, --curves, --dist or --assoc\n"); return 1; }
 	if (tree >= 0 && (matrix || call || curves || dist >= 0 || assoc || trait)) { std::fprintf(stderr, "ERROR: --tree cannot be combined with --matrix, --call, --curves, --dist, --assoc or --trait\n"); return 1; }
 	Output o;
-	o.tree = tree, o.tree_metric = tree_metric_v, o.tree_method = tree_method_v;
+	o.tree = tree, o.tree_metric = tree_metric_v, o.tree_method = tree_method_v, o.tree_boot = tree_boot_v, o.tree_seed = tree_seed;
 	o.trait = trait, o.trait_perm = trait_perm_v, o.trait_seed = trait_seed;
 	o.assoc = assoc, o.assoc_phi = assoc_phi_v, o.assoc_count = assoc_count, o.assoc_sign = assoc_sign_v;
 	o.curves = curves, o.curves_seed = curves_seed;

@@ -55,10 +55,13 @@ __device__ __forceinline__ void join_block_min(long long &c, uint32_t &k, uint32
 	}
 }
 
+// The kernels' bodies are device functions, so that the single-tree kernels and their batched twins (one replicate per blockIdx.y, every
+// array at a stride; pga_pan_boot, k_boot.hpp) are the same code.
+
 // label[p] = p, aux[p] = R or 1, flag |= an entry out of the input range.  One workgroup per row.
 template <bool NJ>
-__global__ __launch_bounds__(BLOCK) void k_join_init(const int32_t *__restrict__ d, int32_t n, int32_t ld, int32_t *__restrict__ label, long long *__restrict__ aux,
-                                                     int32_t *__restrict__ flag)
+__device__ __forceinline__ void join_init_body(const int32_t *__restrict__ d, int32_t n, int32_t ld, int32_t *__restrict__ label, long long *__restrict__ aux,
+                                               int32_t *__restrict__ flag)
 {
 	__shared__ unsigned long long sh[BLOCK / WAVE];
 	const int32_t row = (int32_t)blockIdx.x;
@@ -86,8 +89,15 @@ __global__ __launch_bounds__(BLOCK) void k_join_init(const int32_t *__restrict__
 }
 
 template <bool NJ>
-__global__ __launch_bounds__(BLOCK) void k_join_argmin(const int32_t *__restrict__ d, int32_t ld, int32_t r, const int32_t *__restrict__ label,
-                                                       const long long *__restrict__ aux, JoinPart *__restrict__ part)
+__global__ __launch_bounds__(BLOCK) void k_join_init(const int32_t *__restrict__ d, int32_t n, int32_t ld, int32_t *__restrict__ label, long long *__restrict__ aux,
+                                                     int32_t *__restrict__ flag)
+{
+	join_init_body<NJ>(d, n, ld, label, aux, flag);
+}
+
+template <bool NJ>
+__device__ __forceinline__ void join_argmin_body(const int32_t *__restrict__ d, int32_t ld, int32_t r, const int32_t *__restrict__ label,
+                                                 const long long *__restrict__ aux, JoinPart *__restrict__ part)
 {
 	__shared__ unsigned long long sh[2 * BLOCK / WAVE];
 	const int32_t n_cc = (r + JOIN_CW - 1) / JOIN_CW, n_rb = (r + JOIN_RB - 1) / JOIN_RB, n_tile = n_cc * n_rb;
@@ -141,10 +151,17 @@ __global__ __launch_bounds__(BLOCK) void k_join_argmin(const int32_t *__restrict
 	}
 }
 
+template <bool NJ>
+__global__ __launch_bounds__(BLOCK) void k_join_argmin(const int32_t *__restrict__ d, int32_t ld, int32_t r, const int32_t *__restrict__ label,
+                                                       const long long *__restrict__ aux, JoinPart *__restrict__ part)
+{
+	join_argmin_body<NJ>(d, ld, r, label, aux, part);
+}
+
 // step s of the run: record s, the new row and column, R, the compaction, the range flag.  One thread per live position.
 template <bool NJ>
-__global__ __launch_bounds__(BLOCK) void k_join_update(int32_t *__restrict__ d, int32_t ld, int32_t r, int32_t *__restrict__ label, long long *__restrict__ aux,
-                                                       const JoinPart *__restrict__ part, int32_t n_part, long long *__restrict__ rec, int32_t *__restrict__ flag)
+__device__ __forceinline__ void join_update_body(int32_t *__restrict__ d, int32_t ld, int32_t r, int32_t *__restrict__ label, long long *__restrict__ aux,
+                                                 const JoinPart *__restrict__ part, int32_t n_part, long long *__restrict__ rec, int32_t *__restrict__ flag)
 {
 	__shared__ unsigned long long sh[2 * BLOCK / WAVE];
 	long long best = INT64_MAX;
@@ -193,8 +210,15 @@ __global__ __launch_bounds__(BLOCK) void k_join_update(int32_t *__restrict__ d, 
 	}
 }
 
+template <bool NJ>
+__global__ __launch_bounds__(BLOCK) void k_join_update(int32_t *__restrict__ d, int32_t ld, int32_t r, int32_t *__restrict__ label, long long *__restrict__ aux,
+                                                       const JoinPart *__restrict__ part, int32_t n_part, long long *__restrict__ rec, int32_t *__restrict__ flag)
+{
+	join_update_body<NJ>(d, ld, r, label, aux, part, n_part, rec, flag);
+}
+
 // NJ's closing record at r = 3: the live slots x < y < z and their three distances
-__global__ void k_join_final(const int32_t *__restrict__ d, int32_t ld, const int32_t *__restrict__ label, long long *__restrict__ rec)
+__device__ __forceinline__ void join_final_body(const int32_t *__restrict__ d, int32_t ld, const int32_t *__restrict__ label, long long *__restrict__ rec)
 {
 	if (threadIdx.x != 0 || blockIdx.x != 0) return;
 	int32_t p[3] = {0, 1, 2};
@@ -203,4 +227,46 @@ __global__ void k_join_final(const int32_t *__restrict__ d, int32_t ld, const in
 			if (label[p[y]] > label[p[y + 1]]) { const int32_t t = p[y]; p[y] = p[y + 1]; p[y + 1] = t; }
 	rec[0] = label[p[0]], rec[1] = label[p[1]], rec[2] = label[p[2]];
 	rec[3] = d[(size_t)p[0] * (size_t)ld + p[1]], rec[4] = d[(size_t)p[0] * (size_t)ld + p[2]], rec[5] = d[(size_t)p[1] * (size_t)ld + p[2]];
+}
+
+__global__ void k_join_final(const int32_t *__restrict__ d, int32_t ld, const int32_t *__restrict__ label, long long *__restrict__ rec)
+{
+	join_final_body(d, ld, label, rec);
+}
+
+// The batched twins: replicate blockIdx.y of a bootstrap chunk.  All replicates have the same n, ld and live count r, so one launch
+// serves a step of every replicate; d is d_stride words apart, label and aux v_stride entries, part p_stride candidates, rec
+// rec_stride words, and the flags are one word each.
+template <bool NJ>
+__global__ __launch_bounds__(BLOCK) void k_join_init_b(const int32_t *__restrict__ d, int32_t n, int32_t ld, int32_t *__restrict__ label, long long *__restrict__ aux,
+                                                       int32_t *__restrict__ flag, size_t d_stride, int32_t v_stride)
+{
+	const size_t q = blockIdx.y;
+	join_init_body<NJ>(d + q * d_stride, n, ld, label + q * (size_t)v_stride, aux + q * (size_t)v_stride, flag + q);
+}
+
+template <bool NJ>
+__global__ __launch_bounds__(BLOCK) void k_join_argmin_b(const int32_t *__restrict__ d, int32_t ld, int32_t r, const int32_t *__restrict__ label,
+                                                         const long long *__restrict__ aux, JoinPart *__restrict__ part, size_t d_stride, int32_t v_stride,
+                                                         int32_t p_stride)
+{
+	const size_t q = blockIdx.y;
+	join_argmin_body<NJ>(d + q * d_stride, ld, r, label + q * (size_t)v_stride, aux + q * (size_t)v_stride, part + q * (size_t)p_stride);
+}
+
+template <bool NJ>
+__global__ __launch_bounds__(BLOCK) void k_join_update_b(int32_t *__restrict__ d, int32_t ld, int32_t r, int32_t *__restrict__ label, long long *__restrict__ aux,
+                                                         const JoinPart *__restrict__ part, int32_t n_part, long long *__restrict__ rec, int32_t *__restrict__ flag,
+                                                         size_t d_stride, int32_t v_stride, int32_t p_stride, size_t rec_stride)
+{
+	const size_t q = blockIdx.y;
+	join_update_body<NJ>(d + q * d_stride, ld, r, label + q * (size_t)v_stride, aux + q * (size_t)v_stride, part + q * (size_t)p_stride, n_part,
+	                     rec + q * rec_stride, flag + q);
+}
+
+__global__ void k_join_final_b(const int32_t *__restrict__ d, int32_t ld, const int32_t *__restrict__ label, long long *__restrict__ rec, size_t d_stride,
+                               int32_t v_stride, size_t rec_stride)
+{
+	const size_t q = blockIdx.y;
+	join_final_body(d + q * d_stride, ld, label + q * (size_t)v_stride, rec + q * rec_stride);
 }

@@ -2,11 +2,20 @@
 // include/pangene_amd.h).  The distances of pangene dist become fixed-point integers, neighbour-joining or UPGMA joins them in integer
 // arithmetic (DESIGN.md section 8 "Trees": every sum is an integer sum, ties go to the smallest slot numbers), and only the Newick text
 // is floating point.  The joins run on the backend (pga_pan_join), or as the plain loops below when the backend has no such entry.
+// Bootstrap support (pg_pan_boot, pg_pan_boot_records, pangene tree -b; DESIGN.md section 8 "Bootstrap"): the replicates' records come from
+// the backend in chunks (pga_pan_boot), or from the plain loops below, and are folded into per-join counts here, in code both builds share.
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <unordered_map>
 #include <vector>
 #include "pg_internal.hpp"
+
+// The replicates one pan_boot call takes.  It is not in the backend table (the table's last member is pan_boot), so it is found by
+// name: a library whose backend sets pan_boot exports it, a library without pan_boot (the checker build) does not, and the weak
+// declaration is then null.  The two go together: boot_walk treats pan_boot without pga_boot_batch as an error, not as "no backend".
+extern "C" int32_t pga_boot_batch(int32_t n_asm) __attribute__((weak));
 
 namespace pgx {
 namespace {
@@ -131,6 +140,159 @@ int join_run(const int32_t *q, int32_t n, int32_t method, int64_t *rec)
 	return rc;
 }
 
+uint64_t mix64(uint64_t z) // splitmix64's output function (as curves.cpp)
+{
+	z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+	z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+	return z ^ (z >> 31);
+}
+
+// Replicate b of the definition as plain loops: the draws, the resampled rows, shared_count, to_fixed, join_host.  bits[A][W]
+int boot_host(const std::vector<uint32_t> &bits, int32_t M, int32_t A, int32_t metric, int32_t method, uint32_t seed, uint32_t b, int64_t *rec)
+{
+	const size_t W = ((size_t)M + 31) / 32, nn = (size_t)A * (size_t)A;
+	std::vector<uint32_t> rows((size_t)A * W, 0);
+	const uint64_t x0 = mix64((uint64_t)seed << 32 | (uint64_t)b);
+	for (int32_t t = 0; t < M; ++t) {
+		const uint64_t m = mix64(x0 + (uint64_t)(t + 1) * 0x9E3779B97F4A7C15ull) % (uint64_t)M;
+		for (size_t a = 0; a < (size_t)A; ++a)
+			if (bits[a * W + (size_t)(m >> 5)] >> (m & 31) & 1u) rows[a * W + (size_t)(t >> 5)] |= 1u << (t & 31);
+	}
+	std::vector<int32_t> S(nn), q(nn);
+	int rc = shared_count(rows, M, A, S.data());
+	if (rc != 0) return rc;
+	int32_t F;
+	if ((rc = to_fixed(S.data(), A, metric, q.data(), &F)) != 0) return rc;
+	return join_host(q, A, method, rec);
+}
+
+// The records of replicates first .. first + n - 1, chunk by chunk: use(records of the chunk [k][n_rec][6], k) after each.  The backend's
+// chunk is pga_boot_batch(A) replicates, the host loops' one; host memory is bounded by a chunk.  A >= 3
+template <class Use>
+int boot_walk(const std::vector<uint32_t> &bits, int32_t M, int32_t A, int32_t metric, int32_t method, uint32_t seed, int32_t first, int32_t n, Use use)
+{
+	if (A > 65535) return PGA_ERR_RANGE;
+	const pga_backend_t *be = backend_default();
+	const size_t n_rec = (size_t)(method == PG_TREE_NJ ? A - 2 : A - 1);
+	if (be->pan_boot != nullptr) {
+		if (pga_boot_batch == nullptr) { std::fprintf(stderr, "[E::pg_pan_boot] the backend has pan_boot, but the library exports no pga_boot_batch\n"); return PGA_ERR_ARG; }
+		const int32_t batch = std::max(1, pga_boot_batch(A));
+		for (int32_t k = 0; k < n; k += batch) {
+			const pga_boot_in_t in{bits.data(), M, A, metric, method, seed, first + k, std::min(batch, n - k), nullptr};
+			pga_boot_out_t res{};
+			const int rc = be->pan_boot(&in, &res);
+			if (rc != 0) return rc;
+			use(res.rec, in.n_rep);
+		}
+		return 0;
+	}
+	std::vector<int64_t> rec(6 * n_rec);
+	for (int32_t k = 0; k < n; ++k) {
+		const int rc = boot_host(bits, M, A, metric, method, seed, (uint32_t)(first + k), rec.data());
+		if (rc != 0) return rc == 1 ? PGA_ERR_ARG : rc; // (1: PANGENE_TREE_STOP_AFTER, which is for timing a single tree)
+		use(rec.data(), 1);
+	}
+	return 0;
+}
+
+// Support of the reference tree's joins among the replicates, by exact comparison of leaf sets.  The reference's leaves are numbered in
+// the order its own subtrees list them (Day's numbering), so that the leaves below each of its joins are an interval [lo, hi]; a set of
+// a replicate is the same set exactly when its smallest and its largest number span as many numbers as it has leaves and that interval
+// is one of the reference's.  NJ compares splits of the unrooted tree, each by its side without the last-numbered leaf: for the
+// reference that side is [lo, hi] or [0, lo - 1]; for a replicate's join that holds the leaf it is everything else, collected on
+// the way down from the trifurcation to that leaf.  O(A) a replicate.
+struct Support {
+	struct Span { int32_t lo, hi, sz; };
+	static Span both(const Span &a, const Span &b) { return Span{std::min(a.lo, b.lo), std::max(a.hi, b.hi), a.sz + b.sz}; }
+	int32_t A, n_lab; // n_lab: the joins that can be supported: A - 3 (NJ), A - 2 (UPGMA)
+	bool nj;
+	int32_t last_leaf = 0;                          // the leaf numbered A - 1
+	std::vector<int32_t> pos;                       // leaf -> its number
+	std::unordered_map<uint64_t, int32_t> join_of;  // lo << 32 | hi -> join of the reference
+	// of the replicate being folded; nodes: leaf x = x, join t = A + t
+	std::vector<Span> span;
+	std::vector<int32_t> at, up, kid, chain, seen;  // node at a slot; parent; the two children of a join; seen[s] = the last replicate that supported s
+	int32_t n_seen = 0;
+
+	Support(const int64_t *rec, int32_t A_, int32_t method)
+	    : A(A_), n_lab(std::max(method == PG_TREE_NJ ? A_ - 3 : A_ - 2, 0)), nj(method == PG_TREE_NJ), pos((size_t)A_), span((size_t)A_ + (size_t)n_lab), at((size_t)A_),
+	      up((size_t)A_ + (size_t)n_lab), kid(2 * (size_t)n_lab), seen((size_t)n_lab, 0)
+	{
+		const size_t n = (size_t)A;
+		std::vector<int32_t> head(n), tail(n), next(n, -1), cnt(n, 1), first((size_t)n_lab), last((size_t)n_lab), size_of((size_t)n_lab);
+		for (size_t x = 0; x < n; ++x) head[x] = tail[x] = (int32_t)x;
+		const int32_t n_join = nj ? A - 3 : A - 1;
+		for (int32_t s = 0; s < n_join; ++s) { // the leaves below slot i, then those below slot j
+			const size_t i = (size_t)rec[6 * (size_t)s], j = (size_t)rec[6 * (size_t)s + 1];
+			next[(size_t)tail[i]] = head[j], tail[i] = tail[j], cnt[i] += cnt[j];
+			if (s < n_lab) first[(size_t)s] = head[i], last[(size_t)s] = tail[i], size_of[(size_t)s] = cnt[i];
+		}
+		const size_t root = (size_t)rec[6 * (size_t)(nj ? n_join : n_join - 1)];
+		if (nj) { // the three subtrees of the closing record, one after the other
+			const size_t y = (size_t)rec[6 * (size_t)n_join + 1], z = (size_t)rec[6 * (size_t)n_join + 2];
+			next[(size_t)tail[root]] = head[y], next[(size_t)tail[y]] = head[z];
+		}
+		int32_t k = 0;
+		for (int32_t x = head[root]; x >= 0; x = next[(size_t)x]) last_leaf = x, pos[(size_t)x] = k++;
+		for (int32_t s = 0; s < n_lab; ++s) {
+			int32_t l = pos[(size_t)first[(size_t)s]], h = pos[(size_t)last[(size_t)s]]; // (h - l + 1 = size_of[s])
+			if (nj && h == A - 1) h = l - 1, l = 0;
+			join_of.emplace((uint64_t)(uint32_t)l << 32 | (uint32_t)h, s);
+		}
+	}
+	void hit(const Span &c, int32_t *count)
+	{
+		if (c.hi - c.lo + 1 != c.sz) return;
+		const auto it = join_of.find((uint64_t)(uint32_t)c.lo << 32 | (uint32_t)c.hi);
+		if (it != join_of.end() && seen[(size_t)it->second] != n_seen) seen[(size_t)it->second] = n_seen, ++count[(size_t)it->second];
+	}
+	// one replicate's records -> count[s] += 1 for every supported s
+	void fold(const int64_t *rec, int32_t *count)
+	{
+		++n_seen;
+		for (int32_t x = 0; x < A; ++x) span[(size_t)x] = Span{pos[(size_t)x], pos[(size_t)x], 1}, at[(size_t)x] = x;
+		for (int32_t t = 0; t < n_lab; ++t) {
+			const size_t i = (size_t)rec[6 * (size_t)t], j = (size_t)rec[6 * (size_t)t + 1];
+			const int32_t v = A + t;
+			span[(size_t)v] = both(span[(size_t)at[i]], span[(size_t)at[j]]);
+			kid[2 * (size_t)t] = at[i], kid[2 * (size_t)t + 1] = at[j];
+			up[(size_t)at[i]] = up[(size_t)at[j]] = v;
+			at[i] = v;
+			if (!nj || span[(size_t)v].hi != A - 1) hit(span[(size_t)v], count);
+		}
+		if (!nj) return;
+		// the joins that hold the last leaf: from the trifurcation down to it, each against everything that is not below it
+		const int64_t *fin = rec + 6 * (size_t)n_lab;
+		const int32_t top[3] = {at[(size_t)fin[0]], at[(size_t)fin[1]], at[(size_t)fin[2]]};
+		for (const int32_t v : top) up[(size_t)v] = -1;
+		chain.clear();
+		for (int32_t v = last_leaf; v >= 0; v = up[(size_t)v]) chain.push_back(v);
+		Span rest{A, -1, 0};
+		for (const int32_t v : top)
+			if (v != chain.back()) rest = both(rest, span[(size_t)v]);
+		for (size_t m = chain.size() - 1; m >= 1; --m) {
+			const int32_t v = chain[m], c = chain[m - 1]; // v is a join, c its child on the way
+			hit(rest, count);
+			const int32_t *kd = kid.data() + 2 * (size_t)(v - A);
+			rest = both(rest, span[(size_t)(kd[0] == c ? kd[1] : kd[0])]);
+		}
+	}
+};
+
+// count[n_rec] of the reference records rec over replicates 1 .. B; A >= 3
+int boot_support(const std::vector<uint32_t> &bits, int32_t M, int32_t A, int32_t metric, int32_t method, int32_t B, uint32_t seed, const int64_t *rec, int32_t *count)
+{
+	const int32_t n_rec = method == PG_TREE_NJ ? A - 2 : A - 1;
+	std::fill(count, count + n_rec, 0);
+	count[n_rec - 1] = B; // NJ's closing record, UPGMA's root: by definition
+	if (B == 0 || n_rec < 2) return 0; // A < 4 (NJ): no join that can be supported, and no device work
+	Support sup(rec, A, method);
+	const size_t stride = 6 * (size_t)n_rec;
+	return boot_walk(bits, M, A, metric, method, seed, 1, B, [&](const int64_t *r, int32_t k) {
+		for (int32_t x = 0; x < k; ++x) sup.fold(r + stride * (size_t)x, count);
+	});
+}
+
 std::string quoted(const std::string &s)
 {
 	if (s.find_first_of("(),:;[]' \t\n") == std::string::npos) return s;
@@ -146,8 +308,14 @@ std::string len_text(double fixed, int32_t F)
 	return b;
 }
 
-// the records of n >= 3 leaves -> one Newick line
-std::string newick(const std::vector<std::string> &names, const int64_t *rec, int32_t method, int32_t F)
+// "P" behind the node of a join: count of B replicates in per cent, rounded half up; nothing without a bootstrap
+std::string support_text(const int32_t *count, size_t s, int32_t B)
+{
+	return B > 0 ? std::to_string((200 * (int64_t)count[s] + B) / (2 * (int64_t)B)) : std::string();
+}
+
+// the records of n >= 3 leaves -> one Newick line; B > 0: count[] labels the joins' nodes
+std::string newick(const std::vector<std::string> &names, const int64_t *rec, int32_t method, int32_t F, const int32_t *count = nullptr, int32_t B = 0)
 {
 	const size_t n = names.size();
 	std::vector<std::string> sub(n);
@@ -157,7 +325,7 @@ std::string newick(const std::vector<std::string> &names, const int64_t *rec, in
 		for (size_t s = 0; s + 3 < n; ++s, rec += 6) {
 			const size_t i = (size_t)rec[0], j = (size_t)rec[1];
 			const double li = ((double)rec[2] + (double)(rec[3] - rec[4]) / (double)(rec[5] - 2)) / 2.0, lj = (double)rec[2] - li;
-			sub[i] = "(" + sub[i] + len_text(li, F) + "," + sub[j] + len_text(lj, F) + ")";
+			sub[i] = "(" + sub[i] + len_text(li, F) + "," + sub[j] + len_text(lj, F) + ")" + support_text(count, s, B);
 			std::string().swap(sub[j]);
 		}
 		const size_t x = (size_t)rec[0], y = (size_t)rec[1], z = (size_t)rec[2];
@@ -168,7 +336,7 @@ std::string newick(const std::vector<std::string> &names, const int64_t *rec, in
 	for (size_t s = 0; s + 1 < n; ++s, rec += 6) {
 		const size_t i = (size_t)rec[0], j = (size_t)rec[1];
 		const double h = (double)rec[2] / 2.0;
-		sub[i] = "(" + sub[i] + len_text(h - height[i], F) + "," + sub[j] + len_text(h - height[j], F) + ")";
+		sub[i] = "(" + sub[i] + len_text(h - height[i], F) + "," + sub[j] + len_text(h - height[j], F) + ")" + (s + 2 < n ? support_text(count, s, B) : std::string());
 		std::string().swap(sub[j]);
 		height[i] = h, root = i;
 	}
@@ -197,7 +365,7 @@ int tree_records(const std::vector<uint32_t> &bits, int32_t M, int32_t A, int32_
 
 int tree_run(const char *route, const std::vector<std::string> &names, const std::vector<uint32_t> &bits, int32_t M, const pg_tree_opt_t *o, double t_start)
 {
-	if ((o->metric != PG_DIST_JACCARD && o->metric != PG_DIST_DIFF) || (o->method != PG_TREE_NJ && o->method != PG_TREE_UPGMA)) return PGA_ERR_ARG;
+	if ((o->metric != PG_DIST_JACCARD && o->metric != PG_DIST_DIFF) || (o->method != PG_TREE_NJ && o->method != PG_TREE_UPGMA) || o->n_boot < 0) return PGA_ERR_ARG;
 	const int32_t A = (int32_t)names.size();
 	const double t_prep = now_sec() - t_start;
 	std::vector<int32_t> q;
@@ -208,6 +376,13 @@ int tree_run(const char *route, const std::vector<std::string> &names, const std
 		const int rc = tree_records(bits, M, A, o->metric, o->method, q, rec.data(), &F);
 		if (rc != 0) return rc;
 	}
+	std::vector<int32_t> count((size_t)std::max(A, 1), 0);
+	if (A >= 3 && o->n_boot > 0) {
+		const double t0 = now_sec();
+		const int rc = boot_support(bits, M, A, o->metric, o->method, o->n_boot, o->seed, rec.data(), count.data());
+		if (rc != 0) return rc;
+		t_join += now_sec() - t0;
+	}
 	const double t1 = now_sec();
 	std::string s;
 	if (A == 0) s = ";\n";
@@ -215,7 +390,7 @@ int tree_run(const char *route, const std::vector<std::string> &names, const std
 	else if (A == 2) {
 		const std::string h = len_text((double)q[1] / 2.0, F);
 		s = "(" + quoted(names[0]) + h + "," + quoted(names[1]) + h + ");\n";
-	} else s = newick(names, rec.data(), o->method, F);
+	} else s = newick(names, rec.data(), o->method, F, count.data(), o->n_boot);
 	FILE *fp = out_stream();
 	std::fwrite(s.data(), 1, s.size(), fp);
 	std::fflush(fp);
@@ -269,6 +444,37 @@ int pg_pan_tree(const uint8_t *presence, int32_t n_item, int32_t n_asm, int32_t 
 	presence_bits(presence, n_item, n_asm, bits);
 	std::vector<int32_t> q;
 	return tree_records(bits, n_item, n_asm, metric, method, q, rec, frac_bits);
+}
+
+static bool boot_args_ok(const uint8_t *presence, int32_t n_item, int32_t n_asm, int32_t metric, int32_t method)
+{
+	return (metric == PG_DIST_JACCARD || metric == PG_DIST_DIFF) && (method == PG_TREE_NJ || method == PG_TREE_UPGMA) && n_item >= 0 && n_asm >= 3 &&
+	       !((size_t)n_item > 0 && presence == nullptr);
+}
+
+int pg_pan_boot(const uint8_t *presence, int32_t n_item, int32_t n_asm, int32_t metric, int32_t method, int32_t n_boot, uint32_t seed, int64_t *rec,
+                int32_t *frac_bits, int32_t *count)
+{
+	if (!boot_args_ok(presence, n_item, n_asm, metric, method) || n_boot < 0 || rec == nullptr || frac_bits == nullptr || count == nullptr) return PGA_ERR_ARG;
+	std::vector<uint32_t> bits;
+	presence_bits(presence, n_item, n_asm, bits);
+	std::vector<int32_t> q;
+	const int rc = tree_records(bits, n_item, n_asm, metric, method, q, rec, frac_bits);
+	return rc != 0 ? rc : boot_support(bits, n_item, n_asm, metric, method, n_boot, seed, rec, count);
+}
+
+int pg_pan_boot_records(const uint8_t *presence, int32_t n_item, int32_t n_asm, int32_t metric, int32_t method, uint32_t seed, int32_t first, int32_t n,
+                        int64_t *rec_out)
+{
+	if (!boot_args_ok(presence, n_item, n_asm, metric, method) || first < 1 || n < 0 || (int64_t)first + n - 1 > INT32_MAX || (n > 0 && rec_out == nullptr)) return PGA_ERR_ARG;
+	std::vector<uint32_t> bits;
+	presence_bits(presence, n_item, n_asm, bits);
+	const size_t stride = 6 * (size_t)(method == PG_TREE_NJ ? n_asm - 2 : n_asm - 1);
+	int64_t *at = rec_out;
+	return boot_walk(bits, n_item, n_asm, metric, method, seed, first, n, [&](const int64_t *r, int32_t k) {
+		std::memcpy(at, r, sizeof(int64_t) * stride * (size_t)k);
+		at += stride * (size_t)k;
+	});
 }
 
 } // extern "C"
