@@ -316,18 +316,35 @@ int64_t pg_pan_assoc(const uint8_t *presence, int32_t n_gene, int32_t n_asm, con
  * trait file); pg_write_trait: the graph in memory after pg_graph_gen (errors: pg_last_error); pg_pan_trait: any presence matrix,
  * row-major uint8 [n_gene][n_asm], and labels, row-major int8 [n_trait][n_asm] (1, 0, -1 = missing): fills
  * out[5][n_trait][n_gene] = N, t, a, s, k (a = -1, s = k = 0 for a gene that is not eligible, and for every gene of a trait with
- * t = 0 or t = N) and returns 0 or a negative PGA_ERR_*. */
+ * t = 0 or t = N) and returns 0 or a negative PGA_ERR_*.
+ * Lineage-aware test (lineage = PG_LINEAGE_NJ or PG_LINEAGE_UPGMA; DESIGN.md section 8 "Lineage-aware trait test" holds the definition):
+ * population structure confounds the counts above -- a gene and a trait that sit in the same clade give a tiny p_fisher from one
+ * evolutionary event -- so every line gains the pairwise comparisons on a tree.  The tree is the one `pangene tree -t gene -m jaccard`
+ * builds with that method over ALL assemblies of the matrix (NJ's closing trifurcation (x, y, z) read as ((x, y), z); the numbers below
+ * belong to the unrooted tree).  A leaf with a trait value has the type (gene bit, y); a pair is two typed leaves that differ in both,
+ * 11-00 supporting and 10-01 opposing; a pair set is a set of pairs whose tree paths share no vertex.  pairs = the size of a largest
+ * pair set, supp / opp = the most supporting / opposing pairs a largest pair set can have (integers, the backend's pga_pan_pairs).
+ * With `for` = supp when D >= 0 and opp otherwise, `against` the other, and P2(k, n) = min(1, 2 P(X >= max(k, n - k))) for X binomial
+ * (n, 1/2), 1 for n = 0: p_pair_best = P2(for, pairs), p_pair_worst = P2(pairs - against, pairs).  Five more columns,
+ * "pairs supp opp p_pair_best p_pair_worst", the p values as %.3e; without lineage the output is what it was.  At most 65 535 assemblies.
+ * pg_pan_pairs: presence and labels as for pg_pan_trait, rec = the records of a tree over the n_asm assemblies as pg_pan_tree or
+ * pg_pan_join return them for `method` (any such tree; not read when n_asm < 3: one leaf is a tree, two are one join): fills
+ * out[3][n_trait][n_gene] = pairs, supp, opp and returns 0 or a negative PGA_ERR_* (records that name a slot out of range or a
+ * retired one: PGA_ERR_ARG). */
+enum { PG_LINEAGE_NONE = 0, PG_LINEAGE_NJ = 1, PG_LINEAGE_UPGMA = 2 };
 typedef struct {
 	int32_t  n_perm;    /* permutations; 0: none [1000] */
 	uint32_t seed;      /* seed of the orders [11] */
 	int32_t  min_count; /* a gene is eligible when min(a, N - a) >= min_count; >= 1 [1] */
 	int32_t  reserved;
 	double   max_p;     /* keep the lines with p_fisher <= max_p [1: all] */
+	int32_t  lineage;   /* PG_LINEAGE_NONE, PG_LINEAGE_NJ or PG_LINEAGE_UPGMA: the pairwise comparisons on that tree [none] */
 } pg_trait_opt_t;
 void pg_trait_opt_init(pg_trait_opt_t *o);
 int  pg_trait_file(const char *gfa_fn, const char *trait_fn, const pg_trait_opt_t *o);
 void pg_write_trait(pg_graph_t *g, const char *trait_fn, const pg_trait_opt_t *o);
 int  pg_pan_trait(const uint8_t *presence, const int8_t *labels, int32_t n_gene, int32_t n_asm, int32_t n_trait, const pg_trait_opt_t *o, int32_t *out);
+int  pg_pan_pairs(const uint8_t *presence, const int8_t *labels, int32_t n_gene, int32_t n_asm, int32_t n_trait, const int64_t *rec, int32_t method, int32_t *out);
 
 /* Last error of the path (0 = none).  The reference aborts on invariant violations; this library
  * records a status instead, prints one line to stderr, and leaves the graph empty. */

@@ -94,7 +94,7 @@ typedef struct {
  * Device layout limits (PGA_ERR_RANGE otherwise): coordinates inside a block < 2^31 (contigs beyond that arrive as virtual contigs,
  * see pga_genome_block_t; what remains out of reach is a single cluster of overlapping hits spanning 2^30 bp), < 2^30 hits and < 2^31
  * exons per shard, < 2^20 genes, < 2^24 genomes. */
-#define PGA_ABI_VERSION 12u  /* bumped whenever a struct of this header or the order of pga_backend_t changes; pga_create refuses another */
+#define PGA_ABI_VERSION 13u  /* bumped whenever a struct of this header or the order of pga_backend_t changes; pga_create refuses another */
 typedef struct {
 	uint32_t abi_version;        /* = PGA_ABI_VERSION of the header the caller was compiled against (PGA_ERR_ARG otherwise) */
 	int32_t n_genome;            /* genomes in this shard (may include genomes with 0 hits) */
@@ -427,6 +427,29 @@ typedef struct { const int64_t *rec; int32_t n_rec; } pga_boot_out_t;
 int pga_pan_boot(const pga_boot_in_t *in, pga_boot_out_t *out);
 int32_t pga_boot_batch(int32_t n_asm);
 
+/* Lineage-aware pairwise comparisons (include/pangene_amd.h pg_pan_pairs, pangene trait -L; DESIGN.md section 8 "Lineage-aware trait
+ * test"): per gene and label row, the largest set of leaf pairs of a binary tree that contrast in gene and label and whose paths share
+ * no vertex, and the most supporting (11-00) and the most opposing (10-01) pairs such a largest set can have.  Context-free, like
+ * pan_trait.  The tree comes as a postfix program over a stack of subtrees: op 0 pushes the next leaf, op 1 joins the top two entries.
+ * An entry holds N and F_s for the four leaf types s = (gene bit, label); a typed leaf is N = 0, F_s = 0 for its own s and infeasible
+ * for the others, a leaf without a label N = 0 and nothing feasible; a join of l and r is F_s = max(F_s[l] + N[r], N[l] + F_s[r]),
+ * N = max(N[l] + N[r], F_s[l] + F_t[r] + one pair over the contrasting (s, t)), values ordered by (pairs, pairs of the run's side); the
+ * run for the supporting side and the run for the opposing side give out = (pairs, supp, opp) at the last entry left.
+ * In:  op[2 n_leaf - 1] (a well-formed program of n_leaf pushes whose stack never holds more than 16 entries; malformed: PGA_ERR_ARG,
+ *      deeper: PGA_ERR_RANGE -- a caller that visits the child with the larger stack need first stays within
+ *      floor(log2 n_leaf) + 1 <= 16); bits[n_leaf][(n_gene + 31) / 32], assembly-major as for pan_shared, row k = the k-th pushed leaf,
+ *      bits past n_gene zero; label[n_row][n_leaf] int8 (1, 0, negative = none) in the same leaf order.
+ * Out: out[n_row][n_gene][3] = pairs, supp, opp.  The array belongs to the backend and stays valid until its next pan_pairs.
+ * Limits (PGA_ERR_RANGE otherwise): n_leaf <= 65 535 (pairs <= 32 767: the packed values stay below 2^30), n_gene <= 16 777 215. */
+typedef struct {
+	const uint8_t *op;
+	const uint32_t *bits;
+	const int8_t *label;
+	int32_t n_gene, n_leaf, n_row;
+} pga_pairs_in_t;
+typedef struct { const int32_t *out; } pga_pairs_out_t;
+int pga_pan_pairs(const pga_pairs_in_t *in, pga_pairs_out_t *out);
+
 /* the same ABI as a table, so the host driver is written once */
 struct pga_branch_par_s; struct pga_loop_xchg_s;
 typedef struct {
@@ -489,6 +512,7 @@ typedef struct {
 	int  (*pan_trait)(const pga_trait_in_t *, pga_trait_out_t *); /* may be NULL: the host driver then runs the same step itself */
 	int  (*pan_join)(const pga_join_in_t *, pga_join_out_t *); /* may be NULL: the host driver then runs the same step itself */
 	int  (*pan_boot)(const pga_boot_in_t *, pga_boot_out_t *); /* may be NULL: the host driver then runs the same step itself */
+	int  (*pan_pairs)(const pga_pairs_in_t *, pga_pairs_out_t *); /* may be NULL: the host driver then runs the same step itself */
 } pga_backend_t;
 
 const pga_backend_t *pga_backend(void);

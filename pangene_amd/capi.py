@@ -232,21 +232,27 @@ def _assoc_args(argv: Sequence[str]):
 
 
 class pg_trait_opt_t(C.Structure):
-    """Trait options (include/pangene_amd.h): permutations, their seed, smallest min(a, N - a) of a tested gene, p_fisher cutoff of the lines."""
-    _fields_ = [("n_perm", C.c_int32), ("seed", C.c_uint32), ("min_count", C.c_int32), ("reserved", C.c_int32), ("max_p", C.c_double)]
+    """Trait options (include/pangene_amd.h): permutations, their seed, smallest min(a, N - a) of a tested gene, p_fisher cutoff of the lines,
+    the tree of the lineage-aware pairwise comparisons (0 none, 1 nj, 2 upgma)."""
+    _fields_ = [("n_perm", C.c_int32), ("seed", C.c_uint32), ("min_count", C.c_int32), ("reserved", C.c_int32), ("max_p", C.c_double),
+                ("lineage", C.c_int32)]
 
 
 TRAIT_MAX_PERM = 2147483646
+TRAIT_LINEAGES = (None, "nj", "upgma")
 
 
-def trait_opt(lib: C.CDLL, n_perm: int = 1000, seed: int = 11, min_count: int = 1, max_p: float = 1.0) -> pg_trait_opt_t:
+def trait_opt(lib: C.CDLL, n_perm: int = 1000, seed: int = 11, min_count: int = 1, max_p: float = 1.0, lineage=None) -> pg_trait_opt_t:
     if not 0 <= int(n_perm) <= TRAIT_MAX_PERM:
         raise ValueError("n_perm must be in [0, 2^31 - 2]")
     if int(min_count) < 1:
         raise ValueError("min_count must be at least 1")
+    if lineage not in TRAIT_LINEAGES:
+        raise ValueError("lineage must be nj, upgma or None")
     o = pg_trait_opt_t()
     lib.pg_trait_opt_init(C.byref(o))
     o.n_perm, o.seed, o.min_count, o.max_p = int(n_perm), int(seed) & 0xFFFFFFFF, int(min_count), float(max_p)
+    o.lineage = TRAIT_LINEAGES.index(lineage)
     return o
 
 
@@ -275,16 +281,49 @@ def pan_trait(lib: C.CDLL, presence, labels, n_perm: int = 1000, seed: int = 11,
     return {"N": out[0], "t": out[1], "a": out[2], "s": out[3], "k": out[4]}
 
 
+def pan_pairs(lib: C.CDLL, presence, labels, rec, method: str = "nj"):
+    """The lineage-aware pairwise comparisons of a gene x assembly presence matrix (shape (G, A)) with binary traits (labels as for
+    pan_trait) on the tree of the records rec (an int64 array as pan_tree or pan_join return it for `method`; any such tree over the A
+    assemblies, ignored when A < 3) through pg_pan_pairs: a dict of int32 arrays (T, G): pairs (the size of a largest set of contrasting
+    leaf pairs on vertex-disjoint paths), supp and opp (the most supporting and the most opposing pairs such a largest set can have)."""
+    import numpy as np
+    p = _presence(presence)
+    if hasattr(labels, "detach"):  # torch tensor, on any device
+        labels = labels.detach().cpu().numpy()
+    y = np.asarray(labels)
+    if y.ndim == 1:
+        y = y[None, :]
+    G, A = p.shape
+    if y.ndim != 2 or y.shape[1] != A:
+        raise ValueError("labels must be (traits x assemblies) over the assemblies of presence")
+    y = np.ascontiguousarray(np.where(y < 0, -1, np.where(y != 0, 1, 0)), dtype=np.int8)
+    T = y.shape[0]
+    m = TREE_METHODS.index(method)
+    rec = np.ascontiguousarray(rec if rec is not None else np.zeros((0, 6)), dtype=np.int64).reshape(-1, 6)
+    if A >= 3 and rec.shape[0] != A - 2 + m:
+        raise ValueError("rec must hold %d records for %d assemblies and %s" % (A - 2 + m, A, method))
+    out = np.zeros((3, T, G), dtype=np.int32)
+    rc = lib.pg_pan_pairs(p.ctypes.data_as(C.POINTER(C.c_uint8)), y.ctypes.data_as(C.POINTER(C.c_int8)), G, A, T, rec.ctypes.data_as(C.POINTER(C.c_int64)), m,
+                          out.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc != 0:
+        raise RuntimeError("pg_pan_pairs: status %d" % rc)
+    return {"pairs": out[0], "supp": out[1], "opp": out[2]}
+
+
 def _trait_args(argv: Sequence[str]):
-    """(file, permutations, seed) of --trait=FILE / --trait-perm=INT / --trait-seed=INT in argv; file = None without --trait."""
-    f, n, seed = None, 1000, 11
+    """(file, permutations, seed, lineage) of --trait=FILE / --trait-perm=INT / --trait-seed=INT / --trait-lineage=nj|upgma in argv;
+    file = None without --trait."""
+    f, n, seed, lineage = None, 1000, 11, None
     for a in argv:
         if a.startswith("--trait="): f = a.split("=", 1)[1]
         elif a.startswith("--trait-perm="): n = int(a.split("=", 1)[1])
         elif a.startswith("--trait-seed="): seed = int(a.split("=", 1)[1])
+        elif a.startswith("--trait-lineage="): lineage = a.split("=", 1)[1]
     if not 0 <= n <= TRAIT_MAX_PERM:
         raise ValueError("--trait-perm must be in [0, 2^31 - 2]")
-    return f, n, seed
+    if lineage is not None and (lineage not in TRAIT_LINEAGES or f is None):
+        raise ValueError("--trait-lineage must be nj or upgma and needs --trait=FILE")
+    return f, n, seed, lineage
 
 
 class pg_tree_opt_t(C.Structure):
@@ -454,6 +493,7 @@ _API = {
     "pg_trait_file": (C.c_int, [C.c_char_p, C.c_char_p, C.c_void_p]),
     "pg_write_trait": (None, [C.c_void_p, C.c_char_p, C.c_void_p]),
     "pg_pan_trait": (C.c_int, [C.POINTER(C.c_uint8), C.POINTER(C.c_int8), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]),
+    "pg_pan_pairs": (C.c_int, [C.POINTER(C.c_uint8), C.POINTER(C.c_int8), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int32)]),
     "pg_tree_opt_init": (None, [C.c_void_p]),
     "pg_tree_file": (C.c_int, [C.c_char_p, C.c_void_p]),
     "pg_write_tree": (None, [C.c_void_p, C.c_void_p]),
@@ -581,7 +621,7 @@ def run(lib: C.CDLL, files: Sequence[str], argv: Sequence[str] = (), scan_only: 
     assoc_phi, assoc_count, assoc_sign = _assoc_args(argv)
     if assoc_phi is not None and (any(x.startswith("--matrix") for x in argv) or "--call" in argv or n_curves or dist_type is not None):
         raise ValueError("--assoc cannot be combined with --matrix, --call, --curves or --dist")
-    trait_fn, trait_n, trait_seed = _trait_args(argv)
+    trait_fn, trait_n, trait_seed, trait_lineage = _trait_args(argv)
     if trait_fn is not None and (any(x.startswith("--matrix") for x in argv) or "--call" in argv or n_curves or dist_type is not None or assoc_phi is not None):
         raise ValueError("--trait cannot be combined with --matrix, --call, --curves, --dist or --assoc")
     tree_type, tree_metric, tree_method = _tree_args(argv)
@@ -625,7 +665,7 @@ def run(lib: C.CDLL, files: Sequence[str], argv: Sequence[str] = (), scan_only: 
                 if lib.pg_last_error():
                     raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
             elif trait_fn is not None:
-                lib.pg_write_trait(g, trait_fn.encode(), C.byref(trait_opt(lib, trait_n, trait_seed)))
+                lib.pg_write_trait(g, trait_fn.encode(), C.byref(trait_opt(lib, trait_n, trait_seed, lineage=trait_lineage)))
                 if lib.pg_last_error():
                     raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
             elif tree_type is not None:

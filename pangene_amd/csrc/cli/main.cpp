@@ -62,6 +62,7 @@ static int usage(FILE *fp, const pg_opt_t *opt)
 	std::fprintf(fp, "    --trait=FILE  output the association of every gene with the binary traits of FILE (assembly, then 1/0/NA per trait)\n");
 	std::fprintf(fp, "    --trait-perm=INT  --trait: label permutations [1000]\n");
 	std::fprintf(fp, "    --trait-seed=INT  --trait: seed of the permutations [11]\n");
+	std::fprintf(fp, "    --trait-lineage=STR  --trait: add the pairwise comparisons on the nj or upgma tree of the assemblies (pairs supp opp p_pair_best p_pair_worst)\n");
 	std::fprintf(fp, "    --tree[=STR]  output a tree of the assemblies (Newick) from their gene (gene) or gene-adjacency (adj) distances [gene]\n");
 	std::fprintf(fp, "    --tree-metric=STR  distance of --tree: jaccard or diff [jaccard]\n");
 	std::fprintf(fp, "    --tree-method=STR  --tree: nj (neighbour-joining, unrooted; negative branch lengths are printed as they come) or upgma [nj]\n");
@@ -72,7 +73,7 @@ static int usage(FILE *fp, const pg_opt_t *opt)
 	std::fprintf(fp, "        pangene curves [-n INT] [-s INT] <in.gfa>   (accumulation curves of the gfa2matrix matrix of a GFA file)\n");
 	std::fprintf(fp, "        pangene dist [-t gene|adj] [-m jaccard|shared|diff] [-p] <in.gfa>   (pairwise distances of the assemblies of a GFA file)\n");
 	std::fprintf(fp, "        pangene assoc [-r FLOAT] [-c INT] [-s pos|neg|both] [-x INT] <in.gfa>   (co-occurring and avoiding gene pairs of a GFA file)\n");
-	std::fprintf(fp, "        pangene trait -t FILE [-n INT] [-s INT] [-c INT] [-p FLOAT] <in.gfa>   (gene-trait association over the matrix of a GFA file)\n");
+	std::fprintf(fp, "        pangene trait -t FILE [-n INT] [-s INT] [-c INT] [-p FLOAT] <in.gfa>   (gene-trait association over the matrix of a GFA file; -L nj|upgma adds the lineage-aware pairwise comparisons)\n");
 	std::fprintf(fp, "        pangene tree [-t gene|adj] [-m jaccard|diff] [-a nj|upgma] [-b INT] [-s INT] <in.gfa>   (neighbour-joining or UPGMA tree of the assemblies of a GFA file, with bootstrap support)\n");
 	return fp == stdout ? 0 : 1;
 }
@@ -271,6 +272,8 @@ static bool trait_perm(const char *s, int32_t &n) // an integer in [0, 2^31 - 2]
 	return true;
 }
 
+static int trait_lineage(const char *s) { return std::strcmp(s, "nj") == 0 ? PG_LINEAGE_NJ : std::strcmp(s, "upgma") == 0 ? PG_LINEAGE_UPGMA : -1; }
+
 // `pangene trait`: the association of every gene of a GFA file with the binary traits of a trait file
 static int main_trait(int argc, char *argv[])
 {
@@ -278,19 +281,22 @@ static int main_trait(int argc, char *argv[])
 	pg_trait_opt_init(&o);
 	const char *fn = nullptr;
 	int c;
-	while ((c = getopt(argc, argv, "t:n:s:c:p:")) >= 0) {
+	while ((c = getopt(argc, argv, "t:n:s:c:p:L:")) >= 0) {
 		if (c == 't') fn = optarg;
 		else if (c == 'n') { if (!trait_perm(optarg, o.n_perm)) { std::fprintf(stderr, "ERROR: -n must be in [0, 2147483646]\n"); return 1; } }
 		else if (c == 's') o.seed = (uint32_t)std::strtoul(optarg, nullptr, 10);
 		else if (c == 'c') { if ((o.min_count = std::atoi(optarg)) < 1) { std::fprintf(stderr, "ERROR: -c must be at least 1\n"); return 1; } }
 		else if (c == 'p') { char *e; o.max_p = std::strtod(optarg, &e); if (e == optarg || *e != 0 || !(o.max_p >= 0.0)) { std::fprintf(stderr, "ERROR: -p must be a number >= 0\n"); return 1; } }
+		else if (c == 'L') { if ((o.lineage = trait_lineage(optarg)) < 0) { std::fprintf(stderr, "ERROR: -L must be nj or upgma\n"); return 1; } }
 		else return 1;
 	}
 	if (argc - optind < 1) {
 		std::printf("Usage: pangene trait -t FILE [options] <in.gfa>\nOptions:\n  -t FILE   traits: a header line (any first field, one name per trait), then per line an assembly and 1, 0 or NA per trait\n"
 		            "  -n INT    label permutations per trait; 0: none [%d]\n  -s INT    seed of the permutations [%u]\n"
 		            "  -c INT    a gene is tested when it is present in >=INT and absent from >=INT assemblies [%d]\n"
-		            "  -p FLOAT  print the genes with p_fisher <= FLOAT [%g]\n", o.n_perm, o.seed, o.min_count, o.max_p);
+		            "  -p FLOAT  print the genes with p_fisher <= FLOAT [%g]\n"
+		            "  -L STR    lineage-aware test: the pairwise comparisons on the nj or upgma tree of all assemblies (gene content, jaccard);\n"
+		            "            adds the columns pairs, supp, opp, p_pair_best and p_pair_worst [none]\n", o.n_perm, o.seed, o.min_count, o.max_p);
 		return 0;
 	}
 	if (fn == nullptr) { std::fprintf(stderr, "ERROR: pangene trait needs -t FILE\n"); return 1; }
@@ -307,7 +313,7 @@ static int main_trait(int argc, char *argv[])
 // ---------------------------------------------------------------------------------------------------------------
 struct Output { int matrix = 0; bool call = false; int curves = 0; uint32_t curves_seed = 11; int dist = -1, dist_metric = 0; // curves: orders (0: none); dist: PG_DIST_* (-1: none)
 	bool assoc = false; double assoc_phi = 0.8; int assoc_count = 2, assoc_sign = 0;
-	const char *trait = nullptr; int32_t trait_perm = 1000; uint32_t trait_seed = 11;
+	const char *trait = nullptr; int32_t trait_perm = 1000; uint32_t trait_seed = 11; int trait_lineage = 0;
 	int tree = -1, tree_metric = 0, tree_method = 0; int32_t tree_boot = 0; uint32_t tree_seed = 0; }; // tree: PG_DIST_GENE / PG_DIST_ADJ (-1: none)
 
 static int run_path(pg_opt_t &opt, int n_files, char **files, const uint8_t *ids_only, const Output &o, bool graph_lines, bool own_lines, int device = -1)
@@ -363,7 +369,7 @@ static int run_path(pg_opt_t &opt, int n_files, char **files, const uint8_t *ids
 		else if (o.trait) {
 			pg_trait_opt_t to;
 			pg_trait_opt_init(&to);
-			to.n_perm = o.trait_perm, to.seed = o.trait_seed;
+			to.n_perm = o.trait_perm, to.seed = o.trait_seed, to.lineage = o.trait_lineage;
 			pg_write_trait(g, o.trait, &to);
 			if (pg_last_error()) rc = 2;
 		}
@@ -595,6 +601,7 @@ int main(int argc, char *argv[])
 	const char *trait = nullptr; // --trait=FILE
 	int32_t trait_perm_v = 1000;
 	uint32_t trait_seed = 11;
+	int trait_lineage_v = 0; // --trait-lineage: PG_LINEAGE_*
 	int tree = -1, tree_metric_v = PG_DIST_JACCARD, tree_method_v = PG_TREE_NJ; // --tree: PG_DIST_GENE / PG_DIST_ADJ (-1: not asked for)
 	int32_t tree_boot_v = 0;
 	uint32_t tree_seed = 0;
@@ -604,6 +611,7 @@ int main(int argc, char *argv[])
 		{ "dist", optional_argument, nullptr, 308 }, { "dist-metric", required_argument, nullptr, 309 },
 		{ "assoc", optional_argument, nullptr, 310 }, { "assoc-min-count", required_argument, nullptr, 311 }, { "assoc-sign", required_argument, nullptr, 312 },
 		{ "trait", required_argument, nullptr, 313 }, { "trait-perm", required_argument, nullptr, 314 }, { "trait-seed", required_argument, nullptr, 315 },
+		{ "trait-lineage", required_argument, nullptr, 321 },
 		{ "tree", optional_argument, nullptr, 316 }, { "tree-metric", required_argument, nullptr, 317 }, { "tree-method", required_argument, nullptr, 318 },
 		{ "tree-boot", required_argument, nullptr, 319 }, { "tree-seed", required_argument, nullptr, 320 },
 		{ "gpus", required_argument, nullptr, 304 }, { "procs", required_argument, nullptr, 304 },
@@ -694,6 +702,9 @@ int main(int argc, char *argv[])
 		case 320:
 			if (!tree_seed_arg(optarg, tree_seed)) { std::fprintf(stderr, "ERROR: --tree-seed must be in [0, 4294967295]\n"); return 1; }
 			break;
+		case 321:
+			if ((trait_lineage_v = trait_lineage(optarg)) < 0) { std::fprintf(stderr, "ERROR: --trait-lineage must be nj or upgma\n"); return 1; }
+			break;
 		case 401: std::puts(PG_VERSION); return 0;
 		default: break;
 		}
@@ -703,10 +714,11 @@ int main(int argc, char *argv[])
 	if (dist >= 0 && (matrix || call || curves)) { std::fprintf(stderr, "ERROR: --dist cannot be combined with --matrix, --call or --curves\n"); return 1; }
 	if (assoc && (matrix || call || curves || dist >= 0)) { std::fprintf(stderr, "ERROR: --assoc cannot be combined with --matrix, --call, --curves or --dist\n"); return 1; }
 	if (trait && (matrix || call || curves || dist >= 0 || assoc)) { std::fprintf(stderr, "ERROR: --trait cannot be combined with --matrix, --call, --curves, --dist or --assoc\n"); return 1; }
+	if (trait_lineage_v && !trait) { std::fprintf(stderr, "ERROR: --trait-lineage needs --trait=FILE\n"); return 1; }
 	if (tree >= 0 && (matrix || call || curves || dist >= 0 || assoc || trait)) { std::fprintf(stderr, "ERROR: --tree cannot be combined with --matrix, --call, --curves, --dist, --assoc or --trait\n"); return 1; }
 	Output o;
 	o.tree = tree, o.tree_metric = tree_metric_v, o.tree_method = tree_method_v, o.tree_boot = tree_boot_v, o.tree_seed = tree_seed;
-	o.trait = trait, o.trait_perm = trait_perm_v, o.trait_seed = trait_seed;
+	o.trait = trait, o.trait_perm = trait_perm_v, o.trait_seed = trait_seed, o.trait_lineage = trait_lineage_v;
 	o.assoc = assoc, o.assoc_phi = assoc_phi_v, o.assoc_count = assoc_count, o.assoc_sign = assoc_sign_v;
 	o.curves = curves, o.curves_seed = curves_seed;
 	o.dist = dist, o.dist_metric = dist_metric_v;

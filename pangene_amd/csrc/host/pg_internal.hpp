@@ -236,6 +236,8 @@ int dist_items_file(const char *gfa_fn, int32_t type, std::vector<std::string> &
 int dist_items_graph(pg_graph_t *q, int32_t type, std::vector<std::string> &names, std::vector<uint32_t> &bits, int32_t &M);
 void presence_bits(const uint8_t *p, int32_t M, int32_t A, std::vector<uint32_t> &bits);
 int shared_count(const std::vector<uint32_t> &bits, int32_t M, int32_t A, int32_t *S);
+// the records of the tree pangene tree prints for such rows (tree.cpp): rec[A - 2][6] (NJ) or rec[A - 1][6] (UPGMA); nothing for A < 3
+int tree_joins(const std::vector<uint32_t> &bits, int32_t M, int32_t A, int32_t metric, int32_t method, int64_t *rec);
 
 double now_sec();
 const char *stamp();

@@ -4,6 +4,10 @@
 // made and counted on the device and one integer per gene comes back), or from the plain loops below when the backend has no such
 // entry.  Everything the permutation test decides is an integer; phi, the Fisher p and the Benjamini-Hochberg q are computed here,
 // for printing only, by code both builds share.
+// Lineage-aware pairwise comparisons (pg_pan_pairs, pangene trait -L; DESIGN.md section 8 "Lineage-aware trait test"): the tree of all
+// assemblies comes from tree.cpp; per gene and trait the largest set of contrasting leaf pairs on vertex-disjoint paths and its most
+// supporting and most opposing pairs come from the backend (pga_pan_pairs: the tree compiled into a postfix program, one lane per gene), or
+// from the plain loops over the records below; the two binomial p values are computed here, by code both builds share.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -18,6 +22,7 @@ namespace pgx {
 namespace {
 
 constexpr int32_t TRAIT_MAX_COL = 16777215, TRAIT_MAX_GENE = 16777215, TRAIT_MAX_PERM = 2147483646;
+constexpr int32_t PAIRS_MAX_LEAF = 65535, PAIRS_DEPTH = 16; // the backend's limits (include/pangene_hip.h pga_pan_pairs)
 
 uint64_t mix64(uint64_t z) // splitmix64's output function (as curves.cpp)
 {
@@ -76,7 +81,10 @@ void trait_host(const uint32_t *bits, const uint32_t *label, int32_t G, int32_t 
 
 double t_count = 0; // seconds of the last counting step (backend or host loops)
 
-bool opt_ok(const pg_trait_opt_t *o) { return o != nullptr && o->n_perm >= 0 && o->n_perm <= TRAIT_MAX_PERM && o->min_count >= 1 && o->max_p == o->max_p; }
+bool opt_ok(const pg_trait_opt_t *o)
+{
+	return o != nullptr && o->n_perm >= 0 && o->n_perm <= TRAIT_MAX_PERM && o->min_count >= 1 && o->max_p == o->max_p && o->lineage >= 0 && o->lineage <= 2;
+}
 
 // a, s, k of every gene over the N compacted columns; 0 or a PGA_ERR_* code
 int trait_count(const std::vector<uint32_t> &bits, const std::vector<uint32_t> &label, int32_t G, int32_t N, const pg_trait_opt_t *o,
@@ -137,6 +145,167 @@ double fisher(const std::vector<double> &lf, int32_t N, int32_t t, int32_t a, in
 	return sum < 1.0 ? sum : 1.0;
 }
 
+
+// ---- lineage-aware pairwise comparisons ----
+
+// The records of pg_pan_tree / pg_pan_join as a binary tree: node x < A is leaf x, node A + t the t-th join with the children
+// kid[2 t] (the subtree of slot i) and kid[2 t + 1] (of slot j); joins are numbered in record order, so a child's number is below its
+// parent's and the root is the last node.  NJ's closing record (x, y, z) is read as ((x, y), z).  One leaf is a tree, two are one
+// join; neither needs records.  false: the records name a slot out of range, twice in a join, or one that has retired.
+bool pairs_tree(const int64_t *rec, int32_t A, int32_t method, std::vector<int32_t> &kid)
+{
+	kid.clear();
+	if (A < 2) return true;
+	if (A == 2) { kid = {0, 1}; return true; }
+	if (rec == nullptr) return false;
+	std::vector<int32_t> at((size_t)A);
+	for (int32_t x = 0; x < A; ++x) at[(size_t)x] = x;
+	auto join = [&](int64_t i, int64_t j) {
+		if (i < 0 || j < 0 || i >= A || j >= A || i == j || at[(size_t)i] < 0 || at[(size_t)j] < 0) return false;
+		kid.push_back(at[(size_t)i]), kid.push_back(at[(size_t)j]);
+		at[(size_t)i] = A + (int32_t)(kid.size() / 2) - 1, at[(size_t)j] = -1;
+		return true;
+	};
+	const int32_t n_plain = method == PG_TREE_NJ ? A - 3 : A - 1;
+	for (int32_t t = 0; t < n_plain; ++t)
+		if (!join(rec[6 * (size_t)t], rec[6 * (size_t)t + 1])) return false;
+	if (method == PG_TREE_NJ) {
+		const int64_t *fin = rec + 6 * (size_t)n_plain;
+		if (!join(fin[0], fin[1]) || !join(fin[0], fin[2])) return false;
+	}
+	return true;
+}
+
+// The tree as the backend's postfix program: op 0 pushes the next leaf (order[k] = the k-th pushed leaf), op 1 joins the top two
+// entries.  A join visits the child that needs the deeper stack first (the Ershov number: a leaf needs 1, a join of two equal needs one
+// more, of two unequal the larger), ties the subtree of slot i: the stack then never holds more than floor(log2 A) + 1 entries.  Returns
+// that need of the root.
+int32_t pairs_program(const std::vector<int32_t> &kid, int32_t A, std::vector<uint8_t> &op, std::vector<int32_t> &order)
+{
+	op.clear(), order.clear();
+	if (A == 0) return 0;
+	const size_t n_join = kid.size() / 2;
+	std::vector<int32_t> need((size_t)A + n_join, 1);
+	for (size_t t = 0; t < n_join; ++t) {
+		const int32_t a = need[(size_t)kid[2 * t]], b = need[(size_t)kid[2 * t + 1]];
+		need[(size_t)A + t] = a == b ? a + 1 : std::max(a, b);
+	}
+	std::vector<int32_t> todo; // a node to visit, or ~node: emit its join
+	todo.push_back((int32_t)((size_t)A + n_join) - 1);
+	while (!todo.empty()) {
+		const int32_t v = todo.back();
+		todo.pop_back();
+		if (v < 0) op.push_back(1);
+		else if (v < A) op.push_back(0), order.push_back(v);
+		else {
+			const int32_t a = kid[2 * (size_t)(v - A)], b = kid[2 * (size_t)(v - A) + 1];
+			const bool a_first = need[(size_t)a] >= need[(size_t)b];
+			todo.push_back(~v), todo.push_back(a_first ? b : a), todo.push_back(a_first ? a : b);
+		}
+	}
+	return need.back();
+}
+
+// The backend's step on the host, by the definition and over the records themselves (no program, no packing): per trait row, gene and
+// run every node's N and F_s bottom-up in join order.  A value is pairs << 32 | pairs of the run's side in 64 bits, infeasible is
+// PH_NONE or below (the sum of two is still far from wrapping).  out[R][G][3]
+constexpr int64_t PH_NONE = -((int64_t)1 << 60), PH_PAIR = (int64_t)1 << 32;
+struct PairsNode { int64_t N, F[4]; };
+
+void pairs_host(const uint8_t *pres, const int8_t *lab, int32_t G, int32_t A, int32_t R, const std::vector<int32_t> &kid, int32_t *out)
+{
+	const size_t n_join = kid.size() / 2;
+	std::vector<PairsNode> nd((size_t)A + n_join);
+	for (int32_t r = 0; r < R; ++r)
+		for (int32_t g = 0; g < G; ++g) {
+			int32_t *o = out + ((size_t)r * (size_t)G + (size_t)g) * 3;
+			o[0] = o[1] = o[2] = 0;
+			if (A == 0) continue;
+			for (int32_t run = 0; run < 2; ++run) {
+				for (int32_t x = 0; x < A; ++x) {
+					PairsNode &n = nd[(size_t)x];
+					n.N = 0, n.F[0] = n.F[1] = n.F[2] = n.F[3] = PH_NONE;
+					const int8_t y = lab[(size_t)r * (size_t)A + (size_t)x];
+					if (y >= 0) n.F[(pres[(size_t)g * (size_t)A + (size_t)x] ? 2 : 0) + (y > 0 ? 1 : 0)] = 0;
+				}
+				for (size_t t = 0; t < n_join; ++t) {
+					const PairsNode &a = nd[(size_t)kid[2 * t]], &b = nd[(size_t)kid[2 * t + 1]];
+					PairsNode &v = nd[(size_t)A + t];
+					v.N = a.N + b.N;
+					for (int32_t s = 0; s < 4; ++s) { // the contrasting type of s is 3 - s; 3-0 supports, 2-1 opposes
+						const bool supports = s == 0 || s == 3;
+						v.N = std::max(v.N, a.F[s] + b.F[3 - s] + PH_PAIR + (supports == (run == 0) ? 1 : 0));
+						v.F[s] = std::max(std::max(a.F[s] + b.N, a.N + b.F[s]), PH_NONE);
+					}
+				}
+				const int64_t top = nd.back().N;
+				if (run == 0) o[0] = (int32_t)(top >> 32), o[1] = (int32_t)(top & 0xffffffff);
+				else o[2] = (int32_t)(top & 0xffffffff);
+			}
+		}
+}
+
+double t_pairs = 0; // seconds of the last pairs step (backend or host loops)
+
+// pairs, supp, opp of every gene and label row over the tree of the records: out[R][G][3].  0 or a PGA_ERR_* code
+int pairs_count(const uint8_t *pres, const int8_t *lab, int32_t G, int32_t A, int32_t R, const int64_t *rec, int32_t method, std::vector<int32_t> &out)
+{
+	if (A > PAIRS_MAX_LEAF || G > TRAIT_MAX_GENE) return PGA_ERR_RANGE;
+	std::vector<int32_t> kid;
+	if (!pairs_tree(rec, A, method, kid)) return PGA_ERR_ARG;
+	const double t0 = now_sec();
+	out.assign((size_t)R * (size_t)G * 3, 0);
+	const pga_backend_t *be = backend_default();
+	int rc = 0;
+	if (be->pan_pairs != nullptr) {
+		std::vector<uint8_t> op;
+		std::vector<int32_t> order;
+		if (pairs_program(kid, A, op, order) > PAIRS_DEPTH) return PGA_ERR_RANGE; // (out of reach below 65 536 leaves)
+		std::vector<int32_t> pos((size_t)A);
+		for (int32_t k = 0; k < A; ++k) pos[(size_t)order[(size_t)k]] = k;
+		const size_t W = ((size_t)G + 31) / 32;
+		std::vector<uint32_t> bits((size_t)A * W, 0);
+		for (int32_t g = 0; g < G; ++g) {
+			const uint8_t *row = pres + (size_t)g * (size_t)A;
+			for (int32_t x = 0; x < A; ++x)
+				if (row[x]) bits[(size_t)pos[(size_t)x] * W + (size_t)(g >> 5)] |= 1u << (g & 31);
+		}
+		std::vector<int8_t> label((size_t)R * (size_t)A);
+		for (int32_t r = 0; r < R; ++r)
+			for (int32_t k = 0; k < A; ++k) label[(size_t)r * (size_t)A + (size_t)k] = lab[(size_t)r * (size_t)A + (size_t)order[(size_t)k]];
+		const pga_pairs_in_t in{op.data(), bits.data(), label.data(), G, A, R};
+		pga_pairs_out_t res{};
+		rc = be->pan_pairs(&in, &res);
+		if (rc == 0 && !out.empty()) std::memcpy(out.data(), res.out, sizeof(int32_t) * out.size());
+	} else pairs_host(pres, lab, G, A, R, kid, out.data());
+	t_pairs += now_sec() - t0;
+	return rc;
+}
+
+// The exact two-sided binomial p at 1/2: min(1, 2 P(X >= max(k, n - k))), 1 for n = 0.  Up to n = 60 the tail is summed in integers and
+// the result is the correctly rounded quotient (a sum of 2^-7 prints the same digits everywhere); beyond, from the log-factorial table
+// lf (at least n + 1 entries), the small terms first.
+double binom_two_sided(const std::vector<double> &lf, int32_t k, int32_t n)
+{
+	if (n <= 0) return 1.0;
+	const int32_t m = std::max(k, n - k);
+	double p;
+	if (n <= 60) {
+		uint64_t c = 1, sum = 0; // c = C(n, x) from x = n down
+		for (int32_t x = n; x >= m; --x) {
+			sum += c;
+			c = c * (uint64_t)x / (uint64_t)(n - x + 1);
+		}
+		p = std::ldexp((double)sum, 1 - n);
+	} else {
+		const double base = lf[(size_t)n] - (double)n * std::log(2.0);
+		double sum = 0;
+		for (int32_t x = n; x >= m; --x) sum += std::exp(base - lf[(size_t)x] - lf[(size_t)(n - x)]);
+		p = 2.0 * sum;
+	}
+	return p < 1.0 ? p : 1.0;
+}
+
 struct Traits { std::vector<std::string> name; std::vector<int8_t> lab; }; // lab[T][A]
 
 std::vector<std::string> split_tab(const std::string &s)
@@ -192,6 +361,13 @@ void report_time(const char *route, int32_t G, int32_t A, size_t T, int32_t n, d
 	std::fprintf(stderr, "[trait-timing] route=%s genes=%d assemblies=%d traits=%zu perms=%d count_ms=%.3f all_ms=%.3f\n", route, G, A, T, n, t_count * 1e3, t_all * 1e3);
 }
 
+// the same for -L: a second line, so that the first stays what it was
+void report_lineage_time(int32_t rows, double t_tree)
+{
+	if (std::getenv("PANGENE_TRAIT_TIMING") == nullptr) return;
+	std::fprintf(stderr, "[trait-lineage-timing] rows=%d tree_ms=%.3f pairs_ms=%.3f\n", rows, t_tree * 1e3, t_pairs * 1e3);
+}
+
 // every trait of tr over pres[G][A]: counts, statistics, lines.  0 or a PGA_ERR_* code; nothing is written unless every trait went through
 int trait_run(const char *route, const std::vector<std::string> &gene, const std::vector<uint8_t> &pres, int32_t A, const Traits &tr, const pg_trait_opt_t *o,
               double t_start)
@@ -199,9 +375,35 @@ int trait_run(const char *route, const std::vector<std::string> &gene, const std
 	if (!opt_ok(o)) return PGA_ERR_ARG;
 	if (A > TRAIT_MAX_COL) return PGA_ERR_RANGE;
 	const int32_t G = (int32_t)gene.size();
-	t_count = 0;
-	std::string out = "Trait\tGene\tN\tnT\tnG\tnTG\tphi\tp_fisher\tq_bh\tn_ge\tp_perm\n";
+	t_count = t_pairs = 0;
+	std::string out = "Trait\tGene\tN\tnT\tnG\tnTG\tphi\tp_fisher\tq_bh\tn_ge\tp_perm";
+	out += o->lineage ? "\tpairs\tsupp\topp\tp_pair_best\tp_pair_worst\n" : "\n";
 	char b[160];
+	// -L: the tree of ALL assemblies over the genes (pangene tree -t gene -m jaccard), and the pair counts of every trait that has two
+	// values, in one backend call; pc[row_of[ti]][g][3]
+	std::vector<int32_t> pc, row_of(tr.name.size(), -1);
+	double t_tree = 0;
+	if (o->lineage) {
+		if (A > PAIRS_MAX_LEAF) return PGA_ERR_RANGE;
+		std::vector<int8_t> rows;
+		for (size_t ti = 0; ti < tr.name.size(); ++ti) {
+			const int8_t *lab = tr.lab.data() + ti * (size_t)A;
+			int32_t n0 = 0, n1 = 0;
+			for (int32_t c = 0; c < A; ++c) n0 += lab[c] == 0, n1 += lab[c] > 0;
+			if (n0 == 0 || n1 == 0) continue;
+			row_of[ti] = (int32_t)(rows.size() / (size_t)std::max(A, 1));
+			rows.insert(rows.end(), lab, lab + A);
+		}
+		const int32_t method = o->lineage == 1 ? PG_TREE_NJ : PG_TREE_UPGMA;
+		std::vector<int64_t> rec((size_t)6 * (size_t)std::max(A, 1));
+		const double t0 = now_sec();
+		std::vector<uint32_t> bits;
+		presence_bits(pres.data(), G, A, bits);
+		int rc = tree_joins(bits, G, A, PG_DIST_JACCARD, method, rec.data());
+		t_tree = now_sec() - t0;
+		if (rc == 0) rc = pairs_count(pres.data(), rows.data(), G, A, (int32_t)(rows.size() / (size_t)std::max(A, 1)), rec.data(), method, pc);
+		if (rc != 0) return rc;
+	}
 	for (size_t ti = 0; ti < tr.name.size(); ++ti) {
 		One r;
 		const int rc = trait_one(pres.data(), tr.lab.data() + ti * (size_t)A, G, A, o, r);
@@ -232,15 +434,27 @@ int trait_run(const char *route, const std::vector<std::string> &gene, const std
 			out += tr.name[ti], out += '\t', out += gene[(size_t)g];
 			std::snprintf(b, sizeof(b), "\t%d\t%d\t%d\t%d\t%.4f\t%.3e\t%.3e\t", N, t, (int)a, (int)s, phi, pf[e], q[e]);
 			out += b;
-			if (o->n_perm > 0) std::snprintf(b, sizeof(b), "%d\t%.6f\n", r.k[(size_t)g], ((double)r.k[(size_t)g] + 1.0) / ((double)o->n_perm + 1.0));
-			else std::snprintf(b, sizeof(b), "NA\tNA\n");
+			if (o->n_perm > 0) std::snprintf(b, sizeof(b), "%d\t%.6f", r.k[(size_t)g], ((double)r.k[(size_t)g] + 1.0) / ((double)o->n_perm + 1.0));
+			else std::snprintf(b, sizeof(b), "NA\tNA");
 			out += b;
+			if (o->lineage) { // `for` = the side the association points to; lf reaches N >= 2 pairs
+				const int32_t *c = pc.data() + ((size_t)row_of[ti] * (size_t)G + (size_t)g) * 3;
+				const int32_t n_for = D >= 0 ? c[1] : c[2], n_against = D >= 0 ? c[2] : c[1];
+				std::snprintf(b, sizeof(b), "\t%d\t%d\t%d\t%.3e\t%.3e", c[0], c[1], c[2], binom_two_sided(lf, n_for, c[0]), binom_two_sided(lf, c[0] - n_against, c[0]));
+				out += b;
+			}
+			out += '\n';
 		}
 	}
 	FILE *fp = out_stream();
 	std::fwrite(out.data(), 1, out.size(), fp);
 	std::fflush(fp);
 	report_time(route, G, A, tr.name.size(), o->n_perm, now_sec() - t_start);
+	if (o->lineage) {
+		int32_t rows = 0;
+		for (const int32_t r : row_of) rows += r >= 0;
+		report_lineage_time(rows, t_tree);
+	}
 	return 0;
 }
 
@@ -312,6 +526,20 @@ int pg_pan_trait(const uint8_t *presence, const int8_t *labels, int32_t n_gene, 
 			p[g] = r.N, p[plane + g] = r.t, p[2 * plane + g] = e ? r.a[g] : -1, p[3 * plane + g] = e ? r.s[g] : 0, p[4 * plane + g] = e ? r.k[g] : 0;
 		}
 	}
+	return 0;
+}
+
+int pg_pan_pairs(const uint8_t *presence, const int8_t *labels, int32_t n_gene, int32_t n_asm, int32_t n_trait, const int64_t *rec, int32_t method, int32_t *out)
+{
+	if (n_gene < 0 || n_asm < 0 || n_trait < 0 || (method != PG_TREE_NJ && method != PG_TREE_UPGMA) || (n_asm >= 3 && rec == nullptr)) return PGA_ERR_ARG;
+	if (((size_t)n_gene * (size_t)n_asm > 0 && presence == nullptr) || ((size_t)n_trait * (size_t)n_asm > 0 && labels == nullptr)) return PGA_ERR_ARG;
+	if ((size_t)n_trait * (size_t)n_gene > 0 && out == nullptr) return PGA_ERR_ARG;
+	std::vector<int32_t> pc;
+	t_pairs = 0;
+	const int rc = pairs_count(presence, labels, n_gene, n_asm, n_trait, rec, method, pc);
+	if (rc != 0) return rc;
+	const size_t plane = (size_t)n_trait * (size_t)n_gene;
+	for (size_t i = 0; i < plane; ++i) out[i] = pc[3 * i], out[plane + i] = pc[3 * i + 1], out[2 * plane + i] = pc[3 * i + 2];
 	return 0;
 }
 

@@ -399,6 +399,15 @@ int tree_run(const char *route, const std::vector<std::string> &names, const std
 }
 
 } // namespace
+
+int tree_joins(const std::vector<uint32_t> &bits, int32_t M, int32_t A, int32_t metric, int32_t method, int64_t *rec)
+{
+	if (A < 3) return 0;
+	std::vector<int32_t> q;
+	int32_t F;
+	return tree_records(bits, M, A, metric, method, q, rec, &F);
+}
+
 } // namespace pgx
 
 using namespace pgx;
