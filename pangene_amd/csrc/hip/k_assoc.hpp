@@ -5,7 +5,7 @@
 //            eligible row its place among the E eligible ones (the map back to the original row is written by the scan's output
 //            functor); k_assoc_gather copies the eligible rows next to each other.  In a U-shaped pangenome most genes are core or
 //            rare, so E << G and the E^2 work below is a small part of G^2.
-//   pairs    k_assoc_pairs: one workgroup per 128 x 128 tile of the upper triangle of E x E, the tile scheme of k_dist_shared (32-word
+//   pairs    k_assoc_pairs: one workgroup per 128 x 128 tile of the upper triangle of E x E, the tile body of k_dist_shared (BIT_TILE: 32-word
 //            K chunks of the two row blocks in LDS, 8 x 8 micro-tile per thread, v_and_b32 + v_bcnt_u32_b32 with the empty asm that
 //            keeps the compiler from regrouping the adds).  Two differences: the inner loop stops at the last word of the rows (at
 //            200 assemblies that is 8 words of the 32-word chunk), and there is no split K -- the epilogue needs finished counts, and
@@ -22,8 +22,6 @@
 //            kernel once more.  The keys are then radix-sorted (dev_prims.hpp), so the order of the atomics never shows, and
 //            k_assoc_emit writes (g, h, s) with the original row numbers.
 // ------------------------------------------------------------------------------------------------
-constexpr int32_t ASSOC_TILE = DIST_TILE, ASSOC_KC = DIST_KC, ASSOC_LDW = DIST_LDW, ASSOC_SIDE = DIST_SIDE;
-constexpr int32_t ASSOC_LOADS = DIST_LOADS;
 constexpr int32_t ASSOC_ROW_LANES = 8; // lanes that share one row in k_assoc_count
 constexpr double ASSOC_BAND = 1.0 / 1099511627776.0; // 2^-40
 
@@ -37,9 +35,7 @@ __global__ __launch_bounds__(BLOCK) void k_assoc_count(const uint32_t *__restric
 		const uint32_t *row = bits + (size_t)g * (size_t)W;
 		for (int32_t k = l; k < W; k += ASSOC_ROW_LANES) a += __popc(row[k]);
 	}
-	a += __shfl_xor(a, 1, WAVE);
-	a += __shfl_xor(a, 2, WAVE);
-	a += __shfl_xor(a, 4, WAVE);
+	a = row8_sum(a);
 	if (g < G && l == 0) count[g] = a, flag[g] = min(a, A - a) >= min_count ? 1 : 0;
 }
 
@@ -85,7 +81,7 @@ struct AssocPar {
 __global__ __launch_bounds__(BLOCK, 2) void k_assoc_pairs(const uint32_t *__restrict__ cbits, const int32_t *__restrict__ ca, const AssocPar par,
                                                          unsigned long long *__restrict__ counter, uint64_t *__restrict__ keys, uint32_t *__restrict__ vals)
 {
-	__shared__ uint4 sh4[2 * ASSOC_SIDE / 4];
+	__shared__ uint4 sh4[DIST_LDS_WORDS / 4];
 	__shared__ I32 wave_tot[BLOCK / WAVE];
 	__shared__ unsigned long long base_s;
 	uint32_t *sh = (uint32_t *)sh4;
@@ -93,54 +89,9 @@ __global__ __launch_bounds__(BLOCK, 2) void k_assoc_pairs(const uint32_t *__rest
 	const int32_t E = par.E, W = par.W;
 	int32_t ti, tj;
 	dist_tile_of((int32_t)blockIdx.x, ti, tj);
-	const int32_t i0 = ti * ASSOC_TILE, j0 = tj * ASSOC_TILE;
+	const int32_t i0 = ti * DIST_TILE, j0 = tj * DIST_TILE;
 
-	uint32_t acc[8][8];
-#pragma unroll
-	for (int32_t ii = 0; ii < 8; ++ii)
-#pragma unroll
-		for (int32_t jj = 0; jj < 8; ++jj) acc[ii][jj] = 0;
-
-	const uint32_t *sa = sh, *sb = sh + ASSOC_SIDE;
-	for (int32_t c = 0; c < par.n_chunk; ++c) {
-#pragma unroll
-		for (int32_t side = 0; side < 2; ++side) {
-			uint32_t v[ASSOC_LOADS / 2];
-			const int32_t g0 = side ? j0 : i0;
-#pragma unroll
-			for (int32_t r = 0; r < ASSOC_LOADS / 2; ++r) {
-				const int32_t e = t + BLOCK * r, g = g0 + (e >> 5), k = c * ASSOC_KC + (e & 31);
-				v[r] = (g < E && k < W) ? cbits[(size_t)g * (size_t)W + (size_t)k] : 0u;
-			}
-			if (side == 0 && c > 0) __syncthreads(); // everyone is done with the previous chunk
-#pragma unroll
-			for (int32_t r = 0; r < ASSOC_LOADS / 2; ++r) {
-				const int32_t e = t + BLOCK * r;
-				sh[side * ASSOC_SIDE + (e >> 5) * ASSOC_LDW + (e & 31)] = v[r];
-			}
-		}
-		__syncthreads();
-		const int32_t kk_hi = min(ASSOC_KC, (W - c * ASSOC_KC + 3) & ~3); // the words past W are staged as zeros
-#pragma unroll 1
-		for (int32_t kk = 0; kk < kk_hi; kk += 4) {
-			uint4 a[8], b[8];
-#pragma unroll
-			for (int32_t ii = 0; ii < 8; ++ii) a[ii] = *(const uint4 *)(sa + (ty + 16 * ii) * ASSOC_LDW + kk);
-#pragma unroll
-			for (int32_t jj = 0; jj < 8; ++jj) b[jj] = *(const uint4 *)(sb + (tx + 16 * jj) * ASSOC_LDW + kk);
-#pragma unroll
-			for (int32_t ii = 0; ii < 8; ++ii)
-#pragma unroll
-				for (int32_t jj = 0; jj < 8; ++jj) {
-					uint32_t x = acc[ii][jj];
-					x = __popc(a[ii].x & b[jj].x) + x; asm volatile("" : "+v"(x));
-					x = __popc(a[ii].y & b[jj].y) + x; asm volatile("" : "+v"(x));
-					x = __popc(a[ii].z & b[jj].z) + x; asm volatile("" : "+v"(x));
-					x = __popc(a[ii].w & b[jj].w) + x; asm volatile("" : "+v"(x));
-					acc[ii][jj] = x;
-				}
-		}
-	}
+	BIT_TILE(true, cbits, E, cbits, E, W, 0, par.n_chunk)
 
 	// the epilogue: a and V of the thread's 8 rows and 8 columns, then the 64 tests
 	const double Ad = (double)par.A;

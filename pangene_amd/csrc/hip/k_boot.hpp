@@ -15,20 +15,13 @@
 
 constexpr int32_t BOOT_LDS_WORDS = 16384; // the source row's window in LDS: 64 KiB
 
-__device__ __forceinline__ uint64_t boot_mix64(uint64_t z) // splitmix64's output function
-{
-	z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-	z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-	return z ^ (z >> 31);
-}
-
 // grid: (ceil(M / BLOCK), n_rep); replicate first + blockIdx.y -> draws[blockIdx.y][M].  M >= 1.
 __global__ __launch_bounds__(BLOCK) void k_boot_draw(int32_t M, uint32_t seed, uint32_t first, int32_t *__restrict__ draws)
 {
 	const int64_t t = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
 	if (t >= M) return;
-	const uint64_t x0 = boot_mix64((uint64_t)seed << 32 | (uint64_t)(first + blockIdx.y));
-	draws[(size_t)blockIdx.y * (size_t)M + (size_t)t] = (int32_t)(boot_mix64(x0 + (uint64_t)(t + 1) * 0x9E3779B97F4A7C15ull) % (uint64_t)M);
+	const uint64_t x0 = mix64((uint64_t)seed << 32 | (uint64_t)(first + blockIdx.y));
+	draws[(size_t)blockIdx.y * (size_t)M + (size_t)t] = (int32_t)(mix64(x0 + (uint64_t)(t + 1) * 0x9E3779B97F4A7C15ull) % (uint64_t)M);
 }
 
 // grid: (ceil(W / BLOCK), ceil(A / a_per), n_rep); bits[A][W] -> rows[blockIdx.z][A][W].  Dynamic LDS: W words when USE_LDS.

@@ -22,6 +22,21 @@ __device__ __forceinline__ uint32_t hash_u32(uint32_t key) // pg_hash_uint32, pg
 	return key;
 }
 
+__device__ __forceinline__ uint64_t mix64(uint64_t z) // splitmix64's output function
+{
+	z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+	z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+	return z ^ (z >> 31);
+}
+
+// the sum over the 8 neighbouring lanes that share a row (k_assoc_count, k_trait_obs), in every one of them
+__device__ __forceinline__ int32_t row8_sum(int32_t v)
+{
+	v += __shfl_xor(v, 1, WAVE);
+	v += __shfl_xor(v, 2, WAVE);
+	return v + __shfl_xor(v, 4, WAVE);
+}
+
 // Pinned host memory seen from a kernel.  The caches between a CU and the host are not part of the in-stream ordering the kernels
 // rely on among themselves: a plain store may rest in the L2 of the XCD that issued it until a system-scope release -- the one the
 // runtime issues when the host asks about the stream (sync_st), which is why the bulk results (segment counters, degrees,

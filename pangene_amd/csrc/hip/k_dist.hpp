@@ -19,6 +19,54 @@ constexpr int32_t DIST_LOADS = 2 * DIST_TILE * DIST_KC / BLOCK; // words each th
 static_assert(DIST_TILE / 2 * DIST_OUTW <= DIST_LDS_WORDS, "half the finished tile reuses the staging buffer");
 static_assert(BLOCK == 256, "16 x 16 threads of 8 x 8 each");
 
+// The tile body k_dist_shared, k_assoc_pairs (k_assoc.hpp) and k_trait_count (k_trait.hpp) share: acc[ii][jj] = sum over the words of
+// chunks [c_lo, c_hi) of popc(ra[i0 + ty + 16 ii][.] & rb[j0 + tx + 16 jj][.]), rows past na / nb and words past W counting as zero.
+// trim: the inner loop stops at the last word of the rows (the words past W are staged as zeros either way).  It is a macro and not a
+// __forceinline__ function because the compiler optimises such a function on its own before it inlines it, and what comes out differs
+// from the body written in the kernel (other address arithmetic in the staging, other register counts), while the numbers of DESIGN
+// section 8 were measured on exactly this code.  Expanded in the kernel's scope, it uses the kernel's t, tx, ty (thread, column and
+// row of the 16 x 16 layout), i0, j0 (first rows of the tile), sh (DIST_LDS_WORDS words of LDS, 16-byte aligned) and declares and fills
+// uint32_t acc[8][8].  The kernel may use sh again after a __syncthreads().
+#define BIT_TILE(trim, ra, na, rb, nb, W, c_lo, c_hi) \
+	uint32_t acc[8][8]; \
+	_Pragma("unroll") for (int32_t ii = 0; ii < 8; ++ii) \
+		_Pragma("unroll") for (int32_t jj = 0; jj < 8; ++jj) acc[ii][jj] = 0; \
+	const uint32_t *sa = sh, *sb = sh + DIST_SIDE; \
+	for (int32_t c = (c_lo); c < (c_hi); ++c) { \
+		/* row block i, then row block j: word e = t + BLOCK * r of the block's chunk at row e >> 5, word e & 31, so 32 lanes read one */ \
+		/* 128-byte row piece */ \
+		_Pragma("unroll") for (int32_t side = 0; side < 2; ++side) { \
+			uint32_t v[DIST_LOADS / 2]; \
+			const int32_t g0 = side ? j0 : i0, n_row = side ? (nb) : (na); \
+			const uint32_t *src = side ? (rb) : (ra); \
+			_Pragma("unroll") for (int32_t r = 0; r < DIST_LOADS / 2; ++r) { \
+				const int32_t e = t + BLOCK * r, g = g0 + (e >> 5), k = c * DIST_KC + (e & 31); \
+				v[r] = (g < n_row && k < (W)) ? src[(size_t)g * (size_t)(W) + (size_t)k] : 0u; \
+			} \
+			if (side == 0 && c > (c_lo)) __syncthreads(); /* everyone is done with the previous chunk */ \
+			_Pragma("unroll") for (int32_t r = 0; r < DIST_LOADS / 2; ++r) { \
+				const int32_t e = t + BLOCK * r; \
+				sh[side * DIST_SIDE + (e >> 5) * DIST_LDW + (e & 31)] = v[r]; \
+			} \
+		} \
+		__syncthreads(); \
+		const int32_t kk_hi = (trim) ? min(DIST_KC, ((W) - c * DIST_KC + 3) & ~3) : DIST_KC; \
+		_Pragma("unroll 1") for (int32_t kk = 0; kk < kk_hi; kk += 4) { \
+			uint4 a[8], b[8]; \
+			_Pragma("unroll") for (int32_t ii = 0; ii < 8; ++ii) a[ii] = *(const uint4 *)(sa + (ty + 16 * ii) * DIST_LDW + kk); \
+			_Pragma("unroll") for (int32_t jj = 0; jj < 8; ++jj) b[jj] = *(const uint4 *)(sb + (tx + 16 * jj) * DIST_LDW + kk); \
+			_Pragma("unroll") for (int32_t ii = 0; ii < 8; ++ii) \
+				_Pragma("unroll") for (int32_t jj = 0; jj < 8; ++jj) { \
+					uint32_t x = acc[ii][jj]; \
+					x = __popc(a[ii].x & b[jj].x) + x; asm volatile("" : "+v"(x)); \
+					x = __popc(a[ii].y & b[jj].y) + x; asm volatile("" : "+v"(x)); \
+					x = __popc(a[ii].z & b[jj].z) + x; asm volatile("" : "+v"(x)); \
+					x = __popc(a[ii].w & b[jj].w) + x; asm volatile("" : "+v"(x)); \
+					acc[ii][jj] = x; \
+				} \
+		} \
+	}
+
 // the upper-triangle tile q = tj (tj + 1) / 2 + ti, ti <= tj
 __device__ __forceinline__ void dist_tile_of(int32_t q, int32_t &ti, int32_t &tj)
 {
@@ -41,53 +89,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_dist_shared(const uint32_t *__rest
 	const int32_t i0 = ti * DIST_TILE, j0 = tj * DIST_TILE;
 	const int32_t c_lo = sp * cps, c_hi = min(n_chunk, c_lo + cps);
 
-	uint32_t acc[8][8];
-#pragma unroll
-	for (int32_t ii = 0; ii < 8; ++ii)
-#pragma unroll
-		for (int32_t jj = 0; jj < 8; ++jj) acc[ii][jj] = 0;
-
-	const uint32_t *sa = sh, *sb = sh + DIST_SIDE;
-	for (int32_t c = c_lo; c < c_hi; ++c) {
-		// row block i, then row block j: word e = t + BLOCK * r of the block's chunk at row e >> 5, word e & 31, so 32 lanes read one
-		// 128-byte row piece
-#pragma unroll
-		for (int32_t side = 0; side < 2; ++side) {
-			uint32_t v[DIST_LOADS / 2];
-			const int32_t g0 = side ? j0 : i0;
-#pragma unroll
-			for (int32_t r = 0; r < DIST_LOADS / 2; ++r) {
-				const int32_t e = t + BLOCK * r, g = g0 + (e >> 5), k = c * DIST_KC + (e & 31);
-				v[r] = (g < A && k < W) ? bits[(size_t)g * (size_t)W + (size_t)k] : 0u;
-			}
-			if (side == 0 && c > c_lo) __syncthreads(); // everyone is done with the previous chunk
-#pragma unroll
-			for (int32_t r = 0; r < DIST_LOADS / 2; ++r) {
-				const int32_t e = t + BLOCK * r;
-				sh[side * DIST_SIDE + (e >> 5) * DIST_LDW + (e & 31)] = v[r];
-			}
-		}
-		__syncthreads();
-#pragma unroll 1
-		for (int32_t kk = 0; kk < DIST_KC; kk += 4) {
-			uint4 a[8], b[8];
-#pragma unroll
-			for (int32_t ii = 0; ii < 8; ++ii) a[ii] = *(const uint4 *)(sa + (ty + 16 * ii) * DIST_LDW + kk);
-#pragma unroll
-			for (int32_t jj = 0; jj < 8; ++jj) b[jj] = *(const uint4 *)(sb + (tx + 16 * jj) * DIST_LDW + kk);
-#pragma unroll
-			for (int32_t ii = 0; ii < 8; ++ii)
-#pragma unroll
-				for (int32_t jj = 0; jj < 8; ++jj) {
-					uint32_t x = acc[ii][jj];
-					x = __popc(a[ii].x & b[jj].x) + x; asm volatile("" : "+v"(x));
-					x = __popc(a[ii].y & b[jj].y) + x; asm volatile("" : "+v"(x));
-					x = __popc(a[ii].z & b[jj].z) + x; asm volatile("" : "+v"(x));
-					x = __popc(a[ii].w & b[jj].w) + x; asm volatile("" : "+v"(x));
-					acc[ii][jj] = x;
-				}
-		}
-	}
+	BIT_TILE(false, bits, A, bits, A, W, c_lo, c_hi)
 
 	// the finished tile through LDS, rows h * 64 .. h * 64 + 63 at a time; row-wise stores of the tile and (off the diagonal) its mirror
 	int32_t *st = (int32_t *)sh;

@@ -13,14 +13,12 @@
 //          by lane.  The rows live in LDS while 64 of them fit 32 KiB (W <= 128, N <= 4 096) and in a global scratch buffer of the
 //          same layout beyond; the finished rows are written row-major for the count kernel.  The 64-bit % is the compiler's: the
 //          same j as the host's for every x.
-//   count  k_trait_count: one workgroup per 128 genes x 128 permutations, the tile scheme of k_dist_shared / k_assoc_pairs (a third
-//          copy of the staging and the micro-tile: sharing it would have meant touching two kernels whose measured numbers are in
-//          DESIGN §8).  Rectangular grid (x: gene tile, y: permutation tile of the batch).  Epilogue: each count against its row's
-//          lo / hi, the hits of a row summed over the 16 lanes that share it, ONE atomicAdd per (tile, row) with a hit into k[g].
+//   count  k_trait_count: one workgroup per 128 genes x 128 permutations, the tile body of k_dist_shared / k_assoc_pairs (BIT_TILE,
+//          k_dist.hpp) with the inner loop trimmed to the rows' last word.  Rectangular grid (x: gene tile, y: permutation tile of the
+//          batch).  Epilogue: each count against its row's lo / hi, the hits of a row summed over the 16 lanes that share it, ONE
+//          atomicAdd per (tile, row) with a hit into k[g].
 // ------------------------------------------------------------------------------------------------
-constexpr int32_t TRAIT_TILE = DIST_TILE, TRAIT_KC = DIST_KC, TRAIT_LDW = DIST_LDW, TRAIT_SIDE = DIST_SIDE;
-constexpr int32_t TRAIT_LOADS = DIST_LOADS;
-constexpr int32_t TRAIT_ROW_LANES = 8;     // lanes that share one row in k_trait_obs
+constexpr int32_t TRAIT_ROW_LANES = 8;     // lanes that share one row in k_trait_obs (row8_sum)
 constexpr int32_t TRAIT_PERM_LDS_W = 128;  // words of a label row up to which a wave's 64 rows stay in LDS (32 KiB)
 constexpr int32_t TRAIT_NEVER_LO = -1, TRAIT_NEVER_HI = 0x7fffffff;
 
@@ -38,9 +36,7 @@ __global__ __launch_bounds__(BLOCK) void k_trait_obs(const uint32_t *__restrict_
 			a += __popc(w), s += __popc(w & label[k]);
 		}
 	}
-	a += __shfl_xor(a, 1, WAVE), s += __shfl_xor(s, 1, WAVE);
-	a += __shfl_xor(a, 2, WAVE), s += __shfl_xor(s, 2, WAVE);
-	a += __shfl_xor(a, 4, WAVE), s += __shfl_xor(s, 4, WAVE);
+	a = row8_sum(a), s = row8_sum(s);
 	if (g < G && l == 0) {
 		int32_t lo = TRAIT_NEVER_LO, hi = TRAIT_NEVER_HI;
 		if (min(a, N - a) >= min_count) {
@@ -52,20 +48,13 @@ __global__ __launch_bounds__(BLOCK) void k_trait_obs(const uint32_t *__restrict_
 	}
 }
 
-__device__ __forceinline__ uint64_t trait_mix64(uint64_t z) // splitmix64's output function
-{
-	z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-	z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-	return z ^ (z >> 31);
-}
-
 // the swaps of permutation p over the lane's row: word k of the row at row[k * WAVE]
 template <class P> __device__ __forceinline__ void trait_shuffle(P row, int32_t N, uint32_t seed, uint32_t p)
 {
-	uint64_t x = trait_mix64((uint64_t)seed << 32 | (uint64_t)p);
+	uint64_t x = mix64((uint64_t)seed << 32 | (uint64_t)p);
 	for (int32_t i = N - 1; i >= 1; --i) {
 		x += 0x9E3779B97F4A7C15ull;
-		const int32_t j = (int32_t)(trait_mix64(x) % (uint64_t)(i + 1));
+		const int32_t j = (int32_t)(mix64(x) % (uint64_t)(i + 1));
 		const int32_t wi = (i >> 5) * WAVE, wj = (j >> 5) * WAVE;
 		const uint32_t d = ((row[wi] >> (i & 31)) ^ (row[wj] >> (j & 31))) & 1u; // the two labels differ: both flip
 		row[wi] ^= d << (i & 31);
@@ -99,58 +88,12 @@ __global__ __launch_bounds__(BLOCK, 2) void k_trait_count(const uint32_t *__rest
                                                          const int32_t *__restrict__ hi, int32_t G, int32_t nb, int32_t W, int32_t n_chunk,
                                                          int32_t *__restrict__ k_out)
 {
-	__shared__ uint4 sh4[2 * TRAIT_SIDE / 4];
+	__shared__ uint4 sh4[DIST_LDS_WORDS / 4];
 	uint32_t *sh = (uint32_t *)sh4;
 	const int32_t t = (int32_t)threadIdx.x, tx = t & 15, ty = t >> 4;
-	const int32_t i0 = (int32_t)blockIdx.x * TRAIT_TILE, j0 = (int32_t)blockIdx.y * TRAIT_TILE;
+	const int32_t i0 = (int32_t)blockIdx.x * DIST_TILE, j0 = (int32_t)blockIdx.y * DIST_TILE;
 
-	uint32_t acc[8][8];
-#pragma unroll
-	for (int32_t ii = 0; ii < 8; ++ii)
-#pragma unroll
-		for (int32_t jj = 0; jj < 8; ++jj) acc[ii][jj] = 0;
-
-	const uint32_t *sa = sh, *sb = sh + TRAIT_SIDE;
-	for (int32_t c = 0; c < n_chunk; ++c) {
-#pragma unroll
-		for (int32_t side = 0; side < 2; ++side) {
-			uint32_t v[TRAIT_LOADS / 2];
-			const int32_t g0 = side ? j0 : i0, n_row = side ? nb : G;
-			const uint32_t *src = side ? rows : bits;
-#pragma unroll
-			for (int32_t r = 0; r < TRAIT_LOADS / 2; ++r) {
-				const int32_t e = t + BLOCK * r, g = g0 + (e >> 5), k = c * TRAIT_KC + (e & 31);
-				v[r] = (g < n_row && k < W) ? src[(size_t)g * (size_t)W + (size_t)k] : 0u;
-			}
-			if (side == 0 && c > 0) __syncthreads(); // everyone is done with the previous chunk
-#pragma unroll
-			for (int32_t r = 0; r < TRAIT_LOADS / 2; ++r) {
-				const int32_t e = t + BLOCK * r;
-				sh[side * TRAIT_SIDE + (e >> 5) * TRAIT_LDW + (e & 31)] = v[r];
-			}
-		}
-		__syncthreads();
-		const int32_t kk_hi = min(TRAIT_KC, (W - c * TRAIT_KC + 3) & ~3); // the words past W are staged as zeros
-#pragma unroll 1
-		for (int32_t kk = 0; kk < kk_hi; kk += 4) {
-			uint4 a[8], b[8];
-#pragma unroll
-			for (int32_t ii = 0; ii < 8; ++ii) a[ii] = *(const uint4 *)(sa + (ty + 16 * ii) * TRAIT_LDW + kk);
-#pragma unroll
-			for (int32_t jj = 0; jj < 8; ++jj) b[jj] = *(const uint4 *)(sb + (tx + 16 * jj) * TRAIT_LDW + kk);
-#pragma unroll
-			for (int32_t ii = 0; ii < 8; ++ii)
-#pragma unroll
-				for (int32_t jj = 0; jj < 8; ++jj) {
-					uint32_t x = acc[ii][jj];
-					x = __popc(a[ii].x & b[jj].x) + x; asm volatile("" : "+v"(x));
-					x = __popc(a[ii].y & b[jj].y) + x; asm volatile("" : "+v"(x));
-					x = __popc(a[ii].z & b[jj].z) + x; asm volatile("" : "+v"(x));
-					x = __popc(a[ii].w & b[jj].w) + x; asm volatile("" : "+v"(x));
-					acc[ii][jj] = x;
-				}
-		}
-	}
+	BIT_TILE(true, bits, G, rows, nb, W, 0, n_chunk)
 
 	// the epilogue: the thread's 8 columns that exist, then per row its 8 counts against the row's thresholds; the 16 lanes tx = 0..15
 	// of a row are neighbours in the wave, so four shuffles sum the row's hits and lane tx = 0 adds them

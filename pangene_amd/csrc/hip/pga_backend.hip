@@ -73,24 +73,12 @@ extern "C" void pga_host_free(void *ptr) { if (ptr) (void)hipHostFree(ptr); }
 extern "C" int pga_set_device(int32_t device) { if (hipSetDevice(device) != hipSuccess) return PGA_ERR_NO_DEVICE; g_last_dev.store(device); return 0; }
 extern "C" int pga_device_count(void) { int n = 0; return hipGetDeviceCount(&n) == hipSuccess ? n : 0; }
 
-static void curves_release(); // pga_host_curves.hpp
-static void dist_release();   // pga_host_dist.hpp
-static void assoc_release();  // pga_host_assoc.hpp
-static void trait_release();  // pga_host_trait.hpp
-static void join_release();   // pga_host_join.hpp
-static void boot_release();   // pga_host_boot.hpp
-static void pairs_release();  // pga_host_pairs.hpp
+static void pan_release_all(); // pga_host_pan.hpp: the pools of the pga_pan_* entries
 
 extern "C" void pga_host_trim(size_t keep_bytes)
 {
 	if (keep_bytes == 0) { // "give everything back": the cached device blocks too
-		curves_release();
-		dist_release();
-		assoc_release();
-		trait_release();
-		join_release();
-		boot_release();
-		pairs_release();
+		pan_release_all();
 		std::lock_guard<std::mutex> lk(g_dev_mu);
 		for (DevBlock &b : g_dev_cache) (void)hipFree(b.p);
 		g_dev_cache.clear();
@@ -143,6 +131,7 @@ extern "C" const char *pga_strerror(int code)
 #include "pga_host_order.hpp"
 #include "pga_host_io.hpp"
 #include "pga_host_call.hpp"
+#include "pga_host_pan.hpp"
 #include "pga_host_curves.hpp"
 #include "pga_host_dist.hpp"
 #include "pga_host_assoc.hpp"

@@ -11,52 +11,8 @@ constexpr int32_t BOOT_MAX_BATCH = 1024;              // replicates a call takes
 constexpr int64_t BOOT_BUDGET = (int64_t)2 << 30;     // device memory of a call's replicates: what pga_boot_batch divides
 constexpr int64_t BOOT_ROWS_WORDS = (int64_t)64 << 20; // draws + resampled rows of a replicate group: 256 MiB, or one replicate's
 
-namespace {
-struct BootDev {
-	std::mutex mu;
-	hipStream_t st = nullptr;
-	enum { BITS, DRAWS, ROWS, S, D, LABEL, AUX, PART, REC, MX, N_BUF }; // REC: the records, then one flag word per replicate
-	void *p[N_BUF] = {};
-	size_t cap[N_BUF] = {};
-	int64_t *host = nullptr; // page-locked: the records, then the flags
-	size_t host_cap = 0;
-	template <class T> T *get(int i, size_t n) // at least n elements of T in buffer i (contents not kept)
-	{
-		const size_t bytes = sizeof(T) * (n ? n : 1);
-		if (cap[i] < bytes) {
-			if (p[i]) (void)hipFree(p[i]);
-			p[i] = nullptr, cap[i] = 0;
-			if (hipMalloc(&p[i], bytes) != hipSuccess) { p[i] = nullptr; return nullptr; }
-			cap[i] = bytes;
-		}
-		return (T *)p[i];
-	}
-	int64_t *get_host(size_t n)
-	{
-		const size_t bytes = sizeof(int64_t) * (n ? n : 1);
-		if (host_cap < bytes) {
-			if (host) (void)hipHostFree(host);
-			host = nullptr, host_cap = 0;
-			if (hipHostMalloc((void **)&host, bytes, hipHostMallocDefault) != hipSuccess) { host = nullptr; return nullptr; }
-			host_cap = bytes;
-		}
-		return host;
-	}
-	void release()
-	{
-		for (int i = 0; i < N_BUF; ++i) { if (p[i]) (void)hipFree(p[i]); p[i] = nullptr, cap[i] = 0; }
-		if (host) (void)hipHostFree(host);
-		host = nullptr, host_cap = 0;
-	}
-};
-BootDev g_boot;
-}
-
-static void boot_release() { std::lock_guard<std::mutex> lk(g_boot.mu); g_boot.release(); }
-
-#define BOOTCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
-	fprintf(stderr, "[E::pga_pan_boot] %s:%d: %s\n", __FILE__, __LINE__, hipGetErrorString(e_)); return PGA_ERR_NO_DEVICE; } } while (0)
-#define BOOTMEM(p) do { if ((p) == nullptr) return PGA_ERR_NOMEM; } while (0)
+// REC: the records, then one flag word per replicate; page-locked buffer 0: the same
+struct BootBuf { enum { BITS, DRAWS, ROWS, S, D, LABEL, AUX, PART, REC, MX, N_BUF }; };
 
 // Replicates per call: the budget over what a replicate keeps for the whole call -- S (A^2 words), d (A x ld), label, aux, the search's
 // candidates and the records.  The draws and the resampled rows are not in it: the function takes n_asm alone and their size depends on
@@ -91,17 +47,17 @@ static int boot_join_queue(hipStream_t st, int32_t *d_d, int32_t n, int32_t ld, 
 	const size_t d_stride = (size_t)n * (size_t)ld;
 	const unsigned B = (unsigned)n_rep;
 	hipLaunchKernelGGL(k_join_init_b<NJ>, dim3((unsigned)n, B), dim3(BLOCK), 0, st, d_d, n, ld, d_label, d_aux, d_flag, d_stride, n);
-	BOOTCHK(hipGetLastError());
+	PANCHK(g_pan[PAN_BOOT], hipGetLastError());
 	int32_t s = 0;
 	for (int32_t r = n; r > (NJ ? 3 : 1); --r, ++s) {
 		const int32_t n_tile = ((r + JOIN_CW - 1) / JOIN_CW) * ((r + JOIN_RB - 1) / JOIN_RB), n_part = std::min(n_tile, p_stride);
 		hipLaunchKernelGGL(k_join_argmin_b<NJ>, dim3((unsigned)n_part, B), dim3(BLOCK), 0, st, d_d, ld, r, d_label, d_aux, d_part, d_stride, n, p_stride);
 		hipLaunchKernelGGL(k_join_update_b<NJ>, dim3((unsigned)((r + BLOCK - 1) / BLOCK), B), dim3(BLOCK), 0, st, d_d, ld, r, d_label, d_aux, d_part, n_part,
 		                   d_rec + 6 * (size_t)s, d_flag, d_stride, n, p_stride, rec_stride);
-		if ((s & 255) == 255) BOOTCHK(hipGetLastError());
+		if ((s & 255) == 255) PANCHK(g_pan[PAN_BOOT], hipGetLastError());
 	}
 	if (NJ) hipLaunchKernelGGL(k_join_final_b, dim3(1, B), dim3(WAVE), 0, st, d_d, ld, d_label, d_rec + 6 * (size_t)s, d_stride, n, rec_stride);
-	BOOTCHK(hipGetLastError());
+	PANCHK(g_pan[PAN_BOOT], hipGetLastError());
 	return 0;
 }
 
@@ -119,36 +75,32 @@ extern "C" int pga_pan_boot(const pga_boot_in_t *in, pga_boot_out_t *out)
 	const bool nj = in->method == 0, diff = in->metric == 2;
 	const int32_t n_rec = nj ? A - 2 : A - 1, ld = (A + 3) & ~3;
 	const size_t nn = (size_t)A * (size_t)A, rec_stride = 6 * (size_t)n_rec, n_flag64 = ((size_t)n_rep + 1) / 2;
-	std::lock_guard<std::mutex> lk(g_boot.mu);
-	BootDev &m = g_boot;
-	int64_t *h_rec = m.get_host(rec_stride * (size_t)n_rep + n_flag64);
-	BOOTMEM(h_rec);
+	PanDev &m = g_pan[PAN_BOOT];
+	std::lock_guard<std::mutex> lk(m.mu);
+	int64_t *h_rec = m.get_host<int64_t>(0, rec_stride * (size_t)n_rep + n_flag64);
+	PANMEM(h_rec);
 	out->rec = h_rec, out->n_rec = n_rec;
 	if (n_rep == 0) return 0;
 	out->rec = nullptr, out->n_rec = 0;
-	if (m.st == nullptr) BOOTCHK(hipStreamCreateWithFlags(&m.st, hipStreamNonBlocking));
-	hipStream_t st = m.st;
+	hipStream_t st;
+	PANCHK(m, m.stream(&st));
 	// replicates of a group: its draws and rows within the rows budget, one replicate at least
 	const int64_t rep_words = (int64_t)A * W + M;
 	const int32_t g_max = (int32_t)std::max<int64_t>(1, std::min<int64_t>(n_rep, rep_words > 0 ? boot_rows_words() / rep_words : n_rep));
 	const int32_t max_part = join_max_part();
-	uint32_t *d_bits = m.get<uint32_t>(BootDev::BITS, (size_t)A * (size_t)W), *d_rows = m.get<uint32_t>(BootDev::ROWS, (size_t)g_max * (size_t)A * (size_t)W);
-	int32_t *d_draws = m.get<int32_t>(BootDev::DRAWS, (size_t)g_max * (size_t)M), *d_S = m.get<int32_t>(BootDev::S, (size_t)n_rep * nn);
-	int32_t *d_d = m.get<int32_t>(BootDev::D, (size_t)n_rep * (size_t)A * (size_t)ld), *d_label = m.get<int32_t>(BootDev::LABEL, (size_t)n_rep * (size_t)A);
-	int32_t *d_mx = m.get<int32_t>(BootDev::MX, (size_t)n_rep);
-	long long *d_aux = m.get<long long>(BootDev::AUX, (size_t)n_rep * (size_t)A), *d_rec = m.get<long long>(BootDev::REC, rec_stride * (size_t)n_rep + n_flag64);
-	JoinPart *d_part = m.get<JoinPart>(BootDev::PART, (size_t)n_rep * (size_t)max_part);
-	BOOTMEM(d_bits); BOOTMEM(d_rows); BOOTMEM(d_draws); BOOTMEM(d_S); BOOTMEM(d_d); BOOTMEM(d_label); BOOTMEM(d_mx); BOOTMEM(d_aux); BOOTMEM(d_rec); BOOTMEM(d_part);
+	uint32_t *d_bits = m.get<uint32_t>(BootBuf::BITS, (size_t)A * (size_t)W), *d_rows = m.get<uint32_t>(BootBuf::ROWS, (size_t)g_max * (size_t)A * (size_t)W);
+	int32_t *d_draws = m.get<int32_t>(BootBuf::DRAWS, (size_t)g_max * (size_t)M), *d_S = m.get<int32_t>(BootBuf::S, (size_t)n_rep * nn);
+	int32_t *d_d = m.get<int32_t>(BootBuf::D, (size_t)n_rep * (size_t)A * (size_t)ld), *d_label = m.get<int32_t>(BootBuf::LABEL, (size_t)n_rep * (size_t)A);
+	int32_t *d_mx = m.get<int32_t>(BootBuf::MX, (size_t)n_rep);
+	long long *d_aux = m.get<long long>(BootBuf::AUX, (size_t)n_rep * (size_t)A), *d_rec = m.get<long long>(BootBuf::REC, rec_stride * (size_t)n_rep + n_flag64);
+	JoinPart *d_part = m.get<JoinPart>(BootBuf::PART, (size_t)n_rep * (size_t)max_part);
+	PANMEM(d_bits); PANMEM(d_rows); PANMEM(d_draws); PANMEM(d_S); PANMEM(d_d); PANMEM(d_label); PANMEM(d_mx); PANMEM(d_aux); PANMEM(d_rec); PANMEM(d_part);
 	int32_t *d_flag = (int32_t *)(d_rec + rec_stride * (size_t)n_rep);
-	BOOTCHK(hipMemsetAsync(d_flag, 0, sizeof(int64_t) * n_flag64, st));
-	if (diff) BOOTCHK(hipMemsetAsync(d_mx, 0, sizeof(int32_t) * (size_t)n_rep, st));
-	if (W > 0) BOOTCHK(hipMemcpyAsync(d_bits, in->bits, sizeof(uint32_t) * (size_t)A * (size_t)W, hipMemcpyHostToDevice, st));
-	else BOOTCHK(hipMemsetAsync(d_S, 0, sizeof(int32_t) * (size_t)n_rep * nn, st)); // no items: every count is zero
-	// k_dist_shared's launch shape, as pga_pan_shared chooses it
-	const int32_t n_chunk = (W + DIST_KC - 1) / DIST_KC, T = (A + DIST_TILE - 1) / DIST_TILE, n_tile = T * (T + 1) / 2, want = 512;
-	int32_t n_split = n_tile >= want ? 1 : std::min(std::max(n_chunk, 1), (want + n_tile - 1) / n_tile);
-	const int32_t cps = (std::max(n_chunk, 1) + n_split - 1) / n_split;
-	n_split = (std::max(n_chunk, 1) + cps - 1) / cps;
+	PANCHK(m, hipMemsetAsync(d_flag, 0, sizeof(int64_t) * n_flag64, st));
+	if (diff) PANCHK(m, hipMemsetAsync(d_mx, 0, sizeof(int32_t) * (size_t)n_rep, st));
+	if (W > 0) PANCHK(m, hipMemcpyAsync(d_bits, in->bits, sizeof(uint32_t) * (size_t)A * (size_t)W, hipMemcpyHostToDevice, st));
+	else PANCHK(m, hipMemsetAsync(d_S, 0, sizeof(int32_t) * (size_t)n_rep * nn, st)); // no items: every count is zero
+	const DistShape sh = dist_shape(A, W);
 	const bool use_lds = W <= boot_lds_words();
 	const unsigned n_wc = (unsigned)((W + BLOCK - 1) / BLOCK);
 	for (int32_t q0 = 0; q0 < n_rep; q0 += g_max) {
@@ -156,34 +108,32 @@ extern "C" int pga_pan_boot(const pga_boot_in_t *in, pga_boot_out_t *out)
 		int32_t *S_g = d_S + (size_t)q0 * nn;
 		if (W > 0) {
 			hipLaunchKernelGGL(k_boot_draw, dim3((unsigned)(((int64_t)M + BLOCK - 1) / BLOCK), (unsigned)g), dim3(BLOCK), 0, st, M, in->seed, (uint32_t)(in->first + q0), d_draws);
-			BOOTCHK(hipGetLastError());
-			if (in->draws != nullptr) BOOTCHK(hipMemcpyAsync(in->draws + (size_t)q0 * (size_t)M, d_draws, sizeof(int32_t) * (size_t)g * (size_t)M, hipMemcpyDeviceToHost, st));
+			PANCHK(m, hipGetLastError());
+			if (in->draws != nullptr) PANCHK(m, hipMemcpyAsync(in->draws + (size_t)q0 * (size_t)M, d_draws, sizeof(int32_t) * (size_t)g * (size_t)M, hipMemcpyDeviceToHost, st));
 			// assemblies a workgroup takes: as many as still leave about 2 048 workgroups, 32 at the most
 			const int32_t a_per = (int32_t)std::max<int64_t>(1, std::min<int64_t>(32, (int64_t)A * g * n_wc / 2048));
 			const dim3 grid(n_wc, (unsigned)((A + a_per - 1) / a_per), (unsigned)g);
 			if (use_lds) hipLaunchKernelGGL(k_boot_resample<true>, grid, dim3(BLOCK), sizeof(uint32_t) * (size_t)W, st, d_bits, d_draws, M, W, A, a_per, d_rows);
 			else hipLaunchKernelGGL(k_boot_resample<false>, grid, dim3(BLOCK), 0, st, d_bits, d_draws, M, W, A, a_per, d_rows);
-			BOOTCHK(hipGetLastError());
-			if (n_split > 1) BOOTCHK(hipMemsetAsync(S_g, 0, sizeof(int32_t) * (size_t)g * nn, st));
+			PANCHK(m, hipGetLastError());
+			if (sh.n_split > 1) PANCHK(m, hipMemsetAsync(S_g, 0, sizeof(int32_t) * (size_t)g * nn, st));
 			for (int32_t q = 0; q < g; ++q)
-				hipLaunchKernelGGL(k_dist_shared, dim3((unsigned)n_tile * (unsigned)n_split), dim3(BLOCK), 0, st, d_rows + (size_t)q * (size_t)A * (size_t)W, A, W, n_chunk, n_split,
-				                   cps, S_g + (size_t)q * nn);
-			BOOTCHK(hipGetLastError());
+				hipLaunchKernelGGL(k_dist_shared, dim3((unsigned)sh.n_tile * (unsigned)sh.n_split), dim3(BLOCK), 0, st, d_rows + (size_t)q * (size_t)A * (size_t)W, A, W,
+				                   sh.n_chunk, sh.n_split, sh.cps, S_g + (size_t)q * nn);
+			PANCHK(m, hipGetLastError());
 		}
 		if (diff) hipLaunchKernelGGL(k_boot_maxdiff, dim3((unsigned)std::min<size_t>((nn + BLOCK - 1) / BLOCK, 1024), (unsigned)g), dim3(BLOCK), 0, st, S_g, A, d_mx + q0);
 		hipLaunchKernelGGL(k_boot_fixed, dim3((unsigned)A, (unsigned)g), dim3(BLOCK), 0, st, S_g, A, ld, diff ? 1 : 0, d_mx + q0, d_d + (size_t)q0 * (size_t)A * (size_t)ld, d_flag + q0);
-		BOOTCHK(hipGetLastError());
+		PANCHK(m, hipGetLastError());
 	}
 	const int rc = nj ? boot_join_queue<true>(st, d_d, A, ld, n_rep, d_label, d_aux, d_part, max_part, d_rec, rec_stride, d_flag)
 	                  : boot_join_queue<false>(st, d_d, A, ld, n_rep, d_label, d_aux, d_part, max_part, d_rec, rec_stride, d_flag);
 	if (rc != 0) { (void)hipStreamSynchronize(st); return rc; }
-	BOOTCHK(hipMemcpyAsync(h_rec, d_rec, sizeof(int64_t) * (rec_stride * (size_t)n_rep + n_flag64), hipMemcpyDeviceToHost, st));
-	BOOTCHK(hipStreamSynchronize(st));
+	PANCHK(m, hipMemcpyAsync(h_rec, d_rec, sizeof(int64_t) * (rec_stride * (size_t)n_rep + n_flag64), hipMemcpyDeviceToHost, st));
+	PANCHK(m, hipStreamSynchronize(st));
 	const int32_t *h_flag = (const int32_t *)(h_rec + rec_stride * (size_t)n_rep);
 	for (int32_t q = 0; q < n_rep; ++q)
 		if (h_flag[q] != 0) return PGA_ERR_RANGE;
 	out->rec = h_rec, out->n_rec = n_rec;
 	return 0;
 }
-#undef BOOTCHK
-#undef BOOTMEM

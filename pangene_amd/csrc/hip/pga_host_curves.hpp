@@ -3,34 +3,10 @@
 // more than the kernels); pga_host_trim(0) gives them back.  The result waits in a host vector of the library until the next call.
 
 namespace {
-struct CurvesDev {
-	std::mutex mu;
-	hipStream_t st = nullptr;
-	enum { BITS, ORD, RANK, CNT, LEN, OFF, LIST, TILES, HIST, OUT, N_BUF };
-	void *p[N_BUF] = {};
-	size_t cap[N_BUF] = {};
-	std::vector<int32_t> out;
-	template <class T> T *get(int i, size_t n) // at least n elements of T in buffer i (contents not kept)
-	{
-		const size_t bytes = sizeof(T) * (n ? n : 1);
-		if (cap[i] < bytes) {
-			if (p[i]) (void)hipFree(p[i]);
-			p[i] = nullptr, cap[i] = 0;
-			if (hipMalloc(&p[i], bytes) != hipSuccess) { p[i] = nullptr; return nullptr; }
-			cap[i] = bytes;
-		}
-		return (T *)p[i];
-	}
-	void release() { for (int i = 0; i < N_BUF; ++i) { if (p[i]) (void)hipFree(p[i]); p[i] = nullptr, cap[i] = 0; } }
-};
-CurvesDev g_curves;
+struct CurvesBuf { enum { BITS, ORD, RANK, CNT, LEN, OFF, LIST, TILES, HIST, OUT, N_BUF }; };
+static_assert(CurvesBuf::N_BUF <= PAN_MAX_DEV, "the pool has room");
+std::vector<int32_t> g_curves_out; // the result, under the pool's lock
 }
-
-static void curves_release() { std::lock_guard<std::mutex> lk(g_curves.mu); g_curves.release(); }
-
-#define CURVCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
-	fprintf(stderr, "[E::pga_pan_curves] %s:%d: %s\n", __FILE__, __LINE__, hipGetErrorString(e_)); return PGA_ERR_NO_DEVICE; } } while (0)
-#define CURVMEM(p) do { if ((p) == nullptr) return PGA_ERR_NOMEM; } while (0)
 
 extern "C" int pga_pan_curves(const pga_curves_in_t *in, pga_curves_out_t *out)
 {
@@ -45,28 +21,28 @@ extern "C" int pga_pan_curves(const pga_curves_in_t *in, pga_curves_out_t *out)
 			for (int32_t i = 0; i < A; ++i) { if (o[i] < 0 || o[i] >= A || seen[(size_t)o[i]]) return PGA_ERR_ARG; seen[(size_t)o[i]] = 1; }
 		}
 	}
-	std::lock_guard<std::mutex> lk(g_curves.mu);
-	CurvesDev &m = g_curves;
-	m.out.assign((size_t)4 * n * A, 0);
-	out->count = m.out.data();
+	PanDev &m = g_pan[PAN_CURVES];
+	std::lock_guard<std::mutex> lk(m.mu);
+	g_curves_out.assign((size_t)4 * n * A, 0);
+	out->count = g_curves_out.data();
 	if (G == 0 || A == 0 || n == 0) return 0;
 	const int32_t W = (A + 31) / 32;
 	int32_t T = 2;
 	while ((int64_t)T * T < 2 * (int64_t)A) ++T; // ceil(sqrt(2A))
 	const int64_t list_max = (int64_t)G * std::min(T, A);
 	if (list_max >= INT32_MAX || (int64_t)n * 3 * (A + 1) >= INT32_MAX || (int64_t)n * A >= INT32_MAX / 4) return PGA_ERR_RANGE;
-	if (m.st == nullptr) CURVCHK(hipStreamCreateWithFlags(&m.st, hipStreamNonBlocking));
-	hipStream_t st = m.st;
-	uint32_t *d_bits = m.get<uint32_t>(CurvesDev::BITS, (size_t)G * W);
-	int32_t *d_ord = m.get<int32_t>(CurvesDev::ORD, (size_t)n * A), *d_rank = m.get<int32_t>(CurvesDev::RANK, (size_t)n * A);
-	int32_t *d_cnt = m.get<int32_t>(CurvesDev::CNT, (size_t)G), *d_len = m.get<int32_t>(CurvesDev::LEN, (size_t)G), *d_off = m.get<int32_t>(CurvesDev::OFF, (size_t)G);
-	int32_t *d_list = m.get<int32_t>(CurvesDev::LIST, (size_t)list_max);
-	I32 *d_tiles = m.get<I32>(CurvesDev::TILES, (size_t)scan_tiles(G));
-	int32_t *d_hist = m.get<int32_t>(CurvesDev::HIST, (size_t)n * 3 * (A + 1)), *d_out = m.get<int32_t>(CurvesDev::OUT, (size_t)4 * n * A);
-	CURVMEM(d_bits); CURVMEM(d_ord); CURVMEM(d_rank); CURVMEM(d_cnt); CURVMEM(d_len); CURVMEM(d_off); CURVMEM(d_list); CURVMEM(d_tiles); CURVMEM(d_hist); CURVMEM(d_out);
-	CURVCHK(hipMemcpyAsync(d_bits, in->bits, sizeof(uint32_t) * (size_t)G * W, hipMemcpyHostToDevice, st));
-	CURVCHK(hipMemcpyAsync(d_ord, in->order, sizeof(int32_t) * (size_t)n * A, hipMemcpyHostToDevice, st));
-	CURVCHK(hipMemsetAsync(d_hist, 0, sizeof(int32_t) * (size_t)n * 3 * (A + 1), st));
+	hipStream_t st;
+	PANCHK(m, m.stream(&st));
+	uint32_t *d_bits = m.get<uint32_t>(CurvesBuf::BITS, (size_t)G * W);
+	int32_t *d_ord = m.get<int32_t>(CurvesBuf::ORD, (size_t)n * A), *d_rank = m.get<int32_t>(CurvesBuf::RANK, (size_t)n * A);
+	int32_t *d_cnt = m.get<int32_t>(CurvesBuf::CNT, (size_t)G), *d_len = m.get<int32_t>(CurvesBuf::LEN, (size_t)G), *d_off = m.get<int32_t>(CurvesBuf::OFF, (size_t)G);
+	int32_t *d_list = m.get<int32_t>(CurvesBuf::LIST, (size_t)list_max);
+	I32 *d_tiles = m.get<I32>(CurvesBuf::TILES, (size_t)scan_tiles(G));
+	int32_t *d_hist = m.get<int32_t>(CurvesBuf::HIST, (size_t)n * 3 * (A + 1)), *d_out = m.get<int32_t>(CurvesBuf::OUT, (size_t)4 * n * A);
+	PANMEM(d_bits); PANMEM(d_ord); PANMEM(d_rank); PANMEM(d_cnt); PANMEM(d_len); PANMEM(d_off); PANMEM(d_list); PANMEM(d_tiles); PANMEM(d_hist); PANMEM(d_out);
+	PANCHK(m, hipMemcpyAsync(d_bits, in->bits, sizeof(uint32_t) * (size_t)G * W, hipMemcpyHostToDevice, st));
+	PANCHK(m, hipMemcpyAsync(d_ord, in->order, sizeof(int32_t) * (size_t)n * A, hipMemcpyHostToDevice, st));
+	PANCHK(m, hipMemsetAsync(d_hist, 0, sizeof(int32_t) * (size_t)n * 3 * (A + 1), st));
 	auto grid = [](int64_t k) { return dim3((unsigned)((k + BLOCK - 1) / BLOCK)); };
 	hipLaunchKernelGGL(k_curves_rank, grid((int64_t)n * A), dim3(BLOCK), 0, st, d_ord, (int64_t)n * A, A, d_rank);
 	hipLaunchKernelGGL(k_curves_count, grid(G), dim3(BLOCK), 0, st, d_bits, W, G, A, T, d_cnt, d_len);
@@ -79,10 +55,8 @@ extern "C" int pga_pan_curves(const pga_curves_in_t *in, pga_curves_out_t *out)
 	hipLaunchKernelGGL(k_curves_ranks, dim3((unsigned)(n * bpo)), dim3(BLOCK), sizeof(int32_t) * 3 * (size_t)(R + 1), st, d_bits, W, d_ord, d_rank,
 	                   d_cnt, d_off, d_list, G, A, T, R, bpo, d_hist);
 	hipLaunchKernelGGL(k_curves_finish, dim3((unsigned)n), dim3(BLOCK), 0, st, d_hist, A, G, n, d_out);
-	CURVCHK(hipGetLastError());
-	CURVCHK(hipMemcpyAsync(m.out.data(), d_out, sizeof(int32_t) * m.out.size(), hipMemcpyDeviceToHost, st));
-	CURVCHK(hipStreamSynchronize(st));
+	PANCHK(m, hipGetLastError());
+	PANCHK(m, hipMemcpyAsync(g_curves_out.data(), d_out, sizeof(int32_t) * g_curves_out.size(), hipMemcpyDeviceToHost, st));
+	PANCHK(m, hipStreamSynchronize(st));
 	return 0;
 }
-#undef CURVCHK
-#undef CURVMEM

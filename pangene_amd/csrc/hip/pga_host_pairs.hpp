@@ -5,51 +5,10 @@
 // The host checks the program (a malformed one would index the stack out of bounds) and finds the depth it needs, packs the program and
 // the label rows into bit words, uploads, launches k_pairs -- one launch per 65 535 label rows -- and waits once.
 
-namespace {
-struct PairsDev {
-	std::mutex mu;
-	hipStream_t st = nullptr;
+struct PairsBuf {
 	enum { OPS, BITS, HAS, ONE, OUT, N_BUF };
-	void *p[N_BUF] = {};
-	size_t cap[N_BUF] = {};
-	void *host[2] = {}; // page-locked: the packed program and label planes; the results
-	size_t host_cap[2] = {};
-	template <class T> T *get(int i, size_t n) // at least n elements of T in buffer i (contents not kept)
-	{
-		const size_t bytes = sizeof(T) * (n ? n : 1);
-		if (cap[i] < bytes) {
-			if (p[i]) (void)hipFree(p[i]);
-			p[i] = nullptr, cap[i] = 0;
-			if (hipMalloc(&p[i], bytes) != hipSuccess) { p[i] = nullptr; return nullptr; }
-			cap[i] = bytes;
-		}
-		return (T *)p[i];
-	}
-	template <class T> T *get_host(int i, size_t n)
-	{
-		const size_t bytes = sizeof(T) * (n ? n : 1);
-		if (host_cap[i] < bytes) {
-			if (host[i]) (void)hipHostFree(host[i]);
-			host[i] = nullptr, host_cap[i] = 0;
-			if (hipHostMalloc(&host[i], bytes, hipHostMallocDefault) != hipSuccess) { host[i] = nullptr; return nullptr; }
-			host_cap[i] = bytes;
-		}
-		return (T *)host[i];
-	}
-	void release()
-	{
-		for (int i = 0; i < N_BUF; ++i) { if (p[i]) (void)hipFree(p[i]); p[i] = nullptr, cap[i] = 0; }
-		for (int i = 0; i < 2; ++i) { if (host[i]) (void)hipHostFree(host[i]); host[i] = nullptr, host_cap[i] = 0; }
-	}
+	enum { H_IN, H_OUT }; // page-locked: the packed program and label planes; the results
 };
-PairsDev g_pairs;
-}
-
-static void pairs_release() { std::lock_guard<std::mutex> lk(g_pairs.mu); g_pairs.release(); }
-
-#define PAIRSCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
-	fprintf(stderr, "[E::pga_pan_pairs] %s:%d: %s\n", __FILE__, __LINE__, hipGetErrorString(e_)); return PGA_ERR_NO_DEVICE; } } while (0)
-#define PAIRSMEM(p) do { if ((p) == nullptr) return PGA_ERR_NOMEM; } while (0)
 
 extern "C" int pga_pan_pairs(const pga_pairs_in_t *in, pga_pairs_out_t *out)
 {
@@ -70,17 +29,17 @@ extern "C" int pga_pan_pairs(const pga_pairs_in_t *in, pga_pairs_out_t *out)
 	}
 	if (n_op > 0 && (sp != 1 || pushed != L)) return PGA_ERR_ARG;
 	if (depth > PAIRS_DEPTH) return PGA_ERR_RANGE;
-	std::lock_guard<std::mutex> lk(g_pairs.mu);
-	PairsDev &m = g_pairs;
+	PanDev &m = g_pan[PAN_PAIRS];
+	std::lock_guard<std::mutex> lk(m.mu);
 	const size_t n_out = (size_t)R * (size_t)G * 3;
-	int32_t *h_out = m.get_host<int32_t>(1, n_out);
-	PAIRSMEM(h_out);
+	int32_t *h_out = m.get_host<int32_t>(PairsBuf::H_OUT, n_out);
+	PANMEM(h_out);
 	out->out = h_out;
 	if (n_out == 0) return 0;
 	if (L == 0) { memset(h_out, 0, sizeof(int32_t) * n_out); return 0; } // no leaves: no pairs
 	const size_t n_plane = (size_t)R * (size_t)LW;
-	uint32_t *h_in = m.get_host<uint32_t>(0, (size_t)OW + 2 * n_plane);
-	PAIRSMEM(h_in);
+	uint32_t *h_in = m.get_host<uint32_t>(PairsBuf::H_IN, (size_t)OW + 2 * n_plane);
+	PANMEM(h_in);
 	uint32_t *h_ops = h_in, *h_has = h_in + OW, *h_one = h_has + n_plane;
 	memset(h_in, 0, sizeof(uint32_t) * ((size_t)OW + 2 * n_plane));
 	for (int32_t k = 0; k < n_op; ++k) h_ops[k >> 5] |= (uint32_t)in->op[k] << (k & 31);
@@ -91,27 +50,25 @@ extern "C" int pga_pan_pairs(const pga_pairs_in_t *in, pga_pairs_out_t *out)
 			if (lab[x] > 0) h_one[(size_t)r * LW + (size_t)(x >> 5)] |= 1u << (x & 31);
 		}
 	}
-	if (m.st == nullptr) PAIRSCHK(hipStreamCreateWithFlags(&m.st, hipStreamNonBlocking));
-	hipStream_t st = m.st;
+	hipStream_t st;
+	PANCHK(m, m.stream(&st));
 	const size_t n_word = (size_t)L * (size_t)W;
-	uint32_t *d_ops = m.get<uint32_t>(PairsDev::OPS, (size_t)OW), *d_bits = m.get<uint32_t>(PairsDev::BITS, n_word);
-	uint32_t *d_has = m.get<uint32_t>(PairsDev::HAS, n_plane), *d_one = m.get<uint32_t>(PairsDev::ONE, n_plane);
-	int32_t *d_out = m.get<int32_t>(PairsDev::OUT, n_out);
-	PAIRSMEM(d_ops); PAIRSMEM(d_bits); PAIRSMEM(d_has); PAIRSMEM(d_one); PAIRSMEM(d_out);
-	PAIRSCHK(hipMemcpyAsync(d_ops, h_ops, sizeof(uint32_t) * (size_t)OW, hipMemcpyHostToDevice, st));
-	PAIRSCHK(hipMemcpyAsync(d_has, h_has, sizeof(uint32_t) * n_plane, hipMemcpyHostToDevice, st));
-	PAIRSCHK(hipMemcpyAsync(d_one, h_one, sizeof(uint32_t) * n_plane, hipMemcpyHostToDevice, st));
-	PAIRSCHK(hipMemcpyAsync(d_bits, in->bits, sizeof(uint32_t) * n_word, hipMemcpyHostToDevice, st));
+	uint32_t *d_ops = m.get<uint32_t>(PairsBuf::OPS, (size_t)OW), *d_bits = m.get<uint32_t>(PairsBuf::BITS, n_word);
+	uint32_t *d_has = m.get<uint32_t>(PairsBuf::HAS, n_plane), *d_one = m.get<uint32_t>(PairsBuf::ONE, n_plane);
+	int32_t *d_out = m.get<int32_t>(PairsBuf::OUT, n_out);
+	PANMEM(d_ops); PANMEM(d_bits); PANMEM(d_has); PANMEM(d_one); PANMEM(d_out);
+	PANCHK(m, hipMemcpyAsync(d_ops, h_ops, sizeof(uint32_t) * (size_t)OW, hipMemcpyHostToDevice, st));
+	PANCHK(m, hipMemcpyAsync(d_has, h_has, sizeof(uint32_t) * n_plane, hipMemcpyHostToDevice, st));
+	PANCHK(m, hipMemcpyAsync(d_one, h_one, sizeof(uint32_t) * n_plane, hipMemcpyHostToDevice, st));
+	PANCHK(m, hipMemcpyAsync(d_bits, in->bits, sizeof(uint32_t) * n_word, hipMemcpyHostToDevice, st));
 	const unsigned gene_blocks = (unsigned)((G + PAIRS_BLOCK - 1) / PAIRS_BLOCK);
 	const size_t lds = sizeof(int32_t) * 5 * PAIRS_BLOCK * (size_t)std::max(depth - 1, 1);
 	for (int32_t r0 = 0; r0 < R; r0 += 65535) {
 		const unsigned rows = (unsigned)std::min(65535, R - r0);
 		hipLaunchKernelGGL(k_pairs, dim3(gene_blocks, rows, 2), dim3(PAIRS_BLOCK), lds, st, d_ops, d_bits, d_has, d_one, G, W, L, LW, n_op, r0, d_out);
-		PAIRSCHK(hipGetLastError());
+		PANCHK(m, hipGetLastError());
 	}
-	PAIRSCHK(hipMemcpyAsync(h_out, d_out, sizeof(int32_t) * n_out, hipMemcpyDeviceToHost, st));
-	PAIRSCHK(hipStreamSynchronize(st));
+	PANCHK(m, hipMemcpyAsync(h_out, d_out, sizeof(int32_t) * n_out, hipMemcpyDeviceToHost, st));
+	PANCHK(m, hipStreamSynchronize(st));
 	return 0;
 }
-#undef PAIRSCHK
-#undef PAIRSMEM

@@ -10,58 +10,13 @@ constexpr int32_t TRAIT_MAX_COL = 16777215, TRAIT_MAX_GENE = 16777215;
 constexpr int32_t TRAIT_MAX_PERM = 2147483646; // 2^31 - 2
 constexpr int32_t TRAIT_BATCH = 65536;
 
-namespace {
-struct TraitDev {
-	std::mutex mu;
-	hipStream_t st = nullptr;
-	enum { BITS, LABEL, A, S, LO, HI, K, ROWS, WORK, N_BUF };
-	void *p[N_BUF] = {};
-	size_t cap[N_BUF] = {};
-	void *host = nullptr; // page-locked: a, s, k
-	size_t host_cap = 0;
-	template <class T> T *get(int i, size_t n) // at least n elements of T in buffer i (contents not kept)
-	{
-		const size_t bytes = sizeof(T) * (n ? n : 1);
-		if (cap[i] < bytes) {
-			if (p[i]) (void)hipFree(p[i]);
-			p[i] = nullptr, cap[i] = 0;
-			if (hipMalloc(&p[i], bytes) != hipSuccess) { p[i] = nullptr; return nullptr; }
-			cap[i] = bytes;
-		}
-		return (T *)p[i];
-	}
-	int32_t *get_host(size_t n)
-	{
-		const size_t bytes = sizeof(int32_t) * (n ? n : 1);
-		if (host_cap < bytes) {
-			if (host) (void)hipHostFree(host);
-			host = nullptr, host_cap = 0;
-			if (hipHostMalloc(&host, bytes, hipHostMallocDefault) != hipSuccess) { host = nullptr; return nullptr; }
-			host_cap = bytes;
-		}
-		return (int32_t *)host;
-	}
-	void release()
-	{
-		for (int i = 0; i < N_BUF; ++i) { if (p[i]) (void)hipFree(p[i]); p[i] = nullptr, cap[i] = 0; }
-		if (host) (void)hipHostFree(host);
-		host = nullptr, host_cap = 0;
-	}
-};
-TraitDev g_trait;
-}
-
-static void trait_release() { std::lock_guard<std::mutex> lk(g_trait.mu); g_trait.release(); }
+struct TraitBuf { enum { BITS, LABEL, A, S, LO, HI, K, ROWS, WORK, N_BUF }; }; // page-locked buffer 0: a, s, k
 
 extern "C" int32_t pga_trait_batch(void)
 {
 	if (const char *s = getenv("PANGENE_TRAIT_BATCH")) { const long long v = atoll(s); if (v >= 1 && v <= (1 << 22)) return (int32_t)v; }
 	return TRAIT_BATCH;
 }
-
-#define TRAITCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
-	fprintf(stderr, "[E::pga_pan_trait] %s:%d: %s\n", __FILE__, __LINE__, hipGetErrorString(e_)); return PGA_ERR_NO_DEVICE; } } while (0)
-#define TRAITMEM(p) do { if ((p) == nullptr) return PGA_ERR_NOMEM; } while (0)
 
 extern "C" int pga_pan_trait(const pga_trait_in_t *in, pga_trait_out_t *out)
 {
@@ -73,38 +28,38 @@ extern "C" int pga_pan_trait(const pga_trait_in_t *in, pga_trait_out_t *out)
 	if (N > TRAIT_MAX_COL || G > TRAIT_MAX_GENE || n > TRAIT_MAX_PERM) return PGA_ERR_RANGE;
 	const int32_t W = (N + 31) / 32;
 	if (W > 0 && ((G > 0 && in->bits == nullptr) || in->label == nullptr)) return PGA_ERR_ARG;
-	std::lock_guard<std::mutex> lk(g_trait.mu);
-	TraitDev &m = g_trait;
-	int32_t *h_res = m.get_host((size_t)G * 3);
-	TRAITMEM(h_res);
+	PanDev &m = g_pan[PAN_TRAIT];
+	std::lock_guard<std::mutex> lk(m.mu);
+	int32_t *h_res = m.get_host<int32_t>(0, (size_t)G * 3);
+	PANMEM(h_res);
 	out->a = h_res, out->s = h_res + G, out->k = h_res + 2 * (size_t)G;
 	memset(h_res, 0, sizeof(int32_t) * 3 * (size_t)G);
 	if (G == 0 && in->perm_rows == nullptr) return 0;
 	if (W == 0) return 0; // no columns: every count is 0
 	int32_t t_sum = 0;
 	for (int32_t k = 0; k < W; ++k) t_sum += __builtin_popcount(in->label[k]);
-	if (m.st == nullptr) TRAITCHK(hipStreamCreateWithFlags(&m.st, hipStreamNonBlocking));
-	hipStream_t st = m.st;
+	hipStream_t st;
+	PANCHK(m, m.stream(&st));
 
 	const size_t n_word = (size_t)G * (size_t)W;
 	const int32_t B = (int32_t)std::min<int64_t>(pga_trait_batch(), std::max<int32_t>(n, 1));
 	const bool lds = W <= TRAIT_PERM_LDS_W;
 	const int64_t perm_blocks = ((int64_t)B + WAVE - 1) / WAVE;
-	uint32_t *d_bits = m.get<uint32_t>(TraitDev::BITS, n_word), *d_label = m.get<uint32_t>(TraitDev::LABEL, (size_t)W);
-	int32_t *d_a = m.get<int32_t>(TraitDev::A, (size_t)G), *d_s = m.get<int32_t>(TraitDev::S, (size_t)G), *d_lo = m.get<int32_t>(TraitDev::LO, (size_t)G);
-	int32_t *d_hi = m.get<int32_t>(TraitDev::HI, (size_t)G), *d_k = m.get<int32_t>(TraitDev::K, (size_t)G);
-	uint32_t *d_rows = m.get<uint32_t>(TraitDev::ROWS, (size_t)B * (size_t)W);
-	uint32_t *d_work = m.get<uint32_t>(TraitDev::WORK, lds ? 1 : (size_t)perm_blocks * (size_t)W * WAVE);
-	TRAITMEM(d_bits); TRAITMEM(d_label); TRAITMEM(d_a); TRAITMEM(d_s); TRAITMEM(d_lo); TRAITMEM(d_hi); TRAITMEM(d_k); TRAITMEM(d_rows); TRAITMEM(d_work);
-	if (n_word) TRAITCHK(hipMemcpyAsync(d_bits, in->bits, sizeof(uint32_t) * n_word, hipMemcpyHostToDevice, st));
-	TRAITCHK(hipMemcpyAsync(d_label, in->label, sizeof(uint32_t) * (size_t)W, hipMemcpyHostToDevice, st));
-	TRAITCHK(hipMemsetAsync(d_k, 0, sizeof(int32_t) * (size_t)(G ? G : 1), st));
+	uint32_t *d_bits = m.get<uint32_t>(TraitBuf::BITS, n_word), *d_label = m.get<uint32_t>(TraitBuf::LABEL, (size_t)W);
+	int32_t *d_a = m.get<int32_t>(TraitBuf::A, (size_t)G), *d_s = m.get<int32_t>(TraitBuf::S, (size_t)G), *d_lo = m.get<int32_t>(TraitBuf::LO, (size_t)G);
+	int32_t *d_hi = m.get<int32_t>(TraitBuf::HI, (size_t)G), *d_k = m.get<int32_t>(TraitBuf::K, (size_t)G);
+	uint32_t *d_rows = m.get<uint32_t>(TraitBuf::ROWS, (size_t)B * (size_t)W);
+	uint32_t *d_work = m.get<uint32_t>(TraitBuf::WORK, lds ? 1 : (size_t)perm_blocks * (size_t)W * WAVE);
+	PANMEM(d_bits); PANMEM(d_label); PANMEM(d_a); PANMEM(d_s); PANMEM(d_lo); PANMEM(d_hi); PANMEM(d_k); PANMEM(d_rows); PANMEM(d_work);
+	if (n_word) PANCHK(m, hipMemcpyAsync(d_bits, in->bits, sizeof(uint32_t) * n_word, hipMemcpyHostToDevice, st));
+	PANCHK(m, hipMemcpyAsync(d_label, in->label, sizeof(uint32_t) * (size_t)W, hipMemcpyHostToDevice, st));
+	PANCHK(m, hipMemsetAsync(d_k, 0, sizeof(int32_t) * (size_t)(G ? G : 1), st));
 	if (G > 0) {
 		const unsigned row_blocks = (unsigned)(((int64_t)G + BLOCK / TRAIT_ROW_LANES - 1) / (BLOCK / TRAIT_ROW_LANES));
 		hipLaunchKernelGGL(k_trait_obs, dim3(row_blocks), dim3(BLOCK), 0, st, d_bits, d_label, G, W, N, t_sum, in->min_count, d_a, d_s, d_lo, d_hi);
 	}
-	const int32_t n_chunk = (W + TRAIT_KC - 1) / TRAIT_KC;
-	const unsigned gene_tiles = (unsigned)((G + TRAIT_TILE - 1) / TRAIT_TILE);
+	const int32_t n_chunk = (W + DIST_KC - 1) / DIST_KC;
+	const unsigned gene_tiles = (unsigned)((G + DIST_TILE - 1) / DIST_TILE);
 	for (int64_t done = 0; done < n; done += B) {
 		const int32_t nb = (int32_t)std::min<int64_t>(B, (int64_t)n - done);
 		const unsigned pb = (unsigned)((nb + WAVE - 1) / WAVE);
@@ -112,22 +67,20 @@ extern "C" int pga_pan_trait(const pga_trait_in_t *in, pga_trait_out_t *out)
 		if (lds) hipLaunchKernelGGL(k_trait_perm<true>, dim3(pb), dim3(WAVE), 0, st, d_label, N, W, in->seed, p0, nb, d_work, d_rows);
 		else hipLaunchKernelGGL(k_trait_perm<false>, dim3(pb), dim3(WAVE), 0, st, d_label, N, W, in->seed, p0, nb, d_work, d_rows);
 		if (done == 0 && in->perm_rows != nullptr) { // tests only: the label rows of the first batch
-			TRAITCHK(hipGetLastError());
-			TRAITCHK(hipMemcpyAsync(in->perm_rows, d_rows, sizeof(uint32_t) * (size_t)nb * (size_t)W, hipMemcpyDeviceToHost, st));
-			TRAITCHK(hipStreamSynchronize(st));
+			PANCHK(m, hipGetLastError());
+			PANCHK(m, hipMemcpyAsync(in->perm_rows, d_rows, sizeof(uint32_t) * (size_t)nb * (size_t)W, hipMemcpyDeviceToHost, st));
+			PANCHK(m, hipStreamSynchronize(st));
 		}
 		if (G > 0)
-			hipLaunchKernelGGL(k_trait_count, dim3(gene_tiles, (unsigned)((nb + TRAIT_TILE - 1) / TRAIT_TILE)), dim3(BLOCK), 0, st, d_bits, d_rows, d_lo, d_hi, G, nb, W,
+			hipLaunchKernelGGL(k_trait_count, dim3(gene_tiles, (unsigned)((nb + DIST_TILE - 1) / DIST_TILE)), dim3(BLOCK), 0, st, d_bits, d_rows, d_lo, d_hi, G, nb, W,
 			                   n_chunk, d_k);
-		TRAITCHK(hipGetLastError());
+		PANCHK(m, hipGetLastError());
 	}
 	if (G > 0) {
-		TRAITCHK(hipMemcpyAsync(h_res, d_a, sizeof(int32_t) * (size_t)G, hipMemcpyDeviceToHost, st));
-		TRAITCHK(hipMemcpyAsync(h_res + G, d_s, sizeof(int32_t) * (size_t)G, hipMemcpyDeviceToHost, st));
-		TRAITCHK(hipMemcpyAsync(h_res + 2 * (size_t)G, d_k, sizeof(int32_t) * (size_t)G, hipMemcpyDeviceToHost, st));
+		PANCHK(m, hipMemcpyAsync(h_res, d_a, sizeof(int32_t) * (size_t)G, hipMemcpyDeviceToHost, st));
+		PANCHK(m, hipMemcpyAsync(h_res + G, d_s, sizeof(int32_t) * (size_t)G, hipMemcpyDeviceToHost, st));
+		PANCHK(m, hipMemcpyAsync(h_res + 2 * (size_t)G, d_k, sizeof(int32_t) * (size_t)G, hipMemcpyDeviceToHost, st));
 	}
-	TRAITCHK(hipStreamSynchronize(st));
+	PANCHK(m, hipStreamSynchronize(st));
 	return 0;
 }
-#undef TRAITCHK
-#undef TRAITMEM

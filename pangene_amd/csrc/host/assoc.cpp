@@ -92,33 +92,11 @@ int assoc_select(const std::vector<uint32_t> &bits, int32_t G, int32_t A, const 
 	return rc;
 }
 
-// presence, row-major [G][A] (nonzero = gene g in assembly a), -> gene-major bit rows
-void to_bits(const uint8_t *p, int32_t G, int32_t A, std::vector<uint32_t> &bits)
-{
-	const size_t W = ((size_t)A + 31) / 32;
-	bits.assign((size_t)G * W, 0);
-	for (int32_t g = 0; g < G; ++g) {
-		const uint8_t *row = p + (size_t)g * A;
-		uint32_t *b = bits.data() + (size_t)g * W;
-		for (int32_t a = 0; a < A; ++a)
-			if (row[a]) b[a >> 5] |= 1u << (a & 31);
-	}
-}
-
-// the gfa2matrix matrix (occurrences, [n_seg][A]): gene g is in assembly a when its entry is > 0
-void gene_bits(const int32_t *mat, int32_t G, int32_t A, std::vector<uint32_t> &bits)
-{
-	const size_t W = ((size_t)A + 31) / 32;
-	bits.assign((size_t)G * W, 0);
-	for (int32_t g = 0; g < G; ++g)
-		for (int32_t a = 0; a < A; ++a)
-			if (mat[(size_t)g * A + a] > 0) bits[(size_t)g * W + (size_t)(a >> 5)] |= 1u << (a & 31);
-}
-
 void print_assoc(const std::vector<std::string> &gene, int32_t A, const Result &r)
 {
-	FILE *fp = out_stream();
-	std::string s = "GeneA\tGeneB\tnA\tnB\tnAB\tphi\n";
+	OutBuf ob;
+	std::string &s = ob.s;
+	s = "GeneA\tGeneB\tnA\tnB\tnAB\tphi\n";
 	char b[96];
 	for (int64_t i = 0; i < r.n; ++i) {
 		const int32_t g = r.pair[i * 3], h = r.pair[i * 3 + 1], x = r.pair[i * 3 + 2];
@@ -128,10 +106,9 @@ void print_assoc(const std::vector<std::string> &gene, int32_t A, const Result &
 		s += gene[(size_t)g], s += '\t', s += gene[(size_t)h];
 		std::snprintf(b, sizeof(b), "\t%d\t%d\t%d\t%.4f\n", (int)na, (int)nb, (int)x, phi);
 		s += b;
-		if (s.size() >= (1u << 20)) std::fwrite(s.data(), 1, s.size(), fp), s.clear();
+		ob.flush_if_full();
 	}
-	std::fwrite(s.data(), 1, s.size(), fp);
-	std::fflush(fp);
+	ob.finish();
 }
 
 // PANGENE_ASSOC_TIMING=1: one line on stderr per call
@@ -172,10 +149,10 @@ int pg_assoc_file(const char *gfa_fn, const pg_assoc_opt_t *o)
 {
 	const double t0 = now_sec();
 	GfaMatrix m;
-	if (gfa_matrix(gfa_fn, m) != 0) { std::fprintf(stderr, "Error: cannot open %s\n", gfa_fn ? gfa_fn : "-"); return -1; }
+	if (gfa_matrix(gfa_fn, m) != 0) return cannot_open(gfa_fn);
 	const int32_t A = (int32_t)m.asm_a.size(), G = (int32_t)m.seg.size();
 	std::vector<uint32_t> bits;
-	gene_bits(m.mat.data(), G, A, bits);
+	pack_rows(m.mat.data(), G, A, bits); // the gfa2matrix matrix: gene g is in assembly a when its entry is > 0
 	const int rc = assoc_run("file", m.seg, bits, A, o, t0);
 	if (rc != 0) { std::fprintf(stderr, "Error: pan_assoc: %s\n", backend_default()->strerror(rc)); return -2; }
 	return 0;
@@ -191,7 +168,7 @@ void pg_write_assoc(pg_graph_t *q, const pg_assoc_opt_t *o)
 	gene.reserve((size_t)G);
 	for (int32_t i = 0; i < G; ++i) gene.emplace_back(q->d->gene[q->seg[i].gid].name);
 	std::vector<uint32_t> bits;
-	gene_bits(mat.data(), G, A, bits);
+	pack_rows(mat.data(), G, A, bits);
 	const int rc = assoc_run("memory", gene, bits, A, o, t0);
 	if (rc != 0) set_error(rc, "pg_write_assoc");
 }
@@ -200,7 +177,7 @@ int64_t pg_pan_assoc(const uint8_t *presence, int32_t n_gene, int32_t n_asm, con
 {
 	if (n_gene < 0 || n_asm < 0 || cap < 0 || ((size_t)n_gene * (size_t)n_asm > 0 && presence == nullptr) || (cap > 0 && pair == nullptr)) return PGA_ERR_ARG;
 	std::vector<uint32_t> bits;
-	to_bits(presence, n_gene, n_asm, bits);
+	pack_rows(presence, n_gene, n_asm, bits);
 	Result r;
 	const int rc = assoc_select(bits, n_gene, n_asm, o, r);
 	if (rc != 0) return rc;

@@ -12,27 +12,14 @@
 namespace pgx {
 namespace {
 
-uint64_t mix64(uint64_t z) // splitmix64's output function
-{
-	z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-	z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-	return z ^ (z >> 31);
-}
-
-// order 0: the columns as they are; order p >= 1: Fisher-Yates from the last column down, j = next() % (i + 1)
+// order 0: the columns as they are; order p >= 1: fisher_yates_order
 void make_orders(int32_t A, int32_t n, uint32_t seed, std::vector<int32_t> &ord)
 {
 	ord.resize((size_t)n * (size_t)A);
 	for (int32_t p = 0; p < n; ++p) {
 		int32_t *o = ord.data() + (size_t)p * A;
-		for (int32_t i = 0; i < A; ++i) o[i] = i;
-		if (p == 0) continue;
-		uint64_t x = mix64((uint64_t)seed << 32 | (uint64_t)(uint32_t)p);
-		for (int32_t i = A - 1; i >= 1; --i) {
-			x += 0x9E3779B97F4A7C15ull;
-			const uint64_t j = mix64(x) % (uint64_t)(i + 1);
-			std::swap(o[i], o[j]);
-		}
+		if (p == 0) for (int32_t i = 0; i < A; ++i) o[i] = i;
+		else fisher_yates_order(A, seed, (uint32_t)p, o);
 	}
 }
 
@@ -121,28 +108,18 @@ void put_row(std::string &s, const char *stat, int32_t p, const int32_t *v, int3
 
 void print_curves(const std::vector<int32_t> &out, int32_t A, int32_t n)
 {
-	FILE *fp = out_stream();
-	std::string s = "Stat\tPerm";
+	OutBuf ob;
+	std::string &s = ob.s;
+	s = "Stat\tPerm";
 	for (int32_t i = 1; i <= A; ++i) s += '\t', s += std::to_string(i);
 	s += '\n';
 	static const char *const name[4] = { "pan", "core", "new", "unique" };
 	for (int st = 0; st < 4; ++st)
 		for (int32_t p = 0; p < n; ++p) {
 			put_row(s, name[st], p, out.data() + ((size_t)st * n + p) * A, A);
-			if (s.size() >= (1u << 20)) std::fwrite(s.data(), 1, s.size(), fp), s.clear();
+			ob.flush_if_full();
 		}
-	std::fwrite(s.data(), 1, s.size(), fp);
-	std::fflush(fp);
-}
-
-// matrix entries (int32, > 0 = present) -> bit rows
-void to_bits(const int32_t *mat, int32_t G, int32_t A, std::vector<uint32_t> &bits)
-{
-	const size_t W = ((size_t)A + 31) / 32;
-	bits.assign((size_t)G * W, 0);
-	for (int32_t g = 0; g < G; ++g)
-		for (int32_t a = 0; a < A; ++a)
-			if (mat[(size_t)g * A + a] > 0) bits[(size_t)g * W + (size_t)(a >> 5)] |= 1u << (a & 31);
+	ob.finish();
 }
 
 // PANGENE_CURVES_TIMING=1: one line on stderr per call (tests/run_curves_timing.py reads it)
@@ -156,7 +133,7 @@ void report_time(const char *route, int32_t G, int32_t A, int32_t n, double t_pr
 int curves_run(const char *route, const int32_t *mat, int32_t G, int32_t A, const pg_curves_opt_t *o, double t_start)
 {
 	std::vector<uint32_t> bits;
-	to_bits(mat, G, A, bits);
+	pack_rows(mat, G, A, bits); // matrix entries > 0 = present
 	std::vector<int32_t> out;
 	const double t_prep = now_sec() - t_start;
 	const int rc = curves_count(bits, G, A, o, out);
@@ -184,7 +161,7 @@ int pg_curves_file(const char *gfa_fn, const pg_curves_opt_t *o)
 {
 	const double t0 = now_sec();
 	GfaMatrix m;
-	if (gfa_matrix(gfa_fn, m) != 0) { std::fprintf(stderr, "Error: cannot open %s\n", gfa_fn ? gfa_fn : "-"); return -1; }
+	if (gfa_matrix(gfa_fn, m) != 0) return cannot_open(gfa_fn);
 	const int rc = curves_run("file", m.mat.data(), (int32_t)m.seg.size(), (int32_t)m.asm_a.size(), o, t0);
 	if (rc != 0) { std::fprintf(stderr, "Error: pan_curves: %s\n", backend_default()->strerror(rc)); return -2; }
 	return 0;
@@ -203,11 +180,8 @@ void pg_write_curves(pg_graph_t *q, const pg_curves_opt_t *o)
 int pg_pan_curves(const uint8_t *presence, int32_t n_gene, int32_t n_asm, const pg_curves_opt_t *o, int32_t *out)
 {
 	if (n_gene < 0 || n_asm < 0 || o == nullptr || o->n_perm < 0) return PGA_ERR_ARG;
-	const size_t W = ((size_t)n_asm + 31) / 32;
-	std::vector<uint32_t> bits((size_t)n_gene * W, 0);
-	for (int32_t g = 0; g < n_gene; ++g)
-		for (int32_t a = 0; a < n_asm; ++a)
-			if (presence[(size_t)g * n_asm + a]) bits[(size_t)g * W + (size_t)(a >> 5)] |= 1u << (a & 31);
+	std::vector<uint32_t> bits;
+	pack_rows(presence, n_gene, n_asm, bits);
 	std::vector<int32_t> res;
 	const int rc = curves_count(bits, n_gene, n_asm, o, res);
 	if (rc == 0 && !res.empty()) std::memcpy(out, res.data(), sizeof(int32_t) * res.size());

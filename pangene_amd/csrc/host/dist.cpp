@@ -51,31 +51,7 @@ int shared_count(const std::vector<uint32_t> &bits, int32_t M, int32_t A, int32_
 	return 0;
 }
 
-// presence, row-major [M][A] (nonzero = item m in assembly a), -> assembly-major bit rows
-void presence_bits(const uint8_t *p, int32_t M, int32_t A, std::vector<uint32_t> &bits)
-{
-	const size_t W = ((size_t)M + 31) / 32;
-	bits.assign((size_t)A * W, 0);
-	for (int32_t m = 0; m < M; ++m) {
-		const uint8_t *row = p + (size_t)m * A;
-		const uint32_t bit = 1u << (m & 31);
-		uint32_t *col = bits.data() + (size_t)(m >> 5);
-		for (int32_t a = 0; a < A; ++a)
-			if (row[a]) col[(size_t)a * W] |= bit;
-	}
-}
-
 namespace {
-
-// the gfa2matrix matrix (occurrences, [n_seg][A]): gene g is in assembly a when its entry is > 0
-void gene_bits(const int32_t *mat, int32_t G, int32_t A, std::vector<uint32_t> &bits)
-{
-	const size_t W = ((size_t)G + 31) / 32;
-	bits.assign((size_t)A * W, 0);
-	for (int32_t g = 0; g < G; ++g)
-		for (int32_t a = 0; a < A; ++a)
-			if (mat[(size_t)g * A + a] > 0) bits[(size_t)a * W + (size_t)(g >> 5)] |= 1u << (g & 31);
-}
 
 // walks (steps = segment * 2 + reverse; walk w of assembly walk_asm[w]) -> the adjacencies of each assembly as bit rows; M = the
 // distinct adjacencies.  (u, v) and (v ^ 1, u ^ 1) are the same adjacency read from the other strand; the smaller pair is the key.
@@ -106,7 +82,7 @@ int dist_items_file(const char *gfa_fn, int32_t type, std::vector<std::string> &
 	if (gfa_matrix(gfa_fn, m) != 0) return -1;
 	const int32_t A = (int32_t)m.asm_a.size();
 	if (type == PG_DIST_ADJ) adj_bits(m.step, m.walk_off, m.walk_asm, A, bits, M);
-	else M = (int32_t)m.seg.size(), gene_bits(m.mat.data(), M, A, bits);
+	else M = (int32_t)m.seg.size(), pack_cols(m.mat.data(), M, A, bits); // gene g is in assembly a when its entry is > 0
 	names.swap(m.asm_a);
 	return 0;
 }
@@ -132,7 +108,7 @@ int dist_items_graph(pg_graph_t *q, int32_t type, std::vector<std::string> &name
 		std::vector<int32_t> mat;
 		if (graph_matrix(q, names, mat) != 0) return -1;
 		M = q->n_seg;
-		gene_bits(mat.data(), M, (int32_t)names.size(), bits);
+		pack_cols(mat.data(), M, (int32_t)names.size(), bits);
 	}
 	return 0;
 }
@@ -149,9 +125,9 @@ double metric_of(int32_t metric, int32_t ni, int32_t nj, int32_t s)
 
 void print_dist(const std::vector<std::string> &names, const std::vector<int32_t> &S, const pg_dist_opt_t *o)
 {
-	FILE *fp = out_stream();
 	const int32_t A = (int32_t)names.size();
-	std::string s;
+	OutBuf ob;
+	std::string &s = ob.s;
 	if (o->phylip) s = std::to_string(A), s += '\n';
 	else {
 		s = "Asm";
@@ -169,10 +145,9 @@ void print_dist(const std::vector<std::string> &names, const std::vector<int32_t
 			s += b;
 		}
 		s += '\n';
-		if (s.size() >= (1u << 20)) std::fwrite(s.data(), 1, s.size(), fp), s.clear();
+		ob.flush_if_full();
 	}
-	std::fwrite(s.data(), 1, s.size(), fp);
-	std::fflush(fp);
+	ob.finish();
 }
 
 // PANGENE_DIST_TIMING=1: one line on stderr per call
@@ -215,7 +190,7 @@ int pg_dist_file(const char *gfa_fn, const pg_dist_opt_t *o)
 	std::vector<std::string> names;
 	std::vector<uint32_t> bits;
 	int32_t M;
-	if (dist_items_file(gfa_fn, o->type, names, bits, M) != 0) { std::fprintf(stderr, "Error: cannot open %s\n", gfa_fn ? gfa_fn : "-"); return -1; }
+	if (dist_items_file(gfa_fn, o->type, names, bits, M) != 0) return cannot_open(gfa_fn);
 	const int rc = dist_run("file", names, bits, M, o, t0);
 	if (rc != 0) { std::fprintf(stderr, "Error: pan_shared: %s\n", backend_default()->strerror(rc)); return -2; }
 	return 0;
@@ -236,7 +211,7 @@ int pg_pan_shared(const uint8_t *presence, int32_t n_item, int32_t n_asm, int32_
 {
 	if (n_item < 0 || n_asm < 0 || ((size_t)n_item * (size_t)n_asm > 0 && presence == nullptr) || (n_asm > 0 && shared == nullptr)) return PGA_ERR_ARG;
 	std::vector<uint32_t> bits;
-	presence_bits(presence, n_item, n_asm, bits);
+	pack_cols(presence, n_item, n_asm, bits);
 	return shared_count(bits, n_item, n_asm, shared);
 }
 
@@ -245,7 +220,7 @@ int pg_pan_dist(const uint8_t *presence, int32_t n_item, int32_t n_asm, int32_t 
 	if (metric < PG_DIST_JACCARD || metric > PG_DIST_DIFF) return PGA_ERR_ARG;
 	if (n_item < 0 || n_asm < 0 || ((size_t)n_item * (size_t)n_asm > 0 && presence == nullptr) || (n_asm > 0 && out == nullptr)) return PGA_ERR_ARG;
 	std::vector<uint32_t> bits;
-	presence_bits(presence, n_item, n_asm, bits);
+	pack_cols(presence, n_item, n_asm, bits);
 	const size_t A = (size_t)n_asm;
 	std::vector<int32_t> S(A * A);
 	const int rc = shared_count(bits, n_item, n_asm, S.data());

@@ -231,10 +231,9 @@ int gfa_matrix(const char *fn, GfaMatrix &m);
 
 // what pangene dist and pangene tree read (dist.cpp): the items of every assembly -- its genes (PG_DIST_GENE) or the gene adjacencies of
 // its walks (PG_DIST_ADJ) -- as assembly-major bit rows bits[A][(M + 31) / 32], of a GFA file (-1: it cannot be opened) and of the graph
-// in memory; a row-major presence matrix [M][A] as such rows; S[A][A] of the rows (the backend's pan_shared, or host loops)
+// in memory; a row-major presence matrix [M][A] becomes such rows by pack_cols (pan_common.hpp); S[A][A] of the rows (the backend's pan_shared, or host loops)
 int dist_items_file(const char *gfa_fn, int32_t type, std::vector<std::string> &names, std::vector<uint32_t> &bits, int32_t &M);
 int dist_items_graph(pg_graph_t *q, int32_t type, std::vector<std::string> &names, std::vector<uint32_t> &bits, int32_t &M);
-void presence_bits(const uint8_t *p, int32_t M, int32_t A, std::vector<uint32_t> &bits);
 int shared_count(const std::vector<uint32_t> &bits, int32_t M, int32_t A, int32_t *S);
 // the records of the tree pangene tree prints for such rows (tree.cpp): rec[A - 2][6] (NJ) or rec[A - 1][6] (UPGMA); nothing for A < 3
 int tree_joins(const std::vector<uint32_t> &bits, int32_t M, int32_t A, int32_t metric, int32_t method, int64_t *rec);
@@ -262,3 +261,5 @@ extern double g_phase[PH_COUNT];
 struct Phase { int id; double t0; explicit Phase(int i) : id(i), t0(now_sec()) {} ~Phase() { g_phase[id] += now_sec() - t0; } };
 
 } // namespace pgx
+
+#include "pan_common.hpp"

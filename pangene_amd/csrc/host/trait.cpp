@@ -24,24 +24,11 @@ namespace {
 constexpr int32_t TRAIT_MAX_COL = 16777215, TRAIT_MAX_GENE = 16777215, TRAIT_MAX_PERM = 2147483646;
 constexpr int32_t PAIRS_MAX_LEAF = 65535, PAIRS_DEPTH = 16; // the backend's limits (include/pangene_hip.h pga_pan_pairs)
 
-uint64_t mix64(uint64_t z) // splitmix64's output function (as curves.cpp)
-{
-	z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-	z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-	return z ^ (z >> 31);
-}
-
 // order p >= 1 of N columns: make_orders' sequence (curves.cpp)
 void make_order(int32_t N, uint32_t seed, uint32_t p, std::vector<int32_t> &o)
 {
 	o.resize((size_t)N);
-	for (int32_t i = 0; i < N; ++i) o[(size_t)i] = i;
-	uint64_t x = mix64((uint64_t)seed << 32 | (uint64_t)p);
-	for (int32_t i = N - 1; i >= 1; --i) {
-		x += 0x9E3779B97F4A7C15ull;
-		const uint64_t j = mix64(x) % (uint64_t)(i + 1);
-		std::swap(o[(size_t)i], o[(size_t)j]);
-	}
+	fisher_yates_order(N, seed, p, o.data());
 }
 
 // The backend's step on the host, by the definition: every permutation's label row from its order, every eligible gene's count,
@@ -376,7 +363,9 @@ int trait_run(const char *route, const std::vector<std::string> &gene, const std
 	if (A > TRAIT_MAX_COL) return PGA_ERR_RANGE;
 	const int32_t G = (int32_t)gene.size();
 	t_count = t_pairs = 0;
-	std::string out = "Trait\tGene\tN\tnT\tnG\tnTG\tphi\tp_fisher\tq_bh\tn_ge\tp_perm";
+	OutBuf ob;
+	std::string &out = ob.s;
+	out = "Trait\tGene\tN\tnT\tnG\tnTG\tphi\tp_fisher\tq_bh\tn_ge\tp_perm";
 	out += o->lineage ? "\tpairs\tsupp\topp\tp_pair_best\tp_pair_worst\n" : "\n";
 	char b[160];
 	// -L: the tree of ALL assemblies over the genes (pangene tree -t gene -m jaccard), and the pair counts of every trait that has two
@@ -398,7 +387,7 @@ int trait_run(const char *route, const std::vector<std::string> &gene, const std
 		std::vector<int64_t> rec((size_t)6 * (size_t)std::max(A, 1));
 		const double t0 = now_sec();
 		std::vector<uint32_t> bits;
-		presence_bits(pres.data(), G, A, bits);
+		pack_cols(pres.data(), G, A, bits);
 		int rc = tree_joins(bits, G, A, PG_DIST_JACCARD, method, rec.data());
 		t_tree = now_sec() - t0;
 		if (rc == 0) rc = pairs_count(pres.data(), rows.data(), G, A, (int32_t)(rows.size() / (size_t)std::max(A, 1)), rec.data(), method, pc);
@@ -446,9 +435,7 @@ int trait_run(const char *route, const std::vector<std::string> &gene, const std
 			out += '\n';
 		}
 	}
-	FILE *fp = out_stream();
-	std::fwrite(out.data(), 1, out.size(), fp);
-	std::fflush(fp);
+	ob.finish();
 	report_time(route, G, A, tr.name.size(), o->n_perm, now_sec() - t_start);
 	if (o->lineage) {
 		int32_t rows = 0;
@@ -482,7 +469,7 @@ int pg_trait_file(const char *gfa_fn, const char *trait_fn, const pg_trait_opt_t
 {
 	const double t0 = now_sec();
 	GfaMatrix m;
-	if (gfa_matrix(gfa_fn, m) != 0) { std::fprintf(stderr, "Error: cannot open %s\n", gfa_fn ? gfa_fn : "-"); return -1; }
+	if (gfa_matrix(gfa_fn, m) != 0) return cannot_open(gfa_fn);
 	Traits tr;
 	if (read_traits(trait_fn, m.asm_a, tr) != 0) return -3;
 	std::vector<uint8_t> pres;

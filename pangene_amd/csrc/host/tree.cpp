@@ -140,13 +140,6 @@ int join_run(const int32_t *q, int32_t n, int32_t method, int64_t *rec)
 	return rc;
 }
 
-uint64_t mix64(uint64_t z) // splitmix64's output function (as curves.cpp)
-{
-	z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-	z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-	return z ^ (z >> 31);
-}
-
 // Replicate b of the definition as plain loops: the draws, the resampled rows, shared_count, to_fixed, join_host.  bits[A][W]
 int boot_host(const std::vector<uint32_t> &bits, int32_t M, int32_t A, int32_t metric, int32_t method, uint32_t seed, uint32_t b, int64_t *rec)
 {
@@ -384,16 +377,15 @@ int tree_run(const char *route, const std::vector<std::string> &names, const std
 		t_join += now_sec() - t0;
 	}
 	const double t1 = now_sec();
-	std::string s;
+	OutBuf ob;
+	std::string &s = ob.s;
 	if (A == 0) s = ";\n";
 	else if (A == 1) s = "(" + quoted(names[0]) + ");\n";
 	else if (A == 2) {
 		const std::string h = len_text((double)q[1] / 2.0, F);
 		s = "(" + quoted(names[0]) + h + "," + quoted(names[1]) + h + ");\n";
 	} else s = newick(names, rec.data(), o->method, F, count.data(), o->n_boot);
-	FILE *fp = out_stream();
-	std::fwrite(s.data(), 1, s.size(), fp);
-	std::fflush(fp);
+	ob.finish();
 	report_time(route, M, A, t_prep, now_sec() - t1);
 	return 0;
 }
@@ -426,7 +418,7 @@ int pg_tree_file(const char *gfa_fn, const pg_tree_opt_t *o)
 	std::vector<std::string> names;
 	std::vector<uint32_t> bits;
 	int32_t M;
-	if (dist_items_file(gfa_fn, o->type, names, bits, M) != 0) { std::fprintf(stderr, "Error: cannot open %s\n", gfa_fn ? gfa_fn : "-"); return -1; }
+	if (dist_items_file(gfa_fn, o->type, names, bits, M) != 0) return cannot_open(gfa_fn);
 	const int rc = tree_run("file", names, bits, M, o, t0);
 	if (rc != 0) { std::fprintf(stderr, "Error: pangene tree: %s\n", backend_default()->strerror(rc)); return -2; }
 	return 0;
@@ -450,7 +442,7 @@ int pg_pan_tree(const uint8_t *presence, int32_t n_item, int32_t n_asm, int32_t 
 	if ((metric != PG_DIST_JACCARD && metric != PG_DIST_DIFF) || (method != PG_TREE_NJ && method != PG_TREE_UPGMA)) return PGA_ERR_ARG;
 	if (n_item < 0 || n_asm < 3 || ((size_t)n_item > 0 && presence == nullptr) || rec == nullptr || frac_bits == nullptr) return PGA_ERR_ARG;
 	std::vector<uint32_t> bits;
-	presence_bits(presence, n_item, n_asm, bits);
+	pack_cols(presence, n_item, n_asm, bits);
 	std::vector<int32_t> q;
 	return tree_records(bits, n_item, n_asm, metric, method, q, rec, frac_bits);
 }
@@ -466,7 +458,7 @@ int pg_pan_boot(const uint8_t *presence, int32_t n_item, int32_t n_asm, int32_t 
 {
 	if (!boot_args_ok(presence, n_item, n_asm, metric, method) || n_boot < 0 || rec == nullptr || frac_bits == nullptr || count == nullptr) return PGA_ERR_ARG;
 	std::vector<uint32_t> bits;
-	presence_bits(presence, n_item, n_asm, bits);
+	pack_cols(presence, n_item, n_asm, bits);
 	std::vector<int32_t> q;
 	const int rc = tree_records(bits, n_item, n_asm, metric, method, q, rec, frac_bits);
 	return rc != 0 ? rc : boot_support(bits, n_item, n_asm, metric, method, n_boot, seed, rec, count);
@@ -477,7 +469,7 @@ int pg_pan_boot_records(const uint8_t *presence, int32_t n_item, int32_t n_asm, 
 {
 	if (!boot_args_ok(presence, n_item, n_asm, metric, method) || first < 1 || n < 0 || (int64_t)first + n - 1 > INT32_MAX || (n > 0 && rec_out == nullptr)) return PGA_ERR_ARG;
 	std::vector<uint32_t> bits;
-	presence_bits(presence, n_item, n_asm, bits);
+	pack_cols(presence, n_item, n_asm, bits);
 	const size_t stride = 6 * (size_t)(method == PG_TREE_NJ ? n_asm - 2 : n_asm - 1);
 	int64_t *at = rec_out;
 	return boot_walk(bits, n_item, n_asm, metric, method, seed, first, n, [&](const int64_t *r, int32_t k) {

@@ -3,7 +3,7 @@ bound them with a timeout.  The product library (HIP kernels) runs matrices no G
 the numpy restatement (exact integers) check every one of them completely: the output is sparse, so the full sorted record arrays
 and the phi arrays are compared, never a sample.  Prints one line per case and "ALL OK" at the end; exits 1 at the first difference.
 
-    python tests/support/assoc_direct.py {large|wide|sizes} [--cpu-only]
+    python tests/support/assoc_direct.py {large|wide|sizes|edges} [--cpu-only]
 
 --cpu-only runs the checker build against the restatement alone (to see that the cases stay affordable without a GPU)."""
 import os
@@ -74,6 +74,14 @@ def main():
         assert check(libs, P, "wide", min_phi=0.9, min_count=3) > 0
         P = ar.planted(1000003, 12, 5, n_module=10)  # a million rows, few of them eligible at this count
         check(libs, P, "million rows", min_phi=0.95, min_count=6)
+    elif which == "edges":
+        # the shapes at which the tile body can go wrong: every row count against every row length.  min_count 1 and phi >= 0 select every
+        # pair of rows that are not constant: with eligible rows E is the row count itself, and the matrix of every density has constant
+        # rows among the others
+        for G in ar.EDGE_ROWS:
+            for A in ar.EDGE_COLS:
+                check(libs, ar.edge_rows(G, A, G + A, eligible=A >= 2), "edges, every row eligible", min_phi=0.0, min_count=1)
+                check(libs, ar.edge_rows(G, A, G + A), "edges", min_phi=0.0, min_count=1)
     else:
         # the cached device buffers: growing, shrinking and growing again in one process
         for i, (G, A) in enumerate([(40, 50), (3000, 700), (10, 2), (0, 9), (7, 0), (0, 0), (1, 1), (2, 4), (129, 33), (257, 4097),

@@ -88,6 +88,22 @@ def read_gfa(path):
     return list(seg), P
 
 
+EDGE_ROWS = (1, 127, 128, 129, 257)          # one partial 128-row tile, an exact one, diagonal + off-diagonal tiles, three tile rows
+EDGE_COLS = (1, 991, 1024, 1025, 2070)       # rows of 1, 31, 32, 33 and 65 words: a partial 32-word chunk, an exact one, a second chunk of 1 word and a third
+
+
+def edge_rows(R, C, seed, eligible=False):
+    """(R, C) bool for the shapes at the edges of the 128 x 128 bit tile: row r has a density of its own, cycling through all-zero, all-one,
+    0.03, 0.3, 0.5 and 0.9.  eligible (C >= 2): every row gets a one and a zero, so that none is constant"""
+    rng = np.random.default_rng(seed)
+    dens = np.array([0.0, 1.0, 0.03, 0.3, 0.5, 0.9])[(np.arange(R) + seed) % 6]
+    P = rng.random((R, C)) < dens[:, None]
+    if eligible:
+        r = np.arange(R)
+        P[r, r % C], P[r, (r + 1) % C] = True, False
+    return P
+
+
 def planted(G, A, seed, n_module=6):
     """(G, A) bool with a U-shaped frequency spectrum (most genes nearly core or rare) and planted modules: groups of genes that copy
     one pattern (correlated) or its complement (anti-correlated), a few of them with one assembly flipped"""

@@ -3,7 +3,7 @@ bound them with a timeout.  The product library (HIP kernel) runs matrices no GF
 the numpy restatement check them where that is affordable, invariants and 64 sampled rows where it is not.  Prints one line per case
 and "ALL OK" at the end; exits 1 at the first difference.
 
-    python tests/support/dist_direct.py {large|sizes}"""
+    python tests/support/dist_direct.py {large|sizes|edges}"""
 import os
 import sys
 
@@ -14,6 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import assoc_ref as ar  # noqa: E402
 import dist_ref as dr  # noqa: E402
 
 
@@ -70,6 +71,12 @@ def main():
         check_exact(hip, ora, P, "split K")
         P = presence(5000, 1500, 3)
         check_sampled(capi.pan_shared(hip, torch.from_numpy(P).cuda()), P, "torch cuda tensor")
+    elif which == "edges":
+        # the shapes at which the tile body can go wrong: every row count against every row length, rows of every density in each; at
+        # A <= 128 there is one tile, so the rows of 33 and 65 words run split K in 2 and 3 slices that add into a zeroed S
+        for A in ar.EDGE_ROWS:
+            for M in ar.EDGE_COLS + (33 * 32, 65 * 32):
+                check_exact(hip, ora, ar.edge_rows(A, M, A + M).T, "edges")
     else:
         # the cached device buffers: growing, shrinking and growing again in one process
         for i, (M, A) in enumerate([(40, 50), (3000, 700), (10, 2), (0, 9), (7, 0), (0, 0), (1, 1), (33, 129), (4097, 257),

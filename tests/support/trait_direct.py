@@ -3,7 +3,7 @@ the test can bound them with a timeout.  The product library (HIP kernels) runs 
 restatement (tests/support/trait_ref.py) checks a, s and k of every gene and trait completely, never a sample.  Prints one line per
 case and "ALL OK" at the end; exits 1 at the first difference.
 
-    python tests/support/trait_direct.py {large|batches|sizes|rows} [--cpu-only]
+    python tests/support/trait_direct.py {large|batches|sizes|rows|edges} [--cpu-only]
 
 --cpu-only runs the checker build against the restatement instead (to see that the cases stay affordable without a GPU)."""
 import ctypes as C
@@ -121,6 +121,22 @@ def main():
             lib.pg_trim_host_cache(0)  # gives the buffers back; the next call allocates again
         P = ar.planted(500, 300, 99)
         check(lib, P, labels(P, 9), "after trim", n_perm=100, min_count=3)
+    elif which == "edges":
+        # the shapes at which the tile body can go wrong: every gene count against every row length, 129 permutations in batches of 128,
+        # so that the second batch is one row of a second permutation tile; product and checker build against the restatement
+        import oracle_host
+        ora = oracle_host.load()
+        os.environ["PANGENE_TRAIT_BATCH"] = "128"
+        for A in ar.EDGE_COLS:
+            y = (np.random.default_rng(A).random(A) < 0.4).astype(np.int8)
+            if A > 1:
+                y[0], y[-1] = 1, 0  # both values occur
+            for G in ar.EDGE_ROWS:
+                P = ar.edge_rows(G, A, G + A)
+                want = check(lib, P, y, "edges", n_perm=129, seed=5)
+                got = capi.pan_trait(ora, P, y, n_perm=129, seed=5)
+                assert all(np.array_equal(got[key], want[key]) for key in want), "checker build differs"
+        del os.environ["PANGENE_TRAIT_BATCH"]
     elif which == "rows":
         # the permuted label rows themselves: pins the device's 64-bit %
         assert not cpu_only

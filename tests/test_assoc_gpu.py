@@ -81,7 +81,7 @@ def test_too_many_pairs(built, tmp_path):
     assert rc == 0 and out.count(b"\n") == 7
 
 
-@pytest.mark.parametrize("which", ["large", "wide", "sizes"])
+@pytest.mark.parametrize("which", ["large", "wide", "sizes", "edges"])
 def test_direct_cases(built, which):
     """pg_pan_assoc on matrices no GFA fixture reaches, compared completely with the checker build and the restatement
     (tests/support/assoc_direct.py): G = 20 003 x A = 1 001 with planted modules, the forced second run and a cuda tensor (large);

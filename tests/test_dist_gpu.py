@@ -68,7 +68,7 @@ def test_refused_when_sharded(built):
     assert rc == 1 and out == b"" and b"--dist" in err
 
 
-@pytest.mark.parametrize("which", ["large", "sizes"])
+@pytest.mark.parametrize("which", ["large", "sizes", "edges"])
 def test_direct_cases(built, which):
     """pg_pan_shared on matrices no GFA fixture reaches (A = 12 003, M = 70 001; split K at A = 200) and on a run of growing and
     shrinking sizes that reuse the cached buffers (tests/support/dist_direct.py)"""

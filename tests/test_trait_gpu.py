@@ -91,7 +91,7 @@ def test_refused_when_sharded(built):
     assert rc == 1 and out == b"" and b"--trait" in err
 
 
-@pytest.mark.parametrize("which", ["large", "batches", "sizes", "rows"])
+@pytest.mark.parametrize("which", ["large", "batches", "sizes", "rows", "edges"])
 def test_direct_cases(built, which):
     """pg_pan_trait on matrices no GFA fixture reaches, a, s and k compared completely with the restatement
     (tests/support/trait_direct.py): G = 20 003 x A = 1 001 with planted traits, n = 2 000 (large); n = one batch - 1, one batch, one
