@@ -346,6 +346,42 @@ void pg_write_trait(pg_graph_t *g, const char *trait_fn, const pg_trait_opt_t *o
 int  pg_pan_trait(const uint8_t *presence, const int8_t *labels, int32_t n_gene, int32_t n_asm, int32_t n_trait, const pg_trait_opt_t *o, int32_t *out);
 int  pg_pan_pairs(const uint8_t *presence, const int8_t *labels, int32_t n_gene, int32_t n_asm, int32_t n_trait, const int64_t *rec, int32_t method, int32_t *out);
 
+/* Quantitative traits: which genes go with a continuous phenotype of the assemblies (MIC values, growth rates, host ranges) -- the
+ * Wilcoxon rank-sum (Mann-Whitney) test of the carriers of a gene against the others, with the permutation test of pg_trait_*.
+ * The trait file has the shape pg_trait_* read (same line reader, header, '#' and blank lines, an assembly the file does not name
+ * missing for every trait, the same errors with their line number); a field is NA or empty (missing) or a decimal number that strtod
+ * consumes entirely with a finite result: nan, inf, an overflowing exponent such as 1e999, trailing characters and a bare '-' are errors.
+ * Per trait the columns with a value are compacted, in matrix order, to N columns with values v.  Doubled midrank
+ * r2[c] = 2 #{v < v_c} + #{v == v_c} + 1 (comparison of doubles: -0.0 equals 0.0); centred doubled rank c2[c] = r2[c] - (N + 1), so
+ * sum c2 = 0 and |c2| <= N - 1.  A trait with N < 2 or with all values equal prints a note on stderr and no lines.
+ * For gene g: a = |B_g| over the N columns, D = the sum of c2 over the columns of B_g = R2 - a (N + 1) with R2 the doubled rank sum of
+ * the carriers; g is eligible when min(a, N - a) >= min_count.  Permutation p = 1 .. n_perm is c2_p[r] = c2[o_p[r]], o_p = order p of N
+ * columns exactly as pg_trait_* and pg_curves_* define it (the same swap sequence applied to the value row; seed as there);
+ * D_p = the sum of c2_p over B_g, k_g = #{p : |D_p| >= |D|} -- integers throughout.  On a file of 0s and 1s c2 is N - t for a 1 and
+ * -t for a 0, so D = s N - a t, pg_trait_*'s D, and n_ge and p_perm equal pg_trait_*'s; D changes sign when every value is negated.
+ * Output, tab-separated: "Trait Gene N nG U auc z p_wilcox q_bh n_ge p_perm", one line per eligible gene and trait, traits in file
+ * order, genes in row order: nG = a; U = (D + a (N - a)) / 2, the carriers' Mann-Whitney U, as %.1f (half-integers are exact);
+ * auc = U / (a (N - a)) as %.4f; z = D / sqrt(V) as %.4f with V = a (N - a) / 3 ((N + 1) - T / (N (N - 1))) and T the sum over the
+ * tie groups of t^3 - t -- the tie-corrected normal approximation WITHOUT continuity correction; p_wilcox = erfc(|z| / sqrt 2) as
+ * %.3e; q_bh = Benjamini-Hochberg over the eligible genes of the trait as %.3e; n_ge = k_g; p_perm = (k_g + 1) / (n_perm + 1) as %.6f
+ * (both NA with n_perm = 0).  Only lines with p_wilcox <= max_p are kept (q_bh is over all eligible genes all the same).
+ * At most 32 000 columns with a value per trait (PGA_ERR_RANGE): c2 then splits into two signed bytes and every sum fits int32.
+ * pg_qtrait_file, pg_write_qtrait: as their trait twins, return codes included.  pg_pan_qtrait: any presence matrix, row-major uint8
+ * [n_gene][n_asm], and values, row-major double [n_trait][n_asm] (NaN = missing; an infinite value is PGA_ERR_ARG): fills
+ * out[4][n_trait][n_gene] = N, a, D, k (a = -1, D = k = 0 for a gene that is not eligible, and for every gene of a trait with N < 2 or
+ * one value) and returns 0 or a negative PGA_ERR_*. */
+typedef struct {
+	int32_t  n_perm;    /* permutations; 0: none [1000] */
+	uint32_t seed;      /* seed of the orders [11] */
+	int32_t  min_count; /* a gene is eligible when min(a, N - a) >= min_count; >= 1 [1] */
+	int32_t  reserved;
+	double   max_p;     /* keep the lines with p_wilcox <= max_p [1: all] */
+} pg_qtrait_opt_t;
+void pg_qtrait_opt_init(pg_qtrait_opt_t *o);
+int  pg_qtrait_file(const char *gfa_fn, const char *trait_fn, const pg_qtrait_opt_t *o);
+void pg_write_qtrait(pg_graph_t *g, const char *trait_fn, const pg_qtrait_opt_t *o);
+int  pg_pan_qtrait(const uint8_t *presence, const double *values, int32_t n_gene, int32_t n_asm, int32_t n_trait, const pg_qtrait_opt_t *o, int32_t *out);
+
 /* Last error of the path (0 = none).  The reference aborts on invariant violations; this library
  * records a status instead, prints one line to stderr, and leaves the graph empty. */
 int         pg_last_error(void);

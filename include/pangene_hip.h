@@ -94,7 +94,7 @@ typedef struct {
  * Device layout limits (PGA_ERR_RANGE otherwise): coordinates inside a block < 2^31 (contigs beyond that arrive as virtual contigs,
  * see pga_genome_block_t; what remains out of reach is a single cluster of overlapping hits spanning 2^30 bp), < 2^30 hits and < 2^31
  * exons per shard, < 2^20 genes, < 2^24 genomes. */
-#define PGA_ABI_VERSION 13u  /* bumped whenever a struct of this header or the order of pga_backend_t changes; pga_create refuses another */
+#define PGA_ABI_VERSION 14u  /* bumped whenever a struct of this header or the order of pga_backend_t changes; pga_create refuses another */
 typedef struct {
 	uint32_t abi_version;        /* = PGA_ABI_VERSION of the header the caller was compiled against (PGA_ERR_ARG otherwise) */
 	int32_t n_genome;            /* genomes in this shard (may include genomes with 0 hits) */
@@ -450,6 +450,32 @@ typedef struct {
 typedef struct { const int32_t *out; } pga_pairs_out_t;
 int pga_pan_pairs(const pga_pairs_in_t *in, pga_pairs_out_t *out);
 
+/* Quantitative traits (include/pangene_amd.h pg_pan_qtrait, pangene qtrait; DESIGN.md section 8 "Quantitative traits"): the rank-sum
+ * permutation test of one quantitative trait against every gene.  Context-free, like pan_trait.  Over N = n_col columns (the caller has
+ * already dropped the columns without a value) with c2 the centred doubled midranks of the values (c2 = r2 - (N + 1), sum c2 = 0,
+ * |c2| <= N - 1), a = |B_g| and D = the sum of c2 over the columns of B_g: permutation p = 1 .. n_perm is c2_p[r] = c2[o_p[r]] with o_p
+ * order p of N columns exactly as pan_trait and pan_curves define it (the same swap sequence run over the value row), D_p = the sum of
+ * c2_p over B_g, and k[g] = #{p : |D_p| >= |D|} for an eligible gene (min(a, N - a) >= min_count), 0 for another.  All integers.
+ * In:  bits[n_gene][(n_col + 31) / 32], gene-major as for pan_trait, bits past n_col zero; c2[n_col] int16.  min_count >= 1,
+ *      n_perm >= 0 (PGA_ERR_ARG otherwise).  perm_rows and d_rows: NULL, or -- for tests only -- room for
+ *      min(n_perm, pga_qtrait_batch()) x n_col int16 that receive the permuted rows of the first batch (put together again from the two
+ *      digit planes the count kernel reads), and for min(n_perm, pga_qtrait_batch()) x n_gene int32 that receive that batch's D_p.
+ * Out: a[n_gene], d[n_gene], k[n_gene].  The arrays belong to the backend and stay valid until its next pan_qtrait.
+ * The permutations go through in batches of pga_qtrait_batch() rows, so device memory is bounded by n_gene, n_col and the batch.
+ * Limits (PGA_ERR_RANGE otherwise, before anything is launched): n_col <= 32 000 (c2 = 256 hi + lo with both digits signed bytes, and
+ * |D| <= N (N - 1) / 2 < 2^30: every sum fits int32), n_gene <= 16 777 215, n_perm <= 2^31 - 2. */
+typedef struct {
+	const uint32_t *bits;
+	const int16_t *c2;
+	int32_t n_gene, n_col, min_count, n_perm;
+	uint32_t seed;
+	int16_t *perm_rows;
+	int32_t *d_rows;
+} pga_qtrait_in_t;
+typedef struct { const int32_t *a, *d, *k; } pga_qtrait_out_t;
+int pga_pan_qtrait(const pga_qtrait_in_t *in, pga_qtrait_out_t *out);
+int32_t pga_qtrait_batch(void); /* permutations per batch: 16 384, or PANGENE_QTRAIT_BATCH */
+
 /* the same ABI as a table, so the host driver is written once */
 struct pga_branch_par_s; struct pga_loop_xchg_s;
 typedef struct {
@@ -513,6 +539,7 @@ typedef struct {
 	int  (*pan_join)(const pga_join_in_t *, pga_join_out_t *); /* may be NULL: the host driver then runs the same step itself */
 	int  (*pan_boot)(const pga_boot_in_t *, pga_boot_out_t *); /* may be NULL: the host driver then runs the same step itself */
 	int  (*pan_pairs)(const pga_pairs_in_t *, pga_pairs_out_t *); /* may be NULL: the host driver then runs the same step itself */
+	int  (*pan_qtrait)(const pga_qtrait_in_t *, pga_qtrait_out_t *); /* may be NULL: the host driver then runs the same step itself */
 } pga_backend_t;
 
 const pga_backend_t *pga_backend(void);

@@ -310,6 +310,64 @@ def pan_pairs(lib: C.CDLL, presence, labels, rec, method: str = "nj"):
     return {"pairs": out[0], "supp": out[1], "opp": out[2]}
 
 
+class pg_qtrait_opt_t(C.Structure):
+    """Quantitative-trait options (include/pangene_amd.h): permutations, their seed, smallest min(a, N - a) of a tested gene, p_wilcox cutoff
+    of the lines."""
+    _fields_ = [("n_perm", C.c_int32), ("seed", C.c_uint32), ("min_count", C.c_int32), ("reserved", C.c_int32), ("max_p", C.c_double)]
+
+
+def qtrait_opt(lib: C.CDLL, n_perm: int = 1000, seed: int = 11, min_count: int = 1, max_p: float = 1.0) -> pg_qtrait_opt_t:
+    if not 0 <= int(n_perm) <= TRAIT_MAX_PERM:
+        raise ValueError("n_perm must be in [0, 2^31 - 2]")
+    if int(min_count) < 1:
+        raise ValueError("min_count must be at least 1")
+    o = pg_qtrait_opt_t()
+    lib.pg_qtrait_opt_init(C.byref(o))
+    o.n_perm, o.seed, o.min_count, o.max_p = int(n_perm), int(seed) & 0xFFFFFFFF, int(min_count), float(max_p)
+    return o
+
+
+def pan_qtrait(lib: C.CDLL, presence, values, n_perm: int = 1000, seed: int = 11, min_count: int = 1):
+    """Rank-sum association of a gene x assembly presence matrix (bool numpy array or torch tensor, shape (G, A)) with quantitative
+    traits (values: shape (T, A) or (A,), floating point, NaN = missing) through pg_pan_qtrait: a dict of int32 arrays (T, G): N (columns
+    with a value), a (|B_g|; -1 for a gene that is not tested), D (the sum of the centred doubled midranks over the gene's columns) and
+    k (the permutations of the values with |D_p| >= |D|)."""
+    import numpy as np
+    p = _presence(presence)
+    if hasattr(values, "detach"):  # torch tensor, on any device
+        values = values.detach().cpu().numpy()
+    v = np.asarray(values, dtype=np.float64)
+    if v.ndim == 1:
+        v = v[None, :]
+    G, A = p.shape
+    if v.ndim != 2 or v.shape[1] != A:
+        raise ValueError("values must be (traits x assemblies) over the assemblies of presence")
+    if np.isinf(v).any():
+        raise ValueError("values must be finite or NaN (missing)")
+    v = np.ascontiguousarray(v)
+    T = v.shape[0]
+    o = qtrait_opt(lib, n_perm, seed, min_count)
+    out = np.zeros((4, T, G), dtype=np.int32)
+    rc = lib.pg_pan_qtrait(p.ctypes.data_as(C.POINTER(C.c_uint8)), v.ctypes.data_as(C.POINTER(C.c_double)), G, A, T, C.byref(o), out.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc != 0:
+        raise RuntimeError("pg_pan_qtrait: status %d" % rc)
+    return {"N": out[0], "a": out[1], "D": out[2], "k": out[3]}
+
+
+def _qtrait_args(argv: Sequence[str]):
+    """(file, permutations, seed) of --qtrait=FILE / --qtrait-perm=INT / --qtrait-seed=INT in argv; file = None without --qtrait."""
+    f, n, seed, extra = None, 1000, 11, False
+    for a in argv:
+        if a.startswith("--qtrait="): f = a.split("=", 1)[1]
+        elif a.startswith("--qtrait-perm="): n, extra = int(a.split("=", 1)[1]), True
+        elif a.startswith("--qtrait-seed="): seed, extra = int(a.split("=", 1)[1]), True
+    if not 0 <= n <= TRAIT_MAX_PERM:
+        raise ValueError("--qtrait-perm must be in [0, 2^31 - 2]")
+    if extra and f is None:
+        raise ValueError("--qtrait-perm and --qtrait-seed need --qtrait=FILE")
+    return f, n, seed
+
+
 def _trait_args(argv: Sequence[str]):
     """(file, permutations, seed, lineage) of --trait=FILE / --trait-perm=INT / --trait-seed=INT / --trait-lineage=nj|upgma in argv;
     file = None without --trait."""
@@ -492,6 +550,10 @@ _API = {
     "pg_trait_opt_init": (None, [C.c_void_p]),
     "pg_trait_file": (C.c_int, [C.c_char_p, C.c_char_p, C.c_void_p]),
     "pg_write_trait": (None, [C.c_void_p, C.c_char_p, C.c_void_p]),
+    "pg_qtrait_opt_init": (None, [C.c_void_p]),
+    "pg_qtrait_file": (C.c_int, [C.c_char_p, C.c_char_p, C.c_void_p]),
+    "pg_write_qtrait": (None, [C.c_void_p, C.c_char_p, C.c_void_p]),
+    "pg_pan_qtrait": (C.c_int, [C.POINTER(C.c_uint8), C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]),
     "pg_pan_trait": (C.c_int, [C.POINTER(C.c_uint8), C.POINTER(C.c_int8), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]),
     "pg_pan_pairs": (C.c_int, [C.POINTER(C.c_uint8), C.POINTER(C.c_int8), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int32)]),
     "pg_tree_opt_init": (None, [C.c_void_p]),
@@ -567,7 +629,7 @@ def parse_args(lib: C.CDLL, argv: Sequence[str]) -> pg_opt_t:
         elif a in ("--bed", "--bed=walk"): opt.flag |= PG_F_WRITE_BED_WALK
         elif a == "--bed=raw": opt.flag |= PG_F_WRITE_BED_RAW
         elif a == "--bed=flag": opt.flag |= PG_F_WRITE_BED_FLAG
-        elif a in ("--matrix", "--matrix=presence", "--matrix=count", "--call") or a.startswith("--curves") or a.startswith("--dist") or a.startswith("--assoc") or a.startswith("--trait") or a.startswith("--tree"): pass  # handled by run()
+        elif a in ("--matrix", "--matrix=presence", "--matrix=count", "--call") or a.startswith("--curves") or a.startswith("--dist") or a.startswith("--assoc") or a.startswith("--trait") or a.startswith("--qtrait") or a.startswith("--tree"): pass  # handled by run()
         elif a[:2] in ("-p", "-a", "-f", "-c", "-g", "-r", "-b", "-B", "-y", "-T", "-D", "-C", "-e", "-l", "-m", "-d", "-X", "-I", "-P"):
             v = a[2:] if len(a) > 2 else next(it)
             k = a[1]
@@ -629,6 +691,10 @@ def run(lib: C.CDLL, files: Sequence[str], argv: Sequence[str] = (), scan_only: 
     if tree_type is not None and (any(x.startswith("--matrix") for x in argv) or "--call" in argv or n_curves or dist_type is not None or assoc_phi is not None
                                   or trait_fn is not None):
         raise ValueError("--tree cannot be combined with --matrix, --call, --curves, --dist, --assoc or --trait")
+    qtrait_fn, qtrait_n, qtrait_seed = _qtrait_args(argv)
+    if qtrait_fn is not None and (any(x.startswith("--matrix") for x in argv) or "--call" in argv or n_curves or dist_type is not None or assoc_phi is not None
+                                  or trait_fn is not None or tree_type is not None):
+        raise ValueError("--qtrait cannot be combined with --matrix, --call, --curves, --dist, --assoc, --trait or --tree")
     fd, out = tempfile.mkstemp(prefix="pangene_", suffix=".out")
     os.close(fd)
     lib.pg_set_output(out.encode())
@@ -666,6 +732,10 @@ def run(lib: C.CDLL, files: Sequence[str], argv: Sequence[str] = (), scan_only: 
                     raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
             elif trait_fn is not None:
                 lib.pg_write_trait(g, trait_fn.encode(), C.byref(trait_opt(lib, trait_n, trait_seed, lineage=trait_lineage)))
+                if lib.pg_last_error():
+                    raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
+            elif qtrait_fn is not None:
+                lib.pg_write_qtrait(g, qtrait_fn.encode(), C.byref(qtrait_opt(lib, qtrait_n, qtrait_seed)))
                 if lib.pg_last_error():
                     raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
             elif tree_type is not None:

@@ -63,6 +63,9 @@ static int usage(FILE *fp, const pg_opt_t *opt)
 	std::fprintf(fp, "    --trait-perm=INT  --trait: label permutations [1000]\n");
 	std::fprintf(fp, "    --trait-seed=INT  --trait: seed of the permutations [11]\n");
 	std::fprintf(fp, "    --trait-lineage=STR  --trait: add the pairwise comparisons on the nj or upgma tree of the assemblies (pairs supp opp p_pair_best p_pair_worst)\n");
+	std::fprintf(fp, "    --qtrait=FILE  output the rank-sum association of every gene with the quantitative traits of FILE (assembly, then a number or NA per trait)\n");
+	std::fprintf(fp, "    --qtrait-perm=INT  --qtrait: permutations of the values [1000]\n");
+	std::fprintf(fp, "    --qtrait-seed=INT  --qtrait: seed of the permutations [11]\n");
 	std::fprintf(fp, "    --tree[=STR]  output a tree of the assemblies (Newick) from their gene (gene) or gene-adjacency (adj) distances [gene]\n");
 	std::fprintf(fp, "    --tree-metric=STR  distance of --tree: jaccard or diff [jaccard]\n");
 	std::fprintf(fp, "    --tree-method=STR  --tree: nj (neighbour-joining, unrooted; negative branch lengths are printed as they come) or upgma [nj]\n");
@@ -74,6 +77,7 @@ static int usage(FILE *fp, const pg_opt_t *opt)
 	std::fprintf(fp, "        pangene dist [-t gene|adj] [-m jaccard|shared|diff] [-p] <in.gfa>   (pairwise distances of the assemblies of a GFA file)\n");
 	std::fprintf(fp, "        pangene assoc [-r FLOAT] [-c INT] [-s pos|neg|both] [-x INT] <in.gfa>   (co-occurring and avoiding gene pairs of a GFA file)\n");
 	std::fprintf(fp, "        pangene trait -t FILE [-n INT] [-s INT] [-c INT] [-p FLOAT] <in.gfa>   (gene-trait association over the matrix of a GFA file; -L nj|upgma adds the lineage-aware pairwise comparisons)\n");
+	std::fprintf(fp, "        pangene qtrait -t FILE [-n INT] [-s INT] [-c INT] [-p FLOAT] <in.gfa>   (rank-sum test of every gene against the quantitative traits of a trait file)\n");
 	std::fprintf(fp, "        pangene tree [-t gene|adj] [-m jaccard|diff] [-a nj|upgma] [-b INT] [-s INT] <in.gfa>   (neighbour-joining or UPGMA tree of the assemblies of a GFA file, with bootstrap support)\n");
 	return fp == stdout ? 0 : 1;
 }
@@ -303,6 +307,32 @@ static int main_trait(int argc, char *argv[])
 	return pg_trait_file(argv[optind], fn, &o) == 0 ? 0 : 1;
 }
 
+// `pangene qtrait`: the rank-sum test of every gene of a GFA file against the quantitative traits of a trait file
+static int main_qtrait(int argc, char *argv[])
+{
+	pg_qtrait_opt_t o;
+	pg_qtrait_opt_init(&o);
+	const char *fn = nullptr;
+	int c;
+	while ((c = getopt(argc, argv, "t:n:s:c:p:")) >= 0) {
+		if (c == 't') fn = optarg;
+		else if (c == 'n') { if (!trait_perm(optarg, o.n_perm)) { std::fprintf(stderr, "ERROR: -n must be in [0, 2147483646]\n"); return 1; } }
+		else if (c == 's') o.seed = (uint32_t)std::strtoul(optarg, nullptr, 10);
+		else if (c == 'c') { if ((o.min_count = std::atoi(optarg)) < 1) { std::fprintf(stderr, "ERROR: -c must be at least 1\n"); return 1; } }
+		else if (c == 'p') { char *e; o.max_p = std::strtod(optarg, &e); if (e == optarg || *e != 0 || !(o.max_p >= 0.0)) { std::fprintf(stderr, "ERROR: -p must be a number >= 0\n"); return 1; } }
+		else return 1;
+	}
+	if (argc - optind < 1) {
+		std::printf("Usage: pangene qtrait -t FILE [options] <in.gfa>\nOptions:\n  -t FILE   traits: a header line (any first field, one name per trait), then per line an assembly and a number or NA per trait\n"
+		            "  -n INT    permutations of the values per trait; 0: none [%d]\n  -s INT    seed of the permutations [%u]\n"
+		            "  -c INT    a gene is tested when it is present in >=INT and absent from >=INT assemblies [%d]\n"
+		            "  -p FLOAT  print the genes with p_wilcox <= FLOAT [%g]\n", o.n_perm, o.seed, o.min_count, o.max_p);
+		return 0;
+	}
+	if (fn == nullptr) { std::fprintf(stderr, "ERROR: pangene qtrait needs -t FILE\n"); return 1; }
+	return pg_qtrait_file(argv[optind], fn, &o) == 0 ? 0 : 1;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // `pangene --gpus N`: main.c:117-142 for N devices of one node.  The command forks N - 1 workers BEFORE anything touches the GPU;
 // rank r takes device r and the r-th contiguous block of the PAF files (so that the ranks' W / BED lines, concatenated in rank
@@ -314,6 +344,7 @@ static int main_trait(int argc, char *argv[])
 struct Output { int matrix = 0; bool call = false; int curves = 0; uint32_t curves_seed = 11; int dist = -1, dist_metric = 0; // curves: orders (0: none); dist: PG_DIST_* (-1: none)
 	bool assoc = false; double assoc_phi = 0.8; int assoc_count = 2, assoc_sign = 0;
 	const char *trait = nullptr; int32_t trait_perm = 1000; uint32_t trait_seed = 11; int trait_lineage = 0;
+	const char *qtrait = nullptr; int32_t qtrait_perm = 1000; uint32_t qtrait_seed = 11;
 	int tree = -1, tree_metric = 0, tree_method = 0; int32_t tree_boot = 0; uint32_t tree_seed = 0; }; // tree: PG_DIST_GENE / PG_DIST_ADJ (-1: none)
 
 static int run_path(pg_opt_t &opt, int n_files, char **files, const uint8_t *ids_only, const Output &o, bool graph_lines, bool own_lines, int device = -1)
@@ -371,6 +402,13 @@ static int run_path(pg_opt_t &opt, int n_files, char **files, const uint8_t *ids
 			pg_trait_opt_init(&to);
 			to.n_perm = o.trait_perm, to.seed = o.trait_seed, to.lineage = o.trait_lineage;
 			pg_write_trait(g, o.trait, &to);
+			if (pg_last_error()) rc = 2;
+		}
+		else if (o.qtrait) {
+			pg_qtrait_opt_t qo;
+			pg_qtrait_opt_init(&qo);
+			qo.n_perm = o.qtrait_perm, qo.seed = o.qtrait_seed;
+			pg_write_qtrait(g, o.qtrait, &qo);
 			if (pg_last_error()) rc = 2;
 		}
 		else if (o.tree >= 0) {
@@ -443,6 +481,7 @@ static int run_sharded(pg_opt_t &opt, int W, int n_files, char **files, const Ou
 	if (o.dist >= 0) { std::fprintf(stderr, "ERROR: --dist needs every genome in one process; run it without --gpus\n"); return 1; }
 	if (o.assoc) { std::fprintf(stderr, "ERROR: --assoc needs every genome in one process; run it without --gpus\n"); return 1; }
 	if (o.trait) { std::fprintf(stderr, "ERROR: --trait needs every genome in one process; run it without --gpus\n"); return 1; }
+	if (o.qtrait) { std::fprintf(stderr, "ERROR: --qtrait needs every genome in one process; run it without --gpus\n"); return 1; }
 	if (o.tree >= 0) { std::fprintf(stderr, "ERROR: --tree needs every genome in one process; run it without --gpus\n"); return 1; }
 	const bool dev = pg_backend_is_device() != 0;
 	typedef int (*uid_fn)(void *); typedef int (*init_fn)(int32_t, int32_t, const void *); typedef int (*fin_fn)(void);
@@ -589,6 +628,7 @@ int main(int argc, char *argv[])
 	if (argc >= 2 && std::strcmp(argv[1], "dist") == 0) return main_dist(argc - 1, argv + 1);
 	if (argc >= 2 && std::strcmp(argv[1], "assoc") == 0) return main_assoc(argc - 1, argv + 1);
 	if (argc >= 2 && std::strcmp(argv[1], "trait") == 0) return main_trait(argc - 1, argv + 1);
+	if (argc >= 2 && std::strcmp(argv[1], "qtrait") == 0) return main_qtrait(argc - 1, argv + 1);
 	if (argc >= 2 && std::strcmp(argv[1], "tree") == 0) return main_tree(argc - 1, argv + 1);
 	int matrix = 0, n_gpus = 1; // matrix: 1 presence, 2 counts
 	bool call = false;
@@ -602,6 +642,10 @@ int main(int argc, char *argv[])
 	int32_t trait_perm_v = 1000;
 	uint32_t trait_seed = 11;
 	int trait_lineage_v = 0; // --trait-lineage: PG_LINEAGE_*
+	const char *qtrait = nullptr; // --qtrait=FILE
+	int32_t qtrait_perm_v = 1000;
+	uint32_t qtrait_seed = 11;
+	bool qtrait_extra = false; // a --qtrait-* option was given
 	int tree = -1, tree_metric_v = PG_DIST_JACCARD, tree_method_v = PG_TREE_NJ; // --tree: PG_DIST_GENE / PG_DIST_ADJ (-1: not asked for)
 	int32_t tree_boot_v = 0;
 	uint32_t tree_seed = 0;
@@ -612,6 +656,7 @@ int main(int argc, char *argv[])
 		{ "assoc", optional_argument, nullptr, 310 }, { "assoc-min-count", required_argument, nullptr, 311 }, { "assoc-sign", required_argument, nullptr, 312 },
 		{ "trait", required_argument, nullptr, 313 }, { "trait-perm", required_argument, nullptr, 314 }, { "trait-seed", required_argument, nullptr, 315 },
 		{ "trait-lineage", required_argument, nullptr, 321 },
+		{ "qtrait", required_argument, nullptr, 322 }, { "qtrait-perm", required_argument, nullptr, 323 }, { "qtrait-seed", required_argument, nullptr, 324 },
 		{ "tree", optional_argument, nullptr, 316 }, { "tree-metric", required_argument, nullptr, 317 }, { "tree-method", required_argument, nullptr, 318 },
 		{ "tree-boot", required_argument, nullptr, 319 }, { "tree-seed", required_argument, nullptr, 320 },
 		{ "gpus", required_argument, nullptr, 304 }, { "procs", required_argument, nullptr, 304 },
@@ -705,6 +750,12 @@ int main(int argc, char *argv[])
 		case 321:
 			if ((trait_lineage_v = trait_lineage(optarg)) < 0) { std::fprintf(stderr, "ERROR: --trait-lineage must be nj or upgma\n"); return 1; }
 			break;
+		case 322: qtrait = optarg; break;
+		case 323:
+			qtrait_extra = true;
+			if (!trait_perm(optarg, qtrait_perm_v)) { std::fprintf(stderr, "ERROR: --qtrait-perm must be in [0, 2147483646]\n"); return 1; }
+			break;
+		case 324: qtrait_extra = true, qtrait_seed = (uint32_t)std::strtoul(optarg, nullptr, 10); break;
 		case 401: std::puts(PG_VERSION); return 0;
 		default: break;
 		}
@@ -716,7 +767,10 @@ int main(int argc, char *argv[])
 	if (trait && (matrix || call || curves || dist >= 0 || assoc)) { std::fprintf(stderr, "ERROR: --trait cannot be combined with --matrix, --call, --curves, --dist or --assoc\n"); return 1; }
 	if (trait_lineage_v && !trait) { std::fprintf(stderr, "ERROR: --trait-lineage needs --trait=FILE\n"); return 1; }
 	if (tree >= 0 && (matrix || call || curves || dist >= 0 || assoc || trait)) { std::fprintf(stderr, "ERROR: --tree cannot be combined with --matrix, --call, --curves, --dist, --assoc or --trait\n"); return 1; }
+	if (qtrait && (matrix || call || curves || dist >= 0 || assoc || trait || tree >= 0)) { std::fprintf(stderr, "ERROR: --qtrait cannot be combined with --matrix, --call, --curves, --dist, --assoc, --trait or --tree\n"); return 1; }
+	if (qtrait_extra && !qtrait) { std::fprintf(stderr, "ERROR: --qtrait-perm and --qtrait-seed need --qtrait=FILE\n"); return 1; }
 	Output o;
+	o.qtrait = qtrait, o.qtrait_perm = qtrait_perm_v, o.qtrait_seed = qtrait_seed;
 	o.tree = tree, o.tree_metric = tree_metric_v, o.tree_method = tree_method_v, o.tree_boot = tree_boot_v, o.tree_seed = tree_seed;
 	o.trait = trait, o.trait_perm = trait_perm_v, o.trait_seed = trait_seed, o.trait_lineage = trait_lineage_v;
 	o.assoc = assoc, o.assoc_phi = assoc_phi_v, o.assoc_count = assoc_count, o.assoc_sign = assoc_sign_v;

@@ -8,7 +8,7 @@
 
 constexpr int PAN_MAX_DEV = 16, PAN_MAX_HOST = 3; // buffers a pool has room for
 
-enum PanEntry { PAN_CURVES, PAN_DIST, PAN_ASSOC, PAN_TRAIT, PAN_JOIN, PAN_BOOT, PAN_PAIRS, PAN_N_ENTRY };
+enum PanEntry { PAN_CURVES, PAN_DIST, PAN_ASSOC, PAN_TRAIT, PAN_JOIN, PAN_BOOT, PAN_PAIRS, PAN_QTRAIT, PAN_N_ENTRY };
 
 namespace {
 struct PanDev {
@@ -54,7 +54,8 @@ struct PanDev {
 		for (int i = 0; i < PAN_MAX_HOST; ++i) { if (host[i]) (void)hipHostFree(host[i]); host[i] = nullptr, host_cap[i] = 0; }
 	}
 };
-PanDev g_pan[PAN_N_ENTRY] = {{"pga_pan_curves"}, {"pga_pan_shared"}, {"pga_pan_assoc"}, {"pga_pan_trait"}, {"pga_pan_join"}, {"pga_pan_boot"}, {"pga_pan_pairs"}};
+PanDev g_pan[PAN_N_ENTRY] = {{"pga_pan_curves"}, {"pga_pan_shared"}, {"pga_pan_assoc"}, {"pga_pan_trait"}, {"pga_pan_join"}, {"pga_pan_boot"}, {"pga_pan_pairs"},
+                            {"pga_pan_qtrait"}};
 }
 
 static void pan_release_all()

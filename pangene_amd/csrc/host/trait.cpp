@@ -8,6 +8,11 @@
 // assemblies comes from tree.cpp; per gene and trait the largest set of contrasting leaf pairs on vertex-disjoint paths and its most
 // supporting and most opposing pairs come from the backend (pga_pan_pairs: the tree compiled into a postfix program, one lane per gene), or
 // from the plain loops over the records below; the two binomial p values are computed here, by code both builds share.
+// Quantitative traits (pg_qtrait_file, pg_write_qtrait, pg_pan_qtrait; DESIGN.md section 8 "Quantitative traits"): the same file shape with
+// numbers for values; per trait the centred doubled midranks c2 of the columns with a value, per gene a and D = the sum of c2 over its
+// columns, and the permutation counts k_g from the backend (pga_pan_qtrait: the permuted value rows as two signed-byte planes, D_p of
+// every gene and permutation as an int8 matrix product) or from the plain loops below; U, auc, z, p_wilcox and q_bh are computed here,
+// by code both builds share.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -294,6 +299,7 @@ double binom_two_sided(const std::vector<double> &lf, int32_t k, int32_t n)
 }
 
 struct Traits { std::vector<std::string> name; std::vector<int8_t> lab; }; // lab[T][A]
+struct QTraits { std::vector<std::string> name; std::vector<double> val; }; // val[T][A], NaN = missing
 
 std::vector<std::string> split_tab(const std::string &s)
 {
@@ -308,16 +314,18 @@ std::vector<std::string> split_tab(const std::string &s)
 	return f;
 }
 
-// 0, or -1 with a message (the line number in it) on stderr
-int read_traits(const char *fn, const std::vector<std::string> &asm_name, Traits &tr)
+// The walk over a trait file both commands share: start(T) once the header is read, then field(trait, assembly, text) for every value,
+// false for one that is not `what`.  0, or -1 with a message (the line number in it) on stderr
+template <class Start, class Field>
+int read_trait_file(const char *fn, const std::vector<std::string> &asm_name, std::vector<std::string> &name, const char *what, Start start, Field field)
 {
 	std::vector<std::string> lines;
 	if (fn == nullptr || read_lines(fn, lines) != 0) { std::fprintf(stderr, "Error: cannot open trait file %s\n", fn ? fn : "(null)"); return -1; }
 	if (lines.empty()) { std::fprintf(stderr, "Error: %s: line 1: no header line\n", fn); return -1; }
 	const std::vector<std::string> h = split_tab(lines[0]);
 	const size_t T = h.size() - 1, A = asm_name.size();
-	tr.name.assign(h.begin() + 1, h.end());
-	tr.lab.assign(T * A, (int8_t)-1);
+	name.assign(h.begin() + 1, h.end());
+	start(T);
 	std::unordered_map<std::string, int32_t> at;
 	for (size_t i = 0; i < A; ++i) at.emplace(asm_name[i], (int32_t)i);
 	std::vector<uint8_t> seen(A, 0);
@@ -330,15 +338,56 @@ int read_traits(const char *fn, const std::vector<std::string> &asm_name, Traits
 		if (it == at.end()) { std::fprintf(stderr, "Error: %s: line %zu: no assembly named %s\n", fn, ln + 1, f[0].c_str()); return -1; }
 		if (seen[(size_t)it->second]) { std::fprintf(stderr, "Error: %s: line %zu: assembly %s is named twice\n", fn, ln + 1, f[0].c_str()); return -1; }
 		seen[(size_t)it->second] = 1;
-		for (size_t j = 0; j < T; ++j) {
-			const std::string &v = f[j + 1];
-			int8_t x;
-			if (v == "1") x = 1; else if (v == "0") x = 0; else if (v == "NA" || v.empty()) x = -1;
-			else { std::fprintf(stderr, "Error: %s: line %zu: value %s is not 1, 0 or NA\n", fn, ln + 1, v.c_str()); return -1; }
-			tr.lab[j * A + (size_t)it->second] = x;
-		}
+		for (size_t j = 0; j < T; ++j)
+			if (!field(j, (size_t)it->second, f[j + 1])) { std::fprintf(stderr, "Error: %s: line %zu: value %s is not %s\n", fn, ln + 1, f[j + 1].c_str(), what); return -1; }
 	}
 	return 0;
+}
+
+int read_traits(const char *fn, const std::vector<std::string> &asm_name, Traits &tr)
+{
+	const size_t A = asm_name.size();
+	return read_trait_file(fn, asm_name, tr.name, "1, 0 or NA", [&](size_t T) { tr.lab.assign(T * A, (int8_t)-1); },
+	                       [&](size_t j, size_t c, const std::string &v) {
+		                       int8_t x;
+		                       if (v == "1") x = 1; else if (v == "0") x = 0; else if (v == "NA" || v.empty()) x = -1; else return false;
+		                       tr.lab[j * A + c] = x;
+		                       return true;
+	                       });
+}
+
+// NA or empty: missing (NaN); otherwise a number strtod consumes entirely, with a finite result
+bool qtrait_value(const std::string &v, double &x)
+{
+	x = std::nan("");
+	if (v.empty() || v == "NA") return true;
+	char *e;
+	const double y = std::strtod(v.c_str(), &e);
+	if (e != v.c_str() + v.size() || !std::isfinite(y)) return false;
+	x = y;
+	return true;
+}
+
+int read_qtraits(const char *fn, const std::vector<std::string> &asm_name, QTraits &tr)
+{
+	const size_t A = asm_name.size();
+	return read_trait_file(fn, asm_name, tr.name, "a finite number or NA", [&](size_t T) { tr.val.assign(T * A, std::nan("")); },
+	                       [&](size_t j, size_t c, const std::string &v) { return qtrait_value(v, tr.val[j * A + c]); });
+}
+
+// Benjamini-Hochberg q of p (in row order): sorted ascending, ties by row; q_(i) = min over j >= i of p_(j) m / j, capped at 1
+void bh_q(const std::vector<double> &p, std::vector<double> &q)
+{
+	const size_t m = p.size();
+	q.assign(m, 0.0);
+	std::vector<size_t> idx(m);
+	std::iota(idx.begin(), idx.end(), (size_t)0);
+	std::stable_sort(idx.begin(), idx.end(), [&](size_t x, size_t y) { return p[x] < p[y]; }); // ties by row
+	double run = 1.0;
+	for (size_t j = m; j >= 1; --j) {
+		run = std::min(run, p[idx[j - 1]] * (double)m / (double)j);
+		q[idx[j - 1]] = run;
+	}
 }
 
 // PANGENE_TRAIT_TIMING=1: one line on stderr per call
@@ -404,16 +453,9 @@ int trait_run(const char *route, const std::vector<std::string> &gene, const std
 		std::vector<int32_t> el;
 		for (int32_t g = 0; g < G; ++g) if (r.elig[(size_t)g]) el.push_back(g);
 		const size_t m = el.size();
-		std::vector<double> pf(m), q(m);
+		std::vector<double> pf(m), q;
 		for (size_t e = 0; e < m; ++e) pf[e] = fisher(lf, N, t, r.a[(size_t)el[e]], r.s[(size_t)el[e]]);
-		std::vector<size_t> idx(m);
-		std::iota(idx.begin(), idx.end(), (size_t)0);
-		std::stable_sort(idx.begin(), idx.end(), [&](size_t x, size_t y) { return pf[x] < pf[y]; }); // ties by row
-		double run = 1.0;
-		for (size_t j = m; j >= 1; --j) {
-			run = std::min(run, pf[idx[j - 1]] * (double)m / (double)j);
-			q[idx[j - 1]] = run;
-		}
+		bh_q(pf, q);
 		for (size_t e = 0; e < m; ++e) {
 			if (!(pf[e] <= o->max_p)) continue;
 			const int32_t g = el[e];
@@ -442,6 +484,158 @@ int trait_run(const char *route, const std::vector<std::string> &gene, const std
 		for (const int32_t r : row_of) rows += r >= 0;
 		report_lineage_time(rows, t_tree);
 	}
+	return 0;
+}
+
+// ---- quantitative traits ----
+
+constexpr int32_t QTRAIT_MAX_COL = 32000; // the backend's limit (include/pangene_hip.h pga_pan_qtrait): |c2| <= 31 999 is two signed bytes
+
+// The centred doubled midranks of v[N]: r2[c] = 2 #{v < v_c} + #{v == v_c} + 1, c2 = r2 - (N + 1); returns T = the sum over the tie
+// groups of t^3 - t.  Doubles are compared as doubles, so -0.0 and 0.0 tie.
+int64_t qtrait_ranks(const std::vector<double> &v, std::vector<int16_t> &c2)
+{
+	const int32_t N = (int32_t)v.size();
+	c2.assign((size_t)N, 0);
+	std::vector<int32_t> idx((size_t)N);
+	std::iota(idx.begin(), idx.end(), 0);
+	std::sort(idx.begin(), idx.end(), [&](int32_t x, int32_t y) { return v[(size_t)x] < v[(size_t)y]; });
+	int64_t T = 0;
+	for (int32_t b = 0; b < N;) {
+		int32_t e = b + 1;
+		while (e < N && v[(size_t)idx[(size_t)e]] == v[(size_t)idx[(size_t)b]]) ++e;
+		const int64_t t = e - b;
+		T += t * t * t - t;
+		for (int32_t i = b; i < e; ++i) c2[(size_t)idx[(size_t)i]] = (int16_t)(2 * b + (e - b) + 1 - (N + 1));
+		b = e;
+	}
+	return T;
+}
+
+// The backend's step on the host, by the definition: every permutation's value row from its order by indexing, every eligible gene's sum
+// over its set bits, |D_p| >= |D|.  bits[G][W], c2[N]
+void qtrait_host(const uint32_t *bits, const int16_t *c2, int32_t G, int32_t N, int32_t W, int32_t min_count, int32_t n, uint32_t seed,
+                 std::vector<int32_t> &a, std::vector<int32_t> &d, std::vector<int32_t> &k)
+{
+	a.assign((size_t)G, 0), d.assign((size_t)G, 0), k.assign((size_t)G, 0);
+	auto row_sum = [&](const uint32_t *b, const int16_t *val) {
+		int64_t sum = 0;
+		for (int32_t w = 0; w < W; ++w)
+			for (uint32_t x = b[w]; x; x &= x - 1) sum += val[w * 32 + __builtin_ctz(x)];
+		return sum;
+	};
+	std::vector<int32_t> el;
+	for (int32_t g = 0; g < G; ++g) {
+		const uint32_t *b = bits + (size_t)g * W;
+		int32_t ca = 0;
+		for (int32_t w = 0; w < W; ++w) ca += __builtin_popcount(b[w]);
+		a[(size_t)g] = ca, d[(size_t)g] = (int32_t)row_sum(b, c2);
+		if (std::min(ca, N - ca) >= min_count) el.push_back(g);
+	}
+	std::vector<int32_t> o;
+	std::vector<int16_t> cp((size_t)N);
+	for (int32_t p = 1; p <= n && !el.empty(); ++p) {
+		make_order(N, seed, (uint32_t)p, o);
+		for (int32_t r = 0; r < N; ++r) cp[(size_t)r] = c2[o[(size_t)r]];
+		for (const int32_t g : el)
+			if (std::llabs(row_sum(bits + (size_t)g * W, cp.data())) >= std::llabs((int64_t)d[(size_t)g])) ++k[(size_t)g];
+	}
+}
+
+bool qopt_ok(const pg_qtrait_opt_t *o)
+{
+	return o != nullptr && o->n_perm >= 0 && o->n_perm <= TRAIT_MAX_PERM && o->min_count >= 1 && o->max_p == o->max_p;
+}
+
+// One trait over a presence matrix pres[G][A] (nonzero = present) and values val[A] (NaN = missing).  flat: N < 2 or one value only
+struct QOne { int32_t N = 0; int64_t T = 0; bool flat = true; std::vector<int32_t> a, d, k; std::vector<uint8_t> elig; };
+
+int qtrait_one(const uint8_t *pres, const double *val, int32_t G, int32_t A, const pg_qtrait_opt_t *o, QOne &r)
+{
+	std::vector<int32_t> col;
+	std::vector<double> v;
+	for (int32_t c = 0; c < A; ++c) {
+		if (val[c] != val[c]) continue;
+		if (!std::isfinite(val[c])) return PGA_ERR_ARG;
+		col.push_back(c), v.push_back(val[c]);
+	}
+	const int32_t N = (int32_t)col.size(), W = (N + 31) / 32;
+	r.N = N, r.T = 0, r.flat = true;
+	r.a.assign((size_t)G, 0), r.d.assign((size_t)G, 0), r.k.assign((size_t)G, 0), r.elig.assign((size_t)G, 0);
+	if (N > QTRAIT_MAX_COL) return PGA_ERR_RANGE;
+	if (G > TRAIT_MAX_GENE) return PGA_ERR_RANGE;
+	for (int32_t i = 1; i < N; ++i) if (v[(size_t)i] != v[0]) r.flat = false;
+	if (r.flat) return 0; // nothing to test
+	std::vector<int16_t> c2;
+	r.T = qtrait_ranks(v, c2);
+	std::vector<uint32_t> bits((size_t)G * W, 0);
+	for (int32_t g = 0; g < G; ++g) {
+		const uint8_t *row = pres + (size_t)g * A;
+		uint32_t *b = bits.data() + (size_t)g * W;
+		for (int32_t i = 0; i < N; ++i) if (row[col[(size_t)i]]) b[i >> 5] |= 1u << (i & 31);
+	}
+	const double t0 = now_sec();
+	const pga_backend_t *be = backend_default();
+	int rc = 0;
+	if (be->pan_qtrait != nullptr) {
+		const pga_qtrait_in_t in{bits.data(), c2.data(), G, N, o->min_count, o->n_perm, o->seed, nullptr, nullptr};
+		pga_qtrait_out_t res{};
+		rc = be->pan_qtrait(&in, &res);
+		if (rc == 0) r.a.assign(res.a, res.a + (size_t)G), r.d.assign(res.d, res.d + (size_t)G), r.k.assign(res.k, res.k + (size_t)G);
+	} else qtrait_host(bits.data(), c2.data(), G, N, W, o->min_count, o->n_perm, o->seed, r.a, r.d, r.k);
+	t_count += now_sec() - t0;
+	if (rc != 0) return rc;
+	for (int32_t g = 0; g < G; ++g) r.elig[(size_t)g] = std::min(r.a[(size_t)g], N - r.a[(size_t)g]) >= o->min_count;
+	return 0;
+}
+
+// every trait of tr over pres[G][A]: counts, statistics, lines.  0 or a PGA_ERR_* code; nothing is written unless every trait went through.
+// z is the tie-corrected normal approximation of the rank sum WITHOUT continuity correction.
+int qtrait_run(const char *route, const std::vector<std::string> &gene, const std::vector<uint8_t> &pres, int32_t A, const QTraits &tr, const pg_qtrait_opt_t *o,
+               double t_start)
+{
+	if (!qopt_ok(o)) return PGA_ERR_ARG;
+	const int32_t G = (int32_t)gene.size();
+	t_count = 0;
+	OutBuf ob;
+	std::string &out = ob.s;
+	out = "Trait\tGene\tN\tnG\tU\tauc\tz\tp_wilcox\tq_bh\tn_ge\tp_perm\n";
+	char b[200];
+	for (size_t ti = 0; ti < tr.name.size(); ++ti) {
+		QOne r;
+		const int rc = qtrait_one(pres.data(), tr.val.data() + ti * (size_t)A, G, A, o, r);
+		if (rc != 0) return rc;
+		const int32_t N = r.N;
+		if (r.flat) { std::fprintf(stderr, "Note: trait %s has %s over its %d assemblies; skipped\n", tr.name[ti].c_str(), N < 2 ? "no two values" : "one value", N); continue; }
+		std::vector<int32_t> el;
+		for (int32_t g = 0; g < G; ++g) if (r.elig[(size_t)g]) el.push_back(g);
+		const size_t m = el.size();
+		const double tie = (double)(N + 1) - (double)r.T / ((double)N * (double)(N - 1));
+		std::vector<double> z(m), pw(m), q;
+		for (size_t e = 0; e < m; ++e) {
+			const int64_t a = r.a[(size_t)el[e]];
+			const double V = (double)(a * (N - a)) / 3.0 * tie;
+			z[e] = (double)r.d[(size_t)el[e]] / std::sqrt(V);
+			pw[e] = std::erfc(std::fabs(z[e]) / std::sqrt(2.0));
+		}
+		bh_q(pw, q);
+		for (size_t e = 0; e < m; ++e) {
+			if (!(pw[e] <= o->max_p)) continue;
+			const int32_t g = el[e];
+			const int64_t a = r.a[(size_t)g], D = r.d[(size_t)g], ab = a * (N - a);
+			const double U = (double)(D + ab) * 0.5;
+			out += tr.name[ti], out += '\t', out += gene[(size_t)g];
+			std::snprintf(b, sizeof(b), "\t%d\t%d\t%.1f\t%.4f\t%.4f\t%.3e\t%.3e\t", N, (int)a, U, U / (double)ab, z[e], pw[e], q[e]);
+			out += b;
+			if (o->n_perm > 0) std::snprintf(b, sizeof(b), "%d\t%.6f", r.k[(size_t)g], ((double)r.k[(size_t)g] + 1.0) / ((double)o->n_perm + 1.0));
+			else std::snprintf(b, sizeof(b), "NA\tNA");
+			out += b, out += '\n';
+		}
+	}
+	ob.finish();
+	if (std::getenv("PANGENE_TRAIT_TIMING") != nullptr)
+		std::fprintf(stderr, "[qtrait-timing] route=%s genes=%d assemblies=%d traits=%zu perms=%d count_ms=%.3f all_ms=%.3f\n", route, G, A, tr.name.size(), o->n_perm,
+		             t_count * 1e3, (now_sec() - t_start) * 1e3);
 	return 0;
 }
 
@@ -527,6 +721,62 @@ int pg_pan_pairs(const uint8_t *presence, const int8_t *labels, int32_t n_gene, 
 	if (rc != 0) return rc;
 	const size_t plane = (size_t)n_trait * (size_t)n_gene;
 	for (size_t i = 0; i < plane; ++i) out[i] = pc[3 * i], out[plane + i] = pc[3 * i + 1], out[2 * plane + i] = pc[3 * i + 2];
+	return 0;
+}
+
+void pg_qtrait_opt_init(pg_qtrait_opt_t *o)
+{
+	std::memset(o, 0, sizeof(*o));
+	o->n_perm = 1000, o->seed = 11, o->min_count = 1, o->max_p = 1.0;
+}
+
+int pg_qtrait_file(const char *gfa_fn, const char *trait_fn, const pg_qtrait_opt_t *o)
+{
+	const double t0 = now_sec();
+	GfaMatrix m;
+	if (gfa_matrix(gfa_fn, m) != 0) return cannot_open(gfa_fn);
+	QTraits tr;
+	if (read_qtraits(trait_fn, m.asm_a, tr) != 0) return -3;
+	std::vector<uint8_t> pres;
+	to_presence(m.mat.data(), m.mat.size(), pres);
+	const int rc = qtrait_run("file", m.seg, pres, (int32_t)m.asm_a.size(), tr, o, t0);
+	if (rc != 0) { std::fprintf(stderr, "Error: pan_qtrait: %s\n", backend_default()->strerror(rc)); return -2; }
+	return 0;
+}
+
+void pg_write_qtrait(pg_graph_t *q, const char *trait_fn, const pg_qtrait_opt_t *o)
+{
+	const double t0 = now_sec();
+	std::vector<std::string> names, gene;
+	std::vector<int32_t> mat;
+	if (graph_matrix(q, names, mat) != 0) return;
+	QTraits tr;
+	if (read_qtraits(trait_fn, names, tr) != 0) { set_error(PGA_ERR_ARG, "pg_write_qtrait: bad trait file"); return; }
+	const int32_t G = q->n_seg;
+	gene.reserve((size_t)G);
+	for (int32_t i = 0; i < G; ++i) gene.emplace_back(q->d->gene[q->seg[i].gid].name);
+	std::vector<uint8_t> pres;
+	to_presence(mat.data(), mat.size(), pres);
+	const int rc = qtrait_run("memory", gene, pres, (int32_t)names.size(), tr, o, t0);
+	if (rc != 0) set_error(rc, "pg_write_qtrait");
+}
+
+int pg_pan_qtrait(const uint8_t *presence, const double *values, int32_t n_gene, int32_t n_asm, int32_t n_trait, const pg_qtrait_opt_t *o, int32_t *out)
+{
+	if (n_gene < 0 || n_asm < 0 || n_trait < 0 || !qopt_ok(o)) return PGA_ERR_ARG;
+	if (((size_t)n_gene * (size_t)n_asm > 0 && presence == nullptr) || ((size_t)n_trait * (size_t)n_asm > 0 && values == nullptr)) return PGA_ERR_ARG;
+	if ((size_t)n_trait * (size_t)n_gene > 0 && out == nullptr) return PGA_ERR_ARG;
+	const size_t G = (size_t)n_gene, plane = (size_t)n_trait * G;
+	for (int32_t ti = 0; ti < n_trait; ++ti) {
+		QOne r;
+		const int rc = qtrait_one(presence, values + (size_t)ti * (size_t)n_asm, n_gene, n_asm, o, r);
+		if (rc != 0) return rc;
+		int32_t *p = out + (size_t)ti * G;
+		for (size_t g = 0; g < G; ++g) {
+			const bool e = r.elig[g] != 0;
+			p[g] = r.N, p[plane + g] = e ? r.a[g] : -1, p[2 * plane + g] = e ? r.d[g] : 0, p[3 * plane + g] = e ? r.k[g] : 0;
+		}
+	}
 	return 0;
 }
 
