@@ -274,6 +274,46 @@ int  pg_pan_boot(const uint8_t *presence, int32_t n_item, int32_t n_asm, int32_t
 int  pg_pan_boot_records(const uint8_t *presence, int32_t n_item, int32_t n_asm, int32_t metric, int32_t method, uint32_t seed, int32_t first, int32_t n,
                          int64_t *rec_out);
 
+/* Clusters of the assemblies: k-medoids (PAM) over the fixed-point distances of pg_tree_* (DESIGN.md section 8 "Clusters" holds the
+ * definition; jaccard or diff, shared is refused).  With TD(M) the sum over the assemblies of their distance to the nearest medoid of M:
+ * BUILD picks k medoids one by one, each the assembly that lowers TD the most (ties to the smallest index); SWAP then exchanges, at most
+ * max_iter times, the pair (x not a medoid, m a medoid) with the smallest TD(M - m + x) - TD(M), ties to the smallest x and then the
+ * smallest m, and stops -- converged -- when no exchange lowers TD.  Integers throughout.  The medoids in ascending order are clusters
+ * 0 .. k - 1 (printed 1 .. k); a medoid belongs to its own cluster, any other assembly to the medoid with the smallest (distance, index).
+ * The silhouette of assembly o of cluster c comes from sums[o][c'] = the sum of its distances to the members of c': a = sums[o][c] /
+ * (size_c - 1), b = the smallest sums[o][c'] / size_c' over c' != c (compared by cross-multiplication, the first of equal ones),
+ * s = (b - a) / max(a, b) as one double division of the cross-products; 0 in a cluster of one and where a = b = 0.  A mean silhouette is
+ * the sum in assembly order, in double, over the count.  k_lo .. k_hi are run independently; the assignment is printed for the k with the
+ * largest mean silhouette, ties to the smallest k.
+ * Output, tab-separated, three blocks, each behind a header line that starts with '#':
+ *   K  k TD mean_sil swaps converged        one line per k of the range
+ *   C  cluster medoid size mean_sil         the chosen k, clusters 1 .. k, medoid = the assembly's name
+ *   A  assembly cluster medoid dist sil     the assemblies in gfa2matrix order
+ * TD and dist in distance units as %.6f, silhouettes as %.4f.  A k that does not converge within max_iter: a note on stderr, converged 0.
+ * Fewer than 3 assemblies, or a k outside [2, assemblies - 1]: an error, nothing is printed.
+ * pg_cluster_file: a GFA file (0, -1 when it cannot be opened, -2 on any other error); pg_write_cluster: the graph in memory after
+ * pg_graph_gen (pg_last_error() is PGA_ERR_ARG, -3, after such a refusal, and the command line then exits with status 1 as it does for
+ * a file).  pg_pan_medoids: q = int32 [n][n], symmetric, zero diagonal, no negative entry (PGA_ERR_ARG otherwise), every entry below
+ * 2^29 (PGA_ERR_RANGE), 3 <= n <= 65 535, 2 <= k <= min(n - 1, 1 024), max_iter >= 0; fills medoid[k], label[n], dist[n], size[k],
+ * sums[n][k], td, n_swap, converged and the first rec_cap of the *n_rec = k + n_swap records rec[.][3]: BUILD's (x, -1, gain), then the
+ * swaps' (x, m, delta).  pg_pan_cluster: a presence matrix, row-major uint8 [n_item][n_asm], through the shared-item counts and the
+ * fixed-point distances (*frac_bits = F) to the same results.  Both return 0 or PGA_ERR_*.  The runs come from the backend's
+ * pga_pan_medoids. */
+typedef struct {
+	int32_t type;     /* PG_DIST_GENE or PG_DIST_ADJ [gene] */
+	int32_t metric;   /* PG_DIST_JACCARD or PG_DIST_DIFF [jaccard] */
+	int32_t k_lo;     /* the smallest k of the range, >= 2 [2] */
+	int32_t k_hi;     /* the largest, >= k_lo [2] */
+	int32_t max_iter; /* swap iterations per k at the most [1000] */
+} pg_cluster_opt_t;
+void pg_cluster_opt_init(pg_cluster_opt_t *o);
+int  pg_cluster_file(const char *gfa_fn, const pg_cluster_opt_t *o);
+void pg_write_cluster(pg_graph_t *g, const pg_cluster_opt_t *o);
+int  pg_pan_medoids(const int32_t *q, int32_t n, int32_t k, int32_t max_iter, int32_t *medoid, int32_t *label, int32_t *dist, int32_t *size, int64_t *sums, int64_t *rec,
+                    int32_t rec_cap, int32_t *n_rec, int32_t *n_swap, int64_t *td, int32_t *converged);
+int  pg_pan_cluster(const uint8_t *presence, int32_t n_item, int32_t n_asm, int32_t metric, int32_t k, int32_t max_iter, int32_t *medoid, int32_t *label, int32_t *dist,
+                    int32_t *size, int64_t *sums, int64_t *rec, int32_t rec_cap, int32_t *n_rec, int32_t *n_swap, int64_t *td, int32_t *converged, int32_t *frac_bits);
+
 /* Gene associations: which genes travel together over the assemblies and which exclude each other.  Over the presence matrix of
  * gfa2matrix (gene g is in assembly a when its entry is > 0; rows in segment order), with A assemblies, a = |B_g|, b = |B_h|,
  * s = |B_g & B_h|: V_g = a (A - a), D = s A - a b, phi(g, h) = D / sqrt(V_g V_h).  Gene g is eligible when min(a, A - a) >= min_count

@@ -94,7 +94,7 @@ typedef struct {
  * Device layout limits (PGA_ERR_RANGE otherwise): coordinates inside a block < 2^31 (contigs beyond that arrive as virtual contigs,
  * see pga_genome_block_t; what remains out of reach is a single cluster of overlapping hits spanning 2^30 bp), < 2^30 hits and < 2^31
  * exons per shard, < 2^20 genes, < 2^24 genomes. */
-#define PGA_ABI_VERSION 14u  /* bumped whenever a struct of this header or the order of pga_backend_t changes; pga_create refuses another */
+#define PGA_ABI_VERSION 15u  /* bumped whenever a struct of this header or the order of pga_backend_t changes; pga_create refuses another */
 typedef struct {
 	uint32_t abi_version;        /* = PGA_ABI_VERSION of the header the caller was compiled against (PGA_ERR_ARG otherwise) */
 	int32_t n_genome;            /* genomes in this shard (may include genomes with 0 hits) */
@@ -476,6 +476,33 @@ typedef struct { const int32_t *a, *d, *k; } pga_qtrait_out_t;
 int pga_pan_qtrait(const pga_qtrait_in_t *in, pga_qtrait_out_t *out);
 int32_t pga_qtrait_batch(void); /* permutations per batch: 16 384, or PANGENE_QTRAIT_BATCH */
 
+/* k-medoids clusters (include/pangene_amd.h pg_pan_medoids, pangene cluster; DESIGN.md section 8 "Clusters"): PAM over a fixed-point
+ * distance matrix, in integers throughout.  Context-free, like pan_join.  TD(M) = the sum over o of the smallest q[o][m], m in M.
+ * BUILD: M empty, D[o] = 2^29; k times, over x not in M, the largest gain(x) = sum over o of max(0, D[o] - q[x][o]), ties to the smallest
+ * x; M += x, D[o] = min(D[o], q[x][o]); record (x, -1, gain).  SWAP, at most max_iter times: over x not in M and m in M the smallest
+ * delta(x, m) = TD(M - m + x) - TD(M), ties to the smallest x and then the smallest m (assembly indices); delta >= 0: converged, stop;
+ * otherwise M = M - m + x and the record is (x, m, delta).  Result: the medoids ascending, cluster c = the c-th of them; a medoid labels
+ * itself, any other o takes the medoid with the smallest (q[o][m], m); dist[o] = q[o][medoid of o]; size[c]; td = TD(M);
+ * sums[o][c] = the sum of q[o][p] over the p of cluster c.
+ * In:  q[n][n], symmetric, zero diagonal, 0 <= q < 2^29 (the caller's promise: pg_pan_medoids checks it before it calls).
+ * Out: medoid[k], label[n], dist[n], size[k], sums[n][k], rec[n_rec][3] with n_rec = k + n_swap, td, converged (1: an iteration found no
+ *      negative delta; 0: max_iter iterations all swapped).  The arrays belong to the backend and stay valid until its next pan_medoids.
+ * The swap iterations are queued in chunks of 8 (PANGENE_MEDOIDS_BATCH, for tests) with one read of the status a chunk;
+ * PANGENE_MEDOIDS_ROWS (tests) fixes the rows a workgroup of the swap kernel walks.
+ * Limits: n >= 3, 2 <= k <= n - 1, max_iter >= 0 (PGA_ERR_ARG otherwise); n <= 65 535, k <= 1 024 (PGA_ERR_RANGE, before anything is
+ * launched).  Device memory: the matrix, n x k int64 twice over, and a few arrays of n. */
+typedef struct {
+	const int32_t *q;
+	int32_t n, k, max_iter;
+} pga_medoids_in_t;
+typedef struct {
+	const int32_t *medoid, *label, *dist, *size;
+	const int64_t *sums, *rec;
+	int64_t td;
+	int32_t n_rec, n_swap, converged;
+} pga_medoids_out_t;
+int pga_pan_medoids(const pga_medoids_in_t *in, pga_medoids_out_t *out);
+
 /* the same ABI as a table, so the host driver is written once */
 struct pga_branch_par_s; struct pga_loop_xchg_s;
 typedef struct {
@@ -540,6 +567,7 @@ typedef struct {
 	int  (*pan_boot)(const pga_boot_in_t *, pga_boot_out_t *); /* may be NULL: the host driver then runs the same step itself */
 	int  (*pan_pairs)(const pga_pairs_in_t *, pga_pairs_out_t *); /* may be NULL: the host driver then runs the same step itself */
 	int  (*pan_qtrait)(const pga_qtrait_in_t *, pga_qtrait_out_t *); /* may be NULL: the host driver then runs the same step itself */
+	int  (*pan_medoids)(const pga_medoids_in_t *, pga_medoids_out_t *); /* may be NULL: the host driver then runs the same step itself */
 } pga_backend_t;
 
 const pga_backend_t *pga_backend(void);

@@ -483,6 +483,109 @@ def pan_boot_records(lib: C.CDLL, presence, metric: str = "jaccard", method: str
     return rec
 
 
+class pg_cluster_opt_t(C.Structure):
+    """Cluster options (include/pangene_amd.h): items (PG_DIST_GENE / PG_DIST_ADJ), distance (jaccard or diff), the range of k and the
+    swap iterations per k at the most."""
+    _fields_ = [("type", C.c_int32), ("metric", C.c_int32), ("k_lo", C.c_int32), ("k_hi", C.c_int32), ("max_iter", C.c_int32)]
+
+
+def cluster_opt(lib: C.CDLL, k_lo: int = 2, k_hi: int | None = None, type: str = "gene", metric: str = "jaccard", max_iter: int = 1000) -> pg_cluster_opt_t:
+    if metric not in TREE_METRICS:
+        raise ValueError("metric must be jaccard or diff (shared is not a distance)")
+    k_hi = k_lo if k_hi is None else k_hi
+    if not 2 <= int(k_lo) <= int(k_hi) <= TREE_MAX_BOOT:
+        raise ValueError("k must be INT or INT-INT with 2 <= INT")
+    if not 0 <= int(max_iter) <= TREE_MAX_BOOT:
+        raise ValueError("max_iter must be in [0, 2^31 - 1]")
+    o = pg_cluster_opt_t()
+    lib.pg_cluster_opt_init(C.byref(o))
+    o.type, o.metric, o.k_lo, o.k_hi, o.max_iter = DIST_TYPES.index(type), DIST_METRICS.index(metric), int(k_lo), int(k_hi), int(max_iter)
+    return o
+
+
+def _medoids_call(n, k, call):
+    """The out arrays of pg_pan_medoids / pg_pan_cluster and the dict both return; call(pointers...) -> status.  The records are asked
+    for again with more room when a run swapped more often than the first call had room for."""
+    import numpy as np
+    medoid, label, dist, size = (np.zeros(m, dtype=np.int32) for m in (k, n, n, k))
+    sums = np.zeros((n, k), dtype=np.int64)
+    n_rec, n_swap, conv, td = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int64(0)
+    cap = k + 256
+    while True:
+        rec = np.zeros((cap, 3), dtype=np.int64)
+        i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        i64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
+        rc = call(i32(medoid), i32(label), i32(dist), i32(size), i64(sums), i64(rec), cap, C.byref(n_rec), C.byref(n_swap), C.byref(td), C.byref(conv))
+        if rc != 0:
+            return rc, None
+        if n_rec.value <= cap:
+            break
+        cap = n_rec.value
+    return 0, {"medoid": medoid, "label": label, "dist": dist, "size": size, "sums": sums, "rec": rec[:n_rec.value].copy(), "td": int(td.value),
+               "n_swap": int(n_swap.value), "converged": int(conv.value)}
+
+
+def pan_medoids(lib: C.CDLL, q, k: int, max_iter: int = 1000):
+    """k-medoids over a fixed-point distance matrix (int32 numpy array or torch tensor, shape (n, n), symmetric, zero diagonal, entries in
+    [0, 2^29), n >= 3, 2 <= k <= min(n - 1, 1024)) through pg_pan_medoids: a dict with medoid (k,), label (n,), dist (n,), size (k,) int32,
+    sums (n, k) int64, rec (k + n_swap, 3) int64 -- BUILD's (x, -1, gain), then the swaps' (x, m, delta) --, td, n_swap and converged."""
+    import numpy as np
+    if hasattr(q, "detach"):  # torch tensor, on any device
+        q = q.detach().cpu().numpy()
+    q = np.ascontiguousarray(q, dtype=np.int32)
+    if q.ndim != 2 or q.shape[0] != q.shape[1]:
+        raise ValueError("q must be a square matrix")
+    n, k = q.shape[0], int(k)
+    rc, res = _medoids_call(n, max(k, 1), lambda *a: lib.pg_pan_medoids(q.ctypes.data_as(C.POINTER(C.c_int32)), n, k, int(max_iter), *a))
+    if rc != 0:
+        raise RuntimeError("pg_pan_medoids: status %d" % rc)
+    return res
+
+
+def pan_cluster(lib: C.CDLL, presence, k: int, metric: str = "jaccard", max_iter: int = 1000):
+    """k-medoids clusters of the assemblies of an item x assembly presence matrix (bool numpy array or torch tensor, shape (M, A), A >= 3)
+    through pg_pan_cluster: (the dict pan_medoids returns, F) with distances in units of 2^-F."""
+    if metric not in TREE_METRICS:
+        raise ValueError("metric must be jaccard or diff (shared is not a distance)")
+    p = _presence(presence)
+    M, A = p.shape
+    F = C.c_int32(0)
+    k = int(k)
+    rc, res = _medoids_call(A, max(k, 1), lambda *a: lib.pg_pan_cluster(p.ctypes.data_as(C.POINTER(C.c_uint8)), M, A, DIST_METRICS.index(metric), k, int(max_iter), *a, C.byref(F)))
+    if rc != 0:
+        raise RuntimeError("pg_pan_cluster: status %d" % rc)
+    return res, int(F.value)
+
+
+def _cluster_args(argv: Sequence[str]):
+    """(k_lo, k_hi, type, metric, iterations) of --cluster=INT[-INT] / --cluster-type=STR / --cluster-metric=STR / --cluster-iter=INT in
+    argv; k_lo = None without --cluster."""
+    lo = hi = None
+    t, m, it, extra = "gene", "jaccard", 1000, False
+    for x in argv:
+        if x.startswith("--cluster="):
+            a, dash, b = x.split("=", 1)[1].partition("-")
+            if not a.isdigit() or (dash and not b.isdigit()):
+                raise ValueError("--cluster must be INT or INT-INT with 2 <= INT")
+            lo, hi = int(a), int(b) if dash else int(a)
+            if not 2 <= lo <= hi <= TREE_MAX_BOOT:
+                raise ValueError("--cluster must be INT or INT-INT with 2 <= INT")
+        elif x.startswith("--cluster-type="): t, extra = x.split("=", 1)[1], True
+        elif x.startswith("--cluster-metric="): m, extra = x.split("=", 1)[1], True
+        elif x.startswith("--cluster-iter="): it, extra = int(x.split("=", 1)[1]), True
+        elif x.startswith("--cluster"):  # a bare --cluster, --cluster-type without a value, an unknown --cluster-* word
+            raise ValueError("unknown option or missing value: " + x)
+    if t not in DIST_TYPES:
+        raise ValueError("--cluster-type must be gene or adj")
+    if m not in TREE_METRICS:
+        raise ValueError("--cluster-metric must be jaccard or diff")
+    if not 0 <= it <= TREE_MAX_BOOT:
+        raise ValueError("--cluster-iter must be in [0, 2^31 - 1]")
+    if extra and lo is None:
+        raise ValueError("--cluster-type, --cluster-metric and --cluster-iter need --cluster=INT[-INT]")
+    return lo, hi, t, m, it
+
+
 def _tree_boot_args(argv: Sequence[str]):
     """(replicates, seed) of --tree-boot=INT / --tree-seed=INT in argv"""
     b, seed = 0, 0
@@ -514,6 +617,9 @@ def _tree_args(argv: Sequence[str]):
         raise ValueError("--tree-method must be nj or upgma")
     return t, m, a
 
+
+# medoid, label, dist, size, sums, rec, rec_cap, n_rec, n_swap, td, converged of pg_pan_medoids / pg_pan_cluster
+_MEDOIDS_OUT = [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
 
 _API = {
     "pg_opt_init": (None, [C.POINTER(pg_opt_t)]),
@@ -561,6 +667,11 @@ _API = {
     "pg_write_tree": (None, [C.c_void_p, C.c_void_p]),
     "pg_pan_join": (C.c_int, [C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "pg_pan_tree": (C.c_int, [C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    "pg_cluster_opt_init": (None, [C.c_void_p]),
+    "pg_cluster_file": (C.c_int, [C.c_char_p, C.c_void_p]),
+    "pg_write_cluster": (None, [C.c_void_p, C.c_void_p]),
+    "pg_pan_medoids": (C.c_int, [C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32] + _MEDOIDS_OUT),
+    "pg_pan_cluster": (C.c_int, [C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + _MEDOIDS_OUT + [C.POINTER(C.c_int32)]),
     "pg_pan_boot": (C.c_int, [C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
                               C.POINTER(C.c_int32)]),
     "pg_pan_boot_records": (C.c_int, [C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
@@ -629,7 +740,7 @@ def parse_args(lib: C.CDLL, argv: Sequence[str]) -> pg_opt_t:
         elif a in ("--bed", "--bed=walk"): opt.flag |= PG_F_WRITE_BED_WALK
         elif a == "--bed=raw": opt.flag |= PG_F_WRITE_BED_RAW
         elif a == "--bed=flag": opt.flag |= PG_F_WRITE_BED_FLAG
-        elif a in ("--matrix", "--matrix=presence", "--matrix=count", "--call") or a.startswith("--curves") or a.startswith("--dist") or a.startswith("--assoc") or a.startswith("--trait") or a.startswith("--qtrait") or a.startswith("--tree"): pass  # handled by run()
+        elif a in ("--matrix", "--matrix=presence", "--matrix=count", "--call") or a.startswith("--curves") or a.startswith("--dist") or a.startswith("--assoc") or a.startswith("--trait") or a.startswith("--qtrait") or a.startswith("--tree") or a.startswith("--cluster"): pass  # handled by run()
         elif a[:2] in ("-p", "-a", "-f", "-c", "-g", "-r", "-b", "-B", "-y", "-T", "-D", "-C", "-e", "-l", "-m", "-d", "-X", "-I", "-P"):
             v = a[2:] if len(a) > 2 else next(it)
             k = a[1]
@@ -695,6 +806,10 @@ def run(lib: C.CDLL, files: Sequence[str], argv: Sequence[str] = (), scan_only: 
     if qtrait_fn is not None and (any(x.startswith("--matrix") for x in argv) or "--call" in argv or n_curves or dist_type is not None or assoc_phi is not None
                                   or trait_fn is not None or tree_type is not None):
         raise ValueError("--qtrait cannot be combined with --matrix, --call, --curves, --dist, --assoc, --trait or --tree")
+    cl_lo, cl_hi, cl_type, cl_metric, cl_iter = _cluster_args(argv)
+    if cl_lo is not None and (any(x.startswith("--matrix") for x in argv) or "--call" in argv or n_curves or dist_type is not None or assoc_phi is not None
+                              or trait_fn is not None or tree_type is not None or qtrait_fn is not None):
+        raise ValueError("--cluster cannot be combined with --matrix, --call, --curves, --dist, --assoc, --trait, --tree or --qtrait")
     fd, out = tempfile.mkstemp(prefix="pangene_", suffix=".out")
     os.close(fd)
     lib.pg_set_output(out.encode())
@@ -740,6 +855,10 @@ def run(lib: C.CDLL, files: Sequence[str], argv: Sequence[str] = (), scan_only: 
                     raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
             elif tree_type is not None:
                 lib.pg_write_tree(g, C.byref(tree_opt(lib, tree_type, tree_metric, tree_method, tree_boot, tree_seed)))
+                if lib.pg_last_error():
+                    raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
+            elif cl_lo is not None:
+                lib.pg_write_cluster(g, C.byref(cluster_opt(lib, cl_lo, cl_hi, cl_type, cl_metric, cl_iter)))
                 if lib.pg_last_error():
                     raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
             elif opt.flag & PG_F_WRITE_BED_WALK: lib.pg_write_bed(d, 1)

@@ -71,6 +71,10 @@ static int usage(FILE *fp, const pg_opt_t *opt)
 	std::fprintf(fp, "    --tree-method=STR  --tree: nj (neighbour-joining, unrooted; negative branch lengths are printed as they come) or upgma [nj]\n");
 	std::fprintf(fp, "    --tree-boot=INT    --tree: bootstrap replicates over the items; inner nodes are labelled with their support in per cent [0]\n");
 	std::fprintf(fp, "    --tree-seed=INT    seed of the bootstrap draws [0]\n");
+	std::fprintf(fp, "    --cluster=INT[-INT]  output k-medoids clusters of the assemblies for k = INT, or for every k of the range and the assignment of the best one\n");
+	std::fprintf(fp, "    --cluster-type=STR   --cluster: items, gene or adj [gene]\n");
+	std::fprintf(fp, "    --cluster-metric=STR --cluster: distance, jaccard or diff [jaccard]\n");
+	std::fprintf(fp, "    --cluster-iter=INT   --cluster: swap iterations per k at the most [1000]\n");
 	std::fprintf(fp, "  Also: pangene gfa2matrix [-c] [-d FILE] [-p] <in.gfa>   (pangene.js gfa2matrix on a GFA file)\n");
 	std::fprintf(fp, "        pangene call [-m INT] [-w] [-b] [-e] [-d] [-p] [-s] [-r STR] <in.gfa>   (pangene.js call on a GFA file)\n");
 	std::fprintf(fp, "        pangene curves [-n INT] [-s INT] <in.gfa>   (accumulation curves of the gfa2matrix matrix of a GFA file)\n");
@@ -79,6 +83,7 @@ static int usage(FILE *fp, const pg_opt_t *opt)
 	std::fprintf(fp, "        pangene trait -t FILE [-n INT] [-s INT] [-c INT] [-p FLOAT] <in.gfa>   (gene-trait association over the matrix of a GFA file; -L nj|upgma adds the lineage-aware pairwise comparisons)\n");
 	std::fprintf(fp, "        pangene qtrait -t FILE [-n INT] [-s INT] [-c INT] [-p FLOAT] <in.gfa>   (rank-sum test of every gene against the quantitative traits of a trait file)\n");
 	std::fprintf(fp, "        pangene tree [-t gene|adj] [-m jaccard|diff] [-a nj|upgma] [-b INT] [-s INT] <in.gfa>   (neighbour-joining or UPGMA tree of the assemblies of a GFA file, with bootstrap support)\n");
+	std::fprintf(fp, "        pangene cluster [-t gene|adj] [-m jaccard|diff] -k INT[-INT] [-i INT] <in.gfa>   (k-medoids clusters of the assemblies of a GFA file, their medoids and silhouettes)\n");
 	return fp == stdout ? 0 : 1;
 }
 
@@ -236,6 +241,48 @@ static int main_tree(int argc, char *argv[])
 	return pg_tree_file(argv[optind], &o) == 0 ? 0 : 1;
 }
 
+// "INT" or "INT-INT": a k or a range of k, 2 <= lo <= hi; digits only
+static bool cluster_range(const char *s, int32_t &lo, int32_t &hi)
+{
+	char *end = nullptr;
+	if (*s < '0' || *s > '9') return false;
+	const long long a = std::strtoll(s, &end, 10);
+	long long b = a;
+	if (*end == '-') {
+		const char *t = end + 1;
+		if (*t < '0' || *t > '9') return false;
+		b = std::strtoll(t, &end, 10);
+	}
+	if (*end != 0 || a < 2 || b < a || b > 2147483647ll) return false;
+	lo = (int32_t)a, hi = (int32_t)b;
+	return true;
+}
+
+// `pangene cluster`: k-medoids clusters of the assemblies of a GFA file over the distances `pangene dist` prints
+static int main_cluster(int argc, char *argv[])
+{
+	pg_cluster_opt_t o;
+	pg_cluster_opt_init(&o);
+	bool have_k = false;
+	int c;
+	while ((c = getopt(argc, argv, "t:m:k:i:")) >= 0) {
+		if (c == 't') { if ((o.type = dist_type(optarg)) < 0) { std::fprintf(stderr, "ERROR: -t must be gene or adj\n"); return 1; } }
+		else if (c == 'm') { if ((o.metric = tree_metric(optarg)) < 0) { std::fprintf(stderr, "ERROR: -m must be jaccard or diff (shared is not a distance)\n"); return 1; } }
+		else if (c == 'k') { if (!(have_k = cluster_range(optarg, o.k_lo, o.k_hi))) { std::fprintf(stderr, "ERROR: -k must be INT or INT-INT with 2 <= INT\n"); return 1; } }
+		else if (c == 'i') { if (!tree_boot(optarg, o.max_iter)) { std::fprintf(stderr, "ERROR: -i must be in [0, 2147483647]\n"); return 1; } }
+		else return 1;
+	}
+	if (argc - optind < 1) {
+		std::printf("Usage: pangene cluster -k INT[-INT] [options] <in.gfa>\nOptions:\n  -k INT[-INT]  clusters: one k, or a range whose k with the largest mean silhouette is printed in full\n"
+		            "  -t STR   items: gene (gene content) or adj (gene adjacencies of the walks) [gene]\n"
+		            "  -m STR   distance: jaccard or diff [jaccard]\n"
+		            "  -i INT   swap iterations per k at the most [1000]\n");
+		return 0;
+	}
+	if (!have_k) { std::fprintf(stderr, "ERROR: pangene cluster needs -k INT[-INT]\n"); return 1; }
+	return pg_cluster_file(argv[optind], &o) == 0 ? 0 : 1;
+}
+
 static int assoc_sign(const char *s) { return std::strcmp(s, "both") == 0 ? PG_ASSOC_BOTH : std::strcmp(s, "pos") == 0 ? PG_ASSOC_POS : std::strcmp(s, "neg") == 0 ? PG_ASSOC_NEG : -1; }
 static bool assoc_phi(const char *s, double &r) // a number in [0, 1]
 {
@@ -345,7 +392,8 @@ struct Output { int matrix = 0; bool call = false; int curves = 0; uint32_t curv
 	bool assoc = false; double assoc_phi = 0.8; int assoc_count = 2, assoc_sign = 0;
 	const char *trait = nullptr; int32_t trait_perm = 1000; uint32_t trait_seed = 11; int trait_lineage = 0;
 	const char *qtrait = nullptr; int32_t qtrait_perm = 1000; uint32_t qtrait_seed = 11;
-	int tree = -1, tree_metric = 0, tree_method = 0; int32_t tree_boot = 0; uint32_t tree_seed = 0; }; // tree: PG_DIST_GENE / PG_DIST_ADJ (-1: none)
+	int tree = -1, tree_metric = 0, tree_method = 0; int32_t tree_boot = 0; uint32_t tree_seed = 0; // tree: PG_DIST_GENE / PG_DIST_ADJ (-1: none)
+	int32_t cluster_lo = 0, cluster_hi = 0, cluster_iter = 1000; int cluster_type = 0, cluster_metric = 0; }; // cluster_lo: 0 = none
 
 static int run_path(pg_opt_t &opt, int n_files, char **files, const uint8_t *ids_only, const Output &o, bool graph_lines, bool own_lines, int device = -1)
 {
@@ -418,6 +466,13 @@ static int run_path(pg_opt_t &opt, int n_files, char **files, const uint8_t *ids
 			pg_write_tree(g, &tro);
 			if (pg_last_error()) rc = 2;
 		}
+		else if (o.cluster_lo) {
+			pg_cluster_opt_t clo;
+			pg_cluster_opt_init(&clo);
+			clo.type = o.cluster_type, clo.metric = o.cluster_metric, clo.k_lo = o.cluster_lo, clo.k_hi = o.cluster_hi, clo.max_iter = o.cluster_iter;
+			pg_write_cluster(g, &clo);
+			if (pg_last_error()) rc = pg_last_error() == -3 ? 1 : 2; // -3, PGA_ERR_ARG: a k outside [2, assemblies - 1] or fewer than 3 assemblies -- a refusal, as on `pangene cluster`
+		}
 		else if (opt.flag & PG_F_WRITE_BED_WALK) { if (own_lines) pg_write_bed(d, 1); }
 		else if (opt.flag & PG_F_WRITE_BED_FLAG) { if (own_lines) pg_write_bed(d, 0); }
 		else {
@@ -483,6 +538,7 @@ static int run_sharded(pg_opt_t &opt, int W, int n_files, char **files, const Ou
 	if (o.trait) { std::fprintf(stderr, "ERROR: --trait needs every genome in one process; run it without --gpus\n"); return 1; }
 	if (o.qtrait) { std::fprintf(stderr, "ERROR: --qtrait needs every genome in one process; run it without --gpus\n"); return 1; }
 	if (o.tree >= 0) { std::fprintf(stderr, "ERROR: --tree needs every genome in one process; run it without --gpus\n"); return 1; }
+	if (o.cluster_lo) { std::fprintf(stderr, "ERROR: --cluster needs every genome in one process; run it without --gpus\n"); return 1; }
 	const bool dev = pg_backend_is_device() != 0;
 	typedef int (*uid_fn)(void *); typedef int (*init_fn)(int32_t, int32_t, const void *); typedef int (*fin_fn)(void);
 	uid_fn rccl_uid = nullptr; init_fn rccl_init = nullptr; fin_fn rccl_fin = nullptr;
@@ -630,6 +686,7 @@ int main(int argc, char *argv[])
 	if (argc >= 2 && std::strcmp(argv[1], "trait") == 0) return main_trait(argc - 1, argv + 1);
 	if (argc >= 2 && std::strcmp(argv[1], "qtrait") == 0) return main_qtrait(argc - 1, argv + 1);
 	if (argc >= 2 && std::strcmp(argv[1], "tree") == 0) return main_tree(argc - 1, argv + 1);
+	if (argc >= 2 && std::strcmp(argv[1], "cluster") == 0) return main_cluster(argc - 1, argv + 1);
 	int matrix = 0, n_gpus = 1; // matrix: 1 presence, 2 counts
 	bool call = false;
 	int curves = 0; // orders of --curves (0: not asked for)
@@ -649,6 +706,9 @@ int main(int argc, char *argv[])
 	int tree = -1, tree_metric_v = PG_DIST_JACCARD, tree_method_v = PG_TREE_NJ; // --tree: PG_DIST_GENE / PG_DIST_ADJ (-1: not asked for)
 	int32_t tree_boot_v = 0;
 	uint32_t tree_seed = 0;
+	int32_t cluster_lo = 0, cluster_hi = 0, cluster_iter_v = 1000; // --cluster: the range of k (0: not asked for)
+	int cluster_type_v = PG_DIST_GENE, cluster_metric_v = PG_DIST_JACCARD;
+	bool cluster_extra = false; // a --cluster-* option was given
 	static const struct option lopts[] = {
 		{ "bed", optional_argument, nullptr, 301 }, { "ori-sc", no_argument, nullptr, 302 }, { "matrix", optional_argument, nullptr, 303 }, { "call", no_argument, nullptr, 305 },
 		{ "curves", optional_argument, nullptr, 306 }, { "curves-seed", required_argument, nullptr, 307 },
@@ -659,6 +719,8 @@ int main(int argc, char *argv[])
 		{ "qtrait", required_argument, nullptr, 322 }, { "qtrait-perm", required_argument, nullptr, 323 }, { "qtrait-seed", required_argument, nullptr, 324 },
 		{ "tree", optional_argument, nullptr, 316 }, { "tree-metric", required_argument, nullptr, 317 }, { "tree-method", required_argument, nullptr, 318 },
 		{ "tree-boot", required_argument, nullptr, 319 }, { "tree-seed", required_argument, nullptr, 320 },
+		{ "cluster", required_argument, nullptr, 325 }, { "cluster-type", required_argument, nullptr, 326 }, { "cluster-metric", required_argument, nullptr, 327 },
+		{ "cluster-iter", required_argument, nullptr, 328 },
 		{ "gpus", required_argument, nullptr, 304 }, { "procs", required_argument, nullptr, 304 },
 		{ "version", no_argument, nullptr, 401 }, { nullptr, 0, nullptr, 0 } };
 	pg_opt_t opt;
@@ -756,6 +818,21 @@ int main(int argc, char *argv[])
 			if (!trait_perm(optarg, qtrait_perm_v)) { std::fprintf(stderr, "ERROR: --qtrait-perm must be in [0, 2147483646]\n"); return 1; }
 			break;
 		case 324: qtrait_extra = true, qtrait_seed = (uint32_t)std::strtoul(optarg, nullptr, 10); break;
+		case 325:
+			if (!cluster_range(optarg, cluster_lo, cluster_hi)) { std::fprintf(stderr, "ERROR: --cluster must be INT or INT-INT with 2 <= INT\n"); return 1; }
+			break;
+		case 326:
+			cluster_extra = true;
+			if ((cluster_type_v = dist_type(optarg)) < 0) { std::fprintf(stderr, "ERROR: --cluster-type must be gene or adj\n"); return 1; }
+			break;
+		case 327:
+			cluster_extra = true;
+			if ((cluster_metric_v = tree_metric(optarg)) < 0) { std::fprintf(stderr, "ERROR: --cluster-metric must be jaccard or diff (shared is not a distance)\n"); return 1; }
+			break;
+		case 328:
+			cluster_extra = true;
+			if (!tree_boot(optarg, cluster_iter_v)) { std::fprintf(stderr, "ERROR: --cluster-iter must be in [0, 2147483647]\n"); return 1; }
+			break;
 		case 401: std::puts(PG_VERSION); return 0;
 		default: break;
 		}
@@ -769,7 +846,13 @@ int main(int argc, char *argv[])
 	if (tree >= 0 && (matrix || call || curves || dist >= 0 || assoc || trait)) { std::fprintf(stderr, "ERROR: --tree cannot be combined with --matrix, --call, --curves, --dist, --assoc or --trait\n"); return 1; }
 	if (qtrait && (matrix || call || curves || dist >= 0 || assoc || trait || tree >= 0)) { std::fprintf(stderr, "ERROR: --qtrait cannot be combined with --matrix, --call, --curves, --dist, --assoc, --trait or --tree\n"); return 1; }
 	if (qtrait_extra && !qtrait) { std::fprintf(stderr, "ERROR: --qtrait-perm and --qtrait-seed need --qtrait=FILE\n"); return 1; }
+	if (cluster_lo && (matrix || call || curves || dist >= 0 || assoc || trait || tree >= 0 || qtrait)) {
+		std::fprintf(stderr, "ERROR: --cluster cannot be combined with --matrix, --call, --curves, --dist, --assoc, --trait, --tree or --qtrait\n");
+		return 1;
+	}
+	if (cluster_extra && !cluster_lo) { std::fprintf(stderr, "ERROR: --cluster-type, --cluster-metric and --cluster-iter need --cluster=INT[-INT]\n"); return 1; }
 	Output o;
+	o.cluster_lo = cluster_lo, o.cluster_hi = cluster_hi, o.cluster_iter = cluster_iter_v, o.cluster_type = cluster_type_v, o.cluster_metric = cluster_metric_v;
 	o.qtrait = qtrait, o.qtrait_perm = qtrait_perm_v, o.qtrait_seed = qtrait_seed;
 	o.tree = tree, o.tree_metric = tree_metric_v, o.tree_method = tree_method_v, o.tree_boot = tree_boot_v, o.tree_seed = tree_seed;
 	o.trait = trait, o.trait_perm = trait_perm_v, o.trait_seed = trait_seed, o.trait_lineage = trait_lineage_v;
