@@ -3,7 +3,7 @@ bound them with a timeout.  The product library (HIP kernels) runs matrices no G
 the numpy restatement (exact integers) check every one of them completely: the output is sparse, so the full sorted record arrays
 and the phi arrays are compared, never a sample.  Prints one line per case and "ALL OK" at the end; exits 1 at the first difference.
 
-    python tests/support/assoc_direct.py {large|wide|sizes|edges} [--cpu-only]
+    python tests/support/assoc_direct.py {large|wide|sizes|edges|threshold|band337|band801} [--cpu-only]
 
 --cpu-only runs the checker build against the restatement alone (to see that the cases stay affordable without a GPU)."""
 import os
@@ -40,6 +40,34 @@ def check(libs, P, label, given=None, **kw):
     return len(want)
 
 
+def check_band(libs, p, a, s, cmp):
+    """band_matrix(a, s) at the thresholds p and p + 1 (and for D < 0 with the signs apart) against the records worked out from (a, s).
+    pg_pan_assoc is called on the bytes as they are: at 16.7 M columns the copies of capi.pan_assoc cost as much as the call, and the
+    phi it returns is computed by the wrapper from the records, not by the library."""
+    import ctypes as C
+    from pangene_amd import capi
+    P = ar.band_matrix(a, s)
+    cnt = [int(np.count_nonzero(r)) for r in P]
+    if cnt != [a] * 4 or int(np.count_nonzero(P[0] & P[1])) != s or not np.array_equal(P[0], P[3]) or not np.array_equal(P[1], P[2]):
+        sys.exit("band_matrix(%d, %d) does not have the counts asked for" % (a, s))
+    D = s * ar.MAX_ASM - a * a
+    ok, ts = True, []
+    for at, sign in [(p, "both"), (p + 1, "both")] + ([(p, "neg"), (p, "pos")] if D < 0 else []):
+        want = ar.band_expected(a, s, at, sign)[0]
+        assert len(want) == (2 if sign != "neg" else 0) + (4 if (cmp >= 0 and at == p and sign != "pos") else 0)
+        for lib in libs:
+            t0 = time.perf_counter()
+            got = np.full((8, 3), -1, dtype=np.int32)
+            n = lib.pg_pan_assoc(P.ctypes.data_as(C.POINTER(C.c_uint8)), 4, P.shape[1], C.byref(capi.assoc_opt(lib, at / 1000.0, 2, sign)),
+                                 got.ctypes.data_as(C.POINTER(C.c_int32)), len(got))
+            ts.append(time.perf_counter() - t0)
+            ok = ok and n == len(want) and np.array_equal(got[:len(want)], want)
+    print("band p=%d a=%d s=%d D%s0 %s: libraries %.2f s: %s" % (p, a, s, "<" if D < 0 else ">", ("below", "equal", "above")[cmp + 1], sum(ts), "ok" if ok else "DIFFERENT"),
+          flush=True)
+    if not ok:
+        sys.exit(1)
+
+
 def main():
     which = sys.argv[1]
     cpu_only = "--cpu-only" in sys.argv[2:]
@@ -74,6 +102,24 @@ def main():
         assert check(libs, P, "wide", min_phi=0.9, min_count=3) > 0
         P = ar.planted(1000003, 12, 5, n_module=10)  # a million rows, few of them eligible at this count
         check(libs, P, "million rows", min_phi=0.95, min_count=6)
+    elif which == "threshold":
+        # the decision at equality: every slot of an off-diagonal and of a diagonal tile exactly on the threshold, one permille below it
+        # and one above, on either side of D = 0 and under every sign; then the exact small cases of the checker's test
+        for label, P, p, side, cross, same in ar.tie_tiles():
+            for at in (p, p + 1, p - 1):
+                for sign in ar.SIGNS:
+                    n = check(libs, P, label, min_phi=at / 1000.0, min_count=2, sign=sign)
+                    assert n == ar.tie_count(p, side, cross, same, at, sign), "the restatement misses the count the matrix was built for"
+        for A, a, b, s, p in ar.exact_threshold_cases():
+            P = ar.two_rows(A, a, b, s)
+            for at, n in ((p, 1), (p + 1, 0), (p - 1, 1)):
+                assert check(libs, P, "exact (a=%d b=%d s=%d)" % (a, b, s), min_phi=at / 1000.0, min_count=2) == n
+    elif which in ("band337", "band801"):
+        # the guard band at the documented limit A = 16 777 215, where the doubles of the pre-test round: every case of the search for one p
+        cases = ar.band_cases(int(which[4:]))
+        for p, a, s, cmp in cases:
+            check_band(libs, p, a, s, cmp)
+        print("band: %d cases" % len(cases), flush=True)
     elif which == "edges":
         # the shapes at which the tile body can go wrong: every row count against every row length.  min_count 1 and phi >= 0 select every
         # pair of rows that are not constant: with eligible rows E is the row count itself, and the matrix of every density has constant

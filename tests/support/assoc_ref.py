@@ -124,3 +124,110 @@ def planted(G, A, seed, n_module=6):
                 row[rng.integers(0, A)] ^= True
             P[r] = row
     return P
+
+
+def two_rows(A, a, b, s):
+    """(2, A) bool: |B_0| = a, |B_1| = b, |B_0 & B_1| = s"""
+    assert s <= min(a, b) and a + b - s <= A
+    P = np.zeros((2, A), dtype=bool)
+    P[0, :a] = True
+    P[1, a - s:a - s + b] = True
+    return P
+
+
+def exact_threshold_cases(max_A=40):
+    """(A, a, b, s, p) with 10^6 D^2 = p^2 V_g V_h exactly and p not a multiple of 100"""
+    from math import isqrt
+    out = []
+    for A in range(4, max_A + 1):
+        for a in range(2, A - 1):
+            for b in range(a, A - 1):
+                VV = a * (A - a) * b * (A - b)
+                for s in range(max(0, a + b - A), min(a, b) + 1):
+                    D = s * A - a * b
+                    if D == 0:
+                        continue
+                    n = 10 ** 6 * D * D
+                    if n % VV:
+                        continue
+                    p = isqrt(n // VV)
+                    if p * p == n // VV and 0 < p < 1000 and p % 100:
+                        out.append((A, a, b, s, p))
+    return out
+
+
+TIE_P = (337, 801)
+
+
+def tie_tiles():
+    """[(label, P (G, 4000) bool, p, side, cross pairs, identical-row pairs)]: matrices whose every cross pair sits EXACTLY on the
+    threshold p / 1000.  A = 4000, X and Y rows of 2000 bits with |X & Y| = 1000 + side p: D = side 4000 p, V = 4 10^6, so
+    10^6 D^2 = p^2 V^2 for any p.  Off-diagonal tile: G = 256, rows 0 .. 127 = X and 128 .. 255 = Y, so the 128 x 128 cross pairs are
+    every (thread, ii, jj) slot of the tile (0, 1).  Diagonal tile: G = 130, rows alternating X, Y (li < lj, a partial tile)."""
+    out = []
+    for p in TIE_P:
+        for side in (1, -1):
+            s = 1000 + side * p
+            xy = two_rows(4000, 2000, 2000, s)
+            off = xy[np.arange(256) // 128]
+            dia = xy[np.arange(130) % 2]
+            out.append(("ties off-diagonal p=%d side=%+d" % (p, side), off, p, side, 128 * 128, 2 * (128 * 127 // 2)))
+            out.append(("ties diagonal p=%d side=%+d" % (p, side), dia, p, side, 65 * 65, 2 * (65 * 64 // 2)))
+    return out
+
+
+def tie_count(p, side, cross, same, at, sign):
+    """the pairs select() must give for a matrix of tie_tiles() at the threshold at / 1000: the identical rows (phi = 1) unless the sign
+    is neg, the cross pairs when at <= p and the sign admits D = side 4000 p"""
+    return (same if sign != "neg" else 0) + (cross if at <= p and sign in ("both", "pos" if side > 0 else "neg") else 0)
+
+
+BAND = 2 ** 41  # a case is kept when |10^6 D^2 / (p^2 V^2) - 1| < 1 / BAND: strictly inside the kernel's guard band of 2^-40
+
+
+def band_search(p, A=MAX_ASM, negative=False, lo=2, hi=None):
+    """[(a, s, cmp)] at A assemblies: two rows with |X| = |Y| = a, |X & Y| = s, whose 10^6 D^2 is within 2^-41 relative of p^2 V^2;
+    cmp = 0 (equal), 1 (above: selected at p) or -1 (below).  With a = b the condition is linear, 1000 |s A - a^2| against
+    p a (A - a): for every a in [lo, hi) the s nearest to the threshold is taken in int64 (all terms below 2^58), kept when
+    |1000 D - p V| < 16000, and classified in Python integers.  negative: D < 0, s below a^2 / A."""
+    from fractions import Fraction
+    hi = A // 2 if hi is None else hi
+    a = np.arange(lo, hi, dtype=np.int64)
+    V = a * (A - a)
+    T = 1000 * a * a + (-p if negative else p) * V  # 1000 s A is to be near T
+    s = (T + 500 * A) // (1000 * A)
+    r = 1000 * s * A - T
+    keep = (np.abs(r) < 16000) & (s >= 0) & (s <= a) & (2 * a - s <= A)
+    out = []
+    for ai, si in zip(a[keep].tolist(), s[keep].tolist()):
+        D, Vi = si * A - ai * ai, ai * (A - ai)
+        if D == 0 or (D < 0) != negative:
+            continue
+        L, R = 10 ** 6 * D * D, p * p * Vi * Vi
+        if abs(Fraction(L, R) - 1) < Fraction(1, BAND):
+            out.append((ai, si, (L > R) - (L < R)))
+    return out
+
+
+def band_cases(p):
+    """[(p, a, s, cmp)] at A = 16 777 215, the documented limit, where the double-precision pre-test of the device rounds: the searches
+    of band_search for one p (337 or 801), D > 0 over a in [2, A / 2) and D < 0 over a in [2, A - 2)"""
+    return [(p,) + c for c in band_search(p) + band_search(p, negative=True, hi=MAX_ASM - 2)]
+
+
+def band_matrix(a, s, A=MAX_ASM):
+    """(4, A) uint8: rows X, Y, Y, X with |X| = |Y| = a and |X & Y| = s"""
+    P = np.zeros((4, A), dtype=np.uint8)
+    P[0, :a] = P[3, :a] = 1
+    P[1, a - s:2 * a - s] = P[2, a - s:2 * a - s] = 1
+    return P
+
+
+def band_expected(a, s, at, sign="both", A=MAX_ASM):
+    """(pairs int32 (n, 3), phi) of band_matrix(a, s) at the threshold at / 1000 and min_count <= min(a, A - a), from (a, s) alone in
+    Python integers: the identical rows (0, 3) and (1, 2) have D = V > 0, the four cross pairs D = s A - a^2"""
+    D, V = s * A - a * a, a * (A - a)
+    cross = 10 ** 6 * D * D >= at * at * V * V and (sign == "both" or (sign == "pos") == (D >= 0))
+    rows = [(g, h, a if g + h == 3 else s) for g in range(4) for h in range(g + 1, 4) if (sign != "neg" if g + h == 3 else cross)]
+    pairs = np.array(rows, dtype=np.int32).reshape(-1, 3)
+    return pairs, phi(pairs, np.full(4, a, dtype=np.int64), A)

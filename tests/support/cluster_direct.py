@@ -3,7 +3,7 @@ that the test can bound them with a timeout.  The product library (HIP kernels o
 reaches; the numpy restatement (tests/support/cluster_ref.py) checks them where that is affordable, the checker build (host loops of
 tree.cpp) where it is not.  Prints one line per case and "ALL OK" at the end; exits 1 at the first difference.
 
-    python tests/support/cluster_direct.py {sizes|large|uneven|ties|chunks|cached}"""
+    python tests/support/cluster_direct.py {sizes|large|uneven|ties|chunks|cached|magnitude}"""
 import os
 import sys
 
@@ -98,6 +98,17 @@ def main():
             report("chunks batch=" + batch, 300, 8, cr.same(capi.pan_medoids(hip, q, 8), want))
             for it in (0, 1, 2, 4):
                 report("chunks batch=%s max_iter=%d" % (batch, it), 300, 8, cr.same(capi.pan_medoids(hip, q, 8, max_iter=it), cr.medoids(q, 8, it)))
+    elif which == "magnitude":  # entries in the upper half of the range: gain, removal, acc, plus, td and sums are far beyond 32 bits
+        for label, q, k, swaps in cr.magnitude_inputs():
+            want = cr.medoids(q, k)
+            big = max(int(want["td"]), int(want["sums"].max()), int(np.abs(want["rec"][:, 2]).max())) > 1 << 35
+            report("magnitude, " + label, q.shape[0], k, big and want["converged"] == 1 and (swaps is None or want["n_swap"] >= swaps) and
+                   cr.same(capi.pan_medoids(hip, q, k), want), " swaps=%d td=%d" % (want["n_swap"], want["td"]))
+        n, k = cr.MAGNITUDE_CHECKER
+        q = cr.full_random(n, n + k)
+        want = capi.pan_medoids(ora, q, k)
+        report("magnitude, uniform, checker build", n, k, want["converged"] == 1 and want["td"] > 1 << 37 and cr.same(capi.pan_medoids(hip, q, k), want),
+               " swaps=%d td=%d" % (want["n_swap"], want["td"]))
     elif which == "cached":  # the cached device buffers: growing, shrinking and growing again in one process
         for i, (n, k) in enumerate(((40, 3), (700, 20), (3, 2), (257, 200), (1030, 5), (64, 63), (700, 2))):
             q = cr.random_matrix(n, 20 + i, hi=1 << 14)

@@ -169,3 +169,35 @@ def random_matrix(n, seed, hi=1 << 20):
     a = rng.integers(0, hi, size=(n, n))
     q = np.triu(a, 1)
     return (q + q.T).astype(np.int32)
+
+
+def full_random(n, seed):
+    """(n, n) int32: symmetric, zero diagonal, entries uniform in [2^28, 2^29) -- the upper half of the range the definition admits, so
+    that every sum over a few columns needs 64 bits"""
+    rng = np.random.default_rng(seed)
+    q = np.triu(rng.integers(1 << 28, LIMIT, size=(n, n)), 1)
+    return (q + q.T).astype(np.int32)
+
+
+# (n, k) of the uniform matrices against the restatement, the one against the checker build, and (n, k, groups, spread, swaps at the
+# least) of the matrices with structure: planted() on a grid of 2^17, entries up to 3 240 << 17 < 2^29
+MAGNITUDE_RANDOM = ((257, 2), (257, 17), (513, 3))
+MAGNITUDE_CHECKER = (1025, 16)
+MAGNITUDE_PLANTED = ((257, 17, 5, 300, 3), (769, 9, 4, 300, 3), (1281, 2, 2, 300, 1))
+
+
+def magnitude_inputs():
+    """[(label, q, k, swaps at the least or None)] of the `magnitude` cases that the restatement checks.  n = 257 and above: the sums
+    cross workgroups.  The last one has n = 1 281 columns, five or six a lane in the one-workgroup-a-row kernels, and half of them within
+    2^27 of the candidate: a lane's own part of BUILD's first gain passes 2^31 (first_gain_parts)."""
+    out = [("uniform", full_random(n, n + k), k, None) for n, k in MAGNITUDE_RANDOM]
+    out += [("planted", planted(n, g, 1, spread=spread, grid=1 << 17), k, swaps) for n, k, g, spread, swaps in MAGNITUDE_PLANTED]
+    return out
+
+
+def first_gain_parts(q, lanes=256):
+    """the largest sum over the columns o = l (mod lanes) of BUILD's first gain max(0, 2^29 - q[x][o]), x the first medoid"""
+    q = np.asarray(q, dtype=np.int64)
+    x = int(medoids(q, 2, 0)["rec"][0, 0])
+    v = np.maximum(LIMIT - q[x], 0)
+    return max(int(v[l::lanes].sum()) for l in range(lanes))

@@ -25,6 +25,30 @@ def order(A, p, seed=11):
     return o
 
 
+def _mix_u64(z):
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def orders(A, first, n, seed=11):
+    """(n, A) int32: row i = order(A, first + i, seed), first >= 1 -- the same swap sequence with the n generators stepped together in
+    uint64 arrays (products wrap modulo 2^64), for rows too long for the Python-integer loop of order() (tests/test_trait.py checks
+    that the two agree)"""
+    assert first >= 1
+    o = np.tile(np.arange(A, dtype=np.int32), (n, 1))
+    with np.errstate(over="ignore"):
+        x = _mix_u64(np.uint64((seed & 0xFFFFFFFF) << 32) | np.arange(first, first + n, dtype=np.uint64))
+        rows = np.arange(n)
+        for i in range(A - 1, 0, -1):
+            x = x + np.uint64(0x9E3779B97F4A7C15)
+            j = (_mix_u64(x) % np.uint64(i + 1)).astype(np.int64)
+            oi = o[:, i].copy()
+            o[:, i] = o[rows, j]
+            o[rows, j] = oi
+    return o
+
+
 def curves_one(P, o):
     """(4, A) for one order: cum = P[:, order].cumsum(1); pan = genes with cum > 0, core = cum == k, unique = cum == 1, new = diff(pan)."""
     P = np.asarray(P, dtype=bool)

@@ -4,7 +4,7 @@ GFA fixture reaches, and the numpy restatement (tests/support/qtrait_ref.py) che
 sample; where a case says so also the permuted rows and the D_p of the first batch, which come through the tests-only perm_rows and
 d_rows pointers of pga_qtrait_in_t.  Prints one line per case and "ALL OK" at the end; exits 1 at the first difference.
 
-    python tests/support/qtrait_direct.py {identity|tiles|digits|rows|batches|large|buffers|range}"""
+    python tests/support/qtrait_direct.py {identity|tiles|digits|rows|batches|large|buffers|range|limit}"""
 import ctypes as C
 import os
 import sys
@@ -191,6 +191,12 @@ def main():
         both(Q, VQ, given=(torch.from_numpy(Q).cuda(), torch.from_numpy(VQ).cuda()), n_perm=300)
         lib.pg_trim_host_cache(0)  # gives the buffers back; the next call allocates again
         both(ar.planted(500, 300, 99), vals(300, 9), n_perm=100, min_count=3)
+    elif which == "limit":
+        # N at its limit: every digit the planes can hold, int32 accumulators over 32 000 columns, the largest |D| (qtrait_ref.limit_inputs)
+        for label, B, c2 in qr.limit_inputs():
+            got = check(lib, B, c2, qr.LIMIT_PERM, label, rows=True, d_rows=True)
+            if len(c2) == qr.LIMIT_N and (int(got["D"][0]), int(got["D"][1])) != (qr.LIMIT_N ** 2 // 4, -(qr.LIMIT_N ** 2 // 4)):
+                fail("limit: the rows of the largest and the smallest values must reach +-N^2 / 4")
     elif which == "range":
         N = 32001
         c2 = (2 * np.arange(N) - (N - 1)).clip(-32000, 32000)

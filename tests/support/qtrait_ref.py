@@ -26,6 +26,48 @@ def ranks(v):
     return c2, int((cnt ** 3 - cnt).sum())
 
 
+def ranks_sorted(v):
+    """the c2 of ranks(v) by sorting, for rows too long for its N x N comparisons (tests/test_qtrait.py checks that the two agree)"""
+    v = np.asarray(v, dtype=np.float64) + 0.0
+    _, inv, cnt = np.unique(v, return_inverse=True, return_counts=True)
+    cnt = cnt.astype(np.int64)
+    less = np.cumsum(cnt) - cnt
+    return 2 * less[inv] + cnt[inv] - len(v)
+
+
+def digits(c2):
+    """(lo, hi) of the count kernel's two signed-byte planes: c2 = 256 hi + lo, lo in [-128, 127]"""
+    c2 = np.asarray(c2, dtype=np.int64)
+    lo = ((c2 + 128) & 255) - 128
+    return lo, (c2 - lo) >> 8
+
+
+LIMIT_N = 32000   # the largest N: |c2| <= 31 999 fits two signed bytes, |D| <= N^2 / 4 < 2^30
+LIMIT_PERM = 130  # a full 128-permutation tile and two rows of a second
+
+
+def limit_inputs():
+    """[(label, B (130, N) bool, c2 (N,) int64)]: the inputs of the `limit` cases.
+      N = 32 000 without ties: c2 takes every odd value in +-31 999, so hi reaches +-125 and lo, odd like c2, -127 and 127.  Row 0 holds
+        exactly the 16 000 largest values (|D| = 16 000^2 = 2.56e8, the largest the definition allows), row 1 the smallest, row 2 every
+        column of even index, row 3 is empty, row 4 full, the others have random densities.
+      N = 31 999 without ties: every even value in +-31 998, so lo reaches -128 (and 126), hi +-125 again.
+      N = 31 999 with three tie groups of 10 000, 11 000 and 10 999 columns."""
+    out = []
+    for N, ties in ((LIMIT_N, False), (LIMIT_N - 1, False), (LIMIT_N - 1, True)):
+        rng = np.random.default_rng(N + ties)
+        if not ties:
+            c2 = 2 * rng.permutation(N).astype(np.int64) - (N - 1)
+        else:
+            c2 = ranks_sorted(rng.permutation(np.repeat([1.0, 2.0, 3.0], [10000, 11000, 10999])))
+        B = rng.random((130, N)) < rng.random((130, 1))
+        B[0], B[1] = c2 > 0, c2 < 0
+        B[2] = np.arange(N) % 2 == 0
+        B[3], B[4] = False, True
+        out.append(("limit N=%d%s" % (N, ", ties" if ties else ""), B, c2))
+    return out
+
+
 _rows_cache = {}
 
 
@@ -34,6 +76,8 @@ def perm_rows(c2, n, seed=11, first=1):
     that the cases of a test which share them compute each order once."""
     c2 = np.asarray(c2, dtype=np.int64)
     N = len(c2)
+    if N >= trait_ref.LONG_ROW and n:
+        return c2[trait_ref.long_orders(N, first, n, seed)]
     key = (c2.tobytes(), seed)
     have = _rows_cache.get(key, np.empty((0, N), dtype=np.int64))
     need = first - 1 + n

@@ -3,7 +3,7 @@ the test can bound them with a timeout.  The product library (HIP kernels) runs 
 restatement (tests/support/trait_ref.py) checks a, s and k of every gene and trait completely, never a sample.  Prints one line per
 case and "ALL OK" at the end; exits 1 at the first difference.
 
-    python tests/support/trait_direct.py {large|batches|sizes|rows|edges} [--cpu-only]
+    python tests/support/trait_direct.py {large|batches|sizes|rows|edges|wide} [--cpu-only]
 
 --cpu-only runs the checker build against the restatement instead (to see that the cases stay affordable without a GPU)."""
 import ctypes as C
@@ -137,6 +137,23 @@ def main():
                 got = capi.pan_trait(ora, P, y, n_perm=129, seed=5)
                 assert all(np.array_equal(got[key], want[key]) for key in want), "checker build differs"
         del os.environ["PANGENE_TRAIT_BATCH"]
+    elif which == "wide":
+        # thresholds whose 64-bit products pass 2^31, equality on either side, D = 0 and the largest |D| (trait_ref.wide_inputs); 70 000
+        # dependent swaps a lane in the global-memory form of the permutation kernel, whose rows are compared as well
+        import oracle_host
+        ora = oracle_host.load()
+        for label, P, y, must in tr.wide_inputs():
+            want = check(lib, P, y, label, n_perm=tr.WIDE_PERM)
+            assert all(int(want["k"][0, g]) == k for g, k in must.items()), "the restatement misses a count the input was built for"
+            if not cpu_only:
+                got = capi.pan_trait(ora, P, y, n_perm=tr.WIDE_PERM)
+                assert all(np.array_equal(got[key], want[key]) for key in want), "checker build differs"
+                t0 = time.perf_counter()
+                rows = perm_rows(lib, (y != 0).astype(np.uint8), tr.WIDE_PERM, 11)
+                ok = np.array_equal(rows, tr.pack(tr.perm_labels(y, tr.WIDE_PERM, 11)))
+                print("%s: %d permuted rows, library %.2f s: %s" % (label, tr.WIDE_PERM, time.perf_counter() - t0, "ok" if ok else "DIFFERENT"), flush=True)
+                if not ok:
+                    sys.exit(1)
     elif which == "rows":
         # the permuted label rows themselves: pins the device's 64-bit %
         assert not cpu_only

@@ -13,12 +13,25 @@ HEADER = "Trait\tGene\tN\tnT\tnG\tnTG\tphi\tp_fisher\tq_bh\tn_ge\tp_perm"
 INT_COLS = ("N", "nT", "nG", "nTG", "n_ge")
 FLOAT_COLS = ("phi", "p_fisher", "q_bh")
 BLOCK = 4096
+LONG_ROW = 8192  # columns from which the orders come from curves_ref.orders (all of a block at once) instead of curves_ref.order
+_long_orders = {}
+
+
+def long_orders(N, first, n, seed):
+    """curves_ref.orders(N, first, n, seed); the last result is kept, so that the checks of one input compute its orders once"""
+    key = (N, first, n, seed)
+    if key not in _long_orders:
+        _long_orders.clear()
+        _long_orders[key] = curves_ref.orders(N, first, n, seed)
+    return _long_orders[key]
 
 
 def perm_labels(y, n, seed=11, first=1):
     """(n, N) uint8: row i = the labels under permutation first + i, y_p[r] = y[o_p[r]]"""
     y = np.asarray(y, dtype=np.uint8)
     N = len(y)
+    if N >= LONG_ROW and n:
+        return y[long_orders(N, first, n, seed)]
     Y = np.empty((n, N), dtype=np.uint8)
     for i in range(n):
         Y[i] = y[np.asarray(curves_ref.order(N, first + i, seed), dtype=np.int64)] if N else y
@@ -77,6 +90,40 @@ def pan_trait(P, labels, n_perm=1000, seed=11, min_count=1):
         out["a"][ti] = np.where(el, a, -1)
         out["s"][ti] = np.where(el, s, 0)
         out["k"][ti] = np.where(el, k, 0)
+    return out
+
+
+WIDE_PERM = 70  # two waves' worth of lanes in the permutation kernel
+
+
+def wide_inputs():
+    """[(label, P (130, N) bool, y (N,) int8, {row: k it must get})]: the inputs of the `wide` cases, where the 64-bit products of the
+    thresholds lo = floor((a t - |D|) / N), hi = ceil((a t + |D|) / N) pass 2^31.
+      N = 70 001 (a prime; 2 188 words, the last partial), t = 35 000: 100 rows of density 0.1 .. 0.9, 26 of density 0.88 .. 0.995 (a t
+        and s N above 2^31), an empty row, a full one (not eligible), the label row itself (|D| at its maximum t (N - t), lo = -1)
+        and its complement (D = -t (N - t)).
+      N = 70 000, t = 35 000: a t - |D| = N min(s, a - s) and a t + |D| = N max(s, a - s), so every row sits on equality on BOTH sides
+        (a permutation with s_p = lo exactly is a hit); row 0 has a = 40 000, s = 20 000, D = 0 exactly: every permutation is a hit."""
+    out = []
+    for N in (70001, 70000):
+        rng = np.random.default_rng(N)
+        t = 35000
+        y = np.zeros(N, dtype=np.int8)
+        y[rng.permutation(N)[:t]] = 1
+        dens = np.concatenate([np.linspace(0.1, 0.9, 100), np.linspace(0.88, 0.995, 26)])
+        P = np.zeros((130, N), dtype=bool)
+        P[:126] = rng.random((126, N)) < dens[:, None]
+        P[127] = True
+        P[128] = y != 0
+        P[129] = y == 0
+        must = {}
+        if N == 70000:
+            ones, zeros = np.nonzero(y != 0)[0], np.nonzero(y == 0)[0]
+            P[0] = False
+            P[0, ones[:20000]] = True
+            P[0, zeros[:20000]] = True
+            must[0] = WIDE_PERM
+        out.append(("wide N=%d" % N, P, y, must))
     return out
 
 

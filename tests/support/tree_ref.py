@@ -31,12 +31,14 @@ def fixed(S, metric):
 
 def joins(q, method, stats=None):
     """The records (int64, (A - 2, 6) for nj, (A - 1, 6) for upgma) of a symmetric matrix q with a zero diagonal, A >= 3.
-    stats, a dict, receives n_tied: the joins whose smallest criterion was reached by more than one live pair."""
+    stats, a dict, receives n_tied: the joins whose smallest criterion was reached by more than one live pair, and peak: the largest
+    size of a distance, the input's included (set before a RangeError is raised, so that a search can see how far a run went)."""
     d = np.array(q, dtype=np.int64)
     A = d.shape[0]
     live = np.arange(A)
     size = np.ones(A, dtype=np.int64)
     rec, n_tied = [], 0
+    peak = int(np.abs(d).max())
     nj = method == "nj"
     while len(live) > (3 if nj else 1):
         r = len(live)
@@ -55,7 +57,11 @@ def joins(q, method, stats=None):
             new = (d[i, others] + d[j, others] - dij) >> 1
         else:
             new = (size[i] * d[i, others] + size[j] * d[j, others]) // (size[i] + size[j])
-        if new.size and int(np.abs(new).max()) >= LIMIT:
+        if new.size:
+            peak = max(peak, int(np.abs(new).max()))
+            if stats is not None:
+                stats["peak"] = peak
+        if peak >= LIMIT:
             raise RangeError("join")
         d[i, others] = new
         d[others, i] = new
@@ -65,7 +71,7 @@ def joins(q, method, stats=None):
         x, y, z = (int(v) for v in live)
         rec.append((x, y, z, int(d[x, y]), int(d[x, z]), int(d[y, z])))
     if stats is not None:
-        stats["n_tied"] = n_tied
+        stats["n_tied"], stats["peak"] = n_tied, peak
     return np.array(rec, dtype=np.int64).reshape(-1, 6)
 
 
@@ -124,3 +130,43 @@ def lineage_presence(M, A, seed, founders=4, flip=0.02, dup=0.15):
         else:
             P[:, a] = base[:, rng.integers(0, founders)] ^ (rng.random(M) < flip)
     return P
+
+
+IN_MAX = (1 << 29) - 1  # the largest size of an input entry
+SIGNED_SIZES = (3, 4, 5, 63, 65, 129, 257)
+
+
+def signed_matrix(n, seed):
+    """(n, n) int32: symmetric, zero diagonal, entries uniform in [-(2^29 - 1), 2^29 - 1] -- both signs at the full magnitude the
+    definition admits, so that floor(x / 2) and the floored division of UPGMA meet negative sums from the first join on"""
+    rng = np.random.default_rng(seed)
+    a = np.triu(rng.integers(-IN_MAX, IN_MAX + 1, size=(n, n)), 1)
+    return (a + a.T).astype(np.int32)
+
+
+def peak_search(seed=1, steps=400, n=5):
+    """(q, peak, leaving): a hill-climb over n x n signed matrices for a neighbour-joining run that comes as near to the range limit
+    2^30 as it can WITHOUT leaving the range: one entry (and its mirror) is redrawn or set to +-(2^29 - 1) per step, and the step is
+    kept when the run's peak does not fall.  leaving: the first matrix met whose run leaves the range (RangeError), or None."""
+    rng = np.random.default_rng(seed)
+    q = signed_matrix(n, seed).astype(np.int64)
+
+    def run(m):
+        st = {}
+        try:
+            joins(m, "nj", st)
+        except RangeError:
+            return None
+        return st["peak"]
+    best, leaving = run(q), None
+    assert best is not None
+    for _ in range(steps):
+        i, j = sorted(rng.choice(n, size=2, replace=False).tolist())
+        c = q.copy()
+        c[i, j] = c[j, i] = int(rng.choice([IN_MAX, -IN_MAX, int(rng.integers(-IN_MAX, IN_MAX + 1))]))
+        got = run(c)
+        if got is None:
+            leaving = c.astype(np.int32) if leaving is None else leaving
+        elif got >= best:
+            q, best = c, got
+    return q.astype(np.int32), best, leaving

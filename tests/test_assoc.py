@@ -31,13 +31,7 @@ def ora(built):
     return oracle_host.load()
 
 
-def two_rows(A, a, b, s):
-    """(2, A) bool: |B_0| = a, |B_1| = b, |B_0 & B_1| = s"""
-    assert s <= min(a, b) and a + b - s <= A
-    P = np.zeros((2, A), dtype=bool)
-    P[0, :a] = True
-    P[1, a - s:a - s + b] = True
-    return P
+two_rows = ar.two_rows
 
 
 def test_hand_worked_boundary(ora):
@@ -61,25 +55,7 @@ def test_hand_worked_boundary(ora):
     assert capi.pan_assoc(ora, Z, min_phi=0.0, sign="neg")[0].shape == (0, 3)
 
 
-def exact_threshold_cases(max_A=40):
-    """(A, a, b, s, p) with 10^6 D^2 = p^2 V_g V_h exactly and p not a multiple of 100"""
-    from math import isqrt
-    out = []
-    for A in range(4, max_A + 1):
-        for a in range(2, A - 1):
-            for b in range(a, A - 1):
-                VV = a * (A - a) * b * (A - b)
-                for s in range(max(0, a + b - A), min(a, b) + 1):
-                    D = s * A - a * b
-                    if D == 0:
-                        continue
-                    n = 10 ** 6 * D * D
-                    if n % VV:
-                        continue
-                    p = isqrt(n // VV)
-                    if p * p == n // VV and 0 < p < 1000 and p % 100:
-                        out.append((A, a, b, s, p))
-    return out
+exact_threshold_cases = ar.exact_threshold_cases
 
 
 def test_exact_threshold_cases(ora):
@@ -226,3 +202,54 @@ def test_torch_input(ora):
     assert len(b[0]) > 0 and np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
     c = capi.pan_assoc(ora, torch.from_numpy(P).to(torch.uint8), 0.6, sign="neg")
     assert np.array_equal(c[0], ar.select(P, 0.6, 2, "neg")[0])
+
+
+def test_tie_tiles(ora):
+    """the matrices of the `threshold` GPU cases (assoc_ref.tie_tiles): every cross pair exactly on the threshold -- selected at p and at
+    p - 1 with its s, not at p + 1, under the signs that admit its D; the identical rows always, unless the sign is neg"""
+    from pangene_amd import capi
+    tiles = ar.tie_tiles()
+    assert len(tiles) == 8 and {t[2] for t in tiles} == set(ar.TIE_P) and {t[3] for t in tiles} == {1, -1}
+    for label, P, p, side, cross, same in tiles:
+        G, A = P.shape
+        cnt = P.sum(axis=1, dtype=np.int64)
+        s = int((P[0] & P[G // 2 if G == 256 else 1]).sum())
+        assert A == 4000 and (cnt == 2000).all() and s == 1000 + side * p
+        assert 10 ** 6 * (s * A - 2000 * 2000) ** 2 == p * p * (2000 * 2000) ** 2
+        for at in (p, p + 1, p - 1):
+            assert ar.permille(at / 1000.0) == at
+            for sign in ar.SIGNS:
+                want, _ = ar.select(P, at / 1000.0, 2, sign)
+                assert len(want) == ar.tie_count(p, side, cross, same, at, sign), (label, at, sign)
+                got, phi = capi.pan_assoc(ora, P, at / 1000.0, 2, sign)
+                assert got.shape == want.shape and np.array_equal(got, want) and np.array_equal(phi, ar.phi(want, cnt, A)), (label, at, sign)
+        if side * p > 0:
+            assert set(ar.select(P, p / 1000.0, 2, "pos")[0][:, 2].tolist()) == {2000, s}
+
+
+@pytest.mark.parametrize("p,least", [(337, (2, 2, 2, 1)), (801, (0, 2, 2, 0))])
+def test_band_cases(ora, p, least):
+    """the cases of the `band337` / `band801` GPU groups (assoc_ref.band_cases) at A = 16 777 215: the search finds pairs on the threshold,
+    just above and just below it and with D < 0 (p = 337 alone has at least 2, 2, 2 and 1 of them; no pair sits exactly on 0.801), all
+    strictly inside the device's guard band; the checker build decides every one of them as the exact integers do, at p and at p + 1"""
+    from fractions import Fraction
+    import assoc_direct
+    cases = ar.band_cases(p)
+    A = ar.MAX_ASM
+    for _, a, s, cmp in cases:
+        D, V = s * A - a * a, a * (A - a)
+        assert 0 <= s <= a and 2 * a - s <= A and abs(Fraction(10 ** 6 * D * D, p * p * V * V) - 1) < Fraction(1, 2 ** 41)
+        assert cmp == (10 ** 6 * D * D > p * p * V * V) - (10 ** 6 * D * D < p * p * V * V)
+    found = (sum(c[3] == 0 for c in cases), sum(c[3] > 0 for c in cases), sum(c[3] < 0 for c in cases), sum(c[2] * A < c[1] * c[1] for c in cases))
+    assert all(f >= l for f, l in zip(found, least)), found
+    for _, a, s, cmp in cases:
+        assoc_direct.check_band([ora], p, a, s, cmp)
+
+
+def test_band_expected_is_what_select_gives():
+    """the records worked out from (a, s) alone against the restatement itself at 16 777 215 columns, for one pair below the threshold"""
+    a, s = 8234022, 7399639
+    for at in (800, 801):
+        want, cnt = ar.select(ar.band_matrix(a, s) != 0, at / 1000.0, 2)
+        pairs, phi = ar.band_expected(a, s, at)
+        assert len(want) == (6 if at == 800 else 2) and np.array_equal(want, pairs) and np.array_equal(ar.phi(want, cnt, ar.MAX_ASM), phi)

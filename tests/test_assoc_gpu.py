@@ -81,12 +81,15 @@ def test_too_many_pairs(built, tmp_path):
     assert rc == 0 and out.count(b"\n") == 7
 
 
-@pytest.mark.parametrize("which", ["large", "wide", "sizes", "edges"])
+@pytest.mark.parametrize("which", ["large", "wide", "sizes", "edges", "threshold", "band337", "band801"])
 def test_direct_cases(built, which):
     """pg_pan_assoc on matrices no GFA fixture reaches, compared completely with the checker build and the restatement
     (tests/support/assoc_direct.py): G = 20 003 x A = 1 001 with planted modules, the forced second run and a cuda tensor (large);
     G = 70 001 and G = 1 000 003 rows, beyond the row limit of pan_shared (wide); growing and shrinking sizes that reuse the cached
-    buffers, one of them with 6.7 M selected pairs (sizes)"""
+    buffers, one of them with 6.7 M selected pairs (sizes); every slot of an off-diagonal and of a diagonal tile exactly on the threshold, one
+    permille below and above it, on either side of D = 0 and under every sign, and the exact small cases of tests/test_assoc.py
+    (threshold); every pair the search of assoc_ref.band_search finds inside the guard band at A = 16 777 215, on, above and below the
+    threshold, at p and p + 1 (band337, band801)"""
     r = subprocess.run([sys.executable, DIRECT, which], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900, cwd=ROOT)
     out = r.stdout.decode(errors="replace")
     assert r.returncode == 0 and out.rstrip().endswith("ALL OK"), out[-3000:]

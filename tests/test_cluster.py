@@ -281,3 +281,27 @@ def test_usage(built):
     assert rc == 0 and out.startswith(b"Usage: pangene cluster -k INT[-INT] [options] <in.gfa>\n") and b"mean silhouette" in out
     rc, _, err = run_cli([])
     assert b"pangene cluster [-t gene|adj]" in err and b"--cluster=INT[-INT]" in err
+
+
+def test_magnitude_inputs(ora):
+    """the matrices of the `magnitude` GPU cases (cluster_ref.magnitude_inputs): entries up to 2^29 - 1, td, sums and gains beyond 2^32, the largest of them beyond 2^35 (2^37 from n = 513 on),
+    the swaps the structured ones were built for, a lane's share of one gain beyond 2^31; the checker build gives what the restatement
+    gives"""
+    from pangene_amd import capi
+    inputs = cr.magnitude_inputs()
+    assert [(q.shape[0], k) for _, q, k, _ in inputs] == list(cr.MAGNITUDE_RANDOM) + [c[:2] for c in cr.MAGNITUDE_PLANTED]
+    for label, q, k, swaps in inputs:
+        n = q.shape[0]
+        assert n >= 257 and np.array_equal(q, q.T) and not np.diag(q).any() and 1 << 28 < int(q.max()) < cr.LIMIT
+        if label == "uniform":
+            assert int(q[~np.eye(n, dtype=bool)].min()) >= 1 << 28
+        want = cr.medoids(q, k)
+        assert want["converged"] == 1 and (swaps is None or want["n_swap"] >= swaps), (label, n, k, want["n_swap"])
+        sizes = (int(want["td"]), int(want["sums"].max()), int(want["rec"][0, 2]))
+        assert min(sizes) > 1 << 32 and max(sizes) > 1 << (37 if n >= 513 else 35), (label, n, k, sizes)
+        assert cr.same(capi.pan_medoids(ora, q, k), want), (label, n, k)
+    assert sum(w["n_swap"] for w in (cr.medoids(q, k) for label, q, k, _ in inputs if label == "planted")) >= 6
+    assert cr.first_gain_parts(inputs[-1][1]) >= 1 << 31
+    n, k = cr.MAGNITUDE_CHECKER
+    q = cr.full_random(n, n + k)
+    assert cr.same(capi.pan_medoids(ora, q, k), cr.medoids(q, k))

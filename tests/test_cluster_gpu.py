@@ -78,11 +78,12 @@ def test_refused_when_sharded(built):
     assert rc == 1 and out == b"" and b"--cluster" in err
 
 
-@pytest.mark.parametrize("which", ["sizes", "large", "uneven", "ties", "chunks", "cached"])
+@pytest.mark.parametrize("which", ["sizes", "large", "uneven", "ties", "chunks", "cached", "magnitude"])
 def test_direct_cases(built, which):
     """pg_pan_medoids on matrices no GFA fixture reaches (tests/support/cluster_direct.py): sizes across a wave and the tiles of
     candidates against the restatement; 1 025 columns and k = 1 024 against the checker build; one huge cluster with one row a chunk;
-    all-equal distances and copies of columns; the iteration chunks at 1, 8 and 3; growing and shrinking sizes on the cached buffers"""
+    all-equal distances and copies of columns; the iteration chunks at 1, 8 and 3; growing and shrinking sizes on the cached buffers;
+    entries in the upper half of the range at 257 to 1 281 columns, where every sum needs 64 bits (magnitude)"""
     r = subprocess.run([sys.executable, DIRECT, which], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=180, cwd=ROOT)
     out = r.stdout.decode(errors="replace")
     assert r.returncode == 0 and out.rstrip().endswith("ALL OK"), out[-3000:]

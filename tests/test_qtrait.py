@@ -311,3 +311,38 @@ def test_pan_qtrait_arguments(ora):
     W[0, 3] = np.inf
     with pytest.raises(ValueError):
         capi.pan_qtrait(ora, P, W)
+
+
+def test_ranks_by_sorting_are_the_ranks():
+    for seed, ties in ((1, False), (2, True), (3, True)):
+        rng = np.random.default_rng(seed)
+        v = rng.normal(size=301)
+        if ties:
+            v = np.round(v * seed)
+            v[:3] = (0.0, -0.0, 0.0)
+        assert np.array_equal(qr.ranks_sorted(v), qr.ranks(v)[0])
+
+
+def test_limit_inputs(ora):
+    """the inputs of the `limit` GPU cases (qtrait_ref.limit_inputs) meet their own conditions -- hi = +-125 and lo = -128 and 127, the
+    ends of the two signed-byte planes (an odd c2 has an odd lo, so the two ends of lo need both parities of N), the largest |D| of
+    the definition, three tie groups -- and the checker build gives what the restatement gives.  (The
+    checker build reads values, not ranks: the values are the ranks themselves.)"""
+    from pangene_amd import capi
+    for label, B, c2 in qr.limit_inputs():
+        N = len(c2)
+        lo, hi = qr.digits(c2)
+        assert np.array_equal(256 * hi + lo, c2) and int(c2.sum()) == 0 and int(np.abs(c2).max()) <= qr.LIMIT_N - 1, label
+        if "ties" not in label:
+            # every value of the parity of N - 1: the odd ones reach lo = 127 (and -127), the even ones lo = -128 (and 126)
+            assert sorted(c2.tolist()) == list(range(-(N - 1), N, 2))
+            assert (int(hi.max()), int(hi.min()), int(lo.min()), int(lo.max())) == ((125, -125, -127, 127) if N == qr.LIMIT_N else (125, -125, -128, 126))
+        else:
+            assert len(set(c2.tolist())) == 3 and np.array_equal(c2, qr.ranks_sorted(c2))
+        a, D, k, el, first = qr.counts(B, c2, qr.LIMIT_PERM, d_rows=qr.LIMIT_PERM)
+        if N == qr.LIMIT_N:
+            assert int(D[0]) == N * N // 4 == -int(D[1]) and int(a[0]) == N // 2 and 2 ** 27 < N * N // 4 < 2 ** 30
+        assert int(a[3]) == 0 and int(a[4]) == N and not first[:, 3:5].any() and int(k.sum()) > 0 and int(k[0]) == 0, label
+        got = capi.pan_qtrait(ora, B, c2.astype(np.float64), n_perm=qr.LIMIT_PERM)
+        assert np.array_equal(got["a"][0], np.where(el, a, -1)) and np.array_equal(got["D"][0], np.where(el, D, 0)), label
+        assert np.array_equal(got["k"][0], k), label

@@ -76,7 +76,7 @@ def test_refused_when_sharded(built):
     assert rc == 1 and out == b"" and b"--qtrait" in err
 
 
-@pytest.mark.parametrize("which", ["identity", "tiles", "digits", "rows", "batches", "large", "buffers", "range"])
+@pytest.mark.parametrize("which", ["identity", "tiles", "digits", "rows", "batches", "large", "buffers", "range", "limit"])
 def test_direct_cases(built, which):
     """pga_pan_qtrait on matrices no GFA fixture reaches (tests/support/qtrait_direct.py), a, D and k compared completely with the
     restatement.  identity: G = N = 200, gene g in column g alone, distinct values: d_rows[p][g] == perm_rows[p][g] for 130 permutations,
@@ -86,7 +86,8 @@ def test_direct_cases(built, which):
     perm_rows for N = 31, 64, 256 (LDS form), 257 and 4 200 (global form) against c2[order(N, p, seed)], which pins the device's 64-bit
     %.  batches: PANGENE_QTRAIT_BATCH=256 in the child, n = 255, 256, 257, 773.  large: G = 20 003 x N = 1 001 with a planted trait,
     n = 2 000.  buffers: growing then shrinking shapes, cuda tensors, pga_host_trim(0) and again.  range: N = 32 001 is PGA_ERR_RANGE
-    before anything is launched."""
+    before anything is launched.  limit: N = 32 000 and 31 999 without ties (hi = +-125, lo = 127 and -128, |D| = N^2 / 4) and 31 999 with
+    three tie groups, G = 130, n = 130, perm_rows and d_rows completely."""
     env = dict(os.environ)
     env.pop("PANGENE_QTRAIT_BATCH", None)
     if which == "batches":

@@ -288,3 +288,33 @@ def test_pan_trait_arguments(ora):
             capi.pan_trait(ora, P, L, **kw)
     with pytest.raises(ValueError):
         capi.pan_trait(ora, P, L[:, :39])
+
+
+def test_orders_stepped_together_are_the_orders():
+    """curves_ref.orders (uint64 arrays, a block of permutations at once), which the restatement uses for long rows, against
+    curves_ref.order (Python integers): lengths around a word, first > 1, the largest seed"""
+    import curves_ref
+    for A, first, n, seed in ((1, 1, 3, 11), (2, 1, 4, 11), (33, 7, 3, 0xFFFFFFFF), (1000, 1, 5, 11), (4097, 65536, 2, 5)):
+        O = curves_ref.orders(A, first, n, seed)
+        assert O.shape == (n, A) and all(O[i].tolist() == curves_ref.order(A, first + i, seed) for i in range(n)), (A, first, n, seed)
+
+
+def test_wide_thresholds(ora):
+    """the inputs of the `wide` GPU cases (trait_ref.wide_inputs) meet their own conditions -- products above 2^31, the largest |D|,
+    D = 0, equality on the lo side -- and the checker build gives what the restatement gives"""
+    from pangene_amd import capi
+    for label, P, y, must in tr.wide_inputs():
+        N, t = len(y), int(y.sum())
+        a = P.sum(axis=1, dtype=np.int64)
+        s = (P & (y != 0)[None, :]).sum(axis=1, dtype=np.int64)
+        c, d = a * t, np.abs(s * N - a * t)
+        assert N > 65536 and t == 35000 and int((c >= 2 ** 31).sum()) >= 20 and int((s * N >= 2 ** 31).sum()) >= 20, label
+        assert d[128] == t * (N - t) == d[129] and int(d.max()) == t * (N - t) and (c[128] - d[128]) // N in (-1, 0), label
+        if N == 70000:
+            assert d[0] == 0 and must == {0: tr.WIDE_PERM} and bool(((c - d) % N == 0).all()), label
+        want = tr.pan_trait(P, y, n_perm=tr.WIDE_PERM)
+        got = capi.pan_trait(ora, P, y, n_perm=tr.WIDE_PERM)
+        assert all(int(want["k"][0, g]) == k for g, k in must.items()), label
+        assert 0 < int(want["k"].sum()) and int(want["k"][0, 128]) < tr.WIDE_PERM, label
+        for key in ("N", "t", "a", "s", "k"):
+            assert got[key].shape == (1, 130) and np.array_equal(got[key], want[key]), (label, key)

@@ -91,14 +91,15 @@ def test_refused_when_sharded(built):
     assert rc == 1 and out == b"" and b"--trait" in err
 
 
-@pytest.mark.parametrize("which", ["large", "batches", "sizes", "rows", "edges"])
+@pytest.mark.parametrize("which", ["large", "batches", "sizes", "rows", "edges", "wide"])
 def test_direct_cases(built, which):
     """pg_pan_trait on matrices no GFA fixture reaches, a, s and k compared completely with the restatement
     (tests/support/trait_direct.py): G = 20 003 x A = 1 001 with planted traits, n = 2 000 (large); n = one batch - 1, one batch, one
     batch + 1 and three batches + 5, the batch read from the library (batches); N = 4 200, past the LDS form of k_trait_perm, then
     growing and shrinking shapes that reuse the cached buffers, cuda tensors among them (sizes); the permuted label rows of the first
     batch themselves for N = 31, 64, 1 000 and 4 200 against y[order(N, p, seed)], which pins the device's 64-bit % (rows; the rows
-    come through the tests-only perm_rows pointer of pga_trait_in_t)"""
+    come through the tests-only perm_rows pointer of pga_trait_in_t); N = 70 001 and 70 000 with t = 35 000, where the products of
+    the thresholds pass 2^31, with the label row itself, D = 0 and every row on equality, and the 70 permuted rows themselves (wide)"""
     r = subprocess.run([sys.executable, DIRECT, which], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900, cwd=ROOT)
     out = r.stdout.decode(errors="replace")
     assert r.returncode == 0 and out.rstrip().endswith("ALL OK"), out[-3000:]

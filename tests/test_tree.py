@@ -252,3 +252,35 @@ def test_usage(built):
     assert rc == 0 and out.startswith(b"Usage: pangene tree [options] <in.gfa>\n") and b"negative branch lengths" in out
     rc, _, err = run_cli([])
     assert b"pangene tree [-t gene|adj]" in err and b"--tree[=STR]" in err
+
+
+@pytest.mark.parametrize("n", tr.SIGNED_SIZES)
+def test_signed_matrices(ora, n):
+    """the matrices of the `signed` GPU cases: entries of either sign up to 2^29 - 1 in size; floor(x / 2) and the floored division of
+    UPGMA on negative sums, in the checker build as in the restatement"""
+    from pangene_amd import capi
+    q = tr.signed_matrix(n, n)
+    assert np.array_equal(q, q.T) and not np.diag(q).any() and int(np.abs(q).max()) <= tr.IN_MAX
+    if n >= 63:
+        assert int(q.min()) < -(1 << 28) and int(q.max()) > 1 << 28 and int(np.abs(q).max()) > tr.IN_MAX - (1 << 20)
+    for method in tr.METHODS:
+        stats = {}
+        want = tr.joins(q, method, stats)
+        if n >= 63:  # joined distances below zero, and under nj a run that leaves the input's range
+            assert int(want[:n - 3, 2].min()) < 0 and (method == "upgma" or stats["peak"] > 1 << 29)
+        assert np.array_equal(capi.pan_join(ora, q, method), want), method
+
+
+def test_peak_below_the_range_limit(ora):
+    """the hill-climb of tree_ref.peak_search: a neighbour-joining run over 5 slots that peaks within 2^20 of the range limit 2^30 and
+    stays inside; the checker build gives the restatement's records"""
+    from pangene_amd import capi
+    q, peak, leaving = tr.peak_search()
+    stats = {}
+    want = tr.joins(q, "nj", stats)
+    assert (1 << 30) - (1 << 20) <= peak == stats["peak"] < 1 << 30 and int(np.abs(q).max()) <= tr.IN_MAX
+    assert np.array_equal(capi.pan_join(ora, q, "nj"), want)
+    assert np.array_equal(capi.pan_join(ora, q, "upgma"), tr.joins(q, "upgma"))
+    if leaving is not None:
+        with pytest.raises(RuntimeError, match="status -2"):
+            capi.pan_join(ora, leaving, "nj")

@@ -65,11 +65,12 @@ def test_refused_when_sharded(built):
     assert rc == 1 and out == b"" and b"--tree" in err
 
 
-@pytest.mark.parametrize("which", ["sizes", "large", "cached", "equal", "presence", "parts"])
+@pytest.mark.parametrize("which", ["sizes", "large", "cached", "equal", "presence", "parts", "signed"])
 def test_direct_cases(built, which):
     """pg_pan_join on matrices no GFA fixture reaches, for both methods: sizes across the kernels' wave, tile and workgroup boundaries
     against the restatement, 1 025 and 2 049 against the checker build, a run of growing and shrinking sizes on the cached buffers,
-    all-equal distances, pg_pan_tree from presence bytes, and a search whose workgroups stride over several tiles
+    all-equal distances, pg_pan_tree from presence bytes, a search whose workgroups stride over several tiles, and (signed) entries of
+    either sign up to 2^29 - 1, a run that peaks three below the range limit, and the device's own input flag through pga_pan_join
     (tests/support/tree_direct.py)"""
     r = subprocess.run([sys.executable, DIRECT, which], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600, cwd=ROOT)
     out = r.stdout.decode(errors="replace")
