@@ -422,6 +422,43 @@ int  pg_qtrait_file(const char *gfa_fn, const char *trait_fn, const pg_qtrait_op
 void pg_write_qtrait(pg_graph_t *g, const char *trait_fn, const pg_qtrait_opt_t *o);
 int  pg_pan_qtrait(const uint8_t *presence, const double *values, int32_t n_gene, int32_t n_asm, int32_t n_trait, const pg_qtrait_opt_t *o, int32_t *out);
 
+/* PERMANOVA: do the two groups of a binary trait differ in gene content as a whole -- the two-group permutational multivariate analysis
+ * of variance (Anderson 2001; adonis2 of vegan) over the fixed-point distances of pg_tree_* / pg_cluster_* (jaccard or diff with F
+ * fraction bits; shared is refused), with the trait file and the permutations of pg_trait_*.  DESIGN.md section 8 "PERMANOVA" holds the
+ * definition.  Per trait the columns with a value are compacted, in matrix order, to N columns with labels y, n1 = sum y, n0 = N - n1,
+ * and qc is the N x N submatrix of the distances.  A trait with N < 3, n1 = 0 or n0 = 0, and a trait whose qc is all zero, prints a note
+ * on stderr and no line.  Scaling: m = max qc, s the smallest s >= 0 with (m >> s)^2 N (N - 1) < 2^62, e = qc >> s, Fe = F - s,
+ * w = e^2 (int64, zero diagonal).  r[i] = sum_j w[i][j], T = sum r, A(y) = sum over ordered pairs of y_i y_j w[i][j], B(y) = sum y_i r[i],
+ * all below 2^62; SST = T / (2 N), SSW = A / (2 n1) + (T - 2 B + A) / (2 n0), and G(y) = N A - 2 n1 B (128 bits) orders SSW:
+ * 2 n0 n1 SSW = G + n1 T.  Permutation p = 1 .. n_perm is y_p[r] = y[o_p[r]], o_p = order p of N columns exactly as pg_trait_* define it;
+ * k = #{p : G(y_p) <= G(y)}, the permutations whose pseudo-F is at least the observed one (ties count) -- integers throughout.
+ * Output, tab-separated: "Trait N n1 n0 Fbits SS_total SS_within F R2 n_ge p_perm", one line per trait in file order: Fbits = Fe;
+ * SS_total = SST / 4^Fe and SS_within = SSW / 4^Fe as %.6f; F = (SST - SSW) (N - 2) / SSW as %.6f, inf when SSW = 0;
+ * R2 = 1 - SSW / SST as %.4f; n_ge = k; p_perm = (k + 1) / (n_perm + 1) as %.6f, NA with n_perm = 0.  Each double is ONE long double
+ * division of two 128-bit integers: with X = G + n1 T and Y = T n0 n1 - N X, SS_total = T / (2 N), SS_within = X / (2 n0 n1) (both then
+ * scaled by the power of two), F = Y (N - 2) / (N X), R2 = Y / (T n0 n1).
+ * At most 16 384 columns with a value per trait (PGA_ERR_RANGE).
+ * pg_permanova_file, pg_write_permanova: as their trait twins, return codes included.  pg_pan_permanova: any fixed-point matrix
+ * q = int32 [n][n] with o->frac_bits fraction bits, symmetric, zero diagonal, no negative entry (PGA_ERR_ARG otherwise), every entry
+ * below 2^29 (PGA_ERR_RANGE), and labels, row-major int8 [n_trait][n] (1, 0, -1 = missing): fills out[n_trait][7] = N, n1, Fe, T, A, B, k
+ * (Fe = T = A = B = 0 and k = -1 for a trait that prints no line) and returns 0 or a negative PGA_ERR_*.  pg_pan_permanova_presence: a
+ * presence matrix, row-major uint8 [n_item][n_asm], through the shared-item counts and the fixed-point distances of o->metric
+ * (*frac_bits = F; o->frac_bits is not read) to the same.  The sums and k come from the backend's pga_pan_permanova.
+ * sizeof(pg_permanova_opt_t) is 20. */
+typedef struct {
+	int32_t  type;      /* PG_DIST_GENE or PG_DIST_ADJ [gene] */
+	int32_t  metric;    /* PG_DIST_JACCARD or PG_DIST_DIFF [jaccard] */
+	int32_t  n_perm;    /* permutations; 0: none [1000] */
+	uint32_t seed;      /* seed of the orders [11] */
+	int32_t  frac_bits; /* pg_pan_permanova only: the fraction bits F of q, 0 .. 30 [20] */
+} pg_permanova_opt_t;
+void pg_permanova_opt_init(pg_permanova_opt_t *o);
+int  pg_permanova_file(const char *gfa_fn, const char *trait_fn, const pg_permanova_opt_t *o);
+void pg_write_permanova(pg_graph_t *g, const char *trait_fn, const pg_permanova_opt_t *o);
+int  pg_pan_permanova(const int32_t *q, int32_t n, const int8_t *labels, int32_t n_trait, const pg_permanova_opt_t *o, int64_t *out);
+int  pg_pan_permanova_presence(const uint8_t *presence, int32_t n_item, int32_t n_asm, const int8_t *labels, int32_t n_trait, const pg_permanova_opt_t *o,
+                               int64_t *out, int32_t *frac_bits);
+
 /* Last error of the path (0 = none).  The reference aborts on invariant violations; this library
  * records a status instead, prints one line to stderr, and leaves the graph empty. */
 int         pg_last_error(void);

@@ -94,7 +94,7 @@ typedef struct {
  * Device layout limits (PGA_ERR_RANGE otherwise): coordinates inside a block < 2^31 (contigs beyond that arrive as virtual contigs,
  * see pga_genome_block_t; what remains out of reach is a single cluster of overlapping hits spanning 2^30 bp), < 2^30 hits and < 2^31
  * exons per shard, < 2^20 genes, < 2^24 genomes. */
-#define PGA_ABI_VERSION 15u  /* bumped whenever a struct of this header or the order of pga_backend_t changes; pga_create refuses another */
+#define PGA_ABI_VERSION 16u  /* bumped whenever a struct of this header or the order of pga_backend_t changes; pga_create refuses another */
 typedef struct {
 	uint32_t abi_version;        /* = PGA_ABI_VERSION of the header the caller was compiled against (PGA_ERR_ARG otherwise) */
 	int32_t n_genome;            /* genomes in this shard (may include genomes with 0 hits) */
@@ -503,6 +503,34 @@ typedef struct {
 } pga_medoids_out_t;
 int pga_pan_medoids(const pga_medoids_in_t *in, pga_medoids_out_t *out);
 
+/* PERMANOVA (include/pangene_amd.h pg_pan_permanova, pangene permanova; DESIGN.md section 8 "PERMANOVA"): do the two groups of one binary
+ * label row differ in a fixed-point distance matrix as a whole.  Context-free, like pan_trait.  Over n columns (the caller has already
+ * dropped the columns without a label) with e = q >> shift and w[i][j] = e[i][j]^2 (int64, zero diagonal): r[i] = the sum of w[i][.],
+ * T = the sum of r, A(y) = the sum of y_i y_j w[i][j] over ordered pairs, B(y) = the sum of y_i r[i], G(y) = n A(y) - 2 n1 B(y) in
+ * 128 bits.  Permutation p = 1 .. n_perm is y_p[r] = y[o_p[r]], o_p = order p of n columns exactly as pan_trait defines it, and
+ * k = #{p : G(y_p) <= G(y)}.  All integers.
+ * In:  q[n][n], symmetric, zero diagonal, 0 <= q <= q_max, and shift with (q_max >> shift)^2 n (n - 1) < 2^62, so that T, A and B stay
+ *      below 2^62 (the caller's promise: pg_pan_permanova checks the matrix and derives shift before it calls); label[(n + 31) / 32], bit c =
+ *      y_c, bits past n zero; n1 = the set bits.  a_rows, b_rows, perm_rows: NULL, or -- for tests only -- room for
+ *      min(n_perm, pga_permanova_batch()) int64 each that receive A and B of the first batch's permutations, and for as many rows of
+ *      (n + 31) / 32 words that receive its label rows.
+ * Out: t, a and b of the observed row, and k.
+ * The permutations go through in batches of pga_permanova_batch() rows; device memory is the matrix, its D <= 8 signed-byte digit
+ * planes of (n rounded up to 128)^2 bytes and the batch's rows.
+ * Limits: n >= 1, n_perm >= 0, 0 <= shift < 31, 0 <= n1 <= n (PGA_ERR_ARG otherwise); n <= 16 384, n_perm <= 2^31 - 2 (PGA_ERR_RANGE,
+ * before anything is launched). */
+typedef struct {
+	const int32_t *q;
+	const uint32_t *label;
+	int32_t n, shift, q_max, n1, n_perm;
+	uint32_t seed;
+	int64_t *a_rows, *b_rows;
+	uint32_t *perm_rows;
+} pga_permanova_in_t;
+typedef struct { int64_t t, a, b, k; } pga_permanova_out_t;
+int pga_pan_permanova(const pga_permanova_in_t *in, pga_permanova_out_t *out);
+int32_t pga_permanova_batch(void); /* permutations per batch: 16 384, or PANGENE_PERMA_BATCH */
+
 /* the same ABI as a table, so the host driver is written once */
 struct pga_branch_par_s; struct pga_loop_xchg_s;
 typedef struct {
@@ -568,6 +596,7 @@ typedef struct {
 	int  (*pan_pairs)(const pga_pairs_in_t *, pga_pairs_out_t *); /* may be NULL: the host driver then runs the same step itself */
 	int  (*pan_qtrait)(const pga_qtrait_in_t *, pga_qtrait_out_t *); /* may be NULL: the host driver then runs the same step itself */
 	int  (*pan_medoids)(const pga_medoids_in_t *, pga_medoids_out_t *); /* may be NULL: the host driver then runs the same step itself */
+	int  (*pan_permanova)(const pga_permanova_in_t *, pga_permanova_out_t *); /* may be NULL: the host driver then runs the same step itself */
 } pga_backend_t;
 
 const pga_backend_t *pga_backend(void);

@@ -557,6 +557,104 @@ def pan_cluster(lib: C.CDLL, presence, k: int, metric: str = "jaccard", max_iter
     return res, int(F.value)
 
 
+class pg_permanova_opt_t(C.Structure):
+    """PERMANOVA options (include/pangene_amd.h): items, distance, permutations, their seed, and the fraction bits of a matrix handed to
+    pg_pan_permanova."""
+    _fields_ = [("type", C.c_int32), ("metric", C.c_int32), ("n_perm", C.c_int32), ("seed", C.c_uint32), ("frac_bits", C.c_int32)]
+
+
+def permanova_opt(lib: C.CDLL, type: str = "gene", metric: str = "jaccard", n_perm: int = 1000, seed: int = 11, frac_bits: int = 20) -> pg_permanova_opt_t:
+    if type not in DIST_TYPES:
+        raise ValueError("type must be gene or adj")
+    if metric not in TREE_METRICS:
+        raise ValueError("metric must be jaccard or diff (shared is not a distance)")
+    if not 0 <= int(n_perm) <= TRAIT_MAX_PERM:
+        raise ValueError("n_perm must be in [0, 2^31 - 2]")
+    o = pg_permanova_opt_t()
+    lib.pg_permanova_opt_init(C.byref(o))
+    o.type, o.metric, o.n_perm, o.seed, o.frac_bits = DIST_TYPES.index(type), DIST_METRICS.index(metric), int(n_perm), int(seed) & 0xFFFFFFFF, int(frac_bits)
+    return o
+
+
+def _permanova_labels(labels, A):
+    import numpy as np
+    if hasattr(labels, "detach"):  # torch tensor, on any device
+        labels = labels.detach().cpu().numpy()
+    y = np.asarray(labels)
+    if y.ndim == 1:
+        y = y[None, :]
+    if y.ndim != 2 or y.shape[1] != A:
+        raise ValueError("labels must be (traits x assemblies) over the assemblies of the matrix")
+    return np.ascontiguousarray(y, dtype=np.int8)
+
+
+def _permanova_dict(out):
+    return {"N": out[:, 0].copy(), "n1": out[:, 1].copy(), "Fe": out[:, 2].copy(), "T": out[:, 3].copy(), "A": out[:, 4].copy(), "B": out[:, 5].copy(), "k": out[:, 6].copy()}
+
+
+def pan_permanova(lib: C.CDLL, q, labels, n_perm: int = 1000, seed: int = 11, frac_bits: int = 20):
+    """Two-group PERMANOVA of a fixed-point distance matrix (int32 numpy array or torch tensor, shape (n, n), symmetric, zero diagonal,
+    entries in [0, 2^29), frac_bits fraction bits) for binary labels (shape (T, n) or (n,): 1, 0, -1 = missing) through pg_pan_permanova: a
+    dict of int64 arrays (T,): N, n1, Fe, T, A, B and k (-1 for a trait that is not tested: N < 3, an empty group, or no distance above
+    zero)."""
+    import numpy as np
+    if hasattr(q, "detach"):
+        q = q.detach().cpu().numpy()
+    q = np.ascontiguousarray(q, dtype=np.int32)
+    if q.ndim != 2 or q.shape[0] != q.shape[1]:
+        raise ValueError("q must be a square matrix")
+    n = q.shape[0]
+    y = _permanova_labels(labels, n)
+    T = y.shape[0]
+    o = permanova_opt(lib, n_perm=n_perm, seed=seed, frac_bits=frac_bits)
+    out = np.zeros((T, 7), dtype=np.int64)
+    rc = lib.pg_pan_permanova(q.ctypes.data_as(C.POINTER(C.c_int32)), n, y.ctypes.data_as(C.POINTER(C.c_int8)), T, C.byref(o), out.ctypes.data_as(C.POINTER(C.c_int64)))
+    if rc != 0:
+        raise RuntimeError("pg_pan_permanova: status %d" % rc)
+    return _permanova_dict(out)
+
+
+def pan_permanova_presence(lib: C.CDLL, presence, labels, metric: str = "jaccard", n_perm: int = 1000, seed: int = 11):
+    """The same for an item x assembly presence matrix (bool numpy array or torch tensor, shape (M, A)) through pg_pan_permanova_presence:
+    (the dict pan_permanova returns, F) with the distances of `metric` in units of 2^-F."""
+    import numpy as np
+    p = _presence(presence)
+    M, A = p.shape
+    y = _permanova_labels(labels, A)
+    T = y.shape[0]
+    o = permanova_opt(lib, metric=metric, n_perm=n_perm, seed=seed)
+    out = np.zeros((T, 7), dtype=np.int64)
+    F = C.c_int32(0)
+    rc = lib.pg_pan_permanova_presence(p.ctypes.data_as(C.POINTER(C.c_uint8)), M, A, y.ctypes.data_as(C.POINTER(C.c_int8)), T, C.byref(o),
+                                       out.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(F))
+    if rc != 0:
+        raise RuntimeError("pg_pan_permanova_presence: status %d" % rc)
+    return _permanova_dict(out), int(F.value)
+
+
+def _permanova_args(argv: Sequence[str]):
+    """(file, type, metric, permutations, seed) of --permanova=FILE / --permanova-type=STR / --permanova-metric=STR / --permanova-perm=INT /
+    --permanova-seed=INT in argv; file = None without --permanova."""
+    f, t, m, n, seed, extra = None, "gene", "jaccard", 1000, 11, False
+    for x in argv:
+        if x.startswith("--permanova="): f = x.split("=", 1)[1]
+        elif x.startswith("--permanova-type="): t, extra = x.split("=", 1)[1], True
+        elif x.startswith("--permanova-metric="): m, extra = x.split("=", 1)[1], True
+        elif x.startswith("--permanova-perm="): n, extra = int(x.split("=", 1)[1]), True
+        elif x.startswith("--permanova-seed="): seed, extra = int(x.split("=", 1)[1]), True
+        elif x.startswith("--permanova"):
+            raise ValueError("unknown option or missing value: " + x)
+    if t not in DIST_TYPES:
+        raise ValueError("--permanova-type must be gene or adj")
+    if m not in TREE_METRICS:
+        raise ValueError("--permanova-metric must be jaccard or diff")
+    if not 0 <= n <= TRAIT_MAX_PERM:
+        raise ValueError("--permanova-perm must be in [0, 2^31 - 2]")
+    if extra and f is None:
+        raise ValueError("--permanova-type, --permanova-metric, --permanova-perm and --permanova-seed need --permanova=FILE")
+    return f, t, m, n, seed
+
+
 def _cluster_args(argv: Sequence[str]):
     """(k_lo, k_hi, type, metric, iterations) of --cluster=INT[-INT] / --cluster-type=STR / --cluster-metric=STR / --cluster-iter=INT in
     argv; k_lo = None without --cluster."""
@@ -659,6 +757,12 @@ _API = {
     "pg_qtrait_opt_init": (None, [C.c_void_p]),
     "pg_qtrait_file": (C.c_int, [C.c_char_p, C.c_char_p, C.c_void_p]),
     "pg_write_qtrait": (None, [C.c_void_p, C.c_char_p, C.c_void_p]),
+    "pg_permanova_opt_init": (None, [C.c_void_p]),
+    "pg_permanova_file": (C.c_int, [C.c_char_p, C.c_char_p, C.c_void_p]),
+    "pg_write_permanova": (None, [C.c_void_p, C.c_char_p, C.c_void_p]),
+    "pg_pan_permanova": (C.c_int, [C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int8), C.c_int32, C.c_void_p, C.POINTER(C.c_int64)]),
+    "pg_pan_permanova_presence": (C.c_int, [C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.POINTER(C.c_int8), C.c_int32, C.c_void_p, C.POINTER(C.c_int64),
+                                            C.POINTER(C.c_int32)]),
     "pg_pan_qtrait": (C.c_int, [C.POINTER(C.c_uint8), C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]),
     "pg_pan_trait": (C.c_int, [C.POINTER(C.c_uint8), C.POINTER(C.c_int8), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]),
     "pg_pan_pairs": (C.c_int, [C.POINTER(C.c_uint8), C.POINTER(C.c_int8), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int32)]),
@@ -740,7 +844,7 @@ def parse_args(lib: C.CDLL, argv: Sequence[str]) -> pg_opt_t:
         elif a in ("--bed", "--bed=walk"): opt.flag |= PG_F_WRITE_BED_WALK
         elif a == "--bed=raw": opt.flag |= PG_F_WRITE_BED_RAW
         elif a == "--bed=flag": opt.flag |= PG_F_WRITE_BED_FLAG
-        elif a in ("--matrix", "--matrix=presence", "--matrix=count", "--call") or a.startswith("--curves") or a.startswith("--dist") or a.startswith("--assoc") or a.startswith("--trait") or a.startswith("--qtrait") or a.startswith("--tree") or a.startswith("--cluster"): pass  # handled by run()
+        elif a in ("--matrix", "--matrix=presence", "--matrix=count", "--call") or a.startswith("--curves") or a.startswith("--dist") or a.startswith("--assoc") or a.startswith("--trait") or a.startswith("--qtrait") or a.startswith("--tree") or a.startswith("--cluster") or a.startswith("--permanova"): pass  # handled by run()
         elif a[:2] in ("-p", "-a", "-f", "-c", "-g", "-r", "-b", "-B", "-y", "-T", "-D", "-C", "-e", "-l", "-m", "-d", "-X", "-I", "-P"):
             v = a[2:] if len(a) > 2 else next(it)
             k = a[1]
@@ -810,6 +914,10 @@ def run(lib: C.CDLL, files: Sequence[str], argv: Sequence[str] = (), scan_only: 
     if cl_lo is not None and (any(x.startswith("--matrix") for x in argv) or "--call" in argv or n_curves or dist_type is not None or assoc_phi is not None
                               or trait_fn is not None or tree_type is not None or qtrait_fn is not None):
         raise ValueError("--cluster cannot be combined with --matrix, --call, --curves, --dist, --assoc, --trait, --tree or --qtrait")
+    pm_fn, pm_type, pm_metric, pm_n, pm_seed = _permanova_args(argv)
+    if pm_fn is not None and (any(x.startswith("--matrix") for x in argv) or "--call" in argv or n_curves or dist_type is not None or assoc_phi is not None
+                              or trait_fn is not None or tree_type is not None or qtrait_fn is not None or cl_lo is not None):
+        raise ValueError("--permanova cannot be combined with --matrix, --call, --curves, --dist, --assoc, --trait, --tree, --qtrait or --cluster")
     fd, out = tempfile.mkstemp(prefix="pangene_", suffix=".out")
     os.close(fd)
     lib.pg_set_output(out.encode())
@@ -859,6 +967,10 @@ def run(lib: C.CDLL, files: Sequence[str], argv: Sequence[str] = (), scan_only: 
                     raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
             elif cl_lo is not None:
                 lib.pg_write_cluster(g, C.byref(cluster_opt(lib, cl_lo, cl_hi, cl_type, cl_metric, cl_iter)))
+                if lib.pg_last_error():
+                    raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
+            elif pm_fn is not None:
+                lib.pg_write_permanova(g, pm_fn.encode(), C.byref(permanova_opt(lib, pm_type, pm_metric, pm_n, pm_seed)))
                 if lib.pg_last_error():
                     raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
             elif opt.flag & PG_F_WRITE_BED_WALK: lib.pg_write_bed(d, 1)

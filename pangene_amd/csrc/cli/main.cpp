@@ -75,6 +75,11 @@ static int usage(FILE *fp, const pg_opt_t *opt)
 	std::fprintf(fp, "    --cluster-type=STR   --cluster: items, gene or adj [gene]\n");
 	std::fprintf(fp, "    --cluster-metric=STR --cluster: distance, jaccard or diff [jaccard]\n");
 	std::fprintf(fp, "    --cluster-iter=INT   --cluster: swap iterations per k at the most [1000]\n");
+	std::fprintf(fp, "    --permanova=FILE  output the two-group PERMANOVA of the assemblies' distances for the binary traits of FILE (pseudo-F, R2, permutation p)\n");
+	std::fprintf(fp, "    --permanova-type=STR    --permanova: items, gene or adj [gene]\n");
+	std::fprintf(fp, "    --permanova-metric=STR  --permanova: distance, jaccard or diff [jaccard]\n");
+	std::fprintf(fp, "    --permanova-perm=INT    --permanova: label permutations [1000]\n");
+	std::fprintf(fp, "    --permanova-seed=INT    --permanova: seed of the permutations [11]\n");
 	std::fprintf(fp, "  Also: pangene gfa2matrix [-c] [-d FILE] [-p] <in.gfa>   (pangene.js gfa2matrix on a GFA file)\n");
 	std::fprintf(fp, "        pangene call [-m INT] [-w] [-b] [-e] [-d] [-p] [-s] [-r STR] <in.gfa>   (pangene.js call on a GFA file)\n");
 	std::fprintf(fp, "        pangene curves [-n INT] [-s INT] <in.gfa>   (accumulation curves of the gfa2matrix matrix of a GFA file)\n");
@@ -84,6 +89,7 @@ static int usage(FILE *fp, const pg_opt_t *opt)
 	std::fprintf(fp, "        pangene qtrait -t FILE [-n INT] [-s INT] [-c INT] [-p FLOAT] <in.gfa>   (rank-sum test of every gene against the quantitative traits of a trait file)\n");
 	std::fprintf(fp, "        pangene tree [-t gene|adj] [-m jaccard|diff] [-a nj|upgma] [-b INT] [-s INT] <in.gfa>   (neighbour-joining or UPGMA tree of the assemblies of a GFA file, with bootstrap support)\n");
 	std::fprintf(fp, "        pangene cluster [-t gene|adj] [-m jaccard|diff] -k INT[-INT] [-i INT] <in.gfa>   (k-medoids clusters of the assemblies of a GFA file, their medoids and silhouettes)\n");
+	std::fprintf(fp, "        pangene permanova -t FILE [-T gene|adj] [-m jaccard|diff] [-n INT] [-s INT] <in.gfa>   (do the two groups of a binary trait differ in gene content: pseudo-F, R2 and a permutation p per trait)\n");
 	return fp == stdout ? 0 : 1;
 }
 
@@ -380,6 +386,32 @@ static int main_qtrait(int argc, char *argv[])
 	return pg_qtrait_file(argv[optind], fn, &o) == 0 ? 0 : 1;
 }
 
+// `pangene permanova`: the two-group PERMANOVA of the assemblies' distances for every binary trait of a trait file
+static int main_permanova(int argc, char *argv[])
+{
+	pg_permanova_opt_t o;
+	pg_permanova_opt_init(&o);
+	const char *fn = nullptr;
+	int c;
+	while ((c = getopt(argc, argv, "t:T:m:n:s:")) >= 0) {
+		if (c == 't') fn = optarg;
+		else if (c == 'T') { if ((o.type = dist_type(optarg)) < 0) { std::fprintf(stderr, "ERROR: -T must be gene or adj\n"); return 1; } }
+		else if (c == 'm') { if ((o.metric = tree_metric(optarg)) < 0) { std::fprintf(stderr, "ERROR: -m must be jaccard or diff (shared is not a distance)\n"); return 1; } }
+		else if (c == 'n') { if (!trait_perm(optarg, o.n_perm)) { std::fprintf(stderr, "ERROR: -n must be in [0, 2147483646]\n"); return 1; } }
+		else if (c == 's') o.seed = (uint32_t)std::strtoul(optarg, nullptr, 10);
+		else return 1;
+	}
+	if (argc - optind < 1) {
+		std::printf("Usage: pangene permanova -t FILE [options] <in.gfa>\nOptions:\n  -t FILE   traits: a header line (any first field, one name per trait), then per line an assembly and 1, 0 or NA per trait\n"
+		            "  -T STR    items: gene (gene content) or adj (gene adjacencies of the walks) [gene]\n"
+		            "  -m STR    distance: jaccard or diff [jaccard]\n"
+		            "  -n INT    label permutations per trait; 0: none [%d]\n  -s INT    seed of the permutations [%u]\n", o.n_perm, o.seed);
+		return 0;
+	}
+	if (fn == nullptr) { std::fprintf(stderr, "ERROR: pangene permanova needs -t FILE\n"); return 1; }
+	return pg_permanova_file(argv[optind], fn, &o) == 0 ? 0 : 1;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // `pangene --gpus N`: main.c:117-142 for N devices of one node.  The command forks N - 1 workers BEFORE anything touches the GPU;
 // rank r takes device r and the r-th contiguous block of the PAF files (so that the ranks' W / BED lines, concatenated in rank
@@ -393,7 +425,8 @@ struct Output { int matrix = 0; bool call = false; int curves = 0; uint32_t curv
 	const char *trait = nullptr; int32_t trait_perm = 1000; uint32_t trait_seed = 11; int trait_lineage = 0;
 	const char *qtrait = nullptr; int32_t qtrait_perm = 1000; uint32_t qtrait_seed = 11;
 	int tree = -1, tree_metric = 0, tree_method = 0; int32_t tree_boot = 0; uint32_t tree_seed = 0; // tree: PG_DIST_GENE / PG_DIST_ADJ (-1: none)
-	int32_t cluster_lo = 0, cluster_hi = 0, cluster_iter = 1000; int cluster_type = 0, cluster_metric = 0; }; // cluster_lo: 0 = none
+	int32_t cluster_lo = 0, cluster_hi = 0, cluster_iter = 1000; int cluster_type = 0, cluster_metric = 0; // cluster_lo: 0 = none
+	const char *permanova = nullptr; int permanova_type = 0, permanova_metric = 0; int32_t permanova_perm = 1000; uint32_t permanova_seed = 11; };
 
 static int run_path(pg_opt_t &opt, int n_files, char **files, const uint8_t *ids_only, const Output &o, bool graph_lines, bool own_lines, int device = -1)
 {
@@ -473,6 +506,13 @@ static int run_path(pg_opt_t &opt, int n_files, char **files, const uint8_t *ids
 			pg_write_cluster(g, &clo);
 			if (pg_last_error()) rc = pg_last_error() == -3 ? 1 : 2; // -3, PGA_ERR_ARG: a k outside [2, assemblies - 1] or fewer than 3 assemblies -- a refusal, as on `pangene cluster`
 		}
+		else if (o.permanova) {
+			pg_permanova_opt_t po;
+			pg_permanova_opt_init(&po);
+			po.type = o.permanova_type, po.metric = o.permanova_metric, po.n_perm = o.permanova_perm, po.seed = o.permanova_seed;
+			pg_write_permanova(g, o.permanova, &po);
+			if (pg_last_error()) rc = 2;
+		}
 		else if (opt.flag & PG_F_WRITE_BED_WALK) { if (own_lines) pg_write_bed(d, 1); }
 		else if (opt.flag & PG_F_WRITE_BED_FLAG) { if (own_lines) pg_write_bed(d, 0); }
 		else {
@@ -539,6 +579,7 @@ static int run_sharded(pg_opt_t &opt, int W, int n_files, char **files, const Ou
 	if (o.qtrait) { std::fprintf(stderr, "ERROR: --qtrait needs every genome in one process; run it without --gpus\n"); return 1; }
 	if (o.tree >= 0) { std::fprintf(stderr, "ERROR: --tree needs every genome in one process; run it without --gpus\n"); return 1; }
 	if (o.cluster_lo) { std::fprintf(stderr, "ERROR: --cluster needs every genome in one process; run it without --gpus\n"); return 1; }
+	if (o.permanova) { std::fprintf(stderr, "ERROR: --permanova needs every genome in one process; run it without --gpus\n"); return 1; }
 	const bool dev = pg_backend_is_device() != 0;
 	typedef int (*uid_fn)(void *); typedef int (*init_fn)(int32_t, int32_t, const void *); typedef int (*fin_fn)(void);
 	uid_fn rccl_uid = nullptr; init_fn rccl_init = nullptr; fin_fn rccl_fin = nullptr;
@@ -687,6 +728,7 @@ int main(int argc, char *argv[])
 	if (argc >= 2 && std::strcmp(argv[1], "qtrait") == 0) return main_qtrait(argc - 1, argv + 1);
 	if (argc >= 2 && std::strcmp(argv[1], "tree") == 0) return main_tree(argc - 1, argv + 1);
 	if (argc >= 2 && std::strcmp(argv[1], "cluster") == 0) return main_cluster(argc - 1, argv + 1);
+	if (argc >= 2 && std::strcmp(argv[1], "permanova") == 0) return main_permanova(argc - 1, argv + 1);
 	int matrix = 0, n_gpus = 1; // matrix: 1 presence, 2 counts
 	bool call = false;
 	int curves = 0; // orders of --curves (0: not asked for)
@@ -709,6 +751,11 @@ int main(int argc, char *argv[])
 	int32_t cluster_lo = 0, cluster_hi = 0, cluster_iter_v = 1000; // --cluster: the range of k (0: not asked for)
 	int cluster_type_v = PG_DIST_GENE, cluster_metric_v = PG_DIST_JACCARD;
 	bool cluster_extra = false; // a --cluster-* option was given
+	const char *permanova = nullptr; // --permanova=FILE
+	int permanova_type_v = PG_DIST_GENE, permanova_metric_v = PG_DIST_JACCARD;
+	int32_t permanova_perm_v = 1000;
+	uint32_t permanova_seed = 11;
+	bool permanova_extra = false; // a --permanova-* option was given
 	static const struct option lopts[] = {
 		{ "bed", optional_argument, nullptr, 301 }, { "ori-sc", no_argument, nullptr, 302 }, { "matrix", optional_argument, nullptr, 303 }, { "call", no_argument, nullptr, 305 },
 		{ "curves", optional_argument, nullptr, 306 }, { "curves-seed", required_argument, nullptr, 307 },
@@ -721,6 +768,8 @@ int main(int argc, char *argv[])
 		{ "tree-boot", required_argument, nullptr, 319 }, { "tree-seed", required_argument, nullptr, 320 },
 		{ "cluster", required_argument, nullptr, 325 }, { "cluster-type", required_argument, nullptr, 326 }, { "cluster-metric", required_argument, nullptr, 327 },
 		{ "cluster-iter", required_argument, nullptr, 328 },
+		{ "permanova", required_argument, nullptr, 329 }, { "permanova-type", required_argument, nullptr, 330 }, { "permanova-metric", required_argument, nullptr, 331 },
+		{ "permanova-perm", required_argument, nullptr, 332 }, { "permanova-seed", required_argument, nullptr, 333 },
 		{ "gpus", required_argument, nullptr, 304 }, { "procs", required_argument, nullptr, 304 },
 		{ "version", no_argument, nullptr, 401 }, { nullptr, 0, nullptr, 0 } };
 	pg_opt_t opt;
@@ -833,6 +882,20 @@ int main(int argc, char *argv[])
 			cluster_extra = true;
 			if (!tree_boot(optarg, cluster_iter_v)) { std::fprintf(stderr, "ERROR: --cluster-iter must be in [0, 2147483647]\n"); return 1; }
 			break;
+		case 329: permanova = optarg; break;
+		case 330:
+			permanova_extra = true;
+			if ((permanova_type_v = dist_type(optarg)) < 0) { std::fprintf(stderr, "ERROR: --permanova-type must be gene or adj\n"); return 1; }
+			break;
+		case 331:
+			permanova_extra = true;
+			if ((permanova_metric_v = tree_metric(optarg)) < 0) { std::fprintf(stderr, "ERROR: --permanova-metric must be jaccard or diff (shared is not a distance)\n"); return 1; }
+			break;
+		case 332:
+			permanova_extra = true;
+			if (!trait_perm(optarg, permanova_perm_v)) { std::fprintf(stderr, "ERROR: --permanova-perm must be in [0, 2147483646]\n"); return 1; }
+			break;
+		case 333: permanova_extra = true, permanova_seed = (uint32_t)std::strtoul(optarg, nullptr, 10); break;
 		case 401: std::puts(PG_VERSION); return 0;
 		default: break;
 		}
@@ -851,7 +914,13 @@ int main(int argc, char *argv[])
 		return 1;
 	}
 	if (cluster_extra && !cluster_lo) { std::fprintf(stderr, "ERROR: --cluster-type, --cluster-metric and --cluster-iter need --cluster=INT[-INT]\n"); return 1; }
+	if (permanova && (matrix || call || curves || dist >= 0 || assoc || trait || tree >= 0 || qtrait || cluster_lo)) {
+		std::fprintf(stderr, "ERROR: --permanova cannot be combined with --matrix, --call, --curves, --dist, --assoc, --trait, --tree, --qtrait or --cluster\n");
+		return 1;
+	}
+	if (permanova_extra && !permanova) { std::fprintf(stderr, "ERROR: --permanova-type, --permanova-metric, --permanova-perm and --permanova-seed need --permanova=FILE\n"); return 1; }
 	Output o;
+	o.permanova = permanova, o.permanova_type = permanova_type_v, o.permanova_metric = permanova_metric_v, o.permanova_perm = permanova_perm_v, o.permanova_seed = permanova_seed;
 	o.cluster_lo = cluster_lo, o.cluster_hi = cluster_hi, o.cluster_iter = cluster_iter_v, o.cluster_type = cluster_type_v, o.cluster_metric = cluster_metric_v;
 	o.qtrait = qtrait, o.qtrait_perm = qtrait_perm_v, o.qtrait_seed = qtrait_seed;
 	o.tree = tree, o.tree_metric = tree_metric_v, o.tree_method = tree_method_v, o.tree_boot = tree_boot_v, o.tree_seed = tree_seed;
