@@ -459,6 +459,40 @@ int  pg_pan_permanova(const int32_t *q, int32_t n, const int8_t *labels, int32_t
 int  pg_pan_permanova_presence(const uint8_t *presence, int32_t n_item, int32_t n_asm, const int8_t *labels, int32_t n_trait, const pg_permanova_opt_t *o,
                                int64_t *out, int32_t *frac_bits);
 
+/* Mantel test: do two distance matrices of the same assemblies agree -- does gene-order divergence track gene-content divergence, or
+ * gene content an external distance (mantel of vegan).  DESIGN.md section 8 "Mantel test" holds the definition.  Inputs are two
+ * fixed-point matrices qx, qy over the same N assemblies: symmetric, zero diagonal, entries in [0, 2^29).  Per matrix s is the smallest
+ * s >= 0 with (max >> s)^2 N (N - 1) < 2^62 (the rule of pg_permanova_*, applied to each matrix on its own), a = qx >> sx, b = qy >> sy.
+ * Over ordered pairs i != j, M = N (N - 1) of them: Sa = sum a, Sb = sum b, Saa = sum a^2, Sbb = sum b^2 and, for an order o of the
+ * assemblies, Z(o) = sum a[i][j] b[o[i]][o[j]] -- all below 2^62.  Z is Z of the identity; permutation p = 1 .. n_perm uses o_p = order p of
+ * N columns exactly as pg_trait_* define it; n_ge = #{p : Z_p >= Z}, n_le = #{p : Z_p <= Z}, ties in both -- integers throughout.
+ * Output, tab-separated: "X Y N r n_ge n_le p_greater p_less" and one line: X and Y name the matrices (gene:jaccard, adj:diff, ..., or
+ * file); with num = M Z - Sa Sb, va = M Saa - Sa^2, vb = M Sbb - Sb^2 (128 bits), r = (num / sqrtl(va)) / sqrtl(vb) in long double as
+ * %.4f; p_greater = (n_ge + 1) / (n_perm + 1) and p_less = (n_le + 1) / (n_perm + 1) as %.6f, NA with n_perm = 0.  N < 3, va = 0 or
+ * vb = 0: a note on stderr and the header only.  At most 16 384 assemblies (PGA_ERR_RANGE).
+ * pg_mantel_file: X is the distance x_type:x_metric of the GFA file; Y is y_type:y_metric of the same file or, with mat_fn not NULL, the
+ * matrix of that file in either form pg_dist_* print: the table ("Asm" and the names, then a name and its values per line) or relaxed
+ * PHYLIP (a count line, then a name and its values per line), fields between blanks or tabs.  Values by strtod; F is the largest F in
+ * [0, 20] with floor(vmax 2^F + 0.5) < 2^29 and q = floor(v 2^F + 0.5); r does not depend on F.  N is the assemblies both sides name, in
+ * X's order; a name on one side only gets a note on stderr and is left out.  A matrix that is not square, a value that is not a finite
+ * number >= 0, a diagonal value that is not 0, a name given twice and a matrix that is not symmetric after the conversion are errors that
+ * name the file and the line.  Returns 0, -1 (the GFA file cannot be opened), -3 (a bad matrix file) or -2 (the backend's status is on
+ * stderr).  pg_write_mantel: the same for the graph in memory; errors go to pg_last_error.
+ * pg_pan_mantel: any two such matrices, int32 [n][n] each (PGA_ERR_ARG when one is not symmetric, has a diagonal entry that is not zero
+ * or a negative entry, PGA_ERR_RANGE for an entry of 2^29 or more); only n_perm and seed of the options are read.  Fills
+ * out[10] = N, sx, sy, Sa, Sb, Saa, Sbb, Z, n_ge, n_le (Z = 0 and n_ge = n_le = -1 for a pair that is not tested) and returns 0 or a
+ * negative PGA_ERR_*.  Z and the counts come from the backend's pga_pan_mantel.  sizeof(pg_mantel_opt_t) is 24. */
+typedef struct {
+	int32_t  x_type, x_metric; /* X: PG_DIST_GENE or PG_DIST_ADJ, PG_DIST_JACCARD or PG_DIST_DIFF [gene:jaccard] */
+	int32_t  y_type, y_metric; /* Y, unless a matrix file is given [adj:jaccard] */
+	int32_t  n_perm;           /* permutations; 0: none [1000] */
+	uint32_t seed;             /* seed of the orders [11] */
+} pg_mantel_opt_t;
+void pg_mantel_opt_init(pg_mantel_opt_t *o);
+int  pg_mantel_file(const char *gfa_fn, const char *mat_fn, const pg_mantel_opt_t *o);
+void pg_write_mantel(pg_graph_t *g, const char *mat_fn, const pg_mantel_opt_t *o);
+int  pg_pan_mantel(const int32_t *qx, const int32_t *qy, int32_t n, const pg_mantel_opt_t *o, int64_t *out);
+
 /* Last error of the path (0 = none).  The reference aborts on invariant violations; this library
  * records a status instead, prints one line to stderr, and leaves the graph empty. */
 int         pg_last_error(void);

@@ -94,7 +94,7 @@ typedef struct {
  * Device layout limits (PGA_ERR_RANGE otherwise): coordinates inside a block < 2^31 (contigs beyond that arrive as virtual contigs,
  * see pga_genome_block_t; what remains out of reach is a single cluster of overlapping hits spanning 2^30 bp), < 2^30 hits and < 2^31
  * exons per shard, < 2^20 genes, < 2^24 genomes. */
-#define PGA_ABI_VERSION 16u  /* bumped whenever a struct of this header or the order of pga_backend_t changes; pga_create refuses another */
+#define PGA_ABI_VERSION 17u  /* bumped whenever a struct of this header or the order of pga_backend_t changes; pga_create refuses another */
 typedef struct {
 	uint32_t abi_version;        /* = PGA_ABI_VERSION of the header the caller was compiled against (PGA_ERR_ARG otherwise) */
 	int32_t n_genome;            /* genomes in this shard (may include genomes with 0 hits) */
@@ -531,6 +531,30 @@ typedef struct { int64_t t, a, b, k; } pga_permanova_out_t;
 int pga_pan_permanova(const pga_permanova_in_t *in, pga_permanova_out_t *out);
 int32_t pga_permanova_batch(void); /* permutations per batch: 16 384, or PANGENE_PERMA_BATCH */
 
+/* Mantel test (include/pangene_amd.h pg_pan_mantel, pangene mantel; DESIGN.md section 8 "Mantel test"): do two distance matrices of the
+ * same n assemblies agree.  Context-free, like pan_permanova.  An order o of the assemblies gives Z(o) = the sum over ordered pairs
+ * i != j of a[i][j] b[o[i]][o[j]]; Z of the identity is the observed one, permutation p = 1 .. n_perm uses o_p = order p of n columns
+ * exactly as pan_trait defines it, n_ge = #{p : Z_p >= Z}, n_le = #{p : Z_p <= Z} (ties count in both).  All integers.
+ * In:  a[n][n] and b[n][n], already shifted: symmetric, zero diagonal, 0 <= a <= max_a, 0 <= b <= max_b and max_a max_b n (n - 1) < 2^62,
+ *      so that every Z stays below 2^62 (the caller's promise: pg_pan_mantel checks the matrices and derives the shifts before it calls;
+ *      the product is checked here before anything is launched, PGA_ERR_ARG).  z_rows, ord_rows: NULL, or -- for tests only -- room for
+ *      min(n_perm, pga_mantel_batch()) int64 that receive Z of the first batch's permutations, and for as many rows of n uint16 that
+ *      receive its orders.
+ * Out: z of the identity order, n_ge and n_le.
+ * The permutations go through in batches of pga_mantel_batch() orders; device memory is the two matrices and the batch's orders.
+ * Limits: n >= 1, n_perm >= 0, max_a >= 0, max_b >= 0 (PGA_ERR_ARG otherwise); n <= 16 384, n_perm <= 2^31 - 2 (PGA_ERR_RANGE, before
+ * anything is launched). */
+typedef struct {
+	const int32_t *a, *b;
+	int32_t n, max_a, max_b, n_perm;
+	uint32_t seed;
+	int64_t *z_rows;
+	uint16_t *ord_rows;
+} pga_mantel_in_t;
+typedef struct { int64_t z, n_ge, n_le; } pga_mantel_out_t;
+int pga_pan_mantel(const pga_mantel_in_t *in, pga_mantel_out_t *out);
+int32_t pga_mantel_batch(void); /* permutations per batch: 4 096, or PANGENE_MANTEL_BATCH */
+
 /* the same ABI as a table, so the host driver is written once */
 struct pga_branch_par_s; struct pga_loop_xchg_s;
 typedef struct {
@@ -597,6 +621,7 @@ typedef struct {
 	int  (*pan_qtrait)(const pga_qtrait_in_t *, pga_qtrait_out_t *); /* may be NULL: the host driver then runs the same step itself */
 	int  (*pan_medoids)(const pga_medoids_in_t *, pga_medoids_out_t *); /* may be NULL: the host driver then runs the same step itself */
 	int  (*pan_permanova)(const pga_permanova_in_t *, pga_permanova_out_t *); /* may be NULL: the host driver then runs the same step itself */
+	int  (*pan_mantel)(const pga_mantel_in_t *, pga_mantel_out_t *); /* may be NULL: the host driver then runs the same step itself */
 } pga_backend_t;
 
 const pga_backend_t *pga_backend(void);

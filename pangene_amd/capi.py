@@ -655,6 +655,78 @@ def _permanova_args(argv: Sequence[str]):
     return f, t, m, n, seed
 
 
+class pg_mantel_opt_t(C.Structure):
+    """Mantel options (include/pangene_amd.h): the two matrices, the permutations and their seed."""
+    _fields_ = [("x_type", C.c_int32), ("x_metric", C.c_int32), ("y_type", C.c_int32), ("y_metric", C.c_int32), ("n_perm", C.c_int32), ("seed", C.c_uint32)]
+
+
+def _mantel_spec(spec: str, what: str):
+    """(type index, metric index) of gene|adj:jaccard|diff"""
+    t, colon, m = spec.partition(":")
+    if not colon or t not in DIST_TYPES or m not in TREE_METRICS:
+        raise ValueError(what + " must be gene|adj:jaccard|diff")
+    return DIST_TYPES.index(t), DIST_METRICS.index(m)
+
+
+def mantel_opt(lib: C.CDLL, x: str = "gene:jaccard", y: str = "adj:jaccard", n_perm: int = 1000, seed: int = 11) -> pg_mantel_opt_t:
+    xt, xm = _mantel_spec(x, "x")
+    yt, ym = _mantel_spec(y, "y")
+    if not 0 <= int(n_perm) <= TRAIT_MAX_PERM:
+        raise ValueError("n_perm must be in [0, 2^31 - 2]")
+    o = pg_mantel_opt_t()
+    lib.pg_mantel_opt_init(C.byref(o))
+    o.x_type, o.x_metric, o.y_type, o.y_metric, o.n_perm, o.seed = xt, xm, yt, ym, int(n_perm), int(seed) & 0xFFFFFFFF
+    return o
+
+
+def pan_mantel(lib: C.CDLL, qx, qy, n_perm: int = 1000, seed: int = 11):
+    """Mantel test of two fixed-point distance matrices over the same assemblies (int32 numpy arrays or torch tensors, shape (n, n),
+    symmetric, zero diagonal, entries in [0, 2^29)) through pg_pan_mantel: a dict of Python ints N, sx, sy, Sa, Sb, Saa, Sbb, Z, n_ge and
+    n_le (Z = 0 and n_ge = n_le = -1 for a pair that is not tested: N < 3 or a matrix with one value only)."""
+    import numpy as np
+    qs = []
+    for q in (qx, qy):
+        if hasattr(q, "detach"):  # torch tensor, on any device
+            q = q.detach().cpu().numpy()
+        q = np.ascontiguousarray(q, dtype=np.int32)
+        if q.ndim != 2 or q.shape[0] != q.shape[1]:
+            raise ValueError("qx and qy must be square matrices")
+        qs.append(q)
+    if qs[0].shape != qs[1].shape:
+        raise ValueError("qx and qy must be over the same assemblies")
+    o = mantel_opt(lib, n_perm=n_perm, seed=seed)
+    out = np.zeros(10, dtype=np.int64)
+    rc = lib.pg_pan_mantel(qs[0].ctypes.data_as(C.POINTER(C.c_int32)), qs[1].ctypes.data_as(C.POINTER(C.c_int32)), qs[0].shape[0], C.byref(o),
+                           out.ctypes.data_as(C.POINTER(C.c_int64)))
+    if rc != 0:
+        raise RuntimeError("pg_pan_mantel: status %d" % rc)
+    return dict(zip(("N", "sx", "sy", "Sa", "Sb", "Saa", "Sbb", "Z", "n_ge", "n_le"), (int(v) for v in out)))
+
+
+def _mantel_args(argv: Sequence[str]):
+    """(asked for, file, x, y, permutations, seed) of --mantel[=FILE] / --mantel-x=SPEC / --mantel-y=SPEC / --mantel-perm=INT /
+    --mantel-seed=INT in argv."""
+    on, f, x, y, n, seed, extra, have_y = False, None, "gene:jaccard", "adj:jaccard", 1000, 11, False, False
+    for a in argv:
+        if a == "--mantel": on = True
+        elif a.startswith("--mantel="): on, f = True, a.split("=", 1)[1]
+        elif a.startswith("--mantel-x="): x, extra = a.split("=", 1)[1], True
+        elif a.startswith("--mantel-y="): y, extra, have_y = a.split("=", 1)[1], True, True
+        elif a.startswith("--mantel-perm="): n, extra = int(a.split("=", 1)[1]), True
+        elif a.startswith("--mantel-seed="): seed, extra = int(a.split("=", 1)[1]), True
+        elif a.startswith("--mantel"):
+            raise ValueError("unknown option or missing value: " + a)
+    _mantel_spec(x, "--mantel-x")
+    _mantel_spec(y, "--mantel-y")
+    if not 0 <= n <= TRAIT_MAX_PERM:
+        raise ValueError("--mantel-perm must be in [0, 2^31 - 2]")
+    if extra and not on:
+        raise ValueError("--mantel-x, --mantel-y, --mantel-perm and --mantel-seed need --mantel")
+    if have_y and f is not None:
+        raise ValueError("--mantel-y cannot be combined with --mantel=FILE")
+    return on, f, x, y, n, seed
+
+
 def _cluster_args(argv: Sequence[str]):
     """(k_lo, k_hi, type, metric, iterations) of --cluster=INT[-INT] / --cluster-type=STR / --cluster-metric=STR / --cluster-iter=INT in
     argv; k_lo = None without --cluster."""
@@ -763,6 +835,10 @@ _API = {
     "pg_pan_permanova": (C.c_int, [C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int8), C.c_int32, C.c_void_p, C.POINTER(C.c_int64)]),
     "pg_pan_permanova_presence": (C.c_int, [C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.POINTER(C.c_int8), C.c_int32, C.c_void_p, C.POINTER(C.c_int64),
                                             C.POINTER(C.c_int32)]),
+    "pg_mantel_opt_init": (None, [C.c_void_p]),
+    "pg_mantel_file": (C.c_int, [C.c_char_p, C.c_char_p, C.c_void_p]),
+    "pg_write_mantel": (None, [C.c_void_p, C.c_char_p, C.c_void_p]),
+    "pg_pan_mantel": (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.POINTER(C.c_int64)]),
     "pg_pan_qtrait": (C.c_int, [C.POINTER(C.c_uint8), C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]),
     "pg_pan_trait": (C.c_int, [C.POINTER(C.c_uint8), C.POINTER(C.c_int8), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]),
     "pg_pan_pairs": (C.c_int, [C.POINTER(C.c_uint8), C.POINTER(C.c_int8), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int32)]),
@@ -844,7 +920,7 @@ def parse_args(lib: C.CDLL, argv: Sequence[str]) -> pg_opt_t:
         elif a in ("--bed", "--bed=walk"): opt.flag |= PG_F_WRITE_BED_WALK
         elif a == "--bed=raw": opt.flag |= PG_F_WRITE_BED_RAW
         elif a == "--bed=flag": opt.flag |= PG_F_WRITE_BED_FLAG
-        elif a in ("--matrix", "--matrix=presence", "--matrix=count", "--call") or a.startswith("--curves") or a.startswith("--dist") or a.startswith("--assoc") or a.startswith("--trait") or a.startswith("--qtrait") or a.startswith("--tree") or a.startswith("--cluster") or a.startswith("--permanova"): pass  # handled by run()
+        elif a in ("--matrix", "--matrix=presence", "--matrix=count", "--call") or a.startswith("--curves") or a.startswith("--dist") or a.startswith("--assoc") or a.startswith("--trait") or a.startswith("--qtrait") or a.startswith("--tree") or a.startswith("--cluster") or a.startswith("--permanova") or a.startswith("--mantel"): pass  # handled by run()
         elif a[:2] in ("-p", "-a", "-f", "-c", "-g", "-r", "-b", "-B", "-y", "-T", "-D", "-C", "-e", "-l", "-m", "-d", "-X", "-I", "-P"):
             v = a[2:] if len(a) > 2 else next(it)
             k = a[1]
@@ -918,6 +994,10 @@ def run(lib: C.CDLL, files: Sequence[str], argv: Sequence[str] = (), scan_only: 
     if pm_fn is not None and (any(x.startswith("--matrix") for x in argv) or "--call" in argv or n_curves or dist_type is not None or assoc_phi is not None
                               or trait_fn is not None or tree_type is not None or qtrait_fn is not None or cl_lo is not None):
         raise ValueError("--permanova cannot be combined with --matrix, --call, --curves, --dist, --assoc, --trait, --tree, --qtrait or --cluster")
+    mt_on, mt_fn, mt_x, mt_y, mt_n, mt_seed = _mantel_args(argv)
+    if mt_on and (any(x.startswith("--matrix") for x in argv) or "--call" in argv or n_curves or dist_type is not None or assoc_phi is not None
+                  or trait_fn is not None or tree_type is not None or qtrait_fn is not None or cl_lo is not None or pm_fn is not None):
+        raise ValueError("--mantel cannot be combined with --matrix, --call, --curves, --dist, --assoc, --trait, --tree, --qtrait, --cluster or --permanova")
     fd, out = tempfile.mkstemp(prefix="pangene_", suffix=".out")
     os.close(fd)
     lib.pg_set_output(out.encode())
@@ -971,6 +1051,10 @@ def run(lib: C.CDLL, files: Sequence[str], argv: Sequence[str] = (), scan_only: 
                     raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
             elif pm_fn is not None:
                 lib.pg_write_permanova(g, pm_fn.encode(), C.byref(permanova_opt(lib, pm_type, pm_metric, pm_n, pm_seed)))
+                if lib.pg_last_error():
+                    raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
+            elif mt_on:
+                lib.pg_write_mantel(g, mt_fn.encode() if mt_fn is not None else None, C.byref(mantel_opt(lib, mt_x, mt_y, mt_n, mt_seed)))
                 if lib.pg_last_error():
                     raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
             elif opt.flag & PG_F_WRITE_BED_WALK: lib.pg_write_bed(d, 1)

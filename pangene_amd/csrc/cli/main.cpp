@@ -80,6 +80,11 @@ static int usage(FILE *fp, const pg_opt_t *opt)
 	std::fprintf(fp, "    --permanova-metric=STR  --permanova: distance, jaccard or diff [jaccard]\n");
 	std::fprintf(fp, "    --permanova-perm=INT    --permanova: label permutations [1000]\n");
 	std::fprintf(fp, "    --permanova-seed=INT    --permanova: seed of the permutations [11]\n");
+	std::fprintf(fp, "    --mantel[=FILE]   output the Mantel test of two distance matrices of the assemblies, or of one and the matrix of FILE (r, permutation p)\n");
+	std::fprintf(fp, "    --mantel-x=STR    --mantel: the first matrix, gene|adj:jaccard|diff [gene:jaccard]\n");
+	std::fprintf(fp, "    --mantel-y=STR    --mantel: the second matrix, unless FILE is given [adj:jaccard]\n");
+	std::fprintf(fp, "    --mantel-perm=INT --mantel: permutations of the assemblies [1000]\n");
+	std::fprintf(fp, "    --mantel-seed=INT --mantel: seed of the permutations [11]\n");
 	std::fprintf(fp, "  Also: pangene gfa2matrix [-c] [-d FILE] [-p] <in.gfa>   (pangene.js gfa2matrix on a GFA file)\n");
 	std::fprintf(fp, "        pangene call [-m INT] [-w] [-b] [-e] [-d] [-p] [-s] [-r STR] <in.gfa>   (pangene.js call on a GFA file)\n");
 	std::fprintf(fp, "        pangene curves [-n INT] [-s INT] <in.gfa>   (accumulation curves of the gfa2matrix matrix of a GFA file)\n");
@@ -90,6 +95,7 @@ static int usage(FILE *fp, const pg_opt_t *opt)
 	std::fprintf(fp, "        pangene tree [-t gene|adj] [-m jaccard|diff] [-a nj|upgma] [-b INT] [-s INT] <in.gfa>   (neighbour-joining or UPGMA tree of the assemblies of a GFA file, with bootstrap support)\n");
 	std::fprintf(fp, "        pangene cluster [-t gene|adj] [-m jaccard|diff] -k INT[-INT] [-i INT] <in.gfa>   (k-medoids clusters of the assemblies of a GFA file, their medoids and silhouettes)\n");
 	std::fprintf(fp, "        pangene permanova -t FILE [-T gene|adj] [-m jaccard|diff] [-n INT] [-s INT] <in.gfa>   (do the two groups of a binary trait differ in gene content: pseudo-F, R2 and a permutation p per trait)\n");
+	std::fprintf(fp, "        pangene mantel [-x SPEC] [-y SPEC | -f FILE] [-n INT] [-s INT] <in.gfa>   (do two distance matrices of the assemblies agree: Mantel's r and its permutation p)\n");
 	return fp == stdout ? 0 : 1;
 }
 
@@ -412,6 +418,45 @@ static int main_permanova(int argc, char *argv[])
 	return pg_permanova_file(argv[optind], fn, &o) == 0 ? 0 : 1;
 }
 
+// SPEC of `pangene mantel`: gene|adj + ':' + jaccard|diff
+static bool mantel_spec(const char *s, int32_t &type, int32_t &metric)
+{
+	const char *c = std::strchr(s, ':');
+	if (c == nullptr) return false;
+	const std::string t(s, c);
+	const int ty = dist_type(t.c_str()), me = tree_metric(c + 1);
+	if (ty < 0 || me < 0) return false;
+	type = ty, metric = me;
+	return true;
+}
+
+// `pangene mantel`: the Mantel test of two distance matrices of the assemblies of a GFA file, or of one of them and a matrix file
+static int main_mantel(int argc, char *argv[])
+{
+	pg_mantel_opt_t o;
+	pg_mantel_opt_init(&o);
+	const char *fn = nullptr;
+	bool have_y = false;
+	int c;
+	while ((c = getopt(argc, argv, "x:y:f:n:s:")) >= 0) {
+		if (c == 'x') { if (!mantel_spec(optarg, o.x_type, o.x_metric)) { std::fprintf(stderr, "ERROR: -x must be gene|adj:jaccard|diff\n"); return 1; } }
+		else if (c == 'y') { have_y = true; if (!mantel_spec(optarg, o.y_type, o.y_metric)) { std::fprintf(stderr, "ERROR: -y must be gene|adj:jaccard|diff\n"); return 1; } }
+		else if (c == 'f') fn = optarg;
+		else if (c == 'n') { if (!trait_perm(optarg, o.n_perm)) { std::fprintf(stderr, "ERROR: -n must be in [0, 2147483646]\n"); return 1; } }
+		else if (c == 's') o.seed = (uint32_t)std::strtoul(optarg, nullptr, 10);
+		else return 1;
+	}
+	if (argc - optind < 1) {
+		std::printf("Usage: pangene mantel [options] <in.gfa>\nOptions:\n  -x SPEC   the first matrix: gene (gene content) or adj (gene adjacencies of the walks), ':', jaccard or diff [gene:jaccard]\n"
+		            "  -y SPEC   the second matrix [adj:jaccard]\n"
+		            "  -f FILE   the second matrix from FILE instead: the table or the PHYLIP form `pangene dist` prints\n"
+		            "  -n INT    permutations of the assemblies; 0: none [%d]\n  -s INT    seed of the permutations [%u]\n", o.n_perm, o.seed);
+		return 0;
+	}
+	if (have_y && fn != nullptr) { std::fprintf(stderr, "ERROR: -y cannot be combined with -f\n"); return 1; }
+	return pg_mantel_file(argv[optind], fn, &o) == 0 ? 0 : 1;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // `pangene --gpus N`: main.c:117-142 for N devices of one node.  The command forks N - 1 workers BEFORE anything touches the GPU;
 // rank r takes device r and the r-th contiguous block of the PAF files (so that the ranks' W / BED lines, concatenated in rank
@@ -426,7 +471,8 @@ struct Output { int matrix = 0; bool call = false; int curves = 0; uint32_t curv
 	const char *qtrait = nullptr; int32_t qtrait_perm = 1000; uint32_t qtrait_seed = 11;
 	int tree = -1, tree_metric = 0, tree_method = 0; int32_t tree_boot = 0; uint32_t tree_seed = 0; // tree: PG_DIST_GENE / PG_DIST_ADJ (-1: none)
 	int32_t cluster_lo = 0, cluster_hi = 0, cluster_iter = 1000; int cluster_type = 0, cluster_metric = 0; // cluster_lo: 0 = none
-	const char *permanova = nullptr; int permanova_type = 0, permanova_metric = 0; int32_t permanova_perm = 1000; uint32_t permanova_seed = 11; };
+	const char *permanova = nullptr; int permanova_type = 0, permanova_metric = 0; int32_t permanova_perm = 1000; uint32_t permanova_seed = 11;
+	bool mantel = false; const char *mantel_file = nullptr; pg_mantel_opt_t mantel_opt; };
 
 static int run_path(pg_opt_t &opt, int n_files, char **files, const uint8_t *ids_only, const Output &o, bool graph_lines, bool own_lines, int device = -1)
 {
@@ -513,6 +559,10 @@ static int run_path(pg_opt_t &opt, int n_files, char **files, const uint8_t *ids
 			pg_write_permanova(g, o.permanova, &po);
 			if (pg_last_error()) rc = 2;
 		}
+		else if (o.mantel) {
+			pg_write_mantel(g, o.mantel_file, &o.mantel_opt);
+			if (pg_last_error()) rc = 2;
+		}
 		else if (opt.flag & PG_F_WRITE_BED_WALK) { if (own_lines) pg_write_bed(d, 1); }
 		else if (opt.flag & PG_F_WRITE_BED_FLAG) { if (own_lines) pg_write_bed(d, 0); }
 		else {
@@ -580,6 +630,7 @@ static int run_sharded(pg_opt_t &opt, int W, int n_files, char **files, const Ou
 	if (o.tree >= 0) { std::fprintf(stderr, "ERROR: --tree needs every genome in one process; run it without --gpus\n"); return 1; }
 	if (o.cluster_lo) { std::fprintf(stderr, "ERROR: --cluster needs every genome in one process; run it without --gpus\n"); return 1; }
 	if (o.permanova) { std::fprintf(stderr, "ERROR: --permanova needs every genome in one process; run it without --gpus\n"); return 1; }
+	if (o.mantel) { std::fprintf(stderr, "ERROR: --mantel needs every genome in one process; run it without --gpus\n"); return 1; }
 	const bool dev = pg_backend_is_device() != 0;
 	typedef int (*uid_fn)(void *); typedef int (*init_fn)(int32_t, int32_t, const void *); typedef int (*fin_fn)(void);
 	uid_fn rccl_uid = nullptr; init_fn rccl_init = nullptr; fin_fn rccl_fin = nullptr;
@@ -729,6 +780,7 @@ int main(int argc, char *argv[])
 	if (argc >= 2 && std::strcmp(argv[1], "tree") == 0) return main_tree(argc - 1, argv + 1);
 	if (argc >= 2 && std::strcmp(argv[1], "cluster") == 0) return main_cluster(argc - 1, argv + 1);
 	if (argc >= 2 && std::strcmp(argv[1], "permanova") == 0) return main_permanova(argc - 1, argv + 1);
+	if (argc >= 2 && std::strcmp(argv[1], "mantel") == 0) return main_mantel(argc - 1, argv + 1);
 	int matrix = 0, n_gpus = 1; // matrix: 1 presence, 2 counts
 	bool call = false;
 	int curves = 0; // orders of --curves (0: not asked for)
@@ -756,6 +808,10 @@ int main(int argc, char *argv[])
 	int32_t permanova_perm_v = 1000;
 	uint32_t permanova_seed = 11;
 	bool permanova_extra = false; // a --permanova-* option was given
+	bool mantel = false, mantel_extra = false, mantel_y = false; // --mantel[=FILE]; a --mantel-* option was given; --mantel-y was
+	const char *mantel_file = nullptr;
+	pg_mantel_opt_t mantel_opt;
+	pg_mantel_opt_init(&mantel_opt);
 	static const struct option lopts[] = {
 		{ "bed", optional_argument, nullptr, 301 }, { "ori-sc", no_argument, nullptr, 302 }, { "matrix", optional_argument, nullptr, 303 }, { "call", no_argument, nullptr, 305 },
 		{ "curves", optional_argument, nullptr, 306 }, { "curves-seed", required_argument, nullptr, 307 },
@@ -770,6 +826,8 @@ int main(int argc, char *argv[])
 		{ "cluster-iter", required_argument, nullptr, 328 },
 		{ "permanova", required_argument, nullptr, 329 }, { "permanova-type", required_argument, nullptr, 330 }, { "permanova-metric", required_argument, nullptr, 331 },
 		{ "permanova-perm", required_argument, nullptr, 332 }, { "permanova-seed", required_argument, nullptr, 333 },
+		{ "mantel", optional_argument, nullptr, 334 }, { "mantel-x", required_argument, nullptr, 335 }, { "mantel-y", required_argument, nullptr, 336 },
+		{ "mantel-perm", required_argument, nullptr, 337 }, { "mantel-seed", required_argument, nullptr, 338 },
 		{ "gpus", required_argument, nullptr, 304 }, { "procs", required_argument, nullptr, 304 },
 		{ "version", no_argument, nullptr, 401 }, { nullptr, 0, nullptr, 0 } };
 	pg_opt_t opt;
@@ -896,6 +954,20 @@ int main(int argc, char *argv[])
 			if (!trait_perm(optarg, permanova_perm_v)) { std::fprintf(stderr, "ERROR: --permanova-perm must be in [0, 2147483646]\n"); return 1; }
 			break;
 		case 333: permanova_extra = true, permanova_seed = (uint32_t)std::strtoul(optarg, nullptr, 10); break;
+		case 334: mantel = true, mantel_file = optarg; break;
+		case 335:
+			mantel_extra = true;
+			if (!mantel_spec(optarg, mantel_opt.x_type, mantel_opt.x_metric)) { std::fprintf(stderr, "ERROR: --mantel-x must be gene|adj:jaccard|diff\n"); return 1; }
+			break;
+		case 336:
+			mantel_extra = mantel_y = true;
+			if (!mantel_spec(optarg, mantel_opt.y_type, mantel_opt.y_metric)) { std::fprintf(stderr, "ERROR: --mantel-y must be gene|adj:jaccard|diff\n"); return 1; }
+			break;
+		case 337:
+			mantel_extra = true;
+			if (!trait_perm(optarg, mantel_opt.n_perm)) { std::fprintf(stderr, "ERROR: --mantel-perm must be in [0, 2147483646]\n"); return 1; }
+			break;
+		case 338: mantel_extra = true, mantel_opt.seed = (uint32_t)std::strtoul(optarg, nullptr, 10); break;
 		case 401: std::puts(PG_VERSION); return 0;
 		default: break;
 		}
@@ -919,7 +991,14 @@ int main(int argc, char *argv[])
 		return 1;
 	}
 	if (permanova_extra && !permanova) { std::fprintf(stderr, "ERROR: --permanova-type, --permanova-metric, --permanova-perm and --permanova-seed need --permanova=FILE\n"); return 1; }
+	if (mantel && (matrix || call || curves || dist >= 0 || assoc || trait || tree >= 0 || qtrait || cluster_lo || permanova)) {
+		std::fprintf(stderr, "ERROR: --mantel cannot be combined with --matrix, --call, --curves, --dist, --assoc, --trait, --tree, --qtrait, --cluster or --permanova\n");
+		return 1;
+	}
+	if (mantel_extra && !mantel) { std::fprintf(stderr, "ERROR: --mantel-x, --mantel-y, --mantel-perm and --mantel-seed need --mantel\n"); return 1; }
+	if (mantel_y && mantel_file) { std::fprintf(stderr, "ERROR: --mantel-y cannot be combined with --mantel=FILE\n"); return 1; }
 	Output o;
+	o.mantel = mantel, o.mantel_file = mantel_file, o.mantel_opt = mantel_opt;
 	o.permanova = permanova, o.permanova_type = permanova_type_v, o.permanova_metric = permanova_metric_v, o.permanova_perm = permanova_perm_v, o.permanova_seed = permanova_seed;
 	o.cluster_lo = cluster_lo, o.cluster_hi = cluster_hi, o.cluster_iter = cluster_iter_v, o.cluster_type = cluster_type_v, o.cluster_metric = cluster_metric_v;
 	o.qtrait = qtrait, o.qtrait_perm = qtrait_perm_v, o.qtrait_seed = qtrait_seed;
