@@ -94,7 +94,7 @@ typedef struct {
  * Device layout limits (PGA_ERR_RANGE otherwise): coordinates inside a block < 2^31 (contigs beyond that arrive as virtual contigs,
  * see pga_genome_block_t; what remains out of reach is a single cluster of overlapping hits spanning 2^30 bp), < 2^30 hits and < 2^31
  * exons per shard, < 2^20 genes, < 2^24 genomes. */
-#define PGA_ABI_VERSION 17u  /* bumped whenever a struct of this header or the order of pga_backend_t changes; pga_create refuses another */
+#define PGA_ABI_VERSION 18u  /* bumped whenever a struct of this header or the order of pga_backend_t changes; pga_create refuses another */
 typedef struct {
 	uint32_t abi_version;        /* = PGA_ABI_VERSION of the header the caller was compiled against (PGA_ERR_ARG otherwise) */
 	int32_t n_genome;            /* genomes in this shard (may include genomes with 0 hits) */
@@ -622,6 +622,7 @@ typedef struct {
 	int  (*pan_medoids)(const pga_medoids_in_t *, pga_medoids_out_t *); /* may be NULL: the host driver then runs the same step itself */
 	int  (*pan_permanova)(const pga_permanova_in_t *, pga_permanova_out_t *); /* may be NULL: the host driver then runs the same step itself */
 	int  (*pan_mantel)(const pga_mantel_in_t *, pga_mantel_out_t *); /* may be NULL: the host driver then runs the same step itself */
+	int  (*final_arcs)(pga_ctx_t *, const void **, int64_t *); /* may be NULL.  The final arc table of a branch_loop that ran with final_on: host view, count; 1 = not available */
 } pga_backend_t;
 
 const pga_backend_t *pga_backend(void);
@@ -678,7 +679,11 @@ typedef struct pga_branch_par_s {
 	/* final_on != 0 (unsharded form only): n_round = ALL the rounds, and the arc round behind the last one (graph.c:313 of round
 	 * n-1, the graph that is written) is queued as well.  seg_cnt[2 n_seg] (graph.c:125-126 of that round) and n_dist_loci[2 n_seg]
 	 * (branch.c:90 of the last branch step) come back with seg_alive, all in the numbering the loop was entered with; the table
-	 * (arc_table) is in that numbering too: the caller renumbers segments and arcs (monotone, so every order stands). */
+	 * (arc_table) is in that numbering too: the caller renumbers segments and arcs (monotone, so every order stands).
+	 * The loop also queues what follows it in pg_graph_gen before its one wait: PG_SET_FILTER(shadow) of graph.c:316 (the caller's
+	 * set_filter(PGA_FLT_SHADOW) right behind the loop is then a no-op) and the table in its FINAL form -- pg_arc_t records with the
+	 * segments renumbered by seg_alive and the roundings of graph.c:170-172 applied -- which pga_final_arcs hands out.
+	 * PANGENE_LOOP=notail: neither. */
 	int32_t final_on;
 } pga_branch_par_t;
 /* pg_gen_arc (graph.c:87-177) of a sharded run with ONE wait: arc_round + the exchange + arc_merge + arc_set_current, every table
@@ -690,6 +695,13 @@ typedef struct pga_branch_par_s {
 int pga_arc_round_x(pga_ctx_t *ctx, int32_t use_ori, int32_t n_seg, const pga_loop_xchg_t *x, int32_t *seg_cnt, int32_t *deg, int64_t *n_arc);
 int pga_branch_loop(pga_ctx_t *ctx, int32_t n_round, const pga_branch_par_t *par, const int32_t *max_tot_cnt, const int32_t *max_degree,
                     const int32_t *max_dist_loci, uint8_t *seg_alive, const pga_loop_xchg_t *x, int32_t *seg_cnt /* final_on: [2 n_seg], else NULL */, int32_t *n_dist_loci /* likewise */);
+
+/* The table a pga_branch_loop with final_on left in the backend's page-locked memory: *host_view = n_arc records laid out as pg_arc_t
+ * (pangene.h:90-98: x with the renumbered segments, n_genome, tot_cnt, avg_dist, s1, s2, every other bit 0), sorted by x; valid until the
+ * context's next arc round or loop.  No wait, no copy.  Returns 1 when there is no such table: the loop did not run with final_on or did
+ * not return 0, PANGENE_LOOP=notail, the sharded form, or a table larger than the landing area (16 arcs per oriented vertex of the graph
+ * the loop was entered with; PANGENE_FINAL_ARCS_CAP=n records) -- arc_table + the caller's own conversion is the general route. */
+int pga_final_arcs(pga_ctx_t *ctx, const void **host_view, int64_t *n_arc);
 
 /* Optional: run every kernel on this hipStream_t instead of the library's own stream (lets a host
  * framework order its collectives with the kernels without extra synchronisation). */

@@ -39,6 +39,42 @@ __device__ __forceinline__ void rank_genome_body(const uint32_t *flags, const in
 		carry += tot;
 	}
 }
+// The same ranks for ONE CHUNK of a genome by a workgroup of NT threads (the form that rides in the launch of the arc round's walk, k_genes.hpp: that
+// kernel's workgroups have 256 threads, and a whole genome at 256 hits a step would outlast them).  Chunk k of genome g is RK_CHUNK hits from
+// goff[g] + k * RK_CHUNK; its workgroup first counts the walkable hits of the genome in front of the chunk (independent loads, one reduction), then
+// ranks its own hits as above -- every rx[] is written once, with the value k_rank_genome gives it.
+constexpr int RK_CHUNK = 2048;
+template <int NT>
+__device__ __forceinline__ void rank_chunk_body(const uint32_t *flags, const int32_t *goff, int32_t *rx, const int g, const int k, int (*wtot)[NT / WAVE])
+{
+	const int h0 = goff[g], h1 = goff[g + 1], tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+	const int64_t lo64 = (int64_t)h0 + (int64_t)k * RK_CHUNK;
+	if (lo64 >= h1) return; // (uniform: the genome has fewer chunks than the largest one)
+	const int lo = (int)lo64, hi = h1 - lo > RK_CHUNK ? lo + RK_CHUNK : h1;
+	int cnt = 0;
+	for (int i = h0 + tid; i < lo; i += NT) cnt += !(flags[i] & (PGA_F_FLT | PGA_F_SHADOW));
+	cnt = wave_sum(cnt);
+	if (lane == 0) wtot[0][w] = cnt;
+	__syncthreads();
+	int carry = 0;
+#pragma unroll
+	for (int q = 0; q < NT / WAVE; ++q) carry += wtot[0][q];
+	const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+	int par = 1;
+	for (int base = lo; base < hi; base += NT, par ^= 1) { // (wtot[0] is read above by every thread before the first barrier below: the first step uses wtot[1])
+		const int i = base + tid;
+		const uint32_t f = i < hi ? flags[i] : (uint32_t)PGA_F_FLT;
+		const unsigned long long m = __ballot(!(f & (PGA_F_FLT | PGA_F_SHADOW)));
+		if (lane == 0) wtot[par][w] = __popcll(m);
+		__syncthreads();
+		int pre = carry, tot = 0;
+#pragma unroll
+		for (int q = 0; q < NT / WAVE; ++q) { const int t = wtot[par][q]; tot += t; if (q < w) pre += t; }
+		if (i < hi) rx[i] = (pre + __popcll(m & lt)) | ((f & F_CSTIE) ? (int32_t)0x80000000 : 0);
+		carry += tot;
+	}
+}
+
 __global__ __launch_bounds__(RK_T) void k_rank_genome(const uint32_t *flags, const int32_t *goff, int32_t *rx, Gate gate)
 {
 	__shared__ int wtot[2][RK_T / WAVE];

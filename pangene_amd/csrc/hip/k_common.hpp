@@ -7,6 +7,10 @@
 // pass 32 bits: graph.c:73 narrows a distance to int32_t, a negative one goes into the uint64_t sum of graph.c:131-133 sign-extended,
 // and the average of THAT no longer fits (the reference prints ad:i:-2147483647 for such arcs; tests/test_abi.py holds one).
 __device__ __forceinline__ int32_t cvt_i32_x86(double v) { return (v > -2147483649.0 && v < 2147483648.0) ? (int32_t)v : (int32_t)0x80000000; }
+// (int32_t)(int64_t)double the same way (the averaged distance of graph.c:170 as the host driver's fetch_arcs writes it): the 64-bit cvttsd2si
+// truncates, gives 0x8000000000000000 for anything that does not fit (a NaN included), and the narrowing keeps the low word -- 0 then.
+// Doubles of that size are whole numbers, so the range is [-2^63, 2^63).
+__device__ __forceinline__ int32_t cvt_i64lo_x86(double v) { return (v >= -9223372036854775808.0 && v < 9223372036854775808.0) ? (int32_t)(uint32_t)(uint64_t)(int64_t)v : 0; }
 
 // ------------------------------------------------------------------------------------------------
 // small device helpers

@@ -163,14 +163,30 @@ __device__ __forceinline__ int walk_score(const int4 w0, const int4 w1, int ori,
 { // pg_get_score, graph.c:82-85: score_ori unless the dominator's gene is not a vertex and score_dom is at least as large
 	return (ori || w0.w > w1.x || w1.y < 0 || g2s[w1.y] >= 0) ? w0.w : w1.x;
 }
+// Riders (pga_branch_loop, an arc round that a branch round of the same queue follows): pg_gen_rep_pos of that branch round needs the walkable ranks
+// of the cs order -- the flags as this round's sweep left them, which nothing changes before the branch round -- and, under live lists, its records
+// cleared.  Both ride in the walk's launch as workgroups of their own behind the walk's (k_loop_front1 has held them so far, and was as long as the
+// rank chain): the FIRST n_ride workgroups of the launch -- behind the walk's they were its tail, 21.4 -> 27.0 us a launch at configs[1]; in front they
+// start at once and the walk's workgroups fill in behind them -- [0, GL * cpg) rank_chunk_body of (genome, chunk), the rest k_rep_clear.  n_ride = 0: none.
+struct WalkRide { int n_ride, GL, cpg; const int32_t *goff; int32_t *rx; void *rp_out; int64_t n_clear; int clear_bytes; };
 template <int WK_IPT>
-__global__ __launch_bounds__(BLOCK) void k_walk(Walk a)
+__global__ __launch_bounds__(BLOCK) void k_walk(Walk a, WalkRide rd)
 {
 	constexpr int WK_TILE = BLOCK * WK_IPT;
 	__shared__ int32_t s_wave[BLOCK / WAVE], s_carry;
 	if (gate_closed(a.gate)) return;
+	if ((int)blockIdx.x < rd.n_ride) { // (uniform: the whole workgroup)
+		__shared__ int wtot[2][BLOCK / WAVE];
+		const int b = (int)blockIdx.x;
+		if (b < rd.GL * rd.cpg) rank_chunk_body<BLOCK>(a.flags, rd.goff, rd.rx, b / rd.cpg, b % rd.cpg, wtot);
+		else {
+			const int64_t e = (int64_t)(b - rd.GL * rd.cpg) * BLOCK + threadIdx.x;
+			if (e < rd.n_clear) { if (rd.clear_bytes == 8) ((int2 *)rd.rp_out)[e] = make_int2(0, -1); else ((int4 *)rd.rp_out)[e] = make_int4(-1, 0, 0, 0); }
+		}
+		return;
+	}
 	const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-	const int64_t tile0 = (int64_t)blockIdx.x * WK_TILE, base = tile0 + (int64_t)tid * WK_IPT;
+	const int64_t tile0 = (int64_t)((int)blockIdx.x - rd.n_ride) * WK_TILE, base = tile0 + (int64_t)tid * WK_IPT;
 	int mark[WK_IPT];
 #pragma unroll
 	for (int k = 0; k < WK_IPT; ++k) { const int64_t i = base + k; mark[k] = (i < a.n && !(a.flags[a.yperm[i]] & (PGA_F_FLT | PGA_F_SHADOW))) ? (int)i : -1; } // graph.c:108
@@ -449,11 +465,26 @@ __device__ __forceinline__ bool gene_arcs_one(const GeneArcs &a, GeneTable<CAP, 
 // 20 000 genes x 137 hits 218 -> 170 us, configs[1] 49.6 -> 47.9; one wave a gene, which the CU holds no more of -- the LDS tables -- 62)
 constexpr int GA_WAVE_NT = 128;
 // (a template over its three sizes so that other shapes can be measured side by side: PANGENE_GA_WAVE picks one, arc_round_genes)
+// Rider (pga_branch_loop, as WalkRide above): k_rep_fill of the branch round that follows -- the ranks rode one launch earlier, the walk's tags are
+// complete -- as workgroups behind the genes' ([Q, ...): thread t of them is k_rep_fill's thread t; per thread, no LDS, no barrier).
+// form: -1 none, else the record form * 2 + CLEARED.
 template <int NT, int CAP, int HITS, int CAP_LOG2>
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(7))) void k_gene_arcs_wave_t(GeneArcs a)
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(7))) void k_gene_arcs_wave_t(GeneArcs a, RepFill rf, int ride_form)
 {
 	__shared__ GeneTable<CAP, HITS> T;
 	if (gate_closed(a.gate)) return;
+	if ((int)blockIdx.x >= a.Q) { // (only with ride_form >= 0)
+		const int t = ((int)blockIdx.x - a.Q) * NT + (int)threadIdx.x;
+		switch (ride_form) {
+		case RP_FULL * 2: rep_fill_body<RP_FULL, false>(rf, t); break;
+		case RP_FULL * 2 + 1: rep_fill_body<RP_FULL, true>(rf, t); break;
+		case RP_COMPACT * 2: rep_fill_body<RP_COMPACT, false>(rf, t); break;
+		case RP_COMPACT * 2 + 1: rep_fill_body<RP_COMPACT, true>(rf, t); break;
+		case RP_WIDE * 2: rep_fill_body<RP_WIDE, false>(rf, t); break;
+		case RP_WIDE * 2 + 1: rep_fill_body<RP_WIDE, true>(rf, t); break;
+		}
+		return;
+	}
 	const int g = blockIdx.x, tid = threadIdx.x;
 	const int sid = a.g2s[g], z0 = a.zoff[g], z1 = a.zoff[g + 1];
 	if (sid < 0) { // not a vertex: none of its hits may be walkable (graph.c:111)
@@ -512,6 +543,55 @@ __global__ __launch_bounds__(BLOCK) void k_arc_compact(const int4 *gmeta, const 
 			for (int t = 0; t < 16; ++t) sys_store(&host_box[t], dcnt[t]);
 		}
 	}
+}
+
+// The table of the graph that is WRITTEN, in its final form (pga_branch_loop with final_on: queued behind the last arc round, so the run ends with
+// one wait).  What the host driver's fetch_arcs does record by record happens here: the segments are renumbered (new id = alive segments before it,
+// the host's seg_renumber), the three roundings of graph.c:170-172 are applied and the remaining bits are zero -- 32-byte pg_arc_t records, two
+// 16-byte stores each, straight into a pinned landing area of `cap` records.  One scan gives both numberings: (alive segments, arcs) before a segment.
+struct I32x2 {
+	int32_t a, b;
+	__device__ __forceinline__ I32x2 shfl_up(int d) const { return I32x2{__shfl_up(a, d, WAVE), __shfl_up(b, d, WAVE)}; }
+	__device__ __forceinline__ I32x2 shfl(int l) const { return I32x2{__shfl(a, l, WAVE), __shfl(b, l, WAVE)}; }
+};
+struct OpSum2 { __device__ __forceinline__ I32x2 operator()(I32x2 x, I32x2 y) const { return I32x2{x.a + y.a, x.b + y.b}; } };
+struct InAliveGmeta { const uint8_t *alive; const int4 *gm; __device__ __forceinline__ I32x2 operator()(int64_t i) const { const int4 m = gm[i]; return I32x2{alive[i] != 0, m.y + m.z}; } };
+struct OutExclI32x2 { int32_t *pa, *pb; __device__ __forceinline__ void operator()(int64_t i, I32x2, I32x2 ex) const { pa[i] = ex.a, pb[i] = ex.b; } };
+
+__device__ __forceinline__ int4 arc_final_lo(uint64_t x, const pga_arc_part_t &p) { return make_int4((int32_t)(uint32_t)x, (int32_t)(uint32_t)(x >> 32), p.n_genome, p.tot_cnt); }
+__device__ __forceinline__ int4 arc_final_hi(const pga_arc_part_t &p)
+{
+	return make_int4(cvt_i64lo_x86((double)(int64_t)p.sum_dist / p.tot_cnt + .499), cvt_i32_x86((double)p.sum_s1 / p.n_genome + .499), cvt_i32_x86((double)p.sum_s2 / p.n_genome + .499), 0);
+}
+
+// one wave per segment, as k_arc_compact; a table beyond the landing area's capacity leaves only its size (the caller then takes the general route).
+// The size goes into dcnt[10]: the k_mail_flush at the loop's end takes it to the host with the other counters.
+__global__ __launch_bounds__(BLOCK) void k_arc_final(const int4 *gmeta, const int32_t *off, const int32_t *newid, int S, const pga_arc_part_t *stage, int4 *out, int64_t cap, int64_t *dcnt)
+{
+	const int lane = threadIdx.x & 63;
+	const int4 ml = gmeta[S - 1];
+	const int64_t total = (int64_t)off[S - 1] + ml.y + ml.z;
+	if (blockIdx.x == 0 && threadIdx.x == 0) dcnt[10] = total;
+	if (total > cap) return;
+	for (int sid = blockIdx.x * (BLOCK / WAVE) + (threadIdx.x >> 6); sid < S; sid += gridDim.x * (BLOCK / WAVE)) {
+		const int4 m = gmeta[sid];
+		const int o = off[sid], n = m.y + m.z;
+		for (int i = lane; i < n; i += WAVE) {
+			const pga_arc_part_t p = stage[m.x + i];
+			const uint32_t v = (uint32_t)(p.x >> 32), w = (uint32_t)p.x;
+			const uint32_t sv = v >> 1, sw = w >> 1; // (< S: an arc ends at a live segment; anything else was counted as an invariant violation and the run is repeated)
+			const uint64_t x = (uint64_t)((uint32_t)(sv < (uint32_t)S ? newid[sv] : 0) << 1 | (v & 1u)) << 32 | ((uint32_t)(sw < (uint32_t)S ? newid[sw] : 0) << 1 | (w & 1u));
+			out[2 * (size_t)(o + i)] = arc_final_lo(x, p);
+			out[2 * (size_t)(o + i) + 1] = arc_final_hi(p);
+		}
+	}
+}
+
+// (tests) the two conversions of a final record on the device, for given sums
+__global__ void k_arc_final_probe(const pga_arc_part_t *in, int64_t n, int4 *out)
+{
+	const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+	if (i < n) out[i] = arc_final_hi(in[i]);
 }
 
 // the same into the rank's slot of a sharded round's all-gather (k_arcs.hpp, XS_HDR): the table, the segment counters and the table's size

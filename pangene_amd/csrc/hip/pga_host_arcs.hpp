@@ -104,6 +104,25 @@ static void time_mark(pga_ctx *c, TimedLaunch *t, int which, bool end)
 	else { (void)hipEventRecord(t->b, c->st); c->timed.push_back(*t); }
 }
 
+// the buffers and arguments of pg_gen_rep_pos (k_rep_fill, k_branch.hpp) for the walk that stands: pga_rep_pos, and the riders of an arc round (below)
+static int rep_fill_args(pga_ctx *c, RepFill *rf, int32_t **rx_out)
+{
+	const int N = c->N, GL = c->n_genome, Q = c->Q;
+	const int64_t n_ent = (int64_t)Q * GL;
+	int4 *rp = (int4 *)c->pool.get(S_RP_SEG, sizeof(int4) * (size_t)n_ent);
+	int32_t *iv = (int32_t *)c->pool.get(S_RP_IV, sizeof(int32_t) * (size_t)n_ent);
+	int32_t *hzl = (int32_t *)c->pool.get(S_HZLIST, sizeof(int32_t) * PGA_HAZARD_CAP);
+	int32_t *rx = (int32_t *)c->pool.get(S_I32_B, sizeof(int32_t) * (size_t)std::max(N, 1));
+	if (!rp || !iv || !hzl || !rx) return PGA_ERR_NOMEM;
+	*rf = RepFill{ c->tg, n_ent, GL, Q, N, c->NL, c->zx, c->zy, c->zg, c->zst, c->zoff, c->hbk, c->round_tag, c->recA, c->gid, c->flags, rx, c->goff, c->ctg_base, (void *)rp, iv, c->dcnt, hzl, c->vfirst, c->vbase, c->gate };
+	*rx_out = rx;
+	return 0;
+}
+
+// Riders of an arc round inside pga_branch_loop (k_genes.hpp: WalkRide, k_gene_arcs_wave_t): the loop sets ride_want for an arc round that a branch
+// round of the same queue follows; what did ride is remembered with the walk's tag, and that branch round's front leaves it out (rep_pos_impl).
+static bool ride_ranks_now(const pga_ctx *c) { return c->ride_want >= 1 && c->N > 0 && c->tg_valid && !c->timing_rounds; }
+
 // (A) of k_genes.hpp: walk the cm order once, leave every walkable hit's two half-arc records
 static int ensure_half_arcs(pga_ctx *c, int use_ori)
 {
@@ -124,8 +143,21 @@ static int ensure_half_arcs(pga_ctx *c, int use_ori)
 	TimedLaunch tw; if (c->timing_rounds) time_mark(c, &tw, 6, false);
 	const Walk wk = {c->flags, c->ylist, c->wrec, c->g2s, c->hfk, c->hbk, c->hfp, c->hbp, c->round_tag, use_ori, c->NL, c->dcnt, hzl, c->gate};
 	static const int ipt_env = [] { const char *e = getenv("PANGENE_WALK_IPT"); return e ? atoi(e) : 0; }(); // (measurements: 1 / 4 positions a thread whatever the size)
-	if (ipt_env == 4 || (ipt_env != 1 && c->NL >= WK_FEW_FROM)) hipLaunchKernelGGL(k_walk<4>, dim3(nblk(c->NL, BLOCK * 4)), dim3(BLOCK), 0, c->st, wk);
-	else if (c->NL) hipLaunchKernelGGL(k_walk<1>, dim3(nblk(c->NL, BLOCK)), dim3(BLOCK), 0, c->st, wk);
+	const bool four = ipt_env == 4 || (ipt_env != 1 && c->NL >= WK_FEW_FROM);
+	WalkRide rd = { 0, 0, 1, nullptr, nullptr, nullptr, 0, 16 };
+	unsigned nb = four ? nblk(c->NL, BLOCK * 4) : nblk(c->NL, BLOCK);
+	c->ride_done = 0;
+	if (ride_ranks_now(c) && c->NL) { // (the loop's arc round: the ranks and the clear of the next branch round's pg_gen_rep_pos behind the walk's own workgroups)
+		RepFill rf; int32_t *rx;
+		TRY(rep_fill_args(c, &rf, &rx));
+		const int64_t n_clear = c->live_on ? rf.n_ent : 0;
+		const unsigned n_ride = (unsigned)(c->n_genome * c->ride_cpg) + nblk(n_clear);
+		rd = WalkRide{ (int)n_ride, c->n_genome, c->ride_cpg, c->goff, rx, rf.rp_out, n_clear, c->rp_form == RP_COMPACT ? 8 : 16 };
+		nb += n_ride;
+		c->ride_done = 1, c->ride_tag = c->round_tag;
+	}
+	if (four) hipLaunchKernelGGL(k_walk<4>, dim3(nb), dim3(BLOCK), 0, c->st, wk, rd);
+	else if (c->NL) hipLaunchKernelGGL(k_walk<1>, dim3(nb), dim3(BLOCK), 0, c->st, wk, rd);
 	if (c->timing_rounds) time_mark(c, &tw, 6, true);
 	c->ha_valid = true, c->ha_ori = use_ori;
 	return 0;
@@ -158,7 +190,7 @@ static int arc_round_genes(pga_ctx *c, int use_ori, int32_t **seg_cnt_out, int32
 	if (!seg_cnt || !stage || !gmeta) return PGA_ERR_NOMEM;
 	TRY(cur_table(c, cap, S, &t));
 	*seg_cnt_out = seg_cnt, *deg_out = t.dg;
-	c->table_sparse = true;
+	c->table_sparse = true, c->fin_on = false;
 	TimedLaunch tr; if (c->timing_rounds) time_mark(c, &tr, 5, false);
 	TRY(launch_sweep<0>(c, 2)); // graph.c:102
 	TRY(ensure_half_arcs(c, use_ori));
@@ -174,7 +206,15 @@ static int arc_round_genes(pga_ctx *c, int use_ori, int32_t **seg_cnt_out, int32
 	                t.ax, t.s1, t.agid, t.aw, t.vs, t.ve, t.dg, t.vwk, h_round_dev, big, c->ga_ctl, c->dcnt, c->gate, (c->gate.w || c->loop_gated) ? c->loopctl + 2 : (int32_t *)nullptr };
 	// (round 6, measured side by side at configs[1] / human 47 x 20 k, ms per pass: <128 threads, 128 keys, 512 hits> 5.26 / 5.11 -- kept; <64, 64, 256> 5.83 / 4.98;
 	// <128, 64, 256> 5.65 / 5.08; <64, 128, 512> 5.49 / 5.13; <64, 32, 256> 5.90 / 5.05: smaller tables put more genes on a CU and send more of them to the second kernel)
-	hipLaunchKernelGGL((k_gene_arcs_wave_t<GA_WAVE_NT, GA_CAP_WAVE, GA_WAVE_HITS, 7>), dim3((unsigned)c->Q), dim3(GA_WAVE_NT), 0, c->st, ga);
+	RepFill rf = {}; int ride_form = -1; unsigned nb_genes = (unsigned)c->Q;
+	if (c->ride_want >= 2 && c->ride_done == 1 && c->ride_tag == c->round_tag) { // the records of the next branch round's pg_gen_rep_pos behind the genes' workgroups (the ranks rode with the walk)
+		int32_t *rx;
+		TRY(rep_fill_args(c, &rf, &rx));
+		ride_form = c->rp_form * 2 + (c->live_on ? 1 : 0);
+		nb_genes += nblk(c->live_on ? std::max(c->NL, 1) : std::max(c->NL, c->Q), GA_WAVE_NT);
+		c->ride_done = 2;
+	}
+	hipLaunchKernelGGL((k_gene_arcs_wave_t<GA_WAVE_NT, GA_CAP_WAVE, GA_WAVE_HITS, 7>), dim3(nb_genes), dim3(GA_WAVE_NT), 0, c->st, ga, rf, ride_form);
 	hipLaunchKernelGGL(k_gene_arcs_big, dim3((unsigned)std::min(c->Q, 8 * c->n_cu)), dim3(GA_BIG_NT), 0, c->st, ga);
 	if (c->timing_rounds) time_mark(c, &tr, 5, true);
 	if (mail) hipLaunchKernelGGL(k_mail_round, dim3(1), dim3(64), 0, c->st, c->dcnt, c->h_box, h_round_dev ? h_round_dev + 4 * (size_t)S : (int32_t *)nullptr); // invariant / overflow counters for the host; the overflow counter starts again
@@ -200,6 +240,43 @@ static int arc_table_compact(pga_ctx *c, pga_arc_part_t **arcs_out, int64_t *n_o
 	return 0;
 }
 
+// The same table in its final form, QUEUED (pga_branch_loop with final_on, behind its last arc round): the segments renumbered by the `alive`
+// bytes, the roundings of graph.c:170-172 applied, 32-byte pg_arc_t records in the pinned landing area (k_arc_final).  Nothing waits here: the
+// size arrives in the mailbox with the loop's own wait.  A table beyond the landing area leaves only its size.
+static int arc_table_final_queue(pga_ctx *c, const uint8_t *alive, bool *queued)
+{
+	const int S = c->n_seg;
+	*queued = false;
+	if (S == 0 || c->N == 0) return 0;
+	static const long long cap_env = [] { const char *e = getenv("PANGENE_FINAL_ARCS_CAP"); return e ? atoll(e) : 0ll; }(); // (tests: a landing area of this many records)
+	// 16 arcs per oriented vertex of the graph the loop was entered with (pg_flt_high_occ keeps the out-degrees near max_degree = 15 and most vertices
+	// far below it); never more than the table can hold at all
+	const int64_t cap = std::min<int64_t>(cap_env > 0 ? cap_env : 32 * (int64_t)S, 2 * (int64_t)c->N + 2);
+	if (c->h_fin_cap < cap) { // (the arena never takes memory back: a kernel still writing into the old area does no harm)
+		c->h_fin = c->pin.get(32 * (size_t)cap + 64);
+		if (!c->h_fin) { c->h_fin_cap = 0; return PGA_ERR_NOMEM; }
+		c->h_fin_cap = cap;
+	}
+	const pga_arc_part_t *stage = (const pga_arc_part_t *)c->pool.get(S_ARC_STAGE, 0);
+	const int4 *gmeta = (const int4 *)c->pool.get(S_GMETA, 0);
+	int32_t *off = (int32_t *)c->pool.get(S_GOFF, sizeof(int32_t) * (size_t)S), *newid = (int32_t *)c->pool.get(S_FIN_ID, sizeof(int32_t) * (size_t)S);
+	I32x2 *tile = (I32x2 *)c->pool.get(S_TILE, tile_buf_bytes(S));
+	if (!stage || !gmeta || !off || !newid || !tile) return PGA_ERR_NOMEM;
+	int4 *out = nullptr;
+	HIPCHK(hipHostGetDevicePointer((void **)&out, c->h_fin, 0));
+	device_scan<I32x2>(InAliveGmeta{alive, gmeta}, OutExclI32x2{newid, off}, S, tile, OpSum2{}, I32x2{0, 0}, c->st);
+	hipLaunchKernelGGL(k_arc_final, dim3(nblk(S, BLOCK / WAVE)), dim3(BLOCK), 0, c->st, gmeta, (const int32_t *)off, (const int32_t *)newid, S, stage, out, cap, c->dcnt);
+	c->fin_cap = cap, *queued = true;
+	return 0;
+}
+
+extern "C" int pga_final_arcs(pga_ctx_t *c, const void **host_view, int64_t *n_arc)
+{
+	if (!c->fin_on || host_view == nullptr || n_arc == nullptr) return 1;
+	*host_view = c->h_fin, *n_arc = c->fin_n;
+	return 0;
+}
+
 // The reference's formulation -- every temp arc through one global sort (graph.c:127,151): kept as the path of rounds in which a
 // hub gene overflows the LDS table of k_gene_arcs, and (PANGENE_ARC_SORT_PATH=1) as an independent check of the gene path.
 // sweep_done: the round's pg_shadow (graph.c:102) has run already (a gene-path attempt that overflowed): it must not run again --
@@ -210,6 +287,7 @@ static int arc_round_sorted(pga_ctx_t *c, int32_t use_ori, int32_t **seg_cnt_out
 	int32_t *seg_cnt = (int32_t *)c->pool.get(S_SEGCNT, sizeof(int32_t) * 2 * (size_t)std::max(1, S) * SEGCNT_COPIES);
 	if (!seg_cnt) return PGA_ERR_NOMEM;
 	*seg_cnt_out = seg_cnt, *arcs_out = nullptr, *n_arcs_out = 0;
+	c->fin_on = false;
 	if (N == 0) {
 		HIPCHK(hipMemsetAsync(seg_cnt, 0, sizeof(int32_t) * 2 * (size_t)std::max(1, S) * SEGCNT_COPIES, c->st));
 		return sync_st(c);
@@ -408,7 +486,7 @@ extern "C" int pga_arc_set_current(pga_ctx_t *c, const pga_arc_part_t *arcs, int
 {
 	const int n_vtx = 2 * n_seg;
 	c->br_n = n_arc, c->br_S = n_seg, c->br_np = 0;
-	c->cur_tab = arcs, c->cur_tab_n = n_arc, c->table_sparse = false;
+	c->cur_tab = arcs, c->cur_tab_n = n_arc, c->table_sparse = false, c->fin_on = false;
 	if (n_vtx) memset(deg, 0, sizeof(int32_t) * (size_t)n_vtx);
 	CurTable t;
 	TRY(cur_table(c, n_arc, n_seg, &t));

@@ -4,30 +4,34 @@
 
 
 // (pga_branch_loop) the launches of pg_gen_rep_pos left to the fused launches of the round's front (k_loop_front1 / 2, k_branch.hpp): what they need
-struct RepDefer { bool on; RepFill rf; int32_t *rx; unsigned nb; bool cleared; };
+// rode: what of it rode in the launches of the arc round before (pga_host_arcs.hpp: 1 the ranks and the clear, 2 the records as well)
+struct RepDefer { bool on; RepFill rf; int32_t *rx; unsigned nb; bool cleared; int rode; };
 
 static int rep_pos_impl(pga_ctx *c, RepDefer *df)
 {
 	const int N = c->N, GL = c->n_genome, Q = c->Q;
-	if (df) df->on = false;
+	if (df) df->on = false, df->rode = 0;
 	const int64_t n_ent = (int64_t)Q * GL;
-	int4 *rp = (int4 *)c->pool.get(S_RP_SEG, sizeof(int4) * (size_t)n_ent);
-	int32_t *iv = (int32_t *)c->pool.get(S_RP_IV, sizeof(int32_t) * (size_t)n_ent);
-	int32_t *hzl = (int32_t *)c->pool.get(S_HZLIST, sizeof(int32_t) * PGA_HAZARD_CAP);
-	if (!rp || !iv || !hzl) return PGA_ERR_NOMEM;
+	RepFill rf; int32_t *rx;
+	TRY(rep_fill_args(c, &rf, &rx));
+	int4 *rp = (int4 *)rf.rp_out;
 	if (N) {
-		int32_t *rx = (int32_t *)c->pool.get(S_I32_B, sizeof(int32_t) * (size_t)N);
 		I32 *tile = (I32 *)c->pool.get(S_TILE, tile_buf_bytes(N));
-		if (!rx || !tile) return PGA_ERR_NOMEM;
+		if (!tile) return PGA_ERR_NOMEM;
+		const int want = c->ride_want;
+		c->ride_want = 0; // (a walk that has to be made here is nobody's arc round)
 		TRY(ensure_half_arcs(c, c->ha_ori < 0 ? 0 : c->ha_ori)); // which hits are walkable, gene-major (normally left by the arc round just before)
+		c->ride_want = want;
+		TRY(rep_fill_args(c, &rf, &rx)); // (the walk's tag)
 		static const bool rank_scan = env_has("PANGENE_RANK", "scan"); // (tests: the general scan on shards of short genomes too)
 		const bool defer = df && c->gs_np <= (1 << 15) && !rank_scan;
+		// what rode with the arc round before (pga_branch_loop): valid for the walk that stands, under the same gate, the lists as they were
+		const int rode = (defer && c->in_loop && c->ride_done && c->ride_tag == c->round_tag && c->tg_valid) ? c->ride_done : 0;
 		if (defer) ; // (k_loop_front1)
 		else if (c->gs_np <= (1 << 15) && !rank_scan) hipLaunchKernelGGL(k_rank_genome, dim3((unsigned)GL), dim3(RK_T), 0, c->st, (const uint32_t *)c->flags, (const int32_t *)c->goff, rx, c->gate); // rank among the walkable hits of the genome, cs order
 		else device_scan<I32>(InWalkX{c->flags}, OutRank{rx, c->flags}, N, tile, OpSum{}, I32{0}, c->st, c->gate); // rank among the walkable hits, cs order
 		if (!c->tg_valid) { hipLaunchKernelGGL(k_tie_bounds, dim3(nblk(N)), dim3(BLOCK), 0, c->st, (const int4 *)c->recA, (const uint32_t *)c->flags, N, c->tg); c->tg_valid = true; }
-		RepFill rf = { c->tg, n_ent, GL, Q, N, c->NL, c->zx, c->zy, c->zg, c->zst, c->zoff, c->hbk, c->round_tag, c->recA, c->gid, c->flags, rx, c->goff, c->ctg_base, (void *)rp, iv, c->dcnt, hzl, c->vfirst, c->vbase, c->gate };
-		if (defer) { df->on = true, df->rf = rf, df->rx = rx, df->cleared = c->live_on, df->nb = nblk(c->live_on ? std::max(c->NL, 1) : std::max(c->NL, Q)); return 0; }
+		if (defer) { df->on = true, df->rf = rf, df->rx = rx, df->cleared = c->live_on, df->nb = nblk(c->live_on ? std::max(c->NL, 1) : std::max(c->NL, Q)), df->rode = rode; return 0; }
 		if (c->live_on) { // the index holds the live hits only: genes and (gene, genome) groups without an entry are many -- their records by one coalesced fill
 			const unsigned nb = nblk(std::max(c->NL, 1));
 			if (c->rp_form == RP_COMPACT) {
@@ -92,10 +96,12 @@ static inline size_t loop_btot_at(int n_vtx) { return ((size_t)n_vtx + 7) & ~(si
 static void rep_launch_deferred(pga_ctx *c, const RepDefer &d)
 {
 	const RepFill &rf = d.rf;
-	hipLaunchKernelGGL(k_rank_genome, dim3((unsigned)rf.GL), dim3(RK_T), 0, c->st, rf.flags, rf.goff, d.rx, rf.gate);
+	if (d.rode >= 2) return;
+	if (d.rode == 0) hipLaunchKernelGGL(k_rank_genome, dim3((unsigned)rf.GL), dim3(RK_T), 0, c->st, rf.flags, rf.goff, d.rx, rf.gate);
 	const int form = c->rp_form;
 	if (d.cleared) {
-		if (rf.n_ent && form == RP_COMPACT) hipLaunchKernelGGL((k_rep_clear<RP_COMPACT>), dim3(nblk(rf.n_ent)), dim3(BLOCK), 0, c->st, rf.rp_out, rf.n_ent, rf.gate);
+		if (d.rode) ;
+		else if (rf.n_ent && form == RP_COMPACT) hipLaunchKernelGGL((k_rep_clear<RP_COMPACT>), dim3(nblk(rf.n_ent)), dim3(BLOCK), 0, c->st, rf.rp_out, rf.n_ent, rf.gate);
 		else if (rf.n_ent) hipLaunchKernelGGL((k_rep_clear<RP_FULL>), dim3(nblk(rf.n_ent)), dim3(BLOCK), 0, c->st, rf.rp_out, rf.n_ent, rf.gate);
 		if (form == RP_COMPACT) hipLaunchKernelGGL((k_rep_fill<RP_COMPACT, true>), dim3(d.nb), dim3(BLOCK), 0, c->st, rf);
 		else if (form == RP_WIDE) hipLaunchKernelGGL((k_rep_fill<RP_WIDE, true>), dim3(d.nb), dim3(BLOCK), 0, c->st, rf);
@@ -117,8 +123,9 @@ static int branch_enumerate(pga_ctx *c, int32_t **cnt, const RepDefer *df = null
 	if (!pairs || !s1 || !agid || !vs || !ve || !poff) return PGA_ERR_NOMEM;
 	if (df) { // the records of pg_gen_rep_pos and the pair list in one launch (k_loop_front1 ran: ranks, counts, offsets inside each workgroup of 1 024 vertices)
 		const int32_t *pc = (const int32_t *)c->pool.get(S_BR_PC, 0);
-		const LoopFront2 a = { (int)df->nb, n_vtx, (n_vtx + RK_T - 1) / RK_T, vs, ve, s1, agid, c->br_par.diff, poff, pc + loop_btot_at(n_vtx), pc, pairs, c->br_cap, c->dcnt };
-		const dim3 grid(df->nb + nblk(n_vtx, BLOCK / WAVE));
+		const unsigned nb_rep = df->rode >= 2 ? 0u : df->nb; // (the records rode with the arc round's gene kernel: the pair list alone)
+		const LoopFront2 a = { (int)nb_rep, n_vtx, (n_vtx + RK_T - 1) / RK_T, vs, ve, s1, agid, c->br_par.diff, poff, pc + loop_btot_at(n_vtx), pc, pairs, c->br_cap, c->dcnt };
+		const dim3 grid(nb_rep + nblk(n_vtx, BLOCK / WAVE));
 		const int form = c->rp_form;
 		if (df->cleared) {
 			if (form == RP_COMPACT) hipLaunchKernelGGL((k_loop_front2<RP_COMPACT, true>), grid, dim3(BLOCK), 0, c->st, df->rf, a);
@@ -165,9 +172,10 @@ static int branch_pairs_impl(pga_ctx *c, const uint64_t *arc_x, const int32_t *a
 	if (df) { // (pga_branch_loop) the counts, their offsets inside workgroups of 1 024 vertices, the ranks of pg_gen_rep_pos and its clear in ONE launch
 		const int nbc = (n_vtx + RK_T - 1) / RK_T; // <= 64 (one_wg)
 		const RepFill &rf = df->rf;
-		const int64_t n_clear = df->cleared ? rf.n_ent : 0;
-		const LoopFront a = { n_vtx, nbc, rf.GL, vs, ve, s1, branch_diff, pc, poff, pc + loop_btot_at(n_vtx), rf.flags, rf.goff, df->rx, rf.rp_out, n_clear, c->rp_form == RP_COMPACT ? 8 : 16, c->gate };
-		hipLaunchKernelGGL(k_loop_front1, dim3((unsigned)(nbc + rf.GL + (n_clear + RK_T - 1) / RK_T)), dim3(RK_T), 0, c->st, a);
+		const int64_t n_clear = (df->cleared && !df->rode) ? rf.n_ent : 0;
+		const int gl = df->rode ? 0 : rf.GL; // (the ranks and the clear rode with the arc round's walk: the pair counts alone)
+		const LoopFront a = { n_vtx, nbc, gl, vs, ve, s1, branch_diff, pc, poff, pc + loop_btot_at(n_vtx), rf.flags, rf.goff, df->rx, rf.rp_out, n_clear, c->rp_form == RP_COMPACT ? 8 : 16, c->gate };
+		hipLaunchKernelGGL(k_loop_front1, dim3((unsigned)(nbc + gl + (n_clear + RK_T - 1) / RK_T)), dim3(RK_T), 0, c->st, a);
 		if (c->br_cap < 4 * (int64_t)n_vtx && !loop_cap_forced(c)) c->br_cap = 4 * (int64_t)n_vtx;
 		return branch_enumerate(c, cnt, df);
 	}
@@ -462,8 +470,20 @@ extern "C" int pga_branch_loop(pga_ctx_t *c, int32_t n_round, const pga_branch_p
 	// in the header of the round's all-gather (k_xs_compact writes the word whether its gate is open or not) and k_xs_sum_rank stamps the round on every rank when any rank marked; a rank's own arc
 	// round follows its own hits (nothing changed here: its slot stands as it is, k_xs_compact leaves), the collectives are queued all the same.
 	const bool gated = !no_skip && (int64_t)c->round_tag + n_round + 4 < (int64_t)HA_TAG_MAX;
-	struct GateScope { pga_ctx *c; ~GateScope() { c->gate = Gate{nullptr, 0}, c->loop_gated = false, c->in_loop = false; } } gate_scope{c}; // (every way out of this function leaves the launches open)
+	struct GateScope { pga_ctx *c; ~GateScope() { c->gate = Gate{nullptr, 0}, c->loop_gated = false, c->in_loop = false, c->ride_want = 0, c->ride_done = 0; } } gate_scope{c}; // (every way out of this function leaves the launches open)
 	c->loop_gated = gated, c->in_loop = true;
+	// Riders (pga_host_arcs.hpp): an arc round that a branch round of this queue follows carries the front half of that round's pg_gen_rep_pos in its own
+	// launches -- the ranks (and the clear) with the walk, the records with the gene kernel; both run under the arc round's gate, which is the gate of
+	// that branch round's front (something changed in round r).  PANGENE_LOOP_RIDE=0: nothing rides, 1: the ranks only, 2 (default): both.  Not with
+	// the ranks by the general scan, genomes beyond k_rank_genome's reach, the unfused front, timed rounds or the sharded form: the front as it was.
+	static const int ride_env = [] { const char *e = getenv("PANGENE_LOOP_RIDE"); const int v = e ? atoi(e) : 2; return v < 0 ? 0 : v > 2 ? 2 : v; }();
+	int ride = 0;
+	c->ride_want = 0, c->ride_done = 0;
+	if (ride_env && x == nullptr && !c->timing_rounds && !env_has("PANGENE_LOOP_FUSE", "0") && !env_has("PANGENE_RANK", "scan") && c->gs_np <= (1 << 15)) {
+		int64_t maxg = 0;
+		for (size_t g = 0; g + 1 < c->h_goff.size(); ++g) maxg = std::max<int64_t>(maxg, (int64_t)c->h_goff[g + 1] - c->h_goff[g]);
+		if (maxg <= (1 << 15)) ride = ride_env, c->ride_cpg = (int)std::max<int64_t>(1, (maxg + RK_CHUNK - 1) / RK_CHUNK);
+	}
 	const uint32_t tag_before = c->round_tag;
 	HIPCHK(hipMemsetAsync(c->dcnt + 16, 0, sizeof(int64_t), c->st)); // the longest pair list that did not fit (k_loop_front2 / k_pair_offsets)
 	if (gated) HIPCHK(hipMemsetAsync(c->loopctl, 0xff, 4 * sizeof(int32_t), c->st)); // -1: nothing has happened yet; round 0 runs (its branch steps ask for a change in round -1 or later)
@@ -529,13 +549,27 @@ extern "C" int pga_branch_loop(pga_ctx_t *c, int32_t n_round, const pga_branch_p
 			// (sharded: so does the first arc round of the call -- the slot it fills must hold THIS rank's counters, and what the caller left in device
 			// memory are the global ones)
 			if (rebuilt || (x && first_x)) c->gate = Gate{nullptr, 0};
-			TRY(arc_round_genes(c, par->use_ori, &seg_cnt, &deg, nullptr, false)); // (no mail: the kernels raise the sticky flag themselves)
+			c->ride_want = r + 1 < n_round ? ride : 0;
+			const int rc_arc = arc_round_genes(c, par->use_ori, &seg_cnt, &deg, nullptr, false); // (no mail: the kernels raise the sticky flag themselves)
+			c->ride_want = 0;
+			if (rc_arc) return rc_arc;
 			c->br_n = 2 * (int64_t)N + 2, c->br_S = S, c->br_np = 0;
 			if (x) { TRY(loop_exchange_table(c, L, first_x ? Gate{nullptr, 0} : c->gate, gated ? c->loopctl : (int32_t *)nullptr, r)); c->br_n = L.ecap; first_x = false; }
 		}
 	}
 	c->gate = Gate{nullptr, 0};
 	c->arc_deferred = false, c->arc_done = false;
+	// The tail of the run behind the last arc round, before anybody waits: PG_SET_FILTER(shadow) of graph.c:316 and the written graph's table in its
+	// final form, in pinned memory (k_arc_final) -- what the caller would otherwise queue after this loop's wait, with two more waits of its own.
+	// Whatever makes this call return anything but 0 has the whole run repeated, so queuing them early costs nothing.  PANGENE_LOOP=notail: as before.
+	static const bool no_tail = env_has("PANGENE_LOOP", "notail");
+	const bool tail_on = par->final_on && x == nullptr && !no_tail;
+	c->shadow_queued = false, c->fin_on = false;
+	bool fin_queued = false;
+	if (tail_on) {
+		TRY(pga_set_filter(c, PGA_FLT_SHADOW));
+		TRY(arc_table_final_queue(c, alive, &fin_queued));
+	}
 	int32_t *h_ctl = nullptr;
 	if (gated) {
 		if (!c->h_loopctl) c->h_loopctl = (int32_t *)c->pin.get(64);
@@ -602,6 +636,8 @@ extern "C" int pga_branch_loop(pga_ctx_t *c, int32_t n_round, const pga_branch_p
 		return 1;
 	}
 	memcpy(seg_alive, c->h_fetch, (size_t)S);
+	c->shadow_queued = tail_on; // (the run stands: so do the filter and, when it fitted its landing area, the table -- pga_final_arcs)
+	if (fin_queued) c->fin_n = c->h_cnt[10], c->fin_on = c->fin_n >= 0 && c->fin_n <= c->fin_cap;
 	if (par->final_on) memcpy(seg_cnt_host, h_fin, sizeof(int32_t) * (size_t)n_vtx), memcpy(ndl_host, h_fin + n_vtx, sizeof(int32_t) * (size_t)n_vtx);
 	return 0;
 }

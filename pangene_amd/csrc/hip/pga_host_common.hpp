@@ -94,7 +94,7 @@ template <int MODE> static int launch_sweep(pga_ctx *c, int timed_which)
 		HIPCHK(hipEventCreate(&t.a)); HIPCHK(hipEventCreate(&t.b));
 		if (reps != 1) HIPCHK(hipEventRecord(t.a, c->st));
 	}
-	c->walk_valid = false, c->ha_valid = false;
+	c->walk_valid = false, c->ha_valid = false, c->shadow_queued = false; // (a sweep moves the shadow bits: a filter queued before it does not stand for one asked for after it)
 	const int nt = std::max(1, (int)nblk(n_sw, SW_TILE));
 	v.prof = nullptr; v.dbg = 0;
 #ifdef PGA_SW_PROFILE

@@ -146,3 +146,19 @@ extern "C" int pga_selftest_scan(const int32_t *in, const int32_t *seg, int32_t 
 	(void)hipFree(di); (void)hipFree(ds); (void)hipFree(dout); (void)hipFree(tile);
 	return 0;
 }
+
+// the roundings of a final arc record on the device (k_genes.hpp: arc_final_hi): out[4 n] = {avg_dist, s1, s2, 0} of every in[i]
+extern "C" int pga_selftest_arc_final(const pga_arc_part_t *in, int64_t n, int32_t *out)
+{
+	int ndev = 0;
+	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return PGA_ERR_NO_DEVICE;
+	if (n <= 0 || in == nullptr || out == nullptr) return PGA_ERR_ARG;
+	pga_arc_part_t *di; int4 *dout;
+	HIPCHK(hipMalloc((void **)&di, sizeof(pga_arc_part_t) * (size_t)n)); HIPCHK(hipMalloc((void **)&dout, sizeof(int4) * (size_t)n));
+	HIPCHK(hipMemcpy(di, in, sizeof(pga_arc_part_t) * (size_t)n, hipMemcpyHostToDevice));
+	hipLaunchKernelGGL(k_arc_final_probe, dim3(nblk(n)), dim3(BLOCK), 0, 0, (const pga_arc_part_t *)di, n, dout);
+	HIPCHK(hipDeviceSynchronize());
+	HIPCHK(hipMemcpy(out, dout, sizeof(int4) * (size_t)n, hipMemcpyDeviceToHost));
+	(void)hipFree(di); (void)hipFree(dout);
+	return 0;
+}

@@ -69,6 +69,9 @@ extern "C" int pga_shadow(pga_ctx_t *c, int32_t cal_dom_sc, int32_t *stats)
 extern "C" int pga_set_filter(pga_ctx_t *c, int32_t which)
 {
 	if (which < 0 || which > 3) return PGA_ERR_ARG;
+	const bool queued = c->shadow_queued; // (pga_branch_loop with final_on queued this very filter behind its last arc round, and nothing has touched the hits since)
+	c->shadow_queued = false;
+	if (queued && which == PGA_FLT_SHADOW) return 0;
 	c->walk_valid = false, c->ha_valid = false;
 	if (c->N) hipLaunchKernelGGL(k_set_filter, dim3(nblk(c->N)), dim3(BLOCK), 0, c->st, c->flags, c->N, which);
 	return 0;

@@ -1176,9 +1176,27 @@ static int arc_collect(const pg_opt_t *opt, pg_graph_t *q, DataExt *ext)
 }
 
 // bring the round's arc table to the host and apply the three double roundings of graph.c:170-172
-static int fetch_arcs(pg_graph_t *q, DataExt *ext)
+// loop_final: the rounds were queued to the end (branch_loop with final_on).  The backend then has the table in its final form already -- renumbered,
+// rounded, in page-locked memory, there since the loop's own wait (final_arcs): one copy, no backend call that waits, no loop over the records.
+// Whenever it has not (no such entry, a table beyond its landing area, PANGENE_LOOP=notail) the general route below does the same.
+static int fetch_arcs(pg_graph_t *q, DataExt *ext, bool loop_final = false)
 {
 	Phase ph_host(PH_ARC_HOST);
+	if (loop_final && ext->be->final_arcs != nullptr) {
+		const void *view = nullptr;
+		int64_t n = 0;
+		if (ext->be->final_arcs(ext->ctx, &view, &n) == 0) {
+			static_assert(sizeof(pg_arc_t) == 32, "the backend writes pg_arc_t records");
+			q->n_arc = (int32_t)n;
+			if (n > q->m_arc) {
+				q->m_arc = (int32_t)n + ((int32_t)n >> 1) + 16;
+				q->arc = (pg_arc_t *)std::realloc(q->arc, sizeof(pg_arc_t) * (size_t)q->m_arc);
+			}
+			if (n) std::memcpy(q->arc, view, sizeof(pg_arc_t) * (size_t)n);
+			if (std::getenv("PANGENE_TIMING")) std::fprintf(stderr, "[fetch_arcs] the loop left the final table: %lld arcs, no wait\n", (long long)n);
+			return 0;
+		}
+	}
 	{ // the table as one array sorted by x, wherever the last round left it
 		int64_t n = 0;
 		BE_CALL(ext->be->arc_table(ext->ctx, &ext->cur_arcs, &n), "arc_table");
@@ -1521,7 +1539,7 @@ static int graph_gen_impl(const pg_opt_t *opt, pg_graph_t *q)
 		BE_CALL(trace_state(ext, "gen_arc", i + 3), "trace");
 	}
 	BE_CALL(be->set_filter(ctx, PGA_FLT_SHADOW), "set_filter"); // graph.c:316
-	BE_CALL(fetch_arcs(q, ext), "fetch_arcs");
+	BE_CALL(fetch_arcs(q, ext, queued_all), "fetch_arcs");
 	if (queued_all) { // the table is on the host: now the backend may learn the new numbering (gene matrix, a later run)
 		ext->seg_renumber.clear();
 		BE_CALL(flag_vtx(q, ext), "flag_vtx");
