@@ -4,11 +4,10 @@
 // a[i][j] b[o[i]][o[j]]; Z_obs is Z of the identity, and n_ge / n_le count the permutations p with Z_p >= Z_obs / Z_p <= Z_obs.  Unlike
 // k_perma_quad, which permutes a 0/1 label row and so is a matrix product, this permutes the assemblies themselves: per permutation
 // N (N - 1) / 2 gathered multiply-adds, no matrix cores.
-//   order  k_mantel_order: the orders of one batch as uint16 rows ord[p][N] (N <= 16 384).  One lane per permutation runs the swap
-//          sequence curves pins (fisher_yates_order: from the last column down, j = next() % (i + 1), splitmix64 from
-//          mix((seed << 32) | p)) over a private row.  As in k_trait_perm the 64 rows of a wave are lane-interleaved (element k of lane l
-//          at k * 64 + l), in LDS while they fit 32 KiB (N <= 256) and in a global scratch buffer of the same layout beyond; the finished
-//          rows are written row-major.  identity: no swaps -- the observed matrix as a batch of one.
+//   order  k_mantel_order: the orders of one batch as uint16 rows ord[p][N] (N <= 16 384).  One lane per permutation runs the pinned
+//          swap sequence (k_perm.hpp) over a private row that starts as 0 .. N - 1.  The wave's 64 rows are laid out as k_perm.hpp says,
+//          in LDS while they fit (N <= 256) and in a global scratch buffer beyond; the finished rows are written row-major.
+//          identity: no swaps -- the observed matrix as a batch of one.
 //   z      k_mantel_z: a workgroup takes one permutation and MZ_ROWS rows i of a.  It holds o_p in LDS (2 N bytes) and, per row, stages
 //          row o[i] of b into LDS with coalesced loads (4 N bytes), reads a[i][j], j > i, coalesced from global, gathers row[o[j]] from
 //          LDS and accumulates a b in 64 bits; the last row has no j > i and is not staged.  The workgroup's sum is reduced (wave_sum64,
@@ -25,39 +24,15 @@ constexpr int32_t MZ_LDS_HEAD = 64;           // bytes in front of the staged ro
 constexpr int32_t MANTEL_ORDER_LDS_N = 256;   // columns up to which a wave's 64 orders stay in LDS (32 KiB)
 enum { MT_Z = 0, MT_GE = 1, MT_LE = 2, MT_N_OUT = 3 }; // out[]: Z of the observed matrix, n_ge, n_le
 
-// the swaps of permutation p over the lane's row: element k of the row at row[k * WAVE]
-template <class P> __device__ __forceinline__ void mantel_shuffle(P row, int32_t N, uint32_t seed, uint32_t p)
-{
-	uint64_t x = mix64((uint64_t)seed << 32 | (uint64_t)p);
-	for (int32_t i = N - 1; i >= 1; --i) {
-		x += 0x9E3779B97F4A7C15ull;
-		const int32_t j = (int32_t)(mix64(x) % (uint64_t)(i + 1));
-		const uint16_t oi = row[i * WAVE], oj = row[j * WAVE];
-		row[i * WAVE] = oj;
-		row[j * WAVE] = oi;
-	}
-}
-
-// grid: ceil(nb / 64) workgroups of ONE wave; permutation p0 + q of the batch, q < nb, is row q of ord[nb][N].  USE_LDS: the wave's
-// rows in LDS (N <= MANTEL_ORDER_LDS_N); otherwise in work[workgroup][N][64].  Lanes past nb run a permutation nobody reads and write
-// nothing.
+// perm_wave_rows (k_perm.hpp) over rows of N indices: permutation p0 + q of the batch is row q of ord[nb][N].  USE_LDS: the wave's rows
+// in LDS (N <= MANTEL_ORDER_LDS_N); otherwise in work[workgroup][N][64].  identity: no swaps.
 template <bool USE_LDS>
 __global__ __launch_bounds__(WAVE) void k_mantel_order(int32_t N, uint32_t seed, uint32_t p0, int32_t nb, bool identity, uint16_t *__restrict__ work,
                                                        uint16_t *__restrict__ ord)
 {
-	__shared__ uint16_t sh[USE_LDS ? MANTEL_ORDER_LDS_N * WAVE : 1];
-	const int32_t l = (int32_t)threadIdx.x;
-	const int64_t q0 = (int64_t)blockIdx.x * WAVE;
-	uint16_t *mine = USE_LDS ? sh : work + (size_t)blockIdx.x * (size_t)N * WAVE;
-	for (int32_t k = 0; k < N; ++k) mine[k * WAVE + l] = (uint16_t)k;
-	if (!identity) mantel_shuffle(mine + l, N, seed, p0 + (uint32_t)(q0 + l));
-	if (USE_LDS) __syncthreads(); // (one wave: orders the lanes' LDS stores before the reads across lanes below)
-	else __threadfence_block();
-	const int32_t n_row = (int32_t)min((int64_t)WAVE, (int64_t)nb - q0);
-	for (int32_t q = 0; q < n_row; ++q) {
-		uint16_t *out = ord + (size_t)(q0 + q) * (size_t)N;
-		for (int32_t k = l; k < N; k += WAVE) out[k] = mine[k * WAVE + q];
-	}
+	perm_wave_rows<uint16_t, MANTEL_ORDER_LDS_N, USE_LDS>(
+		N, identity ? 0 : N, seed, p0, nb, work, [](int32_t k) { return (uint16_t)k; }, PermSwapValues(),
+		[&](const uint16_t *fin, int64_t q, int32_t l) { perm_row_major(fin, ord + (size_t)q * (size_t)N, N, l); });
 }
 
 // grid: (nb, ceil((N - 1) / MZ_ROWS)), dynamic LDS: mantel_z_lds(N) bytes.  a[N][N], b[N][N], ord[nb][N] with every entry below N;

@@ -6,10 +6,10 @@
 // project on the matrix cores.
 //   obs    k_qtrait_obs: a and D of every row (8 lanes a row, as k_trait_obs: a lane walks the set bits of its words) and the threshold
 //          absD = |D|, INT32_MAX for a row that is not eligible: |D_p| <= N (N - 1) / 2 < 2^30 never reaches it.
-//   perm   k_qtrait_perm: the value rows of one batch of permutations.  One lane per permutation runs the swap sequence k_trait_perm
-//          runs (the same mix64, the same 64-bit %) over a private int16 row and swaps the two values.  The 64 rows of a wave are
-//          lane-interleaved (value c of lane l at c * 64 + l); in LDS while they fit 32 KiB (N <= 256), in a global scratch buffer
-//          of the same layout beyond.  A finished row is written as two signed-byte digit planes lo[nb][K], hi[nb][K] with
+//   perm   k_qtrait_perm: the value rows of one batch of permutations.  One lane per permutation runs the pinned swap sequence
+//          (k_perm.hpp) over a private int16 row and swaps the two values.  The wave's 64 rows are laid out as k_perm.hpp says, in LDS
+//          while they fit (N <= 256) and in a global scratch buffer beyond.  A finished row is written as two signed-byte digit planes
+//          lo[nb][K], hi[nb][K] with
 //          lo = ((c2 + 128) & 255) - 128 in [-128, 127] and hi = (c2 - lo) >> 8 in [-125, 125], c2 = 256 hi + lo; K = N rounded up
 //          to QT_KC, the columns past N written as zero.
 //   count  k_qtrait_count: an int8 GEMM on v_mfma_i32_16x16x64_i8.  One workgroup of four waves per 128 genes x 128 permutations,
@@ -53,47 +53,27 @@ __global__ __launch_bounds__(BLOCK) void k_qtrait_obs(const uint32_t *__restrict
 	if (g < G && l == 0) a_out[g] = a, d_out[g] = d, abs_out[g] = min(a, N - a) >= min_count ? (d < 0 ? -d : d) : QT_NEVER;
 }
 
-// the swaps of permutation p over the lane's row: value c of the row at row[c * WAVE]
-template <class P> __device__ __forceinline__ void qtrait_shuffle(P row, int32_t N, uint32_t seed, uint32_t p)
-{
-	uint64_t x = mix64((uint64_t)seed << 32 | (uint64_t)p);
-	for (int32_t i = N - 1; i >= 1; --i) {
-		x += 0x9E3779B97F4A7C15ull;
-		const int32_t j = (int32_t)(mix64(x) % (uint64_t)(i + 1));
-		const int16_t vi = row[i * WAVE], vj = row[j * WAVE];
-		row[i * WAVE] = vj;
-		row[j * WAVE] = vi;
-	}
-}
-
-// grid: ceil(nb / 64) workgroups of ONE wave; permutation p0 + q of the batch, q < nb, is row q of lo[nb][K] and hi[nb][K].  USE_LDS:
-// the wave's rows in LDS; otherwise in work[workgroup][N][64].  Lanes past nb run a permutation nobody reads and write nothing.
+// perm_wave_rows (k_perm.hpp) over rows of N values: permutation p0 + q of the batch is row q of lo[nb][K] and hi[nb][K].  USE_LDS:
+// the wave's rows in LDS; otherwise in work[workgroup][N][64].
 template <bool USE_LDS>
 __global__ __launch_bounds__(WAVE) void k_qtrait_perm(const int16_t *__restrict__ c2, int32_t N, int32_t K, uint32_t seed, uint32_t p0, int32_t nb,
                                                       int16_t *__restrict__ work, int8_t *__restrict__ lo, int8_t *__restrict__ hi)
 {
-	__shared__ int16_t sh[USE_LDS ? QT_PERM_LDS_N * WAVE : 1];
-	const int32_t l = (int32_t)threadIdx.x;
-	const int64_t q0 = (int64_t)blockIdx.x * WAVE;
-	int16_t *mine = USE_LDS ? sh : work + (size_t)blockIdx.x * (size_t)N * WAVE;
-	for (int32_t c = 0; c < N; ++c) mine[c * WAVE + l] = c2[c];
-	qtrait_shuffle(mine + l, N, seed, p0 + (uint32_t)(q0 + l));
-	if (USE_LDS) __syncthreads(); // (one wave: orders the lanes' LDS stores before the reads across lanes below)
-	else __threadfence_block();
-	const int32_t n_row = (int32_t)min((int64_t)WAVE, (int64_t)nb - q0);
-	for (int32_t q = 0; q < n_row; ++q) { // four columns a lane: one 32-bit store per plane (K is a multiple of 4)
-		uint32_t *out_lo = (uint32_t *)(lo + (size_t)(q0 + q) * (size_t)K), *out_hi = (uint32_t *)(hi + (size_t)(q0 + q) * (size_t)K);
-		for (int32_t c = 4 * l; c < K; c += 4 * WAVE) {
-			uint32_t wl = 0, wh = 0;
+	perm_wave_rows<int16_t, QT_PERM_LDS_N, USE_LDS>(
+		N, N, seed, p0, nb, work, [&](int32_t c) { return c2[c]; }, PermSwapValues(),
+		[&](const int16_t *fin, int64_t q, int32_t l) { // four columns a lane: one 32-bit store per plane (K is a multiple of 4)
+			uint32_t *out_lo = (uint32_t *)(lo + (size_t)q * (size_t)K), *out_hi = (uint32_t *)(hi + (size_t)q * (size_t)K);
+			for (int32_t c = 4 * l; c < K; c += 4 * WAVE) {
+				uint32_t wl = 0, wh = 0;
 #pragma unroll
-			for (int32_t e = 0; e < 4; ++e) {
-				const int32_t v = c + e < N ? (int32_t)mine[(c + e) * WAVE + q] : 0;
-				const int32_t dl = ((v + 128) & 255) - 128, dh = (v - dl) >> 8;
-				wl |= (uint32_t)(dl & 255) << (8 * e), wh |= (uint32_t)(dh & 255) << (8 * e);
+				for (int32_t e = 0; e < 4; ++e) {
+					const int32_t v = c + e < N ? (int32_t)fin[(c + e) * WAVE] : 0;
+					const int32_t dl = ((v + 128) & 255) - 128, dh = (v - dl) >> 8;
+					wl |= (uint32_t)(dl & 255) << (8 * e), wh |= (uint32_t)(dh & 255) << (8 * e);
+				}
+				out_lo[c >> 2] = wl, out_hi[c >> 2] = wh;
 			}
-			out_lo[c >> 2] = wl, out_hi[c >> 2] = wh;
-		}
-	}
+		});
 }
 
 // four bits -> four 0/1 bytes, bit e in byte e (the products of the multiplication share no bit, so nothing carries)

@@ -6,13 +6,9 @@
 //   obs    k_trait_obs: a, s of every row (8 lanes a row, as k_assoc_count), the two thresholds and the eligibility; a row that is not
 //          eligible gets lo = -1 and hi = INT32_MAX, which no count meets.
 //   perm   k_trait_perm: the label rows of one batch of permutations, made here from the one uploaded label row.  One lane per
-//          permutation runs the swap sequence curves pins (Fisher-Yates from the last column down, j = next() % (i + 1), splitmix64
-//          from mix((seed << 32) | p)) over a private bit row: swapping the bits i and j of the row is what applying the order to the
-//          labels gives.  The 64 rows of a wave are lane-interleaved (word k of lane l at k * 64 + l), so a wave's access to "its"
-//          word i >> 5 is one 256-byte line / 64 distinct LDS banks-pairs, and the accesses to the words j >> 5 spread over the banks
-//          by lane.  The rows live in LDS while 64 of them fit 32 KiB (W <= 128, N <= 4 096) and in a global scratch buffer of the
-//          same layout beyond; the finished rows are written row-major for the count kernel.  The 64-bit % is the compiler's: the
-//          same j as the host's for every x.
+//          permutation runs the pinned swap sequence (k_perm.hpp) over a private bit row: swapping the bits i and j of the row is what
+//          applying the order to the labels gives.  The wave's 64 rows are laid out as k_perm.hpp says, in LDS while they fit
+//          (W <= 128, N <= 4 096) and in a global scratch buffer beyond; the finished rows are written row-major for the count kernel.
 //   count  k_trait_count: one workgroup per 128 genes x 128 permutations, the tile body of k_dist_shared / k_assoc_pairs (BIT_TILE,
 //          k_dist.hpp) with the inner loop trimmed to the rows' last word.  Rectangular grid (x: gene tile, y: permutation tile of the
 //          batch).  Epilogue: each count against its row's lo / hi, the hits of a row summed over the 16 lanes that share it, ONE
@@ -48,39 +44,21 @@ __global__ __launch_bounds__(BLOCK) void k_trait_obs(const uint32_t *__restrict_
 	}
 }
 
-// the swaps of permutation p over the lane's row: word k of the row at row[k * WAVE]
-template <class P> __device__ __forceinline__ void trait_shuffle(P row, int32_t N, uint32_t seed, uint32_t p)
-{
-	uint64_t x = mix64((uint64_t)seed << 32 | (uint64_t)p);
-	for (int32_t i = N - 1; i >= 1; --i) {
-		x += 0x9E3779B97F4A7C15ull;
-		const int32_t j = (int32_t)(mix64(x) % (uint64_t)(i + 1));
-		const int32_t wi = (i >> 5) * WAVE, wj = (j >> 5) * WAVE;
-		const uint32_t d = ((row[wi] >> (i & 31)) ^ (row[wj] >> (j & 31))) & 1u; // the two labels differ: both flip
-		row[wi] ^= d << (i & 31);
-		row[wj] ^= d << (j & 31); // (read again: wi may be wj)
-	}
-}
-
-// grid: ceil(nb / 64) workgroups of ONE wave; permutation p0 + q of the batch, q < nb, is row q of rows[nb][W].  USE_LDS: the wave's
-// rows in LDS; otherwise in work[workgroup][W][64].  Lanes past nb run a permutation nobody reads and write nothing.
+// perm_wave_rows (k_perm.hpp) over rows of W words: permutation p0 + q of the batch is row q of rows[nb][W].  USE_LDS: the wave's rows
+// in LDS; otherwise in work[workgroup][W][64].
 template <bool USE_LDS>
 __global__ __launch_bounds__(WAVE) void k_trait_perm(const uint32_t *__restrict__ label, int32_t N, int32_t W, uint32_t seed, uint32_t p0, int32_t nb,
                                                      uint32_t *__restrict__ work, uint32_t *__restrict__ rows)
 {
-	__shared__ uint32_t sh[USE_LDS ? TRAIT_PERM_LDS_W * WAVE : 1];
-	const int32_t l = (int32_t)threadIdx.x;
-	const int64_t q0 = (int64_t)blockIdx.x * WAVE;
-	uint32_t *mine = USE_LDS ? sh : work + (size_t)blockIdx.x * (size_t)W * WAVE;
-	for (int32_t k = 0; k < W; ++k) mine[k * WAVE + l] = label[k];
-	trait_shuffle(mine + l, N, seed, p0 + (uint32_t)(q0 + l));
-	if (USE_LDS) __syncthreads(); // (one wave: orders the lanes' LDS stores before the reads across lanes below)
-	else __threadfence_block();
-	const int32_t n_row = (int32_t)min((int64_t)WAVE, (int64_t)nb - q0);
-	for (int32_t q = 0; q < n_row; ++q) {
-		uint32_t *out = rows + (size_t)(q0 + q) * (size_t)W;
-		for (int32_t k = l; k < W; k += WAVE) out[k] = mine[k * WAVE + q];
-	}
+	perm_wave_rows<uint32_t, TRAIT_PERM_LDS_W, USE_LDS>(
+		W, N, seed, p0, nb, work, [&](int32_t k) { return label[k]; },
+		[](uint32_t *row, int32_t i, int32_t j) {
+			const int32_t wi = (i >> 5) * WAVE, wj = (j >> 5) * WAVE;
+			const uint32_t d = ((row[wi] >> (i & 31)) ^ (row[wj] >> (j & 31))) & 1u; // the two labels differ: both flip
+			row[wi] ^= d << (i & 31);
+			row[wj] ^= d << (j & 31); // (read again: wi may be wj)
+		},
+		[&](const uint32_t *fin, int64_t q, int32_t l) { perm_row_major(fin, rows + (size_t)q * (size_t)W, W, l); });
 }
 
 // grid: (ceil(G / 128), ceil(nb / 128)).  bits[G][W], rows[nb][W], lo / hi[G]; k[g] += hits

@@ -106,6 +106,7 @@ extern "C" const char *pga_strerror(int code)
 // The kernels live in one header per part of the path (k_*.hpp), the host side of the C ABI in one per stage (pga_host_*.hpp, split in
 // round 5: this file had grown to 2 500 lines); everything is ONE translation unit, included in this order.
 #include "k_common.hpp"
+#include "k_perm.hpp"
 #include "k_ingest.hpp"
 #include "k_sweep.hpp"
 #include "k_segsort.hpp"

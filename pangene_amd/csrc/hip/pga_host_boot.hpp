@@ -20,25 +20,16 @@ struct BootBuf { enum { BITS, DRAWS, ROWS, S, D, LABEL, AUX, PART, REC, MX, N_BU
 // A x W words of the bit rows, and 256 MiB of draws and rows -- or one replicate's draws and rows (n_item + A x W words) if that is more.
 extern "C" int32_t pga_boot_batch(int32_t n_asm)
 {
-	if (const char *s = getenv("PANGENE_BOOT_BATCH")) { const long long v = atoll(s); if (v >= 1 && v <= BOOT_MAX_BATCH) return (int32_t)v; }
 	const int64_t A = std::max(n_asm, 1), ld = (A + 3) & ~(int64_t)3;
 	const int64_t per = 4 * A * A + 4 * A * ld + 12 * A + (int64_t)sizeof(JoinPart) * JOIN_MAX_PART + 48 * A + 8;
-	return (int32_t)std::min<int64_t>(std::max<int64_t>(BOOT_BUDGET / per, 1), BOOT_MAX_BATCH);
+	return (int32_t)pan_env("PANGENE_BOOT_BATCH", std::min<int64_t>(std::max<int64_t>(BOOT_BUDGET / per, 1), BOOT_MAX_BATCH), BOOT_MAX_BATCH);
 }
 
 // words of the source row's LDS window: BOOT_LDS_WORDS, or PANGENE_BOOT_LDS_WORDS (tests: the global path at a small n_item)
-static int32_t boot_lds_words()
-{
-	if (const char *s = getenv("PANGENE_BOOT_LDS_WORDS")) { const long long v = atoll(s); if (v >= 1 && v <= BOOT_LDS_WORDS) return (int32_t)v; }
-	return BOOT_LDS_WORDS;
-}
+static int32_t boot_lds_words() { return (int32_t)pan_env("PANGENE_BOOT_LDS_WORDS", BOOT_LDS_WORDS, BOOT_LDS_WORDS); }
 
 // words of draws + resampled rows a replicate group may take: BOOT_ROWS_WORDS, or PANGENE_BOOT_ROWS_WORDS (tests: several groups in a call)
-static int64_t boot_rows_words()
-{
-	if (const char *s = getenv("PANGENE_BOOT_ROWS_WORDS")) { const long long v = atoll(s); if (v >= 1 && v <= BOOT_ROWS_WORDS) return v; }
-	return BOOT_ROWS_WORDS;
-}
+static int64_t boot_rows_words() { return pan_env("PANGENE_BOOT_ROWS_WORDS", BOOT_ROWS_WORDS, BOOT_ROWS_WORDS); }
 
 template <bool NJ>
 static int boot_join_queue(hipStream_t st, int32_t *d_d, int32_t n, int32_t ld, int32_t n_rep, int32_t *d_label, long long *d_aux, JoinPart *d_part, int32_t p_stride,

@@ -10,11 +10,7 @@ constexpr int32_t JOIN_MAX_N = 65535;
 struct JoinBuf { enum { D, LABEL, AUX, PART, REC, N_BUF }; }; // REC: the records, then one word of flag; page-locked buffer 0: the same
 
 // workgroups of k_join_argmin at the most: JOIN_MAX_PART, or PANGENE_JOIN_PARTS (tests: several tiles per workgroup at a small n)
-static int32_t join_max_part()
-{
-	if (const char *s = getenv("PANGENE_JOIN_PARTS")) { const long long v = atoll(s); if (v >= 1 && v <= JOIN_MAX_PART) return (int32_t)v; }
-	return JOIN_MAX_PART;
-}
+static int32_t join_max_part() { return (int32_t)pan_env("PANGENE_JOIN_PARTS", JOIN_MAX_PART, JOIN_MAX_PART); }
 
 template <bool NJ>
 static int join_queue(hipStream_t st, int32_t *d_d, int32_t n, int32_t ld, int32_t *d_label, long long *d_aux, JoinPart *d_part, long long *d_rec, int32_t *d_flag)

@@ -8,7 +8,6 @@
 // and k_mantel_stat counts and clears, one after the other on the one stream.  Nothing is read back between the batches and the host
 // waits once, at the end (tests that ask for z_rows / ord_rows wait once more, after the first batch).
 constexpr int32_t MANTEL_MAX_COL = 16384;
-constexpr int32_t MANTEL_MAX_PERM = 2147483646; // 2^31 - 2
 constexpr int32_t MANTEL_BATCH = 4096;
 
 struct MantelBuf { enum { A, B, ORD, WORK, Z, OUT, ZROWS, N_BUF }; }; // page-locked buffer 0: out
@@ -16,11 +15,7 @@ static_assert(MantelBuf::N_BUF <= PAN_MAX_DEV, "the pool has no room for the Man
 
 static size_t mantel_z_lds(int32_t N) { return ((size_t)MZ_LDS_HEAD + 4 * (size_t)((N + 3) & ~3) + 2 * (size_t)N + 15) & ~(size_t)15; }
 
-extern "C" int32_t pga_mantel_batch(void)
-{
-	if (const char *s = getenv("PANGENE_MANTEL_BATCH")) { const long long v = atoll(s); if (v >= 1 && v <= (1 << 20)) return (int32_t)v; }
-	return MANTEL_BATCH;
-}
+extern "C" int32_t pga_mantel_batch(void) { return (int32_t)pan_env("PANGENE_MANTEL_BATCH", MANTEL_BATCH, 1 << 20); }
 
 extern "C" int pga_pan_mantel(const pga_mantel_in_t *in, pga_mantel_out_t *out)
 {
@@ -29,11 +24,11 @@ extern "C" int pga_pan_mantel(const pga_mantel_in_t *in, pga_mantel_out_t *out)
 	if (in == nullptr || in->a == nullptr || in->b == nullptr) return PGA_ERR_ARG;
 	const int32_t N = in->n, n = in->n_perm;
 	if (N < 1 || n < 0 || in->max_a < 0 || in->max_b < 0) return PGA_ERR_ARG;
-	if (N > MANTEL_MAX_COL || n > MANTEL_MAX_PERM) return PGA_ERR_RANGE; // (before anything is launched)
+	if (N > MANTEL_MAX_COL || n > PAN_MAX_PERM) return PGA_ERR_RANGE; // (before anything is launched)
 	if ((unsigned __int128)((uint64_t)in->max_a * (uint64_t)in->max_b) * ((uint64_t)N * (uint64_t)(N - 1)) >= (unsigned __int128)1 << 62) return PGA_ERR_ARG; // the caller's shifts are too small
-	const int32_t B = (int32_t)std::min<int64_t>(pga_mantel_batch(), std::max<int32_t>(n, 1));
-	const bool lds = N <= MANTEL_ORDER_LDS_N, tests = in->z_rows != nullptr;
-	const int64_t order_blocks = ((int64_t)B + WAVE - 1) / WAVE;
+	PermBatches b(n, pga_mantel_batch(), N <= MANTEL_ORDER_LDS_N);
+	const int32_t B = b.B;
+	const bool tests = in->z_rows != nullptr;
 	const size_t nn = (size_t)N * (size_t)N, z_lds = mantel_z_lds(N);
 	PanDev &m = g_pan[PAN_MANTEL];
 	std::lock_guard<std::mutex> lk(m.mu);
@@ -43,7 +38,7 @@ extern "C" int pga_pan_mantel(const pga_mantel_in_t *in, pga_mantel_out_t *out)
 	PANCHK(m, m.stream(&st));
 	int32_t *d_a = m.get<int32_t>(MantelBuf::A, nn), *d_b = m.get<int32_t>(MantelBuf::B, nn);
 	uint16_t *d_ord = m.get<uint16_t>(MantelBuf::ORD, (size_t)B * (size_t)N);
-	uint16_t *d_work = m.get<uint16_t>(MantelBuf::WORK, lds ? 1 : (size_t)order_blocks * (size_t)N * WAVE);
+	uint16_t *d_work = m.get<uint16_t>(MantelBuf::WORK, b.work((size_t)N));
 	unsigned long long *d_z = m.get<unsigned long long>(MantelBuf::Z, (size_t)B);
 	long long *d_out = m.get<long long>(MantelBuf::OUT, MT_N_OUT);
 	long long *d_zrows = m.get<long long>(MantelBuf::ZROWS, tests ? (size_t)B : 1);
@@ -55,19 +50,17 @@ extern "C" int pga_pan_mantel(const pga_mantel_in_t *in, pga_mantel_out_t *out)
 	PANCHK(m, hipMemsetAsync(d_z, 0, sizeof(unsigned long long) * (size_t)B, st));
 	const unsigned row_blocks = (unsigned)((N - 1 + MZ_ROWS - 1) / MZ_ROWS); // 0 at N = 1: no pair, Z = 0 without a launch
 	auto orders = [&](uint32_t p0, int32_t nb, bool identity) {
-		const unsigned ob = (unsigned)((nb + WAVE - 1) / WAVE);
-		if (lds) hipLaunchKernelGGL(k_mantel_order<true>, dim3(ob), dim3(WAVE), 0, st, N, in->seed, p0, nb, identity, d_work, d_ord);
-		else hipLaunchKernelGGL(k_mantel_order<false>, dim3(ob), dim3(WAVE), 0, st, N, in->seed, p0, nb, identity, d_work, d_ord);
+		perm_launch(b.lds, k_mantel_order<true>, k_mantel_order<false>, nb, st, N, in->seed, p0, nb, identity, d_work, d_ord);
 	};
 	// the observed matrix: a batch of one with the identity order
 	orders(0, 1, true);
 	if (row_blocks) hipLaunchKernelGGL(k_mantel_z, dim3(1, row_blocks), dim3(BLOCK), z_lds, st, d_a, d_b, d_ord, N, d_z);
 	hipLaunchKernelGGL(k_mantel_stat, dim3(1), dim3(BLOCK), 0, st, d_z, 1, true, d_out, (long long *)nullptr);
 	PANCHK(m, hipGetLastError());
-	for (int64_t done = 0; done < n; done += B) {
-		const int32_t nb = (int32_t)std::min<int64_t>(B, (int64_t)n - done);
-		const bool first = done == 0;
-		orders((uint32_t)(done + 1), nb, false); // permutations are numbered from 1
+	for (; b.more(); b.next()) {
+		const int32_t nb = b.nb();
+		const bool first = b.first();
+		orders(b.p0(), nb, false);
 		if (row_blocks) hipLaunchKernelGGL(k_mantel_z, dim3((unsigned)nb, row_blocks), dim3(BLOCK), z_lds, st, d_a, d_b, d_ord, N, d_z);
 		hipLaunchKernelGGL(k_mantel_stat, dim3((unsigned)((nb + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, d_z, nb, false, d_out, first && tests ? d_zrows : (long long *)nullptr);
 		PANCHK(m, hipGetLastError());

@@ -9,11 +9,7 @@ struct MedBuf { enum { Q, D, DS, NN, MED, ISMED, GAIN, SLOT, REMOVAL, CNT, ACC, 
 static_assert(MedBuf::N_BUF <= PAN_MAX_DEV, "the pool has no room for the medoid buffers");
 
 // iterations the host queues between two reads of the status: 8, or PANGENE_MEDOIDS_BATCH (tests)
-static int32_t med_batch()
-{
-	if (const char *s = getenv("PANGENE_MEDOIDS_BATCH")) { const long long v = atoll(s); if (v >= 1 && v <= 1024) return (int32_t)v; }
-	return 8;
-}
+static int32_t med_batch() { return (int32_t)pan_env("PANGENE_MEDOIDS_BATCH", 8, 1024); }
 
 // The launch shape of the row walk over n columns: tiles of BLOCK candidates x chunks of `rows` permuted rows.  Where the tiles alone
 // are fewer than MED_WANT_WG workgroups the rows are cut into as many chunks as it takes to get there, MED_MIN_ROWS rows a chunk at the
@@ -25,7 +21,7 @@ static MedShape med_shape(int32_t n)
 	s.n_tile = (n + BLOCK - 1) / BLOCK;
 	const int32_t want = std::max(1, (MED_WANT_WG + s.n_tile - 1) / s.n_tile);
 	s.rows = std::max(MED_MIN_ROWS, (n + want - 1) / want);
-	if (const char *e = getenv("PANGENE_MEDOIDS_ROWS")) { const long long v = atoll(e); if (v >= 1 && v <= n) s.rows = (int32_t)v; }
+	s.rows = (int32_t)pan_env("PANGENE_MEDOIDS_ROWS", s.rows, n);
 	s.n_chunk = (n + s.rows - 1) / s.rows;
 	return s;
 }

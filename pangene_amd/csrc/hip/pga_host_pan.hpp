@@ -3,7 +3,7 @@
 // their contents are not kept across a growth; results a call leaves in a page-locked buffer stay valid until the same entry's next
 // call.  Every entry locks its own pool, so two different entries may run at the same time.  pga_host_trim(0) gives all of it back
 // (pan_release_all), and the next call allocates again.  Included by pga_backend.hip before the entries' headers; each of those keeps
-// only its enum of buffer numbers.
+// only its enum of buffer numbers.  Below the pools: the count switches (pan_env) and the batch driver of the permutation entries.
 #pragma once
 
 constexpr int PAN_MAX_DEV = 16, PAN_MAX_HOST = 3; // buffers a pool has room for
@@ -67,6 +67,46 @@ static void pan_release_all()
 #define PANCHK(m, x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
 	fprintf(stderr, "[E::%s] %s:%d: %s\n", (m).name, __FILE__, __LINE__, hipGetErrorString(e_)); return PGA_ERR_NO_DEVICE; } } while (0)
 #define PANMEM(p) do { if ((p) == nullptr) return PGA_ERR_NOMEM; } while (0)
+
+// a switch NAME=v that takes a count, 1 <= v <= max; absent or anything else: def
+static int64_t pan_env(const char *name, int64_t def, int64_t max)
+{
+	if (const char *s = getenv(name)) { const long long v = atoll(s); if (v >= 1 && v <= max) return v; }
+	return def;
+}
+
+// The batch driver of the permutation entries (trait, qtrait, permanova, mantel).  n permutations go through in batches of
+// B = min(batch, max(n, 1)) rows made by a one-wave kernel of k_perm.hpp, whose 64 rows per workgroup live in LDS (lds) or in a scratch
+// buffer of work(elems) elements:  for (PermBatches b(n, batch, lds); b.more(); b.next()) with b.p0(), b.nb(), b.first().
+constexpr int32_t PAN_MAX_PERM = 2147483646; // 2^31 - 2
+
+struct PermBatches {
+	int32_t n, B;
+	bool lds;
+	int64_t done = 0;
+	PermBatches(int32_t n_perm, int32_t batch, bool lds_) : n(n_perm), B((int32_t)std::min<int64_t>(batch, std::max<int32_t>(n_perm, 1))), lds(lds_) {}
+	size_t work(size_t elems) const { return lds ? 1 : (size_t)(((int64_t)B + WAVE - 1) / WAVE) * elems * WAVE; }
+	bool more() const { return done < n; }
+	void next() { done += B; }
+	uint32_t p0() const { return (uint32_t)(done + 1); } // permutations are numbered from 1
+	int32_t nb() const { return (int32_t)std::min<int64_t>(B, (int64_t)n - done); }
+	bool first() const { return done == 0; }
+};
+
+// the <true> (LDS) / <false> (scratch buffer) pair of a one-wave permutation kernel over the nb rows of a batch
+template <class... P, class... A> static void perm_launch(bool lds, void (*k_lds)(P...), void (*k_work)(P...), int32_t nb, hipStream_t st, A... a)
+{
+	hipLaunchKernelGGL(lds ? k_lds : k_work, dim3((unsigned)((nb + WAVE - 1) / WAVE)), dim3(WAVE), 0, st, (P)a...);
+}
+
+// the end of trait and qtrait: three device arrays of G counts into the planes h[0 .. 3 G), and the call's one wait
+static int pan_download3(PanDev &m, hipStream_t st, int32_t *h, const int32_t *d0, const int32_t *d1, const int32_t *d2, int32_t G)
+{
+	const int32_t *d[3] = {d0, d1, d2};
+	for (int i = 0; i < 3 && G > 0; ++i) PANCHK(m, hipMemcpyAsync(h + (size_t)i * (size_t)G, d[i], sizeof(int32_t) * (size_t)G, hipMemcpyDeviceToHost, st));
+	PANCHK(m, hipStreamSynchronize(st));
+	return 0;
+}
 
 // The split-K launch shape of k_dist_shared over A rows of W words: n_tile upper-triangle tiles, and where those are fewer than two
 // workgroups per CU on 256 CUs, each tile's n_chunk K chunks in n_split slices of cps chunks (no empty slice) that add into S.

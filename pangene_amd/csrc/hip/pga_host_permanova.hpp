@@ -10,17 +10,12 @@
 // a_rows / b_rows / perm_rows wait once more, after the first batch).  Every plane is launched: telling an all-zero plane apart would
 // take a read of its own.
 constexpr int32_t PERMA_MAX_COL = 16384;
-constexpr int32_t PERMA_MAX_PERM = 2147483646; // 2^31 - 2
 constexpr int32_t PERMA_BATCH = 16384;
 
 struct PermaBuf { enum { Q, PL, R, LABEL, ROWS, WORK, A, OUT, AROWS, BROWS, N_BUF }; }; // page-locked buffer 0: out; 1, 2: a_rows, b_rows (tests)
 static_assert(PermaBuf::N_BUF <= PAN_MAX_DEV, "the pool has no room for the PERMANOVA buffers");
 
-extern "C" int32_t pga_permanova_batch(void)
-{
-	if (const char *s = getenv("PANGENE_PERMA_BATCH")) { const long long v = atoll(s); if (v >= 1 && v <= (1 << 20)) return (int32_t)v; }
-	return PERMA_BATCH;
-}
+extern "C" int32_t pga_permanova_batch(void) { return (int32_t)pan_env("PANGENE_PERMA_BATCH", PERMA_BATCH, 1 << 20); }
 
 extern "C" int pga_pan_permanova(const pga_permanova_in_t *in, pga_permanova_out_t *out)
 {
@@ -29,15 +24,15 @@ extern "C" int pga_pan_permanova(const pga_permanova_in_t *in, pga_permanova_out
 	if (in == nullptr || in->q == nullptr || in->label == nullptr) return PGA_ERR_ARG;
 	const int32_t N = in->n, n = in->n_perm, n1 = in->n1;
 	if (N < 1 || n < 0 || in->shift < 0 || in->shift > 30 || in->q_max < 0 || n1 < 0 || n1 > N) return PGA_ERR_ARG;
-	if (N > PERMA_MAX_COL || n > PERMA_MAX_PERM) return PGA_ERR_RANGE; // (before anything is launched)
+	if (N > PERMA_MAX_COL || n > PAN_MAX_PERM) return PGA_ERR_RANGE; // (before anything is launched)
 	const uint64_t e_max = (uint64_t)(in->q_max >> in->shift), w_max = e_max * e_max;
 	if ((unsigned __int128)w_max * (uint64_t)N * (uint64_t)(N - 1) >= (unsigned __int128)1 << 62) return PGA_ERR_ARG; // the caller's shift is too small
 	int32_t D = 1;
 	for (uint64_t cap = 127; cap < w_max; cap = cap * 256 + 127) ++D; // 127 (256^D - 1) / 255, the largest value D balanced digits hold
 	const int32_t W = (N + 31) / 32, Np = (N + PM_TILE - 1) / PM_TILE * PM_TILE;
-	const int32_t B = (int32_t)std::min<int64_t>(pga_permanova_batch(), std::max<int32_t>(n, 1));
-	const bool lds = W <= TRAIT_PERM_LDS_W, tests = in->a_rows != nullptr || in->b_rows != nullptr;
-	const int64_t perm_blocks = ((int64_t)B + WAVE - 1) / WAVE;
+	PermBatches b(n, pga_permanova_batch(), W <= TRAIT_PERM_LDS_W);
+	const int32_t B = b.B;
+	const bool tests = in->a_rows != nullptr || in->b_rows != nullptr;
 	PanDev &m = g_pan[PAN_PERMANOVA];
 	std::lock_guard<std::mutex> lk(m.mu);
 	int64_t *h_out = m.get_host<int64_t>(0, PM_N_OUT);
@@ -48,7 +43,7 @@ extern "C" int pga_pan_permanova(const pga_permanova_in_t *in, pga_permanova_out
 	int8_t *d_pl = m.get<int8_t>(PermaBuf::PL, (size_t)D * (size_t)Np * (size_t)Np);
 	long long *d_r = m.get<long long>(PermaBuf::R, (size_t)W * 32); // (k_perma_stat indexes it by bit position)
 	uint32_t *d_label = m.get<uint32_t>(PermaBuf::LABEL, (size_t)W), *d_rows = m.get<uint32_t>(PermaBuf::ROWS, (size_t)B * (size_t)W);
-	uint32_t *d_work = m.get<uint32_t>(PermaBuf::WORK, lds ? 1 : (size_t)perm_blocks * (size_t)W * WAVE);
+	uint32_t *d_work = m.get<uint32_t>(PermaBuf::WORK, b.work((size_t)W));
 	unsigned long long *d_a = m.get<unsigned long long>(PermaBuf::A, (size_t)B);
 	long long *d_out = m.get<long long>(PermaBuf::OUT, PM_N_OUT);
 	long long *d_arows = m.get<long long>(PermaBuf::AROWS, tests ? (size_t)B : 1), *d_brows = m.get<long long>(PermaBuf::BROWS, tests ? (size_t)B : 1);
@@ -63,13 +58,10 @@ extern "C" int pga_pan_permanova(const pga_permanova_in_t *in, pga_permanova_out
 	hipLaunchKernelGGL(k_perma_quad, dim3(col_tiles, 1, (unsigned)D), dim3(BLOCK), 0, st, d_label, d_pl, 1, W, Np, d_a);
 	hipLaunchKernelGGL(k_perma_stat, dim3(1), dim3(BLOCK), 0, st, d_label, d_r, 1, W, N, n1, true, d_a, d_out, (long long *)nullptr, (long long *)nullptr);
 	PANCHK(m, hipGetLastError());
-	for (int64_t done = 0; done < n; done += B) {
-		const int32_t nb = (int32_t)std::min<int64_t>(B, (int64_t)n - done);
-		const unsigned pb = (unsigned)((nb + WAVE - 1) / WAVE);
-		const uint32_t p0 = (uint32_t)(done + 1); // permutations are numbered from 1
-		const bool first = done == 0;
-		if (lds) hipLaunchKernelGGL(k_trait_perm<true>, dim3(pb), dim3(WAVE), 0, st, d_label, N, W, in->seed, p0, nb, d_work, d_rows);
-		else hipLaunchKernelGGL(k_trait_perm<false>, dim3(pb), dim3(WAVE), 0, st, d_label, N, W, in->seed, p0, nb, d_work, d_rows);
+	for (; b.more(); b.next()) {
+		const int32_t nb = b.nb();
+		const bool first = b.first();
+		perm_launch(b.lds, k_trait_perm<true>, k_trait_perm<false>, nb, st, d_label, N, W, in->seed, b.p0(), nb, d_work, d_rows);
 		hipLaunchKernelGGL(k_perma_quad, dim3(col_tiles, (unsigned)((nb + PM_TILE - 1) / PM_TILE), (unsigned)D), dim3(BLOCK), 0, st, d_rows, d_pl, nb, W, Np, d_a);
 		hipLaunchKernelGGL(k_perma_stat, dim3((unsigned)((nb + stat_rows - 1) / stat_rows)), dim3(BLOCK), 0, st, d_rows, d_r, nb, W, N, n1, false, d_a, d_out,
 		                   first && tests ? d_arows : (long long *)nullptr, first && tests ? d_brows : (long long *)nullptr);

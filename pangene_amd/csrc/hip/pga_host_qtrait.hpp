@@ -9,16 +9,11 @@
 // ten rounds of the 512 a chip holds at two per CU, and its two planes take 2 x 16 384 x K bytes -- 1 GiB at the limit of
 // K = 32 000 where trait's 65 536 rows would take 4 GiB.
 constexpr int32_t QTRAIT_MAX_COL = 32000, QTRAIT_MAX_GENE = 16777215;
-constexpr int32_t QTRAIT_MAX_PERM = 2147483646; // 2^31 - 2
 constexpr int32_t QTRAIT_BATCH = 16384;
 
 struct QtraitBuf { enum { BITS, C2, A, D, ABSD, K, LO, HI, WORK, DROWS, N_BUF }; }; // page-locked buffer 0: a, d, k; 1: the planes (tests)
 
-extern "C" int32_t pga_qtrait_batch(void)
-{
-	if (const char *s = getenv("PANGENE_QTRAIT_BATCH")) { const long long v = atoll(s); if (v >= 1 && v <= (1 << 20)) return (int32_t)v; }
-	return QTRAIT_BATCH;
-}
+extern "C" int32_t pga_qtrait_batch(void) { return (int32_t)pan_env("PANGENE_QTRAIT_BATCH", QTRAIT_BATCH, 1 << 20); }
 
 extern "C" int pga_pan_qtrait(const pga_qtrait_in_t *in, pga_qtrait_out_t *out)
 {
@@ -27,7 +22,7 @@ extern "C" int pga_pan_qtrait(const pga_qtrait_in_t *in, pga_qtrait_out_t *out)
 	if (in == nullptr) return PGA_ERR_ARG;
 	const int32_t G = in->n_gene, N = in->n_col, n = in->n_perm;
 	if (G < 0 || N < 0 || n < 0 || in->min_count < 1) return PGA_ERR_ARG;
-	if (N > QTRAIT_MAX_COL || G > QTRAIT_MAX_GENE || n > QTRAIT_MAX_PERM) return PGA_ERR_RANGE; // (before anything is launched)
+	if (N > QTRAIT_MAX_COL || G > QTRAIT_MAX_GENE || n > PAN_MAX_PERM) return PGA_ERR_RANGE; // (before anything is launched)
 	const int32_t W = (N + 31) / 32;
 	if (W > 0 && ((G > 0 && in->bits == nullptr) || in->c2 == nullptr)) return PGA_ERR_ARG;
 	PanDev &m = g_pan[PAN_QTRAIT];
@@ -45,16 +40,15 @@ extern "C" int pga_pan_qtrait(const pga_qtrait_in_t *in, pga_qtrait_out_t *out)
 	// would not matter, because the gene side is zero there: bits past N are zero in the rows and words past W are staged as zero.
 	const int32_t K = (N + QT_KC - 1) / QT_KC * QT_KC;
 	const size_t n_word = (size_t)G * (size_t)W;
-	const int32_t B = (int32_t)std::min<int64_t>(pga_qtrait_batch(), std::max<int32_t>(n, 1));
-	const bool lds = N <= QT_PERM_LDS_N, tests_d = in->d_rows != nullptr && G > 0;
-	const int64_t perm_blocks = ((int64_t)B + WAVE - 1) / WAVE;
+	PermBatches b(n, pga_qtrait_batch(), N <= QT_PERM_LDS_N);
+	const bool tests_d = in->d_rows != nullptr && G > 0;
 	uint32_t *d_bits = m.get<uint32_t>(QtraitBuf::BITS, n_word);
 	int16_t *d_c2 = m.get<int16_t>(QtraitBuf::C2, (size_t)W * 32); // (k_qtrait_obs indexes it by bit position: whole words, zero past N)
 	int32_t *d_a = m.get<int32_t>(QtraitBuf::A, (size_t)G), *d_d = m.get<int32_t>(QtraitBuf::D, (size_t)G), *d_abs = m.get<int32_t>(QtraitBuf::ABSD, (size_t)G);
 	int32_t *d_k = m.get<int32_t>(QtraitBuf::K, (size_t)G);
-	int8_t *d_lo = m.get<int8_t>(QtraitBuf::LO, (size_t)B * (size_t)K), *d_hi = m.get<int8_t>(QtraitBuf::HI, (size_t)B * (size_t)K);
-	int16_t *d_work = m.get<int16_t>(QtraitBuf::WORK, lds ? 1 : (size_t)perm_blocks * (size_t)N * WAVE);
-	int32_t *d_drows = m.get<int32_t>(QtraitBuf::DROWS, tests_d ? (size_t)B * (size_t)G : 1);
+	int8_t *d_lo = m.get<int8_t>(QtraitBuf::LO, (size_t)b.B * (size_t)K), *d_hi = m.get<int8_t>(QtraitBuf::HI, (size_t)b.B * (size_t)K);
+	int16_t *d_work = m.get<int16_t>(QtraitBuf::WORK, b.work((size_t)N));
+	int32_t *d_drows = m.get<int32_t>(QtraitBuf::DROWS, tests_d ? (size_t)b.B * (size_t)G : 1);
 	PANMEM(d_bits); PANMEM(d_c2); PANMEM(d_a); PANMEM(d_d); PANMEM(d_abs); PANMEM(d_k); PANMEM(d_lo); PANMEM(d_hi); PANMEM(d_work); PANMEM(d_drows);
 	if (n_word) PANCHK(m, hipMemcpyAsync(d_bits, in->bits, sizeof(uint32_t) * n_word, hipMemcpyHostToDevice, st));
 	PANCHK(m, hipMemsetAsync(d_c2, 0, sizeof(int16_t) * (size_t)W * 32, st));
@@ -66,13 +60,10 @@ extern "C" int pga_pan_qtrait(const pga_qtrait_in_t *in, pga_qtrait_out_t *out)
 	}
 	const unsigned gene_tiles = (unsigned)((G + QT_TILE - 1) / QT_TILE);
 	const bool use_hi = N >= QT_HI_FROM;
-	for (int64_t done = 0; done < n; done += B) {
-		const int32_t nb = (int32_t)std::min<int64_t>(B, (int64_t)n - done);
-		const unsigned pb = (unsigned)((nb + WAVE - 1) / WAVE);
-		const uint32_t p0 = (uint32_t)(done + 1); // permutations are numbered from 1
-		const bool first = done == 0;
-		if (lds) hipLaunchKernelGGL(k_qtrait_perm<true>, dim3(pb), dim3(WAVE), 0, st, d_c2, N, K, in->seed, p0, nb, d_work, d_lo, d_hi);
-		else hipLaunchKernelGGL(k_qtrait_perm<false>, dim3(pb), dim3(WAVE), 0, st, d_c2, N, K, in->seed, p0, nb, d_work, d_lo, d_hi);
+	for (; b.more(); b.next()) {
+		const int32_t nb = b.nb();
+		const bool first = b.first();
+		perm_launch(b.lds, k_qtrait_perm<true>, k_qtrait_perm<false>, nb, st, d_c2, N, K, in->seed, b.p0(), nb, d_work, d_lo, d_hi);
 		int32_t *dr = first && tests_d ? d_drows : nullptr;
 		if (G > 0) {
 			const dim3 grid(gene_tiles, (unsigned)((nb + QT_TILE - 1) / QT_TILE));
@@ -94,11 +85,5 @@ extern "C" int pga_pan_qtrait(const pga_qtrait_in_t *in, pga_qtrait_out_t *out)
 						in->perm_rows[(size_t)q * (size_t)N + (size_t)c] = (int16_t)(256 * (int32_t)h_pl[plane + (size_t)q * K + c] + (int32_t)h_pl[(size_t)q * K + c]);
 		}
 	}
-	if (G > 0) {
-		PANCHK(m, hipMemcpyAsync(h_res, d_a, sizeof(int32_t) * (size_t)G, hipMemcpyDeviceToHost, st));
-		PANCHK(m, hipMemcpyAsync(h_res + G, d_d, sizeof(int32_t) * (size_t)G, hipMemcpyDeviceToHost, st));
-		PANCHK(m, hipMemcpyAsync(h_res + 2 * (size_t)G, d_k, sizeof(int32_t) * (size_t)G, hipMemcpyDeviceToHost, st));
-	}
-	PANCHK(m, hipStreamSynchronize(st));
-	return 0;
+	return pan_download3(m, st, h_res, d_a, d_d, d_k, G);
 }

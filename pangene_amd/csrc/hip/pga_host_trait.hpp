@@ -7,16 +7,11 @@
 // one after the other on the one stream.  Nothing is read back between the batches; a, s and k come down once at the end.
 
 constexpr int32_t TRAIT_MAX_COL = 16777215, TRAIT_MAX_GENE = 16777215;
-constexpr int32_t TRAIT_MAX_PERM = 2147483646; // 2^31 - 2
 constexpr int32_t TRAIT_BATCH = 65536;
 
 struct TraitBuf { enum { BITS, LABEL, A, S, LO, HI, K, ROWS, WORK, N_BUF }; }; // page-locked buffer 0: a, s, k
 
-extern "C" int32_t pga_trait_batch(void)
-{
-	if (const char *s = getenv("PANGENE_TRAIT_BATCH")) { const long long v = atoll(s); if (v >= 1 && v <= (1 << 22)) return (int32_t)v; }
-	return TRAIT_BATCH;
-}
+extern "C" int32_t pga_trait_batch(void) { return (int32_t)pan_env("PANGENE_TRAIT_BATCH", TRAIT_BATCH, 1 << 22); }
 
 extern "C" int pga_pan_trait(const pga_trait_in_t *in, pga_trait_out_t *out)
 {
@@ -25,7 +20,7 @@ extern "C" int pga_pan_trait(const pga_trait_in_t *in, pga_trait_out_t *out)
 	if (in == nullptr) return PGA_ERR_ARG;
 	const int32_t G = in->n_gene, N = in->n_col, n = in->n_perm;
 	if (G < 0 || N < 0 || n < 0 || in->min_count < 1) return PGA_ERR_ARG;
-	if (N > TRAIT_MAX_COL || G > TRAIT_MAX_GENE || n > TRAIT_MAX_PERM) return PGA_ERR_RANGE;
+	if (N > TRAIT_MAX_COL || G > TRAIT_MAX_GENE || n > PAN_MAX_PERM) return PGA_ERR_RANGE;
 	const int32_t W = (N + 31) / 32;
 	if (W > 0 && ((G > 0 && in->bits == nullptr) || in->label == nullptr)) return PGA_ERR_ARG;
 	PanDev &m = g_pan[PAN_TRAIT];
@@ -42,14 +37,12 @@ extern "C" int pga_pan_trait(const pga_trait_in_t *in, pga_trait_out_t *out)
 	PANCHK(m, m.stream(&st));
 
 	const size_t n_word = (size_t)G * (size_t)W;
-	const int32_t B = (int32_t)std::min<int64_t>(pga_trait_batch(), std::max<int32_t>(n, 1));
-	const bool lds = W <= TRAIT_PERM_LDS_W;
-	const int64_t perm_blocks = ((int64_t)B + WAVE - 1) / WAVE;
+	PermBatches b(n, pga_trait_batch(), W <= TRAIT_PERM_LDS_W);
 	uint32_t *d_bits = m.get<uint32_t>(TraitBuf::BITS, n_word), *d_label = m.get<uint32_t>(TraitBuf::LABEL, (size_t)W);
 	int32_t *d_a = m.get<int32_t>(TraitBuf::A, (size_t)G), *d_s = m.get<int32_t>(TraitBuf::S, (size_t)G), *d_lo = m.get<int32_t>(TraitBuf::LO, (size_t)G);
 	int32_t *d_hi = m.get<int32_t>(TraitBuf::HI, (size_t)G), *d_k = m.get<int32_t>(TraitBuf::K, (size_t)G);
-	uint32_t *d_rows = m.get<uint32_t>(TraitBuf::ROWS, (size_t)B * (size_t)W);
-	uint32_t *d_work = m.get<uint32_t>(TraitBuf::WORK, lds ? 1 : (size_t)perm_blocks * (size_t)W * WAVE);
+	uint32_t *d_rows = m.get<uint32_t>(TraitBuf::ROWS, (size_t)b.B * (size_t)W);
+	uint32_t *d_work = m.get<uint32_t>(TraitBuf::WORK, b.work((size_t)W));
 	PANMEM(d_bits); PANMEM(d_label); PANMEM(d_a); PANMEM(d_s); PANMEM(d_lo); PANMEM(d_hi); PANMEM(d_k); PANMEM(d_rows); PANMEM(d_work);
 	if (n_word) PANCHK(m, hipMemcpyAsync(d_bits, in->bits, sizeof(uint32_t) * n_word, hipMemcpyHostToDevice, st));
 	PANCHK(m, hipMemcpyAsync(d_label, in->label, sizeof(uint32_t) * (size_t)W, hipMemcpyHostToDevice, st));
@@ -60,13 +53,10 @@ extern "C" int pga_pan_trait(const pga_trait_in_t *in, pga_trait_out_t *out)
 	}
 	const int32_t n_chunk = (W + DIST_KC - 1) / DIST_KC;
 	const unsigned gene_tiles = (unsigned)((G + DIST_TILE - 1) / DIST_TILE);
-	for (int64_t done = 0; done < n; done += B) {
-		const int32_t nb = (int32_t)std::min<int64_t>(B, (int64_t)n - done);
-		const unsigned pb = (unsigned)((nb + WAVE - 1) / WAVE);
-		const uint32_t p0 = (uint32_t)(done + 1); // permutations are numbered from 1
-		if (lds) hipLaunchKernelGGL(k_trait_perm<true>, dim3(pb), dim3(WAVE), 0, st, d_label, N, W, in->seed, p0, nb, d_work, d_rows);
-		else hipLaunchKernelGGL(k_trait_perm<false>, dim3(pb), dim3(WAVE), 0, st, d_label, N, W, in->seed, p0, nb, d_work, d_rows);
-		if (done == 0 && in->perm_rows != nullptr) { // tests only: the label rows of the first batch
+	for (; b.more(); b.next()) {
+		const int32_t nb = b.nb();
+		perm_launch(b.lds, k_trait_perm<true>, k_trait_perm<false>, nb, st, d_label, N, W, in->seed, b.p0(), nb, d_work, d_rows);
+		if (b.first() && in->perm_rows != nullptr) { // tests only: the label rows of the first batch
 			PANCHK(m, hipGetLastError());
 			PANCHK(m, hipMemcpyAsync(in->perm_rows, d_rows, sizeof(uint32_t) * (size_t)nb * (size_t)W, hipMemcpyDeviceToHost, st));
 			PANCHK(m, hipStreamSynchronize(st));
@@ -76,11 +66,5 @@ extern "C" int pga_pan_trait(const pga_trait_in_t *in, pga_trait_out_t *out)
 			                   n_chunk, d_k);
 		PANCHK(m, hipGetLastError());
 	}
-	if (G > 0) {
-		PANCHK(m, hipMemcpyAsync(h_res, d_a, sizeof(int32_t) * (size_t)G, hipMemcpyDeviceToHost, st));
-		PANCHK(m, hipMemcpyAsync(h_res + G, d_s, sizeof(int32_t) * (size_t)G, hipMemcpyDeviceToHost, st));
-		PANCHK(m, hipMemcpyAsync(h_res + 2 * (size_t)G, d_k, sizeof(int32_t) * (size_t)G, hipMemcpyDeviceToHost, st));
-	}
-	PANCHK(m, hipStreamSynchronize(st));
-	return 0;
+	return pan_download3(m, st, h_res, d_a, d_s, d_k, G);
 }

@@ -237,10 +237,10 @@ int dist_items_graph(pg_graph_t *q, int32_t type, std::vector<std::string> &name
 int shared_count(const std::vector<uint32_t> &bits, int32_t M, int32_t A, int32_t *S);
 // the records of the tree pangene tree prints for such rows (tree.cpp): rec[A - 2][6] (NJ) or rec[A - 1][6] (UPGMA); nothing for A < 3
 int tree_joins(const std::vector<uint32_t> &bits, int32_t M, int32_t A, int32_t metric, int32_t method, int64_t *rec);
-// pangene permanova for such rows (tree.cpp): the distances, then one line per row of lab[T][A] (1, 0, negative = missing) named by
-// trait[T]; 0 or a PGA_ERR_* code, nothing is written unless every trait went through.  trait.cpp reads the trait file and calls it
-int permanova_run(const char *route, const std::vector<std::string> &trait, const std::vector<int8_t> &lab, const std::vector<uint32_t> &bits, int32_t M, int32_t A,
-                  const pg_permanova_opt_t *o, double t_start);
+// the binary traits of a trait file (trait.cpp; pangene trait and pangene permanova read them): lab[T][A] = 1, 0, negative = missing, over the
+// assemblies asm_name; 0, or -1 with a message (the line number in it) on stderr
+struct Traits { std::vector<std::string> name; std::vector<int8_t> lab; };
+int read_traits(const char *fn, const std::vector<std::string> &asm_name, Traits &tr);
 
 double now_sec();
 const char *stamp();

@@ -13,8 +13,6 @@
 // columns, and the permutation counts k_g from the backend (pga_pan_qtrait: the permuted value rows as two signed-byte planes, D_p of
 // every gene and permutation as an int8 matrix product) or from the plain loops below; U, auc, z, p_wilcox and q_bh are computed here,
 // by code both builds share.
-// PERMANOVA (pg_permanova_file, pg_write_permanova; DESIGN.md section 8 "PERMANOVA"): the trait file is read here, by trait's reader; the
-// distances, the test and the text are tree.cpp's (permanova_run).
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -300,7 +298,6 @@ double binom_two_sided(const std::vector<double> &lf, int32_t k, int32_t n)
 	return p < 1.0 ? p : 1.0;
 }
 
-struct Traits { std::vector<std::string> name; std::vector<int8_t> lab; }; // lab[T][A]
 struct QTraits { std::vector<std::string> name; std::vector<double> val; }; // val[T][A], NaN = missing
 
 std::vector<std::string> split_tab(const std::string &s)
@@ -346,6 +343,8 @@ int read_trait_file(const char *fn, const std::vector<std::string> &asm_name, st
 	return 0;
 }
 
+} // namespace
+
 int read_traits(const char *fn, const std::vector<std::string> &asm_name, Traits &tr)
 {
 	const size_t A = asm_name.size();
@@ -357,6 +356,8 @@ int read_traits(const char *fn, const std::vector<std::string> &asm_name, Traits
 		                       return true;
 	                       });
 }
+
+namespace {
 
 // NA or empty: missing (NaN); otherwise a number strtod consumes entirely, with a finite result
 bool qtrait_value(const std::string &v, double &x)
@@ -780,35 +781,6 @@ int pg_pan_qtrait(const uint8_t *presence, const double *values, int32_t n_gene,
 		}
 	}
 	return 0;
-}
-
-int pg_permanova_file(const char *gfa_fn, const char *trait_fn, const pg_permanova_opt_t *o)
-{
-	const double t0 = now_sec();
-	if (o == nullptr) { std::fprintf(stderr, "Error: pan_permanova: no options\n"); return -2; }
-	std::vector<std::string> names;
-	std::vector<uint32_t> bits;
-	int32_t M;
-	if (dist_items_file(gfa_fn, o->type, names, bits, M) != 0) return cannot_open(gfa_fn);
-	Traits tr;
-	if (read_traits(trait_fn, names, tr) != 0) return -3;
-	const int rc = permanova_run("file", tr.name, tr.lab, bits, M, (int32_t)names.size(), o, t0);
-	if (rc != 0) { std::fprintf(stderr, "Error: pan_permanova: %s\n", backend_default()->strerror(rc)); return -2; }
-	return 0;
-}
-
-void pg_write_permanova(pg_graph_t *q, const char *trait_fn, const pg_permanova_opt_t *o)
-{
-	const double t0 = now_sec();
-	if (o == nullptr) { set_error(PGA_ERR_ARG, "pg_write_permanova"); return; }
-	std::vector<std::string> names;
-	std::vector<uint32_t> bits;
-	int32_t M;
-	if (dist_items_graph(q, o->type, names, bits, M) != 0) return;
-	Traits tr;
-	if (read_traits(trait_fn, names, tr) != 0) { set_error(PGA_ERR_ARG, "pg_write_permanova: bad trait file"); return; }
-	const int rc = permanova_run("memory", tr.name, tr.lab, bits, M, (int32_t)names.size(), o, t0);
-	if (rc != 0) set_error(rc, "pg_write_permanova");
 }
 
 } // extern "C"
