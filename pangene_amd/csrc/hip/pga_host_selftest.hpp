@@ -147,6 +147,36 @@ extern "C" int pga_selftest_scan(const int32_t *in, const int32_t *seg, int32_t 
 	return 0;
 }
 
+// what pga_begin left, on whichever route made it (tests/test_stage_a_gpu.py, tests/support/stage_a_direct.py): the packed records, the raw
+// flag words with the values of the internal bits, fidx / gnm / yperm / headpos -- the arrays EVERY route writes (the LDS routes write neither
+// c->cs, ce, cds, offx, rk, pm as planes nor sdom / pdom / pdom0) -- and which route it was.  Reads only; not part of pangene_hip.h.
+typedef struct {
+	int32_t *recA, *recB, *recC;   /* [4 N] each, X order: {cs, seg, ce, pm} {rk, gid, cds, pid} {rank, n_exon, off_exon, score_ori} */
+	uint32_t *flags;               /* [N] the raw flag words, X order */
+	int32_t *fidx, *gnm, *yperm;   /* [N] */
+	int32_t *headpos;              /* [n_genome + 1] */
+	uint32_t f_head, f_multi, f_cstie;          /* out: the values of the internal bits */
+	int32_t route;                 /* out: 0 global radix, 1 per-genome LDS sort, 2 contig bins */
+	int32_t n_unit[3];             /* out: route 1: gs_n[0..2]; route 2: {bin_n_small, bin_n_big, 0}; route 0: zeros */
+	int32_t n_cu;
+} pga_selftest_stage_a_t;
+extern "C" int pga_selftest_stage_a(pga_ctx_t *c, pga_selftest_stage_a_t *out) // after pga_begin: waits for the stream, copies; any pointer may be NULL
+{
+	if (c == nullptr || out == nullptr) return PGA_ERR_ARG;
+	TRY(sync_st(c));
+	const size_t N = (size_t)c->N, GL = (size_t)c->n_genome;
+	auto fetch = [&](void *dst, const void *src, size_t bytes) { return (dst == nullptr || bytes == 0 || hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) == hipSuccess) ? 0 : PGA_ERR_NO_DEVICE; };
+	TRY(fetch(out->recA, c->recA, sizeof(int4) * N)); TRY(fetch(out->recB, c->recB, sizeof(int4) * N)); TRY(fetch(out->recC, c->recC, sizeof(int4) * N));
+	TRY(fetch(out->flags, c->flags, sizeof(uint32_t) * N));
+	TRY(fetch(out->fidx, c->fidx, sizeof(int32_t) * N)); TRY(fetch(out->gnm, c->gnm, sizeof(int32_t) * N)); TRY(fetch(out->yperm, c->yperm, sizeof(int32_t) * N));
+	if (N) TRY(fetch(out->headpos, c->headpos, sizeof(int32_t) * (GL + 1))); // (a shard without hits: pga_begin leaves before anybody writes it)
+	out->f_head = F_HEAD, out->f_multi = F_MULTI, out->f_cstie = F_CSTIE;
+	out->route = c->bin_on ? 2 : c->gs_ok ? 1 : 0, out->n_cu = c->n_cu;
+	for (int k = 0; k < 3; ++k) out->n_unit[k] = out->route == 1 ? c->gs_n[k] : 0;
+	if (out->route == 2) out->n_unit[0] = c->bin_n_small, out->n_unit[1] = c->bin_n_big;
+	return 0;
+}
+
 // the roundings of a final arc record on the device (k_genes.hpp: arc_final_hi): out[4 n] = {avg_dist, s1, s2, 0} of every in[i]
 extern "C" int pga_selftest_arc_final(const pga_arc_part_t *in, int64_t n, int32_t *out)
 {
