@@ -493,6 +493,48 @@ int  pg_mantel_file(const char *gfa_fn, const char *mat_fn, const pg_mantel_opt_
 void pg_write_mantel(pg_graph_t *g, const char *mat_fn, const pg_mantel_opt_t *o);
 int  pg_pan_mantel(const int32_t *qx, const int32_t *qy, int32_t n, const pg_mantel_opt_t *o, int64_t *out);
 
+/* Gain and loss: on which branches of the assemblies' tree were items gained and lost, and which items changed hands many times --
+ * ancestral gene-content reconstruction by parsimony (Wagner parsimony with a gain penalty, as in Count; Fitch parsimony when the two
+ * costs are equal).  DESIGN.md section 8 "Gain and loss" holds the definition.  The items are the rows of the presence matrix (genes, or
+ * with type PG_DIST_ADJ the gene adjacencies of the walks), the tree is the one pg_tree_* build with `metric` and `method` over all
+ * assemblies.  The method defaults to UPGMA, which has a root; NJ is rooted at its closing record (x, y, z), read as ((x, y), z) as
+ * pg_pan_pairs reads it, and gains and losses DEPEND on that reading (the cost does not when gain = loss = 1).  Nodes: leaves
+ * 0 .. A - 1 in matrix order, join record s makes node A + s (NJ's closing record A + s and the root A + s + 1): 2 A - 1 nodes.
+ * A gain (parent absent, child present) costs `gain`, a loss `loss`, 1 .. 255 each.  Per item, bottom-up: a leaf with bit b has
+ * C[b] = 0, C[1 - b] = gain + loss; an inner node C[s] = the sum over its two children c of min(C_c[s], C_c[1 - s] + w(s)), w(0) = gain,
+ * w(1) = loss.  Top-down: the root is present iff C[1] < C[0]; a child of a node in state s switches iff C_c[1 - s] + w(s) < C_c[s]
+ * (mode PG_GAINLOSS_LATE: a tie keeps the parent's state, changes sit towards the tips) or <= (PG_GAINLOSS_EARLY: towards the root).
+ * cost = gain * gains + loss * losses and is the smallest possible; a leaf's state is its bit.  Integers throughout.
+ * Output, tab-separated.  out = PG_GAINLOSS_GENE: "Gene Present Cost Changes Gains Losses Root", one line per item in matrix order with
+ * Changes = Gains + Losses >= min_changes (an adjacency is named by its two steps as a walk writes them, >a<b).  PG_GAINLOSS_NODE:
+ * "Node Child1 Child2 Leaves Present Gains Losses": the leaves first under their assembly names with "." for both children, then the
+ * joins in record order as @s with s = node - A; Present = the items in state 1 at the node, Gains and Losses those on the branch above
+ * it, NA for the root.  No assemblies or no items: the header only.  At most 65 535 assemblies and 16 777 215 items (PGA_ERR_RANGE).
+ * pg_gainloss_file: 0, -1 (the GFA file cannot be opened) or -2 (bad options, or the backend's status on stderr).  pg_write_gainloss: the
+ * same for the graph in memory; errors go to pg_last_error.
+ * pg_pan_gainloss: any presence matrix, row-major uint8 [n_item][n_asm], and any tree over the n_asm assemblies as the records pg_pan_tree
+ * or pg_pan_join return for `method` (not read when n_asm < 3: one leaf is the root, two are one join); of the options only gain, loss
+ * and mode are read.  Fills gene_out[n_item][5] = present, cost, gains, losses, root and node_out[2 n_asm - 1][3] = present, gains,
+ * losses in node order (0 and 0 for the root) and returns 0 or a negative PGA_ERR_* (a NULL, an option out of range, records that name a
+ * slot out of range or a retired one: PGA_ERR_ARG).  The two passes come from the backend's pga_pan_gainloss.
+ * sizeof(pg_gainloss_opt_t) is 32. */
+enum { PG_GAINLOSS_LATE = 0, PG_GAINLOSS_EARLY = 1 };
+enum { PG_GAINLOSS_GENE = 0, PG_GAINLOSS_NODE = 1 };
+typedef struct {
+	int32_t type;        /* PG_DIST_GENE or PG_DIST_ADJ [gene] */
+	int32_t metric;      /* PG_DIST_JACCARD or PG_DIST_DIFF [jaccard] */
+	int32_t method;      /* PG_TREE_NJ or PG_TREE_UPGMA [upgma] */
+	int32_t gain, loss;  /* the cost of a gain and of a loss, 1 .. 255 [1, 1] */
+	int32_t mode;        /* PG_GAINLOSS_LATE or PG_GAINLOSS_EARLY [late] */
+	int32_t out;         /* PG_GAINLOSS_GENE or PG_GAINLOSS_NODE [gene] */
+	int32_t min_changes; /* the gene table keeps the items with Changes >= min_changes [0: all] */
+} pg_gainloss_opt_t;
+void pg_gainloss_opt_init(pg_gainloss_opt_t *o);
+int  pg_gainloss_file(const char *gfa_fn, const pg_gainloss_opt_t *o);
+void pg_write_gainloss(pg_graph_t *g, const pg_gainloss_opt_t *o);
+int  pg_pan_gainloss(const uint8_t *presence, int32_t n_item, int32_t n_asm, const int64_t *rec, int32_t method, const pg_gainloss_opt_t *o, int32_t *gene_out,
+                     int64_t *node_out);
+
 /* Last error of the path (0 = none).  The reference aborts on invariant violations; this library
  * records a status instead, prints one line to stderr, and leaves the graph empty. */
 int         pg_last_error(void);

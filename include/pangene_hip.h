@@ -94,7 +94,7 @@ typedef struct {
  * Device layout limits (PGA_ERR_RANGE otherwise): coordinates inside a block < 2^31 (contigs beyond that arrive as virtual contigs,
  * see pga_genome_block_t; what remains out of reach is a single cluster of overlapping hits spanning 2^30 bp), < 2^30 hits and < 2^31
  * exons per shard, < 2^20 genes, < 2^24 genomes. */
-#define PGA_ABI_VERSION 18u  /* bumped whenever a struct of this header or the order of pga_backend_t changes; pga_create refuses another */
+#define PGA_ABI_VERSION 19u  /* bumped whenever a struct of this header or the order of pga_backend_t changes; pga_create refuses another */
 typedef struct {
 	uint32_t abi_version;        /* = PGA_ABI_VERSION of the header the caller was compiled against (PGA_ERR_ARG otherwise) */
 	int32_t n_genome;            /* genomes in this shard (may include genomes with 0 hits) */
@@ -555,6 +555,35 @@ typedef struct { int64_t z, n_ge, n_le; } pga_mantel_out_t;
 int pga_pan_mantel(const pga_mantel_in_t *in, pga_mantel_out_t *out);
 int32_t pga_mantel_batch(void); /* permutations per batch: 4 096, or PANGENE_MANTEL_BATCH */
 
+/* Gene gain and loss on a tree (include/pangene_amd.h pg_pan_gainloss, pangene gainloss; DESIGN.md section 8 "Gain and loss"): Wagner
+ * parsimony per item, a gain (parent absent, child present) costing `gain` and a loss `loss`.  Context-free, like pan_pairs, and over the
+ * same postfix program: op 0 pushes the next leaf, op 1 joins the top two entries.  Every op makes one node, so a node is named by its op.
+ * Up: an entry is (C0, C1); a leaf with bit b has C[b] = 0, C[1 - b] = gain + loss; a join has C[s] = the sum over its two children c of
+ * min(C_c[s], C_c[1 - s] + w(s)), w(0) = gain, w(1) = loss.  Down: the root is present iff C1 < C0; a child of a parent in state s
+ * switches iff C_c[1 - s] + w(s) < C_c[s] (mode 0, late) or <= (mode 1, early).
+ * In:  op[2 n_leaf - 1] as for pan_pairs (malformed: PGA_ERR_ARG, a stack need above 16: PGA_ERR_RANGE); par[2 n_leaf - 1] = the op of
+ *      the join that takes the node of each op, -1 for the last op, the root (anything else: PGA_ERR_ARG); bits[n_leaf][(n_gene + 31) / 32]
+ *      as for pan_pairs, row k = the k-th pushed leaf; mode 0 or 1 (PGA_ERR_ARG otherwise).  st_rows: NULL, or -- for tests only -- room
+ *      for the first chunk's state rows, uint64 [2 n_leaf - 1][ceil(min(n_gene, pga_gainloss_chunk(n_leaf)) / 64)]: bit i & 63 of word
+ *      i >> 6 of row k = item i is present at the node of op k; bits past n_gene are zero.
+ * Out: gene[n_gene][4] = cost, gains, losses, root state; node[2 n_leaf - 1][3] = in op order the items present at the node and the
+ *      gains and losses on the branch above it (0 and 0 for the root).  The arrays belong to the backend and stay valid until its next
+ *      pan_gainloss.  n_leaf = 0 or n_gene = 0: zeros, nothing is launched.
+ * The items go through in chunks of pga_gainloss_chunk(n_leaf): PANGENE_GAINLOSS_CHUNK rounded up to a multiple of 1 024, or the largest
+ * multiple of 1 024 items whose three bit rows per node fit 1 GiB, never less than 1 024.
+ * Limits (PGA_ERR_RANGE otherwise, before anything is launched): n_leaf <= 65 535, n_gene <= 16 777 215, 1 <= gain, loss <= 255 (every
+ * cost then stays below 2^25). */
+typedef struct {
+	const uint8_t *op;
+	const uint32_t *bits;
+	const int32_t *par;
+	int32_t n_gene, n_leaf, gain, loss, mode;
+	uint64_t *st_rows;
+} pga_gainloss_in_t;
+typedef struct { const int32_t *gene; const int64_t *node; } pga_gainloss_out_t;
+int pga_pan_gainloss(const pga_gainloss_in_t *in, pga_gainloss_out_t *out);
+int32_t pga_gainloss_chunk(int32_t n_leaf);
+
 /* the same ABI as a table, so the host driver is written once */
 struct pga_branch_par_s; struct pga_loop_xchg_s;
 typedef struct {
@@ -623,6 +652,7 @@ typedef struct {
 	int  (*pan_permanova)(const pga_permanova_in_t *, pga_permanova_out_t *); /* may be NULL: the host driver then runs the same step itself */
 	int  (*pan_mantel)(const pga_mantel_in_t *, pga_mantel_out_t *); /* may be NULL: the host driver then runs the same step itself */
 	int  (*final_arcs)(pga_ctx_t *, const void **, int64_t *); /* may be NULL.  The final arc table of a branch_loop that ran with final_on: host view, count; 1 = not available */
+	int  (*pan_gainloss)(const pga_gainloss_in_t *, pga_gainloss_out_t *); /* may be NULL: the host driver then runs the same step itself */
 } pga_backend_t;
 
 const pga_backend_t *pga_backend(void);

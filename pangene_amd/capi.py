@@ -727,6 +727,82 @@ def _mantel_args(argv: Sequence[str]):
     return on, f, x, y, n, seed
 
 
+GAINLOSS_MODES = ("late", "early")
+GAINLOSS_OUTS = ("gene", "node")
+
+
+class pg_gainloss_opt_t(C.Structure):
+    """Gain and loss options (include/pangene_amd.h): the items, the tree, the two costs, the tie rule, the table and its filter."""
+    _fields_ = [("type", C.c_int32), ("metric", C.c_int32), ("method", C.c_int32), ("gain", C.c_int32), ("loss", C.c_int32), ("mode", C.c_int32),
+                ("out", C.c_int32), ("min_changes", C.c_int32)]
+
+
+def gainloss_opt(lib: C.CDLL, type: str = "gene", metric: str = "jaccard", method: str = "upgma", gain: int = 1, loss: int = 1, mode: str = "late",
+                 out: str = "gene", min_changes: int = 0) -> pg_gainloss_opt_t:
+    if type not in DIST_TYPES:
+        raise ValueError("type must be gene or adj")
+    if metric not in TREE_METRICS:
+        raise ValueError("metric must be jaccard or diff")
+    if method not in TREE_METHODS:
+        raise ValueError("method must be upgma or nj")
+    if not (1 <= int(gain) <= 255 and 1 <= int(loss) <= 255):
+        raise ValueError("gain and loss must be in [1, 255]")
+    if mode not in GAINLOSS_MODES:
+        raise ValueError("mode must be late or early")
+    if out not in GAINLOSS_OUTS:
+        raise ValueError("out must be gene or node")
+    if not 0 <= int(min_changes) <= TREE_MAX_BOOT:
+        raise ValueError("min_changes must be in [0, 2^31 - 1]")
+    o = pg_gainloss_opt_t()
+    lib.pg_gainloss_opt_init(C.byref(o))
+    o.type, o.metric, o.method = DIST_TYPES.index(type), DIST_METRICS.index(metric), TREE_METHODS.index(method)
+    o.gain, o.loss, o.mode, o.out, o.min_changes = int(gain), int(loss), GAINLOSS_MODES.index(mode), GAINLOSS_OUTS.index(out), int(min_changes)
+    return o
+
+
+def pan_gainloss(lib: C.CDLL, presence, rec, method: str, gain: int = 1, loss: int = 1, mode: str = "late"):
+    """Gains and losses of the items of an item x assembly presence matrix (bool numpy array or torch tensor, shape (M, A)) on the tree of
+    the records rec (an int64 array as pan_tree or pan_join return it for `method`; any such tree over the A assemblies, ignored when
+    A < 3) through pg_pan_gainloss: a dict of numpy arrays: present, cost, gains, losses and root, int32 (M,), per item; node_present,
+    node_gains and node_losses, int64 (2 A - 1,), per node (leaf x = x, join s = A + s; 0 gains and losses at the root)."""
+    import numpy as np
+    p = _presence(presence)
+    M, A = p.shape
+    m = TREE_METHODS.index(method)
+    rec = np.ascontiguousarray(rec if rec is not None else np.zeros((0, 6)), dtype=np.int64).reshape(-1, 6)
+    if A >= 3 and rec.shape[0] != A - 2 + m:
+        raise ValueError("rec must hold %d records for %d assemblies and %s" % (A - 2 + m, A, method))
+    o = gainloss_opt(lib, method=method, gain=gain, loss=loss, mode=mode)
+    gene = np.zeros((M, 5), dtype=np.int32)
+    node = np.zeros((max(2 * A - 1, 0), 3), dtype=np.int64)
+    rc = lib.pg_pan_gainloss(p.ctypes.data_as(C.POINTER(C.c_uint8)), M, A, rec.ctypes.data_as(C.POINTER(C.c_int64)), m, C.byref(o),
+                             gene.ctypes.data_as(C.POINTER(C.c_int32)), node.ctypes.data_as(C.POINTER(C.c_int64)))
+    if rc != 0:
+        raise RuntimeError("pg_pan_gainloss: status %d" % rc)
+    out = {k: np.ascontiguousarray(gene[:, i]) for i, k in enumerate(("present", "cost", "gains", "losses", "root"))}
+    out.update({"node_" + k: np.ascontiguousarray(node[:, i]) for i, k in enumerate(("present", "gains", "losses"))})
+    return out
+
+
+def _gainloss_args(argv: Sequence[str]):
+    """The options of --gainloss[=gene|node] / --gainloss-type= / --gainloss-metric= / --gainloss-method= / --gainloss-gain= /
+    --gainloss-loss= / --gainloss-resolve= / --gainloss-min= in argv as keywords of gainloss_opt; None without --gainloss."""
+    on, extra, kw = False, False, {}
+    names = {"type": "type", "metric": "metric", "method": "method", "gain": "gain", "loss": "loss", "resolve": "mode", "min": "min_changes"}
+    for a in argv:
+        if a == "--gainloss": on = True
+        elif a.startswith("--gainloss="): on, kw["out"] = True, a.split("=", 1)[1]
+        elif a.startswith("--gainloss-") and "=" in a and a[11:].split("=", 1)[0] in names:
+            k, v = a[11:].split("=", 1)
+            kw[names[k]] = int(v) if k in ("gain", "loss", "min") else v
+            extra = True
+        elif a.startswith("--gainloss"):
+            raise ValueError("unknown option or missing value: " + a)
+    if extra and not on:
+        raise ValueError("--gainloss-type, --gainloss-metric, --gainloss-method, --gainloss-gain, --gainloss-loss, --gainloss-resolve and --gainloss-min need --gainloss")
+    return kw if on else None
+
+
 def _cluster_args(argv: Sequence[str]):
     """(k_lo, k_hi, type, metric, iterations) of --cluster=INT[-INT] / --cluster-type=STR / --cluster-metric=STR / --cluster-iter=INT in
     argv; k_lo = None without --cluster."""
@@ -839,6 +915,10 @@ _API = {
     "pg_mantel_file": (C.c_int, [C.c_char_p, C.c_char_p, C.c_void_p]),
     "pg_write_mantel": (None, [C.c_void_p, C.c_char_p, C.c_void_p]),
     "pg_pan_mantel": (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.POINTER(C.c_int64)]),
+    "pg_gainloss_opt_init": (None, [C.c_void_p]),
+    "pg_gainloss_file": (C.c_int, [C.c_char_p, C.c_void_p]),
+    "pg_write_gainloss": (None, [C.c_void_p, C.c_void_p]),
+    "pg_pan_gainloss": (C.c_int, [C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "pg_pan_qtrait": (C.c_int, [C.POINTER(C.c_uint8), C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]),
     "pg_pan_trait": (C.c_int, [C.POINTER(C.c_uint8), C.POINTER(C.c_int8), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]),
     "pg_pan_pairs": (C.c_int, [C.POINTER(C.c_uint8), C.POINTER(C.c_int8), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int32)]),
@@ -920,7 +1000,7 @@ def parse_args(lib: C.CDLL, argv: Sequence[str]) -> pg_opt_t:
         elif a in ("--bed", "--bed=walk"): opt.flag |= PG_F_WRITE_BED_WALK
         elif a == "--bed=raw": opt.flag |= PG_F_WRITE_BED_RAW
         elif a == "--bed=flag": opt.flag |= PG_F_WRITE_BED_FLAG
-        elif a in ("--matrix", "--matrix=presence", "--matrix=count", "--call") or a.startswith("--curves") or a.startswith("--dist") or a.startswith("--assoc") or a.startswith("--trait") or a.startswith("--qtrait") or a.startswith("--tree") or a.startswith("--cluster") or a.startswith("--permanova") or a.startswith("--mantel"): pass  # handled by run()
+        elif a in ("--matrix", "--matrix=presence", "--matrix=count", "--call") or a.startswith("--curves") or a.startswith("--dist") or a.startswith("--assoc") or a.startswith("--trait") or a.startswith("--qtrait") or a.startswith("--tree") or a.startswith("--cluster") or a.startswith("--permanova") or a.startswith("--mantel") or a.startswith("--gainloss"): pass  # handled by run()
         elif a[:2] in ("-p", "-a", "-f", "-c", "-g", "-r", "-b", "-B", "-y", "-T", "-D", "-C", "-e", "-l", "-m", "-d", "-X", "-I", "-P"):
             v = a[2:] if len(a) > 2 else next(it)
             k = a[1]
@@ -998,6 +1078,11 @@ def run(lib: C.CDLL, files: Sequence[str], argv: Sequence[str] = (), scan_only: 
     if mt_on and (any(x.startswith("--matrix") for x in argv) or "--call" in argv or n_curves or dist_type is not None or assoc_phi is not None
                   or trait_fn is not None or tree_type is not None or qtrait_fn is not None or cl_lo is not None or pm_fn is not None):
         raise ValueError("--mantel cannot be combined with --matrix, --call, --curves, --dist, --assoc, --trait, --tree, --qtrait, --cluster or --permanova")
+    gl_kw = _gainloss_args(argv)
+    if gl_kw is not None and (any(x.startswith("--matrix") for x in argv) or "--call" in argv or n_curves or dist_type is not None or assoc_phi is not None
+                              or trait_fn is not None or tree_type is not None or qtrait_fn is not None or cl_lo is not None or pm_fn is not None or mt_on):
+        raise ValueError("--gainloss cannot be combined with --matrix, --call, --curves, --dist, --assoc, --trait, --tree, --qtrait, --cluster, --permanova or --mantel")
+    gl_opt = gainloss_opt(lib, **gl_kw) if gl_kw is not None else None
     fd, out = tempfile.mkstemp(prefix="pangene_", suffix=".out")
     os.close(fd)
     lib.pg_set_output(out.encode())
@@ -1055,6 +1140,10 @@ def run(lib: C.CDLL, files: Sequence[str], argv: Sequence[str] = (), scan_only: 
                     raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
             elif mt_on:
                 lib.pg_write_mantel(g, mt_fn.encode() if mt_fn is not None else None, C.byref(mantel_opt(lib, mt_x, mt_y, mt_n, mt_seed)))
+                if lib.pg_last_error():
+                    raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
+            elif gl_opt is not None:
+                lib.pg_write_gainloss(g, C.byref(gl_opt))
                 if lib.pg_last_error():
                     raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
             elif opt.flag & PG_F_WRITE_BED_WALK: lib.pg_write_bed(d, 1)

@@ -85,6 +85,14 @@ static int usage(FILE *fp, const pg_opt_t *opt)
 	std::fprintf(fp, "    --mantel-y=STR    --mantel: the second matrix, unless FILE is given [adj:jaccard]\n");
 	std::fprintf(fp, "    --mantel-perm=INT --mantel: permutations of the assemblies [1000]\n");
 	std::fprintf(fp, "    --mantel-seed=INT --mantel: seed of the permutations [11]\n");
+	std::fprintf(fp, "    --gainloss[=STR]  output the gains and losses of every item on the tree of the assemblies, per item (gene) or per branch (node) [gene]\n");
+	std::fprintf(fp, "    --gainloss-type=STR     --gainloss: items, gene or adj [gene]\n");
+	std::fprintf(fp, "    --gainloss-metric=STR   --gainloss: distance of the tree, jaccard or diff [jaccard]\n");
+	std::fprintf(fp, "    --gainloss-method=STR   --gainloss: upgma, or nj rooted at its closing join ((x, y), z): gains and losses depend on that reading [upgma]\n");
+	std::fprintf(fp, "    --gainloss-gain=INT     --gainloss: cost of a gain, 1 to 255 [1]\n");
+	std::fprintf(fp, "    --gainloss-loss=INT     --gainloss: cost of a loss, 1 to 255 [1]\n");
+	std::fprintf(fp, "    --gainloss-resolve=STR  --gainloss: on a tie a change sits towards the tips (late) or towards the root (early) [late]\n");
+	std::fprintf(fp, "    --gainloss-min=INT      --gainloss=gene: print the items with at least INT changes [0]\n");
 	std::fprintf(fp, "  Also: pangene gfa2matrix [-c] [-d FILE] [-p] <in.gfa>   (pangene.js gfa2matrix on a GFA file)\n");
 	std::fprintf(fp, "        pangene call [-m INT] [-w] [-b] [-e] [-d] [-p] [-s] [-r STR] <in.gfa>   (pangene.js call on a GFA file)\n");
 	std::fprintf(fp, "        pangene curves [-n INT] [-s INT] <in.gfa>   (accumulation curves of the gfa2matrix matrix of a GFA file)\n");
@@ -96,6 +104,7 @@ static int usage(FILE *fp, const pg_opt_t *opt)
 	std::fprintf(fp, "        pangene cluster [-t gene|adj] [-m jaccard|diff] -k INT[-INT] [-i INT] <in.gfa>   (k-medoids clusters of the assemblies of a GFA file, their medoids and silhouettes)\n");
 	std::fprintf(fp, "        pangene permanova -t FILE [-T gene|adj] [-m jaccard|diff] [-n INT] [-s INT] <in.gfa>   (do the two groups of a binary trait differ in gene content: pseudo-F, R2 and a permutation p per trait)\n");
 	std::fprintf(fp, "        pangene mantel [-x SPEC] [-y SPEC | -f FILE] [-n INT] [-s INT] <in.gfa>   (do two distance matrices of the assemblies agree: Mantel's r and its permutation p)\n");
+	std::fprintf(fp, "        pangene gainloss [-t gene|adj] [-m jaccard|diff] [-a upgma|nj] [-g INT] [-l INT] [-r late|early] [-o gene|node] [-c INT] <in.gfa>   (gene gains and losses on the tree of the assemblies by parsimony, per item or per branch)\n");
 	return fp == stdout ? 0 : 1;
 }
 
@@ -457,6 +466,47 @@ static int main_mantel(int argc, char *argv[])
 	return pg_mantel_file(argv[optind], fn, &o) == 0 ? 0 : 1;
 }
 
+static bool gainloss_cost(const char *s, int32_t &v) // an integer in [1, 255]
+{
+	char *e;
+	const long long x = std::strtoll(s, &e, 10);
+	if (e == s || *e != 0 || x < 1 || x > 255) return false;
+	v = (int32_t)x;
+	return true;
+}
+static int gainloss_mode(const char *s) { return std::strcmp(s, "late") == 0 ? PG_GAINLOSS_LATE : std::strcmp(s, "early") == 0 ? PG_GAINLOSS_EARLY : -1; }
+static int gainloss_out(const char *s) { return std::strcmp(s, "gene") == 0 ? PG_GAINLOSS_GENE : std::strcmp(s, "node") == 0 ? PG_GAINLOSS_NODE : -1; }
+
+// `pangene gainloss`: the gains and losses of every item of a GFA file on the tree `pangene tree` builds over its assemblies
+static int main_gainloss(int argc, char *argv[])
+{
+	pg_gainloss_opt_t o;
+	pg_gainloss_opt_init(&o);
+	int c;
+	while ((c = getopt(argc, argv, "t:m:a:g:l:r:o:c:")) >= 0) {
+		if (c == 't') { if ((o.type = dist_type(optarg)) < 0) { std::fprintf(stderr, "ERROR: -t must be gene or adj\n"); return 1; } }
+		else if (c == 'm') { if ((o.metric = tree_metric(optarg)) < 0) { std::fprintf(stderr, "ERROR: -m must be jaccard or diff (shared is not a distance)\n"); return 1; } }
+		else if (c == 'a') { if ((o.method = tree_method(optarg)) < 0) { std::fprintf(stderr, "ERROR: -a must be upgma or nj\n"); return 1; } }
+		else if (c == 'g') { if (!gainloss_cost(optarg, o.gain)) { std::fprintf(stderr, "ERROR: -g must be in [1, 255]\n"); return 1; } }
+		else if (c == 'l') { if (!gainloss_cost(optarg, o.loss)) { std::fprintf(stderr, "ERROR: -l must be in [1, 255]\n"); return 1; } }
+		else if (c == 'r') { if ((o.mode = gainloss_mode(optarg)) < 0) { std::fprintf(stderr, "ERROR: -r must be late or early\n"); return 1; } }
+		else if (c == 'o') { if ((o.out = gainloss_out(optarg)) < 0) { std::fprintf(stderr, "ERROR: -o must be gene or node\n"); return 1; } }
+		else if (c == 'c') { if (!tree_boot(optarg, o.min_changes)) { std::fprintf(stderr, "ERROR: -c must be in [0, 2147483647]\n"); return 1; } }
+		else return 1;
+	}
+	if (argc - optind < 1) {
+		std::printf("Usage: pangene gainloss [options] <in.gfa>\nOptions:\n  -t STR   items: gene (gene content) or adj (gene adjacencies of the walks) [gene]\n"
+		            "  -m STR   distance of the tree: jaccard or diff [jaccard]\n"
+		            "  -a STR   tree: upgma, or nj rooted at its closing join, read as ((x, y), z): gains and losses depend on that reading [upgma]\n"
+		            "  -g INT   cost of a gain, 1 to 255 [%d]\n  -l INT   cost of a loss, 1 to 255 [%d]\n"
+		            "  -r STR   on a tie a change sits towards the tips (late) or towards the root (early) [late]\n"
+		            "  -o STR   table: gene (per item: Present Cost Changes Gains Losses Root) or node (per branch: Leaves Present Gains Losses) [gene]\n"
+		            "  -c INT   -o gene: print the items with at least INT changes [%d]\n", o.gain, o.loss, o.min_changes);
+		return 0;
+	}
+	return pg_gainloss_file(argv[optind], &o) == 0 ? 0 : 1;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // `pangene --gpus N`: main.c:117-142 for N devices of one node.  The command forks N - 1 workers BEFORE anything touches the GPU;
 // rank r takes device r and the r-th contiguous block of the PAF files (so that the ranks' W / BED lines, concatenated in rank
@@ -472,7 +522,8 @@ struct Output { int matrix = 0; bool call = false; int curves = 0; uint32_t curv
 	int tree = -1, tree_metric = 0, tree_method = 0; int32_t tree_boot = 0; uint32_t tree_seed = 0; // tree: PG_DIST_GENE / PG_DIST_ADJ (-1: none)
 	int32_t cluster_lo = 0, cluster_hi = 0, cluster_iter = 1000; int cluster_type = 0, cluster_metric = 0; // cluster_lo: 0 = none
 	const char *permanova = nullptr; int permanova_type = 0, permanova_metric = 0; int32_t permanova_perm = 1000; uint32_t permanova_seed = 11;
-	bool mantel = false; const char *mantel_file = nullptr; pg_mantel_opt_t mantel_opt; };
+	bool mantel = false; const char *mantel_file = nullptr; pg_mantel_opt_t mantel_opt;
+	bool gainloss = false; pg_gainloss_opt_t gainloss_opt; };
 
 static int run_path(pg_opt_t &opt, int n_files, char **files, const uint8_t *ids_only, const Output &o, bool graph_lines, bool own_lines, int device = -1)
 {
@@ -563,6 +614,10 @@ static int run_path(pg_opt_t &opt, int n_files, char **files, const uint8_t *ids
 			pg_write_mantel(g, o.mantel_file, &o.mantel_opt);
 			if (pg_last_error()) rc = 2;
 		}
+		else if (o.gainloss) {
+			pg_write_gainloss(g, &o.gainloss_opt);
+			if (pg_last_error()) rc = 2;
+		}
 		else if (opt.flag & PG_F_WRITE_BED_WALK) { if (own_lines) pg_write_bed(d, 1); }
 		else if (opt.flag & PG_F_WRITE_BED_FLAG) { if (own_lines) pg_write_bed(d, 0); }
 		else {
@@ -631,6 +686,7 @@ static int run_sharded(pg_opt_t &opt, int W, int n_files, char **files, const Ou
 	if (o.cluster_lo) { std::fprintf(stderr, "ERROR: --cluster needs every genome in one process; run it without --gpus\n"); return 1; }
 	if (o.permanova) { std::fprintf(stderr, "ERROR: --permanova needs every genome in one process; run it without --gpus\n"); return 1; }
 	if (o.mantel) { std::fprintf(stderr, "ERROR: --mantel needs every genome in one process; run it without --gpus\n"); return 1; }
+	if (o.gainloss) { std::fprintf(stderr, "ERROR: --gainloss needs every genome in one process; run it without --gpus\n"); return 1; }
 	const bool dev = pg_backend_is_device() != 0;
 	typedef int (*uid_fn)(void *); typedef int (*init_fn)(int32_t, int32_t, const void *); typedef int (*fin_fn)(void);
 	uid_fn rccl_uid = nullptr; init_fn rccl_init = nullptr; fin_fn rccl_fin = nullptr;
@@ -781,6 +837,7 @@ int main(int argc, char *argv[])
 	if (argc >= 2 && std::strcmp(argv[1], "cluster") == 0) return main_cluster(argc - 1, argv + 1);
 	if (argc >= 2 && std::strcmp(argv[1], "permanova") == 0) return main_permanova(argc - 1, argv + 1);
 	if (argc >= 2 && std::strcmp(argv[1], "mantel") == 0) return main_mantel(argc - 1, argv + 1);
+	if (argc >= 2 && std::strcmp(argv[1], "gainloss") == 0) return main_gainloss(argc - 1, argv + 1);
 	int matrix = 0, n_gpus = 1; // matrix: 1 presence, 2 counts
 	bool call = false;
 	int curves = 0; // orders of --curves (0: not asked for)
@@ -812,6 +869,9 @@ int main(int argc, char *argv[])
 	const char *mantel_file = nullptr;
 	pg_mantel_opt_t mantel_opt;
 	pg_mantel_opt_init(&mantel_opt);
+	bool gainloss = false, gainloss_extra = false; // --gainloss[=gene|node]; a --gainloss-* option was given
+	pg_gainloss_opt_t gainloss_opt;
+	pg_gainloss_opt_init(&gainloss_opt);
 	static const struct option lopts[] = {
 		{ "bed", optional_argument, nullptr, 301 }, { "ori-sc", no_argument, nullptr, 302 }, { "matrix", optional_argument, nullptr, 303 }, { "call", no_argument, nullptr, 305 },
 		{ "curves", optional_argument, nullptr, 306 }, { "curves-seed", required_argument, nullptr, 307 },
@@ -828,6 +888,9 @@ int main(int argc, char *argv[])
 		{ "permanova-perm", required_argument, nullptr, 332 }, { "permanova-seed", required_argument, nullptr, 333 },
 		{ "mantel", optional_argument, nullptr, 334 }, { "mantel-x", required_argument, nullptr, 335 }, { "mantel-y", required_argument, nullptr, 336 },
 		{ "mantel-perm", required_argument, nullptr, 337 }, { "mantel-seed", required_argument, nullptr, 338 },
+		{ "gainloss", optional_argument, nullptr, 339 }, { "gainloss-type", required_argument, nullptr, 340 }, { "gainloss-metric", required_argument, nullptr, 341 },
+		{ "gainloss-method", required_argument, nullptr, 342 }, { "gainloss-gain", required_argument, nullptr, 343 }, { "gainloss-loss", required_argument, nullptr, 344 },
+		{ "gainloss-resolve", required_argument, nullptr, 345 }, { "gainloss-min", required_argument, nullptr, 346 },
 		{ "gpus", required_argument, nullptr, 304 }, { "procs", required_argument, nullptr, 304 },
 		{ "version", no_argument, nullptr, 401 }, { nullptr, 0, nullptr, 0 } };
 	pg_opt_t opt;
@@ -968,6 +1031,38 @@ int main(int argc, char *argv[])
 			if (!trait_perm(optarg, mantel_opt.n_perm)) { std::fprintf(stderr, "ERROR: --mantel-perm must be in [0, 2147483646]\n"); return 1; }
 			break;
 		case 338: mantel_extra = true, mantel_opt.seed = (uint32_t)std::strtoul(optarg, nullptr, 10); break;
+		case 339:
+			gainloss = true;
+			if (optarg && (gainloss_opt.out = gainloss_out(optarg)) < 0) { std::fprintf(stderr, "ERROR: --gainloss must be gene or node\n"); return 1; }
+			break;
+		case 340:
+			gainloss_extra = true;
+			if ((gainloss_opt.type = dist_type(optarg)) < 0) { std::fprintf(stderr, "ERROR: --gainloss-type must be gene or adj\n"); return 1; }
+			break;
+		case 341:
+			gainloss_extra = true;
+			if ((gainloss_opt.metric = tree_metric(optarg)) < 0) { std::fprintf(stderr, "ERROR: --gainloss-metric must be jaccard or diff (shared is not a distance)\n"); return 1; }
+			break;
+		case 342:
+			gainloss_extra = true;
+			if ((gainloss_opt.method = tree_method(optarg)) < 0) { std::fprintf(stderr, "ERROR: --gainloss-method must be upgma or nj\n"); return 1; }
+			break;
+		case 343:
+			gainloss_extra = true;
+			if (!gainloss_cost(optarg, gainloss_opt.gain)) { std::fprintf(stderr, "ERROR: --gainloss-gain must be in [1, 255]\n"); return 1; }
+			break;
+		case 344:
+			gainloss_extra = true;
+			if (!gainloss_cost(optarg, gainloss_opt.loss)) { std::fprintf(stderr, "ERROR: --gainloss-loss must be in [1, 255]\n"); return 1; }
+			break;
+		case 345:
+			gainloss_extra = true;
+			if ((gainloss_opt.mode = gainloss_mode(optarg)) < 0) { std::fprintf(stderr, "ERROR: --gainloss-resolve must be late or early\n"); return 1; }
+			break;
+		case 346:
+			gainloss_extra = true;
+			if (!tree_boot(optarg, gainloss_opt.min_changes)) { std::fprintf(stderr, "ERROR: --gainloss-min must be in [0, 2147483647]\n"); return 1; }
+			break;
 		case 401: std::puts(PG_VERSION); return 0;
 		default: break;
 		}
@@ -997,7 +1092,16 @@ int main(int argc, char *argv[])
 	}
 	if (mantel_extra && !mantel) { std::fprintf(stderr, "ERROR: --mantel-x, --mantel-y, --mantel-perm and --mantel-seed need --mantel\n"); return 1; }
 	if (mantel_y && mantel_file) { std::fprintf(stderr, "ERROR: --mantel-y cannot be combined with --mantel=FILE\n"); return 1; }
+	if (gainloss && (matrix || call || curves || dist >= 0 || assoc || trait || tree >= 0 || qtrait || cluster_lo || permanova || mantel)) {
+		std::fprintf(stderr, "ERROR: --gainloss cannot be combined with --matrix, --call, --curves, --dist, --assoc, --trait, --tree, --qtrait, --cluster, --permanova or --mantel\n");
+		return 1;
+	}
+	if (gainloss_extra && !gainloss) {
+		std::fprintf(stderr, "ERROR: --gainloss-type, --gainloss-metric, --gainloss-method, --gainloss-gain, --gainloss-loss, --gainloss-resolve and --gainloss-min need --gainloss\n");
+		return 1;
+	}
 	Output o;
+	o.gainloss = gainloss, o.gainloss_opt = gainloss_opt;
 	o.mantel = mantel, o.mantel_file = mantel_file, o.mantel_opt = mantel_opt;
 	o.permanova = permanova, o.permanova_type = permanova_type_v, o.permanova_metric = permanova_metric_v, o.permanova_perm = permanova_perm_v, o.permanova_seed = permanova_seed;
 	o.cluster_lo = cluster_lo, o.cluster_hi = cluster_hi, o.cluster_iter = cluster_iter_v, o.cluster_type = cluster_type_v, o.cluster_metric = cluster_metric_v;

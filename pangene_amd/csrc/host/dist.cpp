@@ -55,8 +55,9 @@ namespace {
 
 // walks (steps = segment * 2 + reverse; walk w of assembly walk_asm[w]) -> the adjacencies of each assembly as bit rows; M = the
 // distinct adjacencies.  (u, v) and (v ^ 1, u ^ 1) are the same adjacency read from the other strand; the smaller pair is the key.
+// key_of: nullptr, or receives the key u << 32 | v of every adjacency
 void adj_bits(const std::vector<int32_t> &step, const std::vector<int64_t> &walk_off, const std::vector<int32_t> &walk_asm, int32_t A,
-              std::vector<uint32_t> &bits, int32_t &M)
+              std::vector<uint32_t> &bits, int32_t &M, std::vector<uint64_t> *key_of = nullptr)
 {
 	std::unordered_map<uint64_t, int32_t> id;
 	std::vector<std::pair<int32_t, int32_t>> has; // (assembly, item)
@@ -68,28 +69,55 @@ void adj_bits(const std::vector<int32_t> &step, const std::vector<int64_t> &walk
 			has.emplace_back(walk_asm[w], it->second);
 		}
 	M = (int32_t)id.size();
+	if (key_of != nullptr) {
+		key_of->resize(id.size());
+		for (const auto &kv : id) (*key_of)[(size_t)kv.second] = kv.first;
+	}
 	const size_t W = ((size_t)M + 31) / 32;
 	bits.assign((size_t)A * W, 0);
 	for (const auto &h : has) bits[(size_t)h.first * W + (size_t)(h.second >> 5)] |= 1u << (h.second & 31);
 }
 
+// what an item is called: a gene by its name, an adjacency by its two steps as a walk writes them (>a<b)
+void adj_names(const std::vector<uint64_t> &key, const std::vector<std::string> &seg, std::vector<std::string> &item_names)
+{
+	item_names.clear();
+	item_names.reserve(key.size());
+	for (const uint64_t k : key) {
+		const uint32_t u = (uint32_t)(k >> 32), v = (uint32_t)k;
+		item_names.push_back((u & 1u ? "<" : ">") + seg[u >> 1] + (v & 1u ? "<" : ">") + seg[v >> 1]);
+	}
+}
+
 } // namespace
 
-// the items of the assemblies of a GFA file as bit rows (0, or -1 when the file cannot be opened), and of the graph in memory
-int dist_items_file(const char *gfa_fn, int32_t type, std::vector<std::string> &names, std::vector<uint32_t> &bits, int32_t &M)
+// the items of the assemblies of a GFA file as bit rows (0, or -1 when the file cannot be opened), and of the graph in memory;
+// item_names: nullptr, or receives what each item is called
+int dist_items_file(const char *gfa_fn, int32_t type, std::vector<std::string> &names, std::vector<uint32_t> &bits, int32_t &M, std::vector<std::string> *item_names)
 {
 	GfaMatrix m;
 	if (gfa_matrix(gfa_fn, m) != 0) return -1;
 	const int32_t A = (int32_t)m.asm_a.size();
-	if (type == PG_DIST_ADJ) adj_bits(m.step, m.walk_off, m.walk_asm, A, bits, M);
-	else M = (int32_t)m.seg.size(), pack_cols(m.mat.data(), M, A, bits); // gene g is in assembly a when its entry is > 0
+	if (type == PG_DIST_ADJ) {
+		std::vector<uint64_t> key;
+		adj_bits(m.step, m.walk_off, m.walk_asm, A, bits, M, item_names ? &key : nullptr);
+		if (item_names) adj_names(key, m.seg, *item_names);
+	} else {
+		M = (int32_t)m.seg.size(), pack_cols(m.mat.data(), M, A, bits); // gene g is in assembly a when its entry is > 0
+		if (item_names) item_names->swap(m.seg);
+	}
 	names.swap(m.asm_a);
 	return 0;
 }
 
-int dist_items_graph(pg_graph_t *q, int32_t type, std::vector<std::string> &names, std::vector<uint32_t> &bits, int32_t &M)
+int dist_items_graph(pg_graph_t *q, int32_t type, std::vector<std::string> &names, std::vector<uint32_t> &bits, int32_t &M, std::vector<std::string> *item_names)
 {
 	names.clear();
+	std::vector<std::string> seg;
+	if (item_names) {
+		seg.reserve((size_t)q->n_seg);
+		for (int32_t i = 0; i < q->n_seg; ++i) seg.emplace_back(q->d->gene[q->seg[i].gid].name);
+	}
 	if (type == PG_DIST_ADJ) {
 		// the walks pg_write_walk prints; the columns are their sample#hap in first-seen order, as gfa2matrix reads them back
 		std::vector<std::string> walk_name;
@@ -103,12 +131,15 @@ int dist_items_graph(pg_graph_t *q, int32_t type, std::vector<std::string> &name
 			if (it.second) names.push_back(walk_name[w]);
 			walk_asm[w] = it.first->second;
 		}
-		adj_bits(step, walk_off, walk_asm, (int32_t)names.size(), bits, M);
+		std::vector<uint64_t> key;
+		adj_bits(step, walk_off, walk_asm, (int32_t)names.size(), bits, M, item_names ? &key : nullptr);
+		if (item_names) adj_names(key, seg, *item_names);
 	} else {
 		std::vector<int32_t> mat;
 		if (graph_matrix(q, names, mat) != 0) return -1;
 		M = q->n_seg;
 		pack_cols(mat.data(), M, (int32_t)names.size(), bits);
+		if (item_names) item_names->swap(seg);
 	}
 	return 0;
 }

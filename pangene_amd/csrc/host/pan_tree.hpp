@@ -67,9 +67,9 @@ struct ItemSource {
 	pg_graph_t *g;
 	bool memory;
 	const char *route() const { return memory ? "memory" : "file"; }
-	int operator()(int32_t type, std::vector<std::string> &names, std::vector<uint32_t> &bits, int32_t &M) const
+	int operator()(int32_t type, std::vector<std::string> &names, std::vector<uint32_t> &bits, int32_t &M, std::vector<std::string> *item_names = nullptr) const
 	{
-		return memory ? dist_items_graph(g, type, names, bits, M) : dist_items_file(gfa_fn, type, names, bits, M);
+		return memory ? dist_items_graph(g, type, names, bits, M, item_names) : dist_items_file(gfa_fn, type, names, bits, M, item_names);
 	}
 };
 inline ItemSource items_of_file(const char *gfa_fn) { return ItemSource{gfa_fn, nullptr, false}; }

@@ -232,8 +232,9 @@ int gfa_matrix(const char *fn, GfaMatrix &m);
 // what pangene dist and pangene tree read (dist.cpp): the items of every assembly -- its genes (PG_DIST_GENE) or the gene adjacencies of
 // its walks (PG_DIST_ADJ) -- as assembly-major bit rows bits[A][(M + 31) / 32], of a GFA file (-1: it cannot be opened) and of the graph
 // in memory; a row-major presence matrix [M][A] becomes such rows by pack_cols (pan_common.hpp); S[A][A] of the rows (the backend's pan_shared, or host loops)
-int dist_items_file(const char *gfa_fn, int32_t type, std::vector<std::string> &names, std::vector<uint32_t> &bits, int32_t &M);
-int dist_items_graph(pg_graph_t *q, int32_t type, std::vector<std::string> &names, std::vector<uint32_t> &bits, int32_t &M);
+// item_names: nullptr, or receives what each item is called (a gene's name; an adjacency's two steps as a walk writes them, >a<b)
+int dist_items_file(const char *gfa_fn, int32_t type, std::vector<std::string> &names, std::vector<uint32_t> &bits, int32_t &M, std::vector<std::string> *item_names = nullptr);
+int dist_items_graph(pg_graph_t *q, int32_t type, std::vector<std::string> &names, std::vector<uint32_t> &bits, int32_t &M, std::vector<std::string> *item_names = nullptr);
 int shared_count(const std::vector<uint32_t> &bits, int32_t M, int32_t A, int32_t *S);
 // the records of the tree pangene tree prints for such rows (tree.cpp): rec[A - 2][6] (NJ) or rec[A - 1][6] (UPGMA); nothing for A < 3
 int tree_joins(const std::vector<uint32_t> &bits, int32_t M, int32_t A, int32_t metric, int32_t method, int64_t *rec);

@@ -1,10 +1,11 @@
-// tree.cpp -- the commands over the pairwise fixed-point distances of the assemblies: ONE translation unit, one header per command with
+// tree.cpp -- the commands over the pairwise fixed-point distances of the assemblies and their tree: ONE translation unit, one header per command with
 // its host loops, its run function, its text output and its extern "C" entries, included in this order (a later one uses what an
 // earlier one defines).
 //   pan_tree.hpp       the fixed-point distances and the entry helpers all four share; the joins, the bootstrap, pangene tree
 //   pan_cluster.hpp    k-medoids, pangene cluster
 //   pan_permanova.hpp  pangene permanova
 //   pan_mantel.hpp     pangene mantel
+//   pan_gainloss.hpp   pangene gainloss (with pan_treeprog.hpp: the records as a tree and as the backend's program, shared with trait.cpp)
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -14,6 +15,7 @@
 #include <unordered_map>
 #include <vector>
 #include "pg_internal.hpp"
+#include "pan_treeprog.hpp"
 
 using namespace pgx;
 
@@ -21,3 +23,4 @@ using namespace pgx;
 #include "pan_cluster.hpp"
 #include "pan_permanova.hpp"
 #include "pan_mantel.hpp"
+#include "pan_gainloss.hpp"
