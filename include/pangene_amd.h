@@ -535,6 +535,40 @@ void pg_write_gainloss(pg_graph_t *g, const pg_gainloss_opt_t *o);
 int  pg_pan_gainloss(const uint8_t *presence, int32_t n_item, int32_t n_asm, const int64_t *rec, int32_t method, const pg_gainloss_opt_t *o, int32_t *gene_out,
                      int64_t *node_out);
 
+/* Co-evolution: which item pairs were gained and lost on the same branches of the assemblies' tree -- the gene-gene association counted
+ * over events on the tree instead of over tips (as Coinfinder's lineage correction and Goldfinder's simultaneous-event score do).
+ * DESIGN.md section 8 "Co-evolution" holds the definition.  Items, tree and reconstruction are exactly those of pg_gainloss_* (type,
+ * metric, method, gain, loss, mode).  Every node but the root has one branch above it: B = 2 A - 2.  Item i has the gain set G_i (node
+ * present, parent absent) and the loss set L_i (the reverse); e_i = |G_i| + |L_i| is the Changes column of pg_gainloss_*.  For i < j:
+ * same = |G_i & G_j| + |L_i & L_j|, opp = |G_i & L_j| + |L_i & G_j|, d = same - opp.  Items with e_i >= min_events are eligible; a pair of
+ * eligible items is selected when 10^6 d^2 >= p^2 e_i e_j, p = floor(1000 min_r + 0.5), and the sign rule of pg_assoc_* holds (pos: d >= 0,
+ * neg: d < 0).  Integers throughout; with B < 2^17 both sides stay below 2^54.
+ * Output, tab-separated, in ascending (i, j): "ItemA ItemB nA nB eA eB same opp r p_hyper": the presence counts, the events, the two
+ * counts, r = d / sqrt(eA eB) (%.4f) and p_hyper = P(X >= same + opp) for X ~ Hypergeometric(B, eA, eB) (%.3e), computed on the host for
+ * the selected pairs.  It is a parsimony reading; under NJ it depends on the rooting; p_hyper treats the branches as exchangeable and is
+ * a screening value.  A <= 1 or no items: the header only.  More than max_pair selected pairs is an error (PGA_ERR_RANGE, one line on
+ * stderr, no table).  pg_coevo_file: 0, -1 (the GFA file cannot be opened) or -2; pg_write_coevo: errors go to pg_last_error.
+ * pg_pan_coevo: any presence matrix [n_item][n_asm] and any tree as for pg_pan_gainloss; of the options type and metric are not read.
+ * Fills events_out[n_item] = e_i (may be NULL) and the first min(cap, n) rows of pair_out[cap][4] = i, j, same, opp, and returns n, the
+ * number selected, or a negative PGA_ERR_*.  The counting and the selection come from the backend's pga_pan_coevo.
+ * sizeof(pg_coevo_opt_t) is 48. */
+typedef struct {
+	int32_t type;        /* PG_DIST_GENE or PG_DIST_ADJ [gene] */
+	int32_t metric;      /* PG_DIST_JACCARD or PG_DIST_DIFF [jaccard] */
+	int32_t method;      /* PG_TREE_NJ or PG_TREE_UPGMA [upgma] */
+	int32_t gain, loss;  /* the cost of a gain and of a loss, 1 .. 255 [1, 1] */
+	int32_t mode;        /* PG_GAINLOSS_LATE or PG_GAINLOSS_EARLY [late] */
+	int32_t min_events;  /* an item is eligible when e_i >= min_events; >= 1 [2] */
+	int32_t sign;        /* PG_ASSOC_BOTH, PG_ASSOC_POS or PG_ASSOC_NEG [both] */
+	double  min_r;       /* smallest |r| of a selected pair, in [0, 1], read as per-mille [0.8] */
+	int64_t max_pair;    /* more selected pairs than this is an error [16 777 216] */
+} pg_coevo_opt_t;
+void    pg_coevo_opt_init(pg_coevo_opt_t *o);
+int     pg_coevo_file(const char *gfa_fn, const pg_coevo_opt_t *o);
+void    pg_write_coevo(pg_graph_t *g, const pg_coevo_opt_t *o);
+int64_t pg_pan_coevo(const uint8_t *presence, int32_t n_item, int32_t n_asm, const int64_t *rec, int32_t method, const pg_coevo_opt_t *o, int32_t *events_out,
+                     int32_t *pair_out, int64_t cap);
+
 /* Last error of the path (0 = none).  The reference aborts on invariant violations; this library
  * records a status instead, prints one line to stderr, and leaves the graph empty. */
 int         pg_last_error(void);

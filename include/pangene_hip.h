@@ -94,7 +94,7 @@ typedef struct {
  * Device layout limits (PGA_ERR_RANGE otherwise): coordinates inside a block < 2^31 (contigs beyond that arrive as virtual contigs,
  * see pga_genome_block_t; what remains out of reach is a single cluster of overlapping hits spanning 2^30 bp), < 2^30 hits and < 2^31
  * exons per shard, < 2^20 genes, < 2^24 genomes. */
-#define PGA_ABI_VERSION 19u  /* bumped whenever a struct of this header or the order of pga_backend_t changes; pga_create refuses another */
+#define PGA_ABI_VERSION 20u  /* bumped whenever a struct of this header or the order of pga_backend_t changes; pga_create refuses another */
 typedef struct {
 	uint32_t abi_version;        /* = PGA_ABI_VERSION of the header the caller was compiled against (PGA_ERR_ARG otherwise) */
 	int32_t n_genome;            /* genomes in this shard (may include genomes with 0 hits) */
@@ -584,6 +584,37 @@ typedef struct { const int32_t *gene; const int64_t *node; } pga_gainloss_out_t;
 int pga_pan_gainloss(const pga_gainloss_in_t *in, pga_gainloss_out_t *out);
 int32_t pga_gainloss_chunk(int32_t n_leaf);
 
+/* Co-evolution (include/pangene_amd.h pg_pan_coevo, pangene coevo; DESIGN.md section 8 "Co-evolution"): the item pairs whose gains and
+ * losses fall on the same branches of a tree.  Context-free.  The reconstruction is pan_gainloss's, over the same program, rows and par,
+ * with the same checks and limits.  Every op but the last (the root) has one branch above its node: B = 2 n_leaf - 2 branches, named by
+ * their op.  Item i has the gain set G_i (node present, parent absent), the loss set L_i (the reverse) and e_i = |G_i| + |L_i| events; it is
+ * eligible when e_i >= min_events.  For two eligible items i < j: same = |G_i & G_j| + |L_i & L_j|, opp = |G_i & L_j| + |L_i & G_j|,
+ * d = same - opp; the pair is selected when 10^6 d^2 >= r_permille^2 e_i e_j (plain 64-bit: both sides are below 2^54) and sign 0 (both),
+ * sign 1 and d >= 0, or sign 2 and d < 0.
+ * In:  as for pan_gainloss; min_events >= 1, r_permille in [0, 1000], sign 0, 1 or 2, max_pair >= 0 (PGA_ERR_ARG otherwise).  ev_rows: NULL,
+ *      or -- for tests only -- room for ev_cap event rows, uint32 [ev_cap][2][ceil(B / 32)]: row e belongs to the e-th eligible item, plane 0
+ *      holds its gains and plane 1 its losses, bit k & 31 of word k >> 5 = the branch above the node of op k; the first min(E, ev_cap) rows
+ *      are filled.
+ * Out: events[n_gene] = e_i; n_pair = the pairs selected; pair[n_pair][4] = i, j, same, opp in ascending (i, j).  The arrays belong to the
+ *      backend and stay valid until its next pan_coevo.  More than max_pair pairs: PGA_ERR_RANGE with n_pair set and pair NULL.
+ *      n_leaf < 2 or n_gene = 0: zeros, nothing is launched.
+ * The items go through the reconstruction in chunks of pga_coevo_chunk(n_leaf): PANGENE_COEVO_CHUNK rounded up to a multiple of 1 024, or
+ * pga_gainloss_chunk(n_leaf).  PANGENE_COEVO_CAP=n sets the number of records the first run of the pairs kernel has room for.
+ * Limits (PGA_ERR_RANGE otherwise): those of pan_gainloss, and at most 4 194 304 eligible items. */
+typedef struct {
+	const uint8_t *op;
+	const uint32_t *bits;
+	const int32_t *par;
+	int32_t n_gene, n_leaf, gain, loss, mode;
+	int32_t min_events, r_permille, sign;
+	int64_t max_pair;
+	uint32_t *ev_rows;
+	int64_t ev_cap;
+} pga_coevo_in_t;
+typedef struct { const int32_t *events; int64_t n_pair; const int32_t *pair; } pga_coevo_out_t;
+int pga_pan_coevo(const pga_coevo_in_t *in, pga_coevo_out_t *out);
+int32_t pga_coevo_chunk(int32_t n_leaf);
+
 /* the same ABI as a table, so the host driver is written once */
 struct pga_branch_par_s; struct pga_loop_xchg_s;
 typedef struct {
@@ -653,6 +684,7 @@ typedef struct {
 	int  (*pan_mantel)(const pga_mantel_in_t *, pga_mantel_out_t *); /* may be NULL: the host driver then runs the same step itself */
 	int  (*final_arcs)(pga_ctx_t *, const void **, int64_t *); /* may be NULL.  The final arc table of a branch_loop that ran with final_on: host view, count; 1 = not available */
 	int  (*pan_gainloss)(const pga_gainloss_in_t *, pga_gainloss_out_t *); /* may be NULL: the host driver then runs the same step itself */
+	int  (*pan_coevo)(const pga_coevo_in_t *, pga_coevo_out_t *); /* may be NULL: the host driver then runs the same step itself */
 } pga_backend_t;
 
 const pga_backend_t *pga_backend(void);

@@ -803,6 +803,88 @@ def _gainloss_args(argv: Sequence[str]):
     return kw if on else None
 
 
+class pg_coevo_opt_t(C.Structure):
+    """Co-evolution options (include/pangene_amd.h): the items, the tree and the reconstruction as for gainloss, then the eligibility, the
+    sign, the smallest |r| and the pair limit."""
+    _fields_ = [("type", C.c_int32), ("metric", C.c_int32), ("method", C.c_int32), ("gain", C.c_int32), ("loss", C.c_int32), ("mode", C.c_int32),
+                ("min_events", C.c_int32), ("sign", C.c_int32), ("min_r", C.c_double), ("max_pair", C.c_int64)]
+
+
+def coevo_opt(lib: C.CDLL, type: str = "gene", metric: str = "jaccard", method: str = "upgma", gain: int = 1, loss: int = 1, mode: str = "late",
+              min_r: float = 0.8, min_events: int = 2, sign: str = "both", max_pair: int = ASSOC_MAX_PAIR) -> pg_coevo_opt_t:
+    if type not in DIST_TYPES:
+        raise ValueError("type must be gene or adj")
+    if metric not in TREE_METRICS:
+        raise ValueError("metric must be jaccard or diff")
+    if method not in TREE_METHODS:
+        raise ValueError("method must be upgma or nj")
+    if not (1 <= int(gain) <= 255 and 1 <= int(loss) <= 255):
+        raise ValueError("gain and loss must be in [1, 255]")
+    if mode not in GAINLOSS_MODES:
+        raise ValueError("mode must be late or early")
+    if not 0.0 <= float(min_r) <= 1.0:
+        raise ValueError("min_r must be in [0, 1]")
+    if not 1 <= int(min_events) <= TREE_MAX_BOOT:
+        raise ValueError("min_events must be in [1, 2^31 - 1]")
+    if sign not in ASSOC_SIGNS:
+        raise ValueError("sign must be pos, neg or both")
+    if int(max_pair) < 0:
+        raise ValueError("max_pair must not be negative")
+    o = pg_coevo_opt_t()
+    lib.pg_coevo_opt_init(C.byref(o))
+    o.type, o.metric, o.method = DIST_TYPES.index(type), DIST_METRICS.index(metric), TREE_METHODS.index(method)
+    o.gain, o.loss, o.mode, o.min_events, o.sign = int(gain), int(loss), GAINLOSS_MODES.index(mode), int(min_events), ASSOC_SIGNS.index(sign)
+    o.min_r, o.max_pair = float(min_r), int(max_pair)
+    return o
+
+
+def pan_coevo(lib: C.CDLL, presence, rec, method: str, gain: int = 1, loss: int = 1, mode: str = "late", min_r: float = 0.8, min_events: int = 2,
+              sign: str = "both", max_pair: int = ASSOC_MAX_PAIR):
+    """Item pairs of an item x assembly presence matrix (bool numpy array or torch tensor, shape (M, A)) whose gains and losses fall on the
+    same branches of the tree of the records rec (as for pan_gainloss) through pg_pan_coevo: (events, pairs) with events an int32 array
+    (M,) of gains + losses per item and pairs an int32 array (n, 4) of (i, j, same, opp), i < j, ascending."""
+    import numpy as np
+    p = _presence(presence)
+    M, A = p.shape
+    m = TREE_METHODS.index(method)
+    rec = np.ascontiguousarray(rec if rec is not None else np.zeros((0, 6)), dtype=np.int64).reshape(-1, 6)
+    if A >= 3 and rec.shape[0] != A - 2 + m:
+        raise ValueError("rec must hold %d records for %d assemblies and %s" % (A - 2 + m, A, method))
+    o = coevo_opt(lib, method=method, gain=gain, loss=loss, mode=mode, min_r=min_r, min_events=min_events, sign=sign, max_pair=max_pair)
+    events = np.zeros(M, dtype=np.int32)
+    cap = 65536
+    while True:  # the call says how many pairs there are; a second one fetches them when the first buffer was too small
+        pairs = np.zeros((cap, 4), dtype=np.int32)
+        n = lib.pg_pan_coevo(p.ctypes.data_as(C.POINTER(C.c_uint8)), M, A, rec.ctypes.data_as(C.POINTER(C.c_int64)), m, C.byref(o),
+                             events.ctypes.data_as(C.POINTER(C.c_int32)), pairs.ctypes.data_as(C.POINTER(C.c_int32)), cap)
+        if n < 0:
+            raise RuntimeError("pg_pan_coevo: status %d" % n)
+        if n <= cap:
+            break
+        cap = n
+    return events, pairs[:n].copy()
+
+
+def _coevo_args(argv: Sequence[str]):
+    """The options of --coevo[=FLOAT] / --coevo-type= / --coevo-metric= / --coevo-method= / --coevo-gain= / --coevo-loss= /
+    --coevo-resolve= / --coevo-min= / --coevo-sign= / --coevo-max= in argv as keywords of coevo_opt; None without --coevo."""
+    on, extra, kw = False, False, {}
+    names = {"type": "type", "metric": "metric", "method": "method", "gain": "gain", "loss": "loss", "resolve": "mode", "min": "min_events", "sign": "sign",
+             "max": "max_pair"}
+    for a in argv:
+        if a == "--coevo": on = True
+        elif a.startswith("--coevo="): on, kw["min_r"] = True, float(a.split("=", 1)[1])
+        elif a.startswith("--coevo-") and "=" in a and a[8:].split("=", 1)[0] in names:
+            k, v = a[8:].split("=", 1)
+            kw[names[k]] = int(v) if k in ("gain", "loss", "min", "max") else v
+            extra = True
+        elif a.startswith("--coevo"):
+            raise ValueError("unknown option or missing value: " + a)
+    if extra and not on:
+        raise ValueError("--coevo-type, --coevo-metric, --coevo-method, --coevo-gain, --coevo-loss, --coevo-resolve, --coevo-min, --coevo-sign and --coevo-max need --coevo")
+    return kw if on else None
+
+
 def _cluster_args(argv: Sequence[str]):
     """(k_lo, k_hi, type, metric, iterations) of --cluster=INT[-INT] / --cluster-type=STR / --cluster-metric=STR / --cluster-iter=INT in
     argv; k_lo = None without --cluster."""
@@ -919,6 +1001,10 @@ _API = {
     "pg_gainloss_file": (C.c_int, [C.c_char_p, C.c_void_p]),
     "pg_write_gainloss": (None, [C.c_void_p, C.c_void_p]),
     "pg_pan_gainloss": (C.c_int, [C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "pg_coevo_opt_init": (None, [C.c_void_p]),
+    "pg_coevo_file": (C.c_int, [C.c_char_p, C.c_void_p]),
+    "pg_write_coevo": (None, [C.c_void_p, C.c_void_p]),
+    "pg_pan_coevo": (C.c_int64, [C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int64]),
     "pg_pan_qtrait": (C.c_int, [C.POINTER(C.c_uint8), C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]),
     "pg_pan_trait": (C.c_int, [C.POINTER(C.c_uint8), C.POINTER(C.c_int8), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]),
     "pg_pan_pairs": (C.c_int, [C.POINTER(C.c_uint8), C.POINTER(C.c_int8), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int32)]),
@@ -1000,7 +1086,7 @@ def parse_args(lib: C.CDLL, argv: Sequence[str]) -> pg_opt_t:
         elif a in ("--bed", "--bed=walk"): opt.flag |= PG_F_WRITE_BED_WALK
         elif a == "--bed=raw": opt.flag |= PG_F_WRITE_BED_RAW
         elif a == "--bed=flag": opt.flag |= PG_F_WRITE_BED_FLAG
-        elif a in ("--matrix", "--matrix=presence", "--matrix=count", "--call") or a.startswith("--curves") or a.startswith("--dist") or a.startswith("--assoc") or a.startswith("--trait") or a.startswith("--qtrait") or a.startswith("--tree") or a.startswith("--cluster") or a.startswith("--permanova") or a.startswith("--mantel") or a.startswith("--gainloss"): pass  # handled by run()
+        elif a in ("--matrix", "--matrix=presence", "--matrix=count", "--call") or a.startswith("--curves") or a.startswith("--dist") or a.startswith("--assoc") or a.startswith("--trait") or a.startswith("--qtrait") or a.startswith("--tree") or a.startswith("--cluster") or a.startswith("--permanova") or a.startswith("--mantel") or a.startswith("--gainloss") or a.startswith("--coevo"): pass  # handled by run()
         elif a[:2] in ("-p", "-a", "-f", "-c", "-g", "-r", "-b", "-B", "-y", "-T", "-D", "-C", "-e", "-l", "-m", "-d", "-X", "-I", "-P"):
             v = a[2:] if len(a) > 2 else next(it)
             k = a[1]
@@ -1083,6 +1169,12 @@ def run(lib: C.CDLL, files: Sequence[str], argv: Sequence[str] = (), scan_only: 
                               or trait_fn is not None or tree_type is not None or qtrait_fn is not None or cl_lo is not None or pm_fn is not None or mt_on):
         raise ValueError("--gainloss cannot be combined with --matrix, --call, --curves, --dist, --assoc, --trait, --tree, --qtrait, --cluster, --permanova or --mantel")
     gl_opt = gainloss_opt(lib, **gl_kw) if gl_kw is not None else None
+    ce_kw = _coevo_args(argv)
+    if ce_kw is not None and (any(x.startswith("--matrix") for x in argv) or "--call" in argv or n_curves or dist_type is not None or assoc_phi is not None
+                              or trait_fn is not None or tree_type is not None or qtrait_fn is not None or cl_lo is not None or pm_fn is not None or mt_on
+                              or gl_kw is not None):
+        raise ValueError("--coevo cannot be combined with --matrix, --call, --curves, --dist, --assoc, --trait, --tree, --qtrait, --cluster, --permanova, --mantel or --gainloss")
+    ce_opt = coevo_opt(lib, **ce_kw) if ce_kw is not None else None
     fd, out = tempfile.mkstemp(prefix="pangene_", suffix=".out")
     os.close(fd)
     lib.pg_set_output(out.encode())
@@ -1144,6 +1236,10 @@ def run(lib: C.CDLL, files: Sequence[str], argv: Sequence[str] = (), scan_only: 
                     raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
             elif gl_opt is not None:
                 lib.pg_write_gainloss(g, C.byref(gl_opt))
+                if lib.pg_last_error():
+                    raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
+            elif ce_opt is not None:
+                lib.pg_write_coevo(g, C.byref(ce_opt))
                 if lib.pg_last_error():
                     raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
             elif opt.flag & PG_F_WRITE_BED_WALK: lib.pg_write_bed(d, 1)

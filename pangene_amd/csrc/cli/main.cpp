@@ -93,6 +93,16 @@ static int usage(FILE *fp, const pg_opt_t *opt)
 	std::fprintf(fp, "    --gainloss-loss=INT     --gainloss: cost of a loss, 1 to 255 [1]\n");
 	std::fprintf(fp, "    --gainloss-resolve=STR  --gainloss: on a tie a change sits towards the tips (late) or towards the root (early) [late]\n");
 	std::fprintf(fp, "    --gainloss-min=INT      --gainloss=gene: print the items with at least INT changes [0]\n");
+	std::fprintf(fp, "    --coevo[=FLOAT]   output the item pairs gained and lost on the same branches of the tree of the assemblies with |r| >= FLOAT [0.8]\n");
+	std::fprintf(fp, "    --coevo-type=STR        --coevo: items, gene or adj [gene]\n");
+	std::fprintf(fp, "    --coevo-metric=STR      --coevo: distance of the tree, jaccard or diff [jaccard]\n");
+	std::fprintf(fp, "    --coevo-method=STR      --coevo: upgma, or nj rooted at its closing join ((x, y), z): the events depend on that reading [upgma]\n");
+	std::fprintf(fp, "    --coevo-gain=INT        --coevo: cost of a gain, 1 to 255 [1]\n");
+	std::fprintf(fp, "    --coevo-loss=INT        --coevo: cost of a loss, 1 to 255 [1]\n");
+	std::fprintf(fp, "    --coevo-resolve=STR     --coevo: on a tie a change sits towards the tips (late) or towards the root (early) [late]\n");
+	std::fprintf(fp, "    --coevo-min=INT         --coevo: an item takes part with at least INT events; with 1 every pair of strain-specific genes of one assembly scores 1 [2]\n");
+	std::fprintf(fp, "    --coevo-sign=STR        --coevo: keep pos, neg or both [both]\n");
+	std::fprintf(fp, "    --coevo-max=INT         --coevo: give up when more than INT pairs pass [16777216]\n");
 	std::fprintf(fp, "  Also: pangene gfa2matrix [-c] [-d FILE] [-p] <in.gfa>   (pangene.js gfa2matrix on a GFA file)\n");
 	std::fprintf(fp, "        pangene call [-m INT] [-w] [-b] [-e] [-d] [-p] [-s] [-r STR] <in.gfa>   (pangene.js call on a GFA file)\n");
 	std::fprintf(fp, "        pangene curves [-n INT] [-s INT] <in.gfa>   (accumulation curves of the gfa2matrix matrix of a GFA file)\n");
@@ -105,6 +115,7 @@ static int usage(FILE *fp, const pg_opt_t *opt)
 	std::fprintf(fp, "        pangene permanova -t FILE [-T gene|adj] [-m jaccard|diff] [-n INT] [-s INT] <in.gfa>   (do the two groups of a binary trait differ in gene content: pseudo-F, R2 and a permutation p per trait)\n");
 	std::fprintf(fp, "        pangene mantel [-x SPEC] [-y SPEC | -f FILE] [-n INT] [-s INT] <in.gfa>   (do two distance matrices of the assemblies agree: Mantel's r and its permutation p)\n");
 	std::fprintf(fp, "        pangene gainloss [-t gene|adj] [-m jaccard|diff] [-a upgma|nj] [-g INT] [-l INT] [-r late|early] [-o gene|node] [-c INT] <in.gfa>   (gene gains and losses on the tree of the assemblies by parsimony, per item or per branch)\n");
+	std::fprintf(fp, "        pangene coevo [-t gene|adj] [-m jaccard|diff] [-a upgma|nj] [-g INT] [-l INT] [-e late|early] [-r FLOAT] [-c INT] [-s pos|neg|both] [-x INT] <in.gfa>   (item pairs gained and lost on the same branches of the tree of the assemblies)\n");
 	return fp == stdout ? 0 : 1;
 }
 
@@ -507,6 +518,57 @@ static int main_gainloss(int argc, char *argv[])
 	return pg_gainloss_file(argv[optind], &o) == 0 ? 0 : 1;
 }
 
+static bool coevo_min(const char *s, int32_t &v) // an integer in [1, 2^31 - 1]
+{
+	char *e;
+	const long long x = std::strtoll(s, &e, 10);
+	if (e == s || *e != 0 || x < 1 || x > 2147483647LL) return false;
+	v = (int32_t)x;
+	return true;
+}
+static bool coevo_max(const char *s, int64_t &v) // a whole number
+{
+	char *e;
+	const long long x = std::strtoll(s, &e, 10);
+	if (e == s || *e != 0 || x < 0) return false;
+	v = x;
+	return true;
+}
+
+// `pangene coevo`: the item pairs of a GFA file whose gains and losses fall on the same branches of the tree `pangene tree` builds
+static int main_coevo(int argc, char *argv[])
+{
+	pg_coevo_opt_t o;
+	pg_coevo_opt_init(&o);
+	int c;
+	while ((c = getopt(argc, argv, "t:m:a:g:l:e:r:c:s:x:")) >= 0) {
+		if (c == 't') { if ((o.type = dist_type(optarg)) < 0) { std::fprintf(stderr, "ERROR: -t must be gene or adj\n"); return 1; } }
+		else if (c == 'm') { if ((o.metric = tree_metric(optarg)) < 0) { std::fprintf(stderr, "ERROR: -m must be jaccard or diff (shared is not a distance)\n"); return 1; } }
+		else if (c == 'a') { if ((o.method = tree_method(optarg)) < 0) { std::fprintf(stderr, "ERROR: -a must be upgma or nj\n"); return 1; } }
+		else if (c == 'g') { if (!gainloss_cost(optarg, o.gain)) { std::fprintf(stderr, "ERROR: -g must be in [1, 255]\n"); return 1; } }
+		else if (c == 'l') { if (!gainloss_cost(optarg, o.loss)) { std::fprintf(stderr, "ERROR: -l must be in [1, 255]\n"); return 1; } }
+		else if (c == 'e') { if ((o.mode = gainloss_mode(optarg)) < 0) { std::fprintf(stderr, "ERROR: -e must be late or early\n"); return 1; } }
+		else if (c == 'r') { if (!assoc_phi(optarg, o.min_r)) { std::fprintf(stderr, "ERROR: -r must be in [0, 1]\n"); return 1; } }
+		else if (c == 'c') { if (!coevo_min(optarg, o.min_events)) { std::fprintf(stderr, "ERROR: -c must be at least 1\n"); return 1; } }
+		else if (c == 's') { if ((o.sign = assoc_sign(optarg)) < 0) { std::fprintf(stderr, "ERROR: -s must be pos, neg or both\n"); return 1; } }
+		else if (c == 'x') { if (!coevo_max(optarg, o.max_pair)) { std::fprintf(stderr, "ERROR: -x must not be negative\n"); return 1; } }
+		else return 1;
+	}
+	if (argc - optind < 1) {
+		std::printf("Usage: pangene coevo [options] <in.gfa>\nOptions:\n  -t STR    items: gene (gene content) or adj (gene adjacencies of the walks) [gene]\n"
+		            "  -m STR    distance of the tree: jaccard or diff [jaccard]\n"
+		            "  -a STR    tree: upgma, or nj rooted at its closing join, read as ((x, y), z): the events depend on that reading [upgma]\n"
+		            "  -g INT    cost of a gain, 1 to 255 [%d]\n  -l INT    cost of a loss, 1 to 255 [%d]\n"
+		            "  -e STR    on a tie a change sits towards the tips (late) or towards the root (early) [late]\n"
+		            "  -r FLOAT  smallest |r| of a reported pair, in [0, 1], read as per-mille [%g]\n"
+		            "  -c INT    an item takes part with at least INT gains and losses; with 1 every pair of strain-specific genes of one assembly scores 1 [%d]\n"
+		            "  -s STR    keep pos (same direction), neg (opposite direction) or both [both]\n"
+		            "  -x INT    give up when more than INT pairs pass [%lld]\n", o.gain, o.loss, o.min_r, o.min_events, (long long)o.max_pair);
+		return 0;
+	}
+	return pg_coevo_file(argv[optind], &o) == 0 ? 0 : 1;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // `pangene --gpus N`: main.c:117-142 for N devices of one node.  The command forks N - 1 workers BEFORE anything touches the GPU;
 // rank r takes device r and the r-th contiguous block of the PAF files (so that the ranks' W / BED lines, concatenated in rank
@@ -523,7 +585,8 @@ struct Output { int matrix = 0; bool call = false; int curves = 0; uint32_t curv
 	int32_t cluster_lo = 0, cluster_hi = 0, cluster_iter = 1000; int cluster_type = 0, cluster_metric = 0; // cluster_lo: 0 = none
 	const char *permanova = nullptr; int permanova_type = 0, permanova_metric = 0; int32_t permanova_perm = 1000; uint32_t permanova_seed = 11;
 	bool mantel = false; const char *mantel_file = nullptr; pg_mantel_opt_t mantel_opt;
-	bool gainloss = false; pg_gainloss_opt_t gainloss_opt; };
+	bool gainloss = false; pg_gainloss_opt_t gainloss_opt;
+	bool coevo = false; pg_coevo_opt_t coevo_opt; };
 
 static int run_path(pg_opt_t &opt, int n_files, char **files, const uint8_t *ids_only, const Output &o, bool graph_lines, bool own_lines, int device = -1)
 {
@@ -618,6 +681,10 @@ static int run_path(pg_opt_t &opt, int n_files, char **files, const uint8_t *ids
 			pg_write_gainloss(g, &o.gainloss_opt);
 			if (pg_last_error()) rc = 2;
 		}
+		else if (o.coevo) {
+			pg_write_coevo(g, &o.coevo_opt);
+			if (pg_last_error()) rc = 2;
+		}
 		else if (opt.flag & PG_F_WRITE_BED_WALK) { if (own_lines) pg_write_bed(d, 1); }
 		else if (opt.flag & PG_F_WRITE_BED_FLAG) { if (own_lines) pg_write_bed(d, 0); }
 		else {
@@ -687,6 +754,7 @@ static int run_sharded(pg_opt_t &opt, int W, int n_files, char **files, const Ou
 	if (o.permanova) { std::fprintf(stderr, "ERROR: --permanova needs every genome in one process; run it without --gpus\n"); return 1; }
 	if (o.mantel) { std::fprintf(stderr, "ERROR: --mantel needs every genome in one process; run it without --gpus\n"); return 1; }
 	if (o.gainloss) { std::fprintf(stderr, "ERROR: --gainloss needs every genome in one process; run it without --gpus\n"); return 1; }
+	if (o.coevo) { std::fprintf(stderr, "ERROR: --coevo needs every genome in one process; run it without --gpus\n"); return 1; }
 	const bool dev = pg_backend_is_device() != 0;
 	typedef int (*uid_fn)(void *); typedef int (*init_fn)(int32_t, int32_t, const void *); typedef int (*fin_fn)(void);
 	uid_fn rccl_uid = nullptr; init_fn rccl_init = nullptr; fin_fn rccl_fin = nullptr;
@@ -838,6 +906,7 @@ int main(int argc, char *argv[])
 	if (argc >= 2 && std::strcmp(argv[1], "permanova") == 0) return main_permanova(argc - 1, argv + 1);
 	if (argc >= 2 && std::strcmp(argv[1], "mantel") == 0) return main_mantel(argc - 1, argv + 1);
 	if (argc >= 2 && std::strcmp(argv[1], "gainloss") == 0) return main_gainloss(argc - 1, argv + 1);
+	if (argc >= 2 && std::strcmp(argv[1], "coevo") == 0) return main_coevo(argc - 1, argv + 1);
 	int matrix = 0, n_gpus = 1; // matrix: 1 presence, 2 counts
 	bool call = false;
 	int curves = 0; // orders of --curves (0: not asked for)
@@ -872,6 +941,9 @@ int main(int argc, char *argv[])
 	bool gainloss = false, gainloss_extra = false; // --gainloss[=gene|node]; a --gainloss-* option was given
 	pg_gainloss_opt_t gainloss_opt;
 	pg_gainloss_opt_init(&gainloss_opt);
+	bool coevo = false, coevo_extra = false; // --coevo[=FLOAT]; a --coevo-* option was given
+	pg_coevo_opt_t coevo_opt;
+	pg_coevo_opt_init(&coevo_opt);
 	static const struct option lopts[] = {
 		{ "bed", optional_argument, nullptr, 301 }, { "ori-sc", no_argument, nullptr, 302 }, { "matrix", optional_argument, nullptr, 303 }, { "call", no_argument, nullptr, 305 },
 		{ "curves", optional_argument, nullptr, 306 }, { "curves-seed", required_argument, nullptr, 307 },
@@ -891,6 +963,10 @@ int main(int argc, char *argv[])
 		{ "gainloss", optional_argument, nullptr, 339 }, { "gainloss-type", required_argument, nullptr, 340 }, { "gainloss-metric", required_argument, nullptr, 341 },
 		{ "gainloss-method", required_argument, nullptr, 342 }, { "gainloss-gain", required_argument, nullptr, 343 }, { "gainloss-loss", required_argument, nullptr, 344 },
 		{ "gainloss-resolve", required_argument, nullptr, 345 }, { "gainloss-min", required_argument, nullptr, 346 },
+		{ "coevo", optional_argument, nullptr, 347 }, { "coevo-type", required_argument, nullptr, 348 }, { "coevo-metric", required_argument, nullptr, 349 },
+		{ "coevo-method", required_argument, nullptr, 350 }, { "coevo-gain", required_argument, nullptr, 351 }, { "coevo-loss", required_argument, nullptr, 352 },
+		{ "coevo-resolve", required_argument, nullptr, 353 }, { "coevo-min", required_argument, nullptr, 354 }, { "coevo-sign", required_argument, nullptr, 355 },
+		{ "coevo-max", required_argument, nullptr, 356 },
 		{ "gpus", required_argument, nullptr, 304 }, { "procs", required_argument, nullptr, 304 },
 		{ "version", no_argument, nullptr, 401 }, { nullptr, 0, nullptr, 0 } };
 	pg_opt_t opt;
@@ -1063,6 +1139,46 @@ int main(int argc, char *argv[])
 			gainloss_extra = true;
 			if (!tree_boot(optarg, gainloss_opt.min_changes)) { std::fprintf(stderr, "ERROR: --gainloss-min must be in [0, 2147483647]\n"); return 1; }
 			break;
+		case 347:
+			coevo = true;
+			if (optarg && !assoc_phi(optarg, coevo_opt.min_r)) { std::fprintf(stderr, "ERROR: --coevo must be in [0, 1]\n"); return 1; }
+			break;
+		case 348:
+			coevo_extra = true;
+			if ((coevo_opt.type = dist_type(optarg)) < 0) { std::fprintf(stderr, "ERROR: --coevo-type must be gene or adj\n"); return 1; }
+			break;
+		case 349:
+			coevo_extra = true;
+			if ((coevo_opt.metric = tree_metric(optarg)) < 0) { std::fprintf(stderr, "ERROR: --coevo-metric must be jaccard or diff (shared is not a distance)\n"); return 1; }
+			break;
+		case 350:
+			coevo_extra = true;
+			if ((coevo_opt.method = tree_method(optarg)) < 0) { std::fprintf(stderr, "ERROR: --coevo-method must be upgma or nj\n"); return 1; }
+			break;
+		case 351:
+			coevo_extra = true;
+			if (!gainloss_cost(optarg, coevo_opt.gain)) { std::fprintf(stderr, "ERROR: --coevo-gain must be in [1, 255]\n"); return 1; }
+			break;
+		case 352:
+			coevo_extra = true;
+			if (!gainloss_cost(optarg, coevo_opt.loss)) { std::fprintf(stderr, "ERROR: --coevo-loss must be in [1, 255]\n"); return 1; }
+			break;
+		case 353:
+			coevo_extra = true;
+			if ((coevo_opt.mode = gainloss_mode(optarg)) < 0) { std::fprintf(stderr, "ERROR: --coevo-resolve must be late or early\n"); return 1; }
+			break;
+		case 354:
+			coevo_extra = true;
+			if (!coevo_min(optarg, coevo_opt.min_events)) { std::fprintf(stderr, "ERROR: --coevo-min must be at least 1\n"); return 1; }
+			break;
+		case 355:
+			coevo_extra = true;
+			if ((coevo_opt.sign = assoc_sign(optarg)) < 0) { std::fprintf(stderr, "ERROR: --coevo-sign must be pos, neg or both\n"); return 1; }
+			break;
+		case 356:
+			coevo_extra = true;
+			if (!coevo_max(optarg, coevo_opt.max_pair)) { std::fprintf(stderr, "ERROR: --coevo-max must not be negative\n"); return 1; }
+			break;
 		case 401: std::puts(PG_VERSION); return 0;
 		default: break;
 		}
@@ -1100,7 +1216,16 @@ int main(int argc, char *argv[])
 		std::fprintf(stderr, "ERROR: --gainloss-type, --gainloss-metric, --gainloss-method, --gainloss-gain, --gainloss-loss, --gainloss-resolve and --gainloss-min need --gainloss\n");
 		return 1;
 	}
+	if (coevo && (matrix || call || curves || dist >= 0 || assoc || trait || tree >= 0 || qtrait || cluster_lo || permanova || mantel || gainloss)) {
+		std::fprintf(stderr, "ERROR: --coevo cannot be combined with --matrix, --call, --curves, --dist, --assoc, --trait, --tree, --qtrait, --cluster, --permanova, --mantel or --gainloss\n");
+		return 1;
+	}
+	if (coevo_extra && !coevo) {
+		std::fprintf(stderr, "ERROR: --coevo-type, --coevo-metric, --coevo-method, --coevo-gain, --coevo-loss, --coevo-resolve, --coevo-min, --coevo-sign and --coevo-max need --coevo\n");
+		return 1;
+	}
 	Output o;
+	o.coevo = coevo, o.coevo_opt = coevo_opt;
 	o.gainloss = gainloss, o.gainloss_opt = gainloss_opt;
 	o.mantel = mantel, o.mantel_file = mantel_file, o.mantel_opt = mantel_opt;
 	o.permanova = permanova, o.permanova_type = permanova_type_v, o.permanova_metric = permanova_metric_v, o.permanova_perm = permanova_perm_v, o.permanova_seed = permanova_seed;

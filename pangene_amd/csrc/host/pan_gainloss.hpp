@@ -13,8 +13,10 @@ inline uint32_t item_bit(const uint32_t *bits, size_t W, int32_t a, int32_t i) {
 
 // The backend's step on the host, by the definition and over the tree itself (no program, no reordering): per item every node's
 // (C0, C1) bottom-up in join order, then the states top-down from the root, a join before its children.  bits[A][W], kid as pairs_tree
-// makes it; gene[M][4] = cost, gains, losses, root; node[2 A - 1][3] in node id order.  A >= 1
-void gainloss_host(const uint32_t *bits, int32_t M, int32_t A, const std::vector<int32_t> &kid, int32_t g, int32_t l, int32_t mode, int32_t *gene, int64_t *node)
+// makes it; gene[M][4] = cost, gains, losses, root; node[2 A - 1][3] in node id order.  A >= 1.  states: nullptr, or receives
+// states[M][2 A - 1], the state of every node per item (pan_coevo.hpp reads the events off it)
+void gainloss_host(const uint32_t *bits, int32_t M, int32_t A, const std::vector<int32_t> &kid, int32_t g, int32_t l, int32_t mode, int32_t *gene, int64_t *node,
+                   uint8_t *states = nullptr)
 {
 	const size_t W = ((size_t)M + 31) / 32, n_join = kid.size() / 2, n_node = (size_t)A + n_join;
 	std::vector<int32_t> C(2 * n_node);
@@ -54,6 +56,7 @@ void gainloss_host(const uint32_t *bits, int32_t M, int32_t A, const std::vector
 		}
 		int32_t *o = gene + 4 * (size_t)i;
 		o[0] = C[2 * root + state[root]], o[1] = gains, o[2] = losses, o[3] = state[root];
+		if (states != nullptr) std::copy(state.begin(), state.end(), states + (size_t)i * n_node);
 	}
 }
 
@@ -83,6 +86,32 @@ void item_counts(const uint32_t *bits, int32_t M, int32_t A, std::vector<int32_t
 
 double t_gainloss = 0; // seconds of the backend step (or the host loops) of the last command
 
+// The tree of kid as the backend sees it: the postfix program (op, order: pairs_program), the node every op makes (node_of) and the op of
+// its parent (par, -1 for the root); rows = the bit rows in push order.  Returns the stack entries the program needs.
+int32_t gainloss_program(const std::vector<uint32_t> &bits, size_t W, int32_t A, const std::vector<int32_t> &kid, std::vector<uint8_t> &op, std::vector<int32_t> &node_of,
+                         std::vector<int32_t> &par, std::vector<uint32_t> &rows)
+{
+	const size_t n_node = (size_t)A + kid.size() / 2;
+	std::vector<int32_t> order;
+	const int32_t need = pairs_program(kid, A, op, order);
+	std::vector<int32_t> up(n_node, -1);
+	for (size_t t = 0; t < kid.size() / 2; ++t) up[(size_t)kid[2 * t]] = up[(size_t)kid[2 * t + 1]] = A + (int32_t)t;
+	// the node each op makes, and the op of its parent: a join's node is the parent of the two it takes
+	std::vector<int32_t> op_of(n_node), made;
+	node_of.resize(op.size()), par.resize(op.size());
+	int32_t pushed = 0;
+	for (size_t k = 0; k < op.size(); ++k) {
+		int32_t v;
+		if (op[k] == 0) v = order[(size_t)pushed++];
+		else v = up[(size_t)made.back()], made.pop_back(), made.pop_back();
+		made.push_back(v), node_of[k] = v, op_of[(size_t)v] = (int32_t)k;
+	}
+	for (size_t k = 0; k < op.size(); ++k) par[k] = up[(size_t)node_of[k]] < 0 ? -1 : op_of[(size_t)up[(size_t)node_of[k]]];
+	rows.resize((size_t)A * W);
+	for (int32_t k = 0; k < A && W > 0; ++k) std::memcpy(rows.data() + (size_t)k * W, bits.data() + (size_t)order[(size_t)k] * W, sizeof(uint32_t) * W);
+	return need;
+}
+
 // bits[A][W] over M items, the tree of kid (pairs_tree): gene_out[M][5] = present, cost, gains, losses, root; node_out[2 A - 1][3] =
 // present, gains, losses in node id order (leaf x = x, join t = A + t).  A >= 1.  0 or a PGA_ERR_* code
 int gainloss_core(const std::vector<uint32_t> &bits, int32_t M, int32_t A, const std::vector<int32_t> &kid, int32_t g, int32_t l, int32_t mode, int32_t *gene_out,
@@ -98,22 +127,9 @@ int gainloss_core(const std::vector<uint32_t> &bits, int32_t M, int32_t A, const
 	std::vector<int32_t> gene_h;
 	if (be->pan_gainloss != nullptr) {
 		std::vector<uint8_t> op;
-		std::vector<int32_t> order;
-		if (pairs_program(kid, A, op, order) > GAINLOSS_DEPTH) return PGA_ERR_RANGE; // (out of reach below 65 536 leaves)
-		std::vector<int32_t> up(n_node, -1);
-		for (size_t t = 0; t < kid.size() / 2; ++t) up[(size_t)kid[2 * t]] = up[(size_t)kid[2 * t + 1]] = A + (int32_t)t;
-		// the node each op makes, and the op of its parent: a join's node is the parent of the two it takes
-		std::vector<int32_t> node_of(op.size()), op_of(n_node), par(op.size()), made;
-		int32_t pushed = 0;
-		for (size_t k = 0; k < op.size(); ++k) {
-			int32_t v;
-			if (op[k] == 0) v = order[(size_t)pushed++];
-			else v = up[(size_t)made.back()], made.pop_back(), made.pop_back();
-			made.push_back(v), node_of[k] = v, op_of[(size_t)v] = (int32_t)k;
-		}
-		for (size_t k = 0; k < op.size(); ++k) par[k] = up[(size_t)node_of[k]] < 0 ? -1 : op_of[(size_t)up[(size_t)node_of[k]]];
-		std::vector<uint32_t> rows((size_t)A * W);
-		for (int32_t k = 0; k < A && W > 0; ++k) std::memcpy(rows.data() + (size_t)k * W, bits.data() + (size_t)order[(size_t)k] * W, sizeof(uint32_t) * W);
+		std::vector<int32_t> node_of, par;
+		std::vector<uint32_t> rows;
+		if (gainloss_program(bits, W, A, kid, op, node_of, par, rows) > GAINLOSS_DEPTH) return PGA_ERR_RANGE; // (out of reach below 65 536 leaves)
 		const pga_gainloss_in_t in{op.data(), rows.data(), par.data(), M, A, g, l, mode, nullptr};
 		pga_gainloss_out_t res{};
 		const int rc = be->pan_gainloss(&in, &res);

@@ -6,6 +6,7 @@
 //   pan_permanova.hpp  pangene permanova
 //   pan_mantel.hpp     pangene mantel
 //   pan_gainloss.hpp   pangene gainloss (with pan_treeprog.hpp: the records as a tree and as the backend's program, shared with trait.cpp)
+//   pan_coevo.hpp      pangene coevo (the reconstruction and the program are pan_gainloss.hpp's)
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -24,3 +25,4 @@ using namespace pgx;
 #include "pan_permanova.hpp"
 #include "pan_mantel.hpp"
 #include "pan_gainloss.hpp"
+#include "pan_coevo.hpp"
