@@ -637,7 +637,10 @@ int     pg_shard_counts(const pg_data_t *d, int64_t *n_hit, int64_t *n_exon);
 
 /* pg_post_process / pg_graph_gen leave the per-hit FLAG fields of the host records (flt, shadow, rank, ...) on the
  * device until a writer needs them: pg_write_graph/pg_write_walk only fetch one flt bit per hit, pg_write_bed
- * fetches everything.  A caller that reads d->genome[j].hit[i] itself calls this first. */
+ * fetches everything.  A caller that reads d->genome[j].hit[i] itself calls this first.
+ * The same holds for what pg_post_process computes per protein and per gene -- d->prot[i].n / avg_score_adj /
+ * max_score_ori / rep and d->gene[i].rep_pid: between pg_post_process and the end of pg_graph_gen they may still hold
+ * the previous pass's values (or zeros); they are current after pg_graph_gen, after any writer, and after this call. */
 int pg_sync_host(pg_data_t *d);
 
 /* Tie-order policy (see DESIGN.md "bit-identity"): 0 canonical stable order everywhere; 1 (default,

@@ -94,7 +94,7 @@ typedef struct {
  * Device layout limits (PGA_ERR_RANGE otherwise): coordinates inside a block < 2^31 (contigs beyond that arrive as virtual contigs,
  * see pga_genome_block_t; what remains out of reach is a single cluster of overlapping hits spanning 2^30 bp), < 2^30 hits and < 2^31
  * exons per shard, < 2^20 genes, < 2^24 genomes. */
-#define PGA_ABI_VERSION 20u  /* bumped whenever a struct of this header or the order of pga_backend_t changes; pga_create refuses another */
+#define PGA_ABI_VERSION 21u /* bumped whenever a struct of this header or the order of pga_backend_t changes; pga_create refuses another */
 typedef struct {
 	uint32_t abi_version;        /* = PGA_ABI_VERSION of the header the caller was compiled against (PGA_ERR_ARG otherwise) */
 	int32_t n_genome;            /* genomes in this shard (may include genomes with 0 hits) */
@@ -685,6 +685,7 @@ typedef struct {
 	int  (*final_arcs)(pga_ctx_t *, const void **, int64_t *); /* may be NULL.  The final arc table of a branch_loop that ran with final_on: host view, count; 1 = not available */
 	int  (*pan_gainloss)(const pga_gainloss_in_t *, pga_gainloss_out_t *); /* may be NULL: the host driver then runs the same step itself */
 	int  (*pan_coevo)(const pga_coevo_in_t *, pga_coevo_out_t *); /* may be NULL: the host driver then runs the same step itself */
+	int  (*post_front)(pga_ctx_t *, double, int32_t, int32_t, const int32_t **); /* may be NULL: the host driver then computes the representatives itself and calls post_apply */
 } pga_backend_t;
 
 const pga_backend_t *pga_backend(void);
@@ -764,6 +765,17 @@ int pga_branch_loop(pga_ctx_t *ctx, int32_t n_round, const pga_branch_par_t *par
  * not return 0, PANGENE_LOOP=notail, the sharded form, or a table larger than the landing area (16 arcs per oriented vertex of the graph
  * the loop was entered with; PANGENE_FINAL_ARCS_CAP=n records) -- arc_table + the caller's own conversion is the general route. */
 int pga_final_arcs(pga_ctx_t *ctx, const void **host_view, int64_t *n_arc);
+
+/* pg_post_process's middle without the host: called right behind post_partials (a run that is not sharded: the sums are this shard's), it does what the driver
+ * otherwise does between a fetch of the sums and post_apply -- n and avg_score_adj of every protein, the representative of every gene (the protein with the largest
+ * key (sum score_adj << 32) + count, hit.c:205-217), the joint-pseudogene predicate of hit.c:176-181 with min_cnt = n_genome * min_vertex_ratio as the host computes
+ * it (joint_pseudo = 0: PG_F_NO_JOINT_PSEUDO) -- and then post_apply's own step.  Nothing is fetched, nothing uploaded, nobody waits.
+ * *host_view = page-locked words that hold, AFTER THE CALLER'S NEXT WAIT for the stream (a fetch, sync, vtx_partials, ...):
+ *   [0] != 0: some gene has two proteins at its largest key.  Which of them the reference takes depends on its unstable sort, which the backend does not replay: the
+ *       shard's state from post_apply on was computed with an arbitrary one of them, and the caller repeats the run from `begin` with its own representatives;
+ *   [16 ..): max_score_ori[n_prot], n[n_prot], avg_score_adj[n_prot], then rep_pid[n_gene] (-1: a gene without proteins).
+ * Valid until the context's next post_front. */
+int pga_post_front(pga_ctx_t *ctx, double min_cnt, int32_t joint_pseudo, int32_t drop_sgl_exon, const int32_t **host_view);
 
 /* Optional: run every kernel on this hipStream_t instead of the library's own stream (lets a host
  * framework order its collectives with the kernels without extra synchronisation). */

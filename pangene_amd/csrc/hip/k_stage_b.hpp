@@ -64,10 +64,57 @@ __global__ __launch_bounds__(PP_T) void k_post_part_lds(const uint32_t *flags, c
 		if (o1) atomicAdd(&sums[(int64_t)5 * P + p], o1);
 	}
 }
-__global__ __launch_bounds__(BLOCK) void k_post_count(unsigned long long *sums, int P)
+// gene_key (or NULL): per gene, the maximum of its proteins' keys (sum score_adj << 32) + count of hit.c:205-217 -- what k_post_rep picks the representative by
+__global__ __launch_bounds__(BLOCK) void k_post_count(unsigned long long *sums, int P, const int32_t *prot_gid = nullptr, int Q = 0, unsigned long long *gene_key = nullptr)
 {
 	const int p = blockIdx.x * BLOCK + threadIdx.x;
-	if (p < P) sums[(int64_t)P + p] = sums[(int64_t)2 * P + p] + sums[(int64_t)3 * P + p];
+	if (p >= P) return;
+	const unsigned long long cnt = sums[(int64_t)2 * P + p] + sums[(int64_t)3 * P + p];
+	sums[(int64_t)P + p] = cnt;
+	if (gene_key) {
+		const int g = prot_gid[p];
+		if (g >= 0 && g < Q) atomicMax(&gene_key[g], (sums[p] << 32) + cnt);
+	}
+}
+
+// pg_flag_representative's protein part (hit.c:205-217) and the per-protein predicate of the joint pseudogene call (hit.c:176-181) where the sums are: what the host
+// driver otherwise computes between a fetch of the six planes and an upload of two byte tables.  A gene's representative is the protein whose key is the gene's
+// maximum (k_post_count).  The reference takes the LAST of equal keys in the order its unstable sort leaves, which only a replay of that sort knows: two proteins of
+// one gene at the maximum set host[0] (page-locked, cleared by the caller), and the caller repeats the step on the host.  Everything the host wants of this step lands
+// in `host` as finished values: [0] tie flag, [16 ..) max_score_ori[P], n[P], avg_score_adj[P], then rep_pid[Q] (preset to -1 by the caller: a gene without proteins has none).
+struct PostFront {
+	const unsigned long long *sums; const int32_t *max_ori, *prot_gid; int P, Q;
+	double min_cnt;        // n_genome * min_vertex_ratio, as the host computes it
+	int joint_pseudo, drop_sgl_exon;
+	const unsigned long long *gene_key; int32_t *gene_rep1 /* [Q], zero: representative + 1 */;
+	uint8_t *rep, *pj;     // [P] each: what k_post_apply reads
+	int32_t *host;
+};
+__global__ __launch_bounds__(BLOCK) void k_post_rep(PostFront a)
+{
+	const int p = blockIdx.x * BLOCK + threadIdx.x;
+	if (p >= a.P) return;
+	const int64_t P = a.P;
+	const unsigned long long key = (a.sums[p] << 32) + a.sums[P + p];
+	const int32_t n = (int32_t)(uint32_t)key;
+	const int32_t avg = n ? cvt_i32_x86((double)(key >> 32) / n + .499) : 0;
+	const int g = a.prot_gid[p];
+	bool is_rep = false;
+	if (g >= 0 && g < a.Q && key == a.gene_key[g]) {
+		is_rep = atomicCAS(&a.gene_rep1[g], 0, p + 1) == 0;
+		if (is_rep) a.host[16 + 3 * P + g] = p;
+		else sys_store(&a.host[0], 1);
+	}
+	bool pj = false;
+	if (a.joint_pseudo) { // (doubles, no contraction: a zero count gives inf or NaN, which compare false)
+		const int32_t ic0 = (int32_t)(long long)a.sums[2 * P + p], ic1 = (int32_t)(long long)a.sums[3 * P + p];
+		const long long s0 = (long long)a.sums[4 * P + p], s1 = (long long)a.sums[5 * P + p];
+		const bool x = ic1 > 0 && (double)ic1 >= a.min_cnt && ((double)s1 / (double)ic1) / ((double)s0 / (double)ic0) >= 0.99;
+		const bool y = (ic1 == 0 || (double)ic1 <= a.min_cnt) && a.drop_sgl_exon;
+		pj = x || y;
+	}
+	a.rep[p] = is_rep, a.pj[p] = pj;
+	a.host[16 + p] = a.max_ori[p], a.host[16 + P + p] = n, a.host[16 + 2 * P + p] = avg;
 }
 
 __global__ __launch_bounds__(BLOCK) void k_post_apply(uint32_t *flags, const int32_t *pid, const int32_t *nex, int32_t *sdom, int n,

@@ -13,7 +13,8 @@
 // still sit in the L2 of the XCD that wrote it.  (A doorbell written by a last tiny kernel and polled by the host was faster
 // still and WRONG for exactly that reason: its fence covers the L2 of one XCD; one run in a few hundred read stale counters.)
 // PANGENE_WAIT=sync selects the plain blocking call.
-static int sync_st(pga_ctx *c)
+// poll_us: how long to poll before parking (the vertex step's wait, which covers stage B too since pga_post_front, polls longer: pga_vtx_partials)
+static int sync_st(pga_ctx *c, double poll_us = 200.0)
 {
 	static const bool poll = [] { const char *e = getenv("PANGENE_WAIT"); return !(e && strcmp(e, "sync") == 0); }();
 	++c->sync_epoch;
@@ -27,7 +28,7 @@ static int sync_st(pga_ctx *c)
 			__builtin_ia32_pause();
 			if ((it & 0x3f) == 0) {
 				timespec t; clock_gettime(CLOCK_MONOTONIC, &t);
-				if ((t.tv_sec - t0.tv_sec) + (t.tv_nsec - t0.tv_nsec) * 1e-9 > 200e-6) break;
+				if ((t.tv_sec - t0.tv_sec) + (t.tv_nsec - t0.tv_nsec) * 1e-9 > poll_us * 1e-6) break;
 			}
 		}
 	}

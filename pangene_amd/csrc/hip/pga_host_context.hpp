@@ -149,7 +149,7 @@ struct PinArena {
 enum { // pool slots
 	S_KEY_A, S_KEY_B, S_VAL_A, S_VAL_B, S_TABLE, S_TILE, S_I32_A, S_I32_B, S_I32_C, S_TAB_A, S_TAB_B, S_TAB_C, S_TAB_D,
 	S_TDIST, S_TS1, S_TS2, S_TGEN, S_SDIST, S_SS1, S_SS2, S_SGEN, S_HEAD, S_SLOT, S_ARCS, S_SEGCNT, S_BITS, S_TRIPLES,
-	S_WALK_VAL, S_WALK_PREV, S_PERM, S_OVPOS, S_OVFILE, S_RUNSTART, S_CDN, S_MG_KEY, S_MG_VAL, S_MG_SRC, S_MG_OUT, S_MG_HEAD, S_MG_SLOT, S_MG_RUN, S_BR_S1, S_BR_GID, S_BR_VS, S_BR_VE, S_BR_PC, S_BR_POFF, S_BR_GRP, S_BR_NDL, S_BR_SEGGID, S_PAIRS, S_NLCNT, S_ARCX, S_ARCW, S_WEAKNEW, S_RP_SEG, S_RP_R, S_RP_CM, S_RP_POS, S_RP_IV, S_DL, S_SCRATCH, S_UPLOAD, S_RAW, S_ARC_STAGE, S_GMETA, S_GOFF, S_DEG, S_BIGLIST, S_STAGE_SID, S_STATS, S_G2S, S_MISC, S_SLOW, S_HZLIST, S_VWK, S_XG_BUF, S_XG_OUT, S_XG_OUT2, S_XSTAT, S_GSLIST, S_UPLOAD2, S_BINS, S_FIN_ID,
+	S_WALK_VAL, S_WALK_PREV, S_PERM, S_OVPOS, S_OVFILE, S_RUNSTART, S_CDN, S_MG_KEY, S_MG_VAL, S_MG_SRC, S_MG_OUT, S_MG_HEAD, S_MG_SLOT, S_MG_RUN, S_BR_S1, S_BR_GID, S_BR_VS, S_BR_VE, S_BR_PC, S_BR_POFF, S_BR_GRP, S_BR_NDL, S_BR_SEGGID, S_PAIRS, S_NLCNT, S_ARCX, S_ARCW, S_WEAKNEW, S_RP_SEG, S_RP_R, S_RP_CM, S_RP_POS, S_RP_IV, S_DL, S_SCRATCH, S_UPLOAD, S_RAW, S_ARC_STAGE, S_GMETA, S_GOFF, S_DEG, S_BIGLIST, S_STAGE_SID, S_STATS, S_G2S, S_MISC, S_SLOW, S_HZLIST, S_VWK, S_XG_BUF, S_XG_OUT, S_XG_OUT2, S_XSTAT, S_GSLIST, S_UPLOAD2, S_BINS, S_FIN_ID, S_FRONT,
 	S_COUNT
 };
 
@@ -203,6 +203,10 @@ struct pga_ctx {
 	int64_t *h_box = 0;     // the same memory as the device sees it
 	void *h_stage = nullptr; size_t h_stage_cap = 0; // pinned landing area of fetch_later
 	void *h_fetch = nullptr; size_t h_fetch_cap = 0; // pinned landing area of pga_fetch
+	int32_t *h_front = nullptr; size_t h_front_cap = 0; // pinned: what pga_post_front leaves for the host (k_post_rep writes it; cap in words)
+	bool front_keys_on = true, front_keys_done = false; // pga_post_partials prepares the genes' keys for a pga_post_front (the context's last pg_post_process took one, or none has run); it did so in this pass
+	bool front_live = false; unsigned long long front_epoch = 0; // ... queued at this sync_epoch: until somebody has waited for the stream the area is the device's
+	size_t lds_post_set = 0, lds_vtx_set = 0; // dynamic LDS k_post_part_lds / k_vtx1_lds have been allowed on this context's device
 	int32_t *h_g2s = nullptr; size_t h_g2s_cap = 0; hipEvent_t g2s_done = nullptr; // pinned staging of flag_vtx's gene -> segment map
 	DevPool pool; PinArena pin;
 	bool walk_valid = false; // S_WALK_VAL / S_WALK_PREV match the current flags and cm order

@@ -192,3 +192,31 @@ extern "C" int pga_selftest_arc_final(const pga_arc_part_t *in, int64_t n, int32
 	(void)hipFree(di); (void)hipFree(dout);
 	return 0;
 }
+
+// k_post_count + k_post_rep (k_stage_b.hpp) on given protein sums, without a context (tests/test_front_gpu.py): sums[6 P] as pga_post_partials leaves them
+// BEFORE k_post_count (plane 1 is overwritten), words[16 + 3 P + Q] / rep[P] / pj[P] as pga_post_front leaves them
+extern "C" int pga_selftest_post_rep(const int64_t *sums, const int32_t *max_ori, const int32_t *prot_gid, int32_t P, int32_t Q, double min_cnt, int32_t joint_pseudo, int32_t drop_sgl_exon,
+                                     int32_t *words, uint8_t *rep, uint8_t *pj)
+{
+	int ndev = 0;
+	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return PGA_ERR_NO_DEVICE;
+	if (P <= 0 || Q <= 0 || !sums || !max_ori || !prot_gid || !words || !rep || !pj) return PGA_ERR_ARG;
+	const size_t nw = 16 + 3 * (size_t)P + (size_t)Q;
+	unsigned long long *d_sums, *d_key; int32_t *d_mx, *d_gid, *d_rep1, *d_words; uint8_t *d_rep;
+	HIPCHK(hipMalloc((void **)&d_sums, sizeof(int64_t) * 6 * (size_t)P)); HIPCHK(hipMalloc((void **)&d_key, sizeof(int64_t) * (size_t)Q));
+	HIPCHK(hipMalloc((void **)&d_mx, sizeof(int32_t) * (size_t)P)); HIPCHK(hipMalloc((void **)&d_gid, sizeof(int32_t) * (size_t)P));
+	HIPCHK(hipMalloc((void **)&d_rep1, sizeof(int32_t) * (size_t)Q));
+	HIPCHK(hipMalloc((void **)&d_words, sizeof(int32_t) * nw)); HIPCHK(hipMalloc((void **)&d_rep, 2 * (size_t)P));
+	HIPCHK(hipMemcpy(d_sums, sums, sizeof(int64_t) * 6 * (size_t)P, hipMemcpyHostToDevice));
+	HIPCHK(hipMemcpy(d_mx, max_ori, sizeof(int32_t) * (size_t)P, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d_gid, prot_gid, sizeof(int32_t) * (size_t)P, hipMemcpyHostToDevice));
+	HIPCHK(hipMemset(d_key, 0, sizeof(int64_t) * (size_t)Q)); HIPCHK(hipMemset(d_rep1, 0, sizeof(int32_t) * (size_t)Q));
+	HIPCHK(hipMemset(d_words, 0, sizeof(int32_t) * 16)); HIPCHK(hipMemset(d_words + 16, 0xff, sizeof(int32_t) * (nw - 16)));
+	hipLaunchKernelGGL(k_post_count, dim3(nblk(P)), dim3(BLOCK), 0, 0, d_sums, P, (const int32_t *)d_gid, Q, d_key);
+	PostFront a = { d_sums, d_mx, d_gid, P, Q, min_cnt, joint_pseudo ? 1 : 0, drop_sgl_exon ? 1 : 0, d_key, d_rep1, d_rep, d_rep + P, d_words };
+	hipLaunchKernelGGL(k_post_rep, dim3(nblk(P)), dim3(BLOCK), 0, 0, a);
+	HIPCHK(hipDeviceSynchronize());
+	HIPCHK(hipMemcpy(words, d_words, sizeof(int32_t) * nw, hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(rep, d_rep, (size_t)P, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(pj, d_rep + P, (size_t)P, hipMemcpyDeviceToHost));
+	(void)hipFree(d_sums); (void)hipFree(d_key); (void)hipFree(d_mx); (void)hipFree(d_gid); (void)hipFree(d_rep1); (void)hipFree(d_words); (void)hipFree(d_rep);
+	return 0;
+}

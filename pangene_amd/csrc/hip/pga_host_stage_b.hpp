@@ -3,9 +3,28 @@
 #pragma once
 
 
+// the tables of pga_post_front: per gene the largest key of its proteins and the representative (+ 1); per protein the two bytes k_post_apply reads
+struct FrontTabs { unsigned long long *gene_key; int32_t *gene_rep1; uint8_t *rep, *pj; };
+static bool front_tabs(pga_ctx *c, FrontTabs *t)
+{
+	const size_t Q = (size_t)std::max(1, c->Q), P = (size_t)std::max(1, c->P);
+	char *b = (char *)c->pool.get(S_FRONT, 12 * Q + 2 * P + 64);
+	if (!b) return false;
+	t->gene_key = (unsigned long long *)b, t->gene_rep1 = (int32_t *)(b + 8 * Q), t->rep = (uint8_t *)(b + 12 * Q), t->pj = t->rep + P;
+	return true;
+}
+
 extern "C" int pga_post_partials(pga_ctx_t *c, int32_t **max_ori, int64_t **sums)
 {
-	zero_multi(c, c->max_ori, sizeof(int32_t) * (size_t)std::max(1, c->P), c->sums, sizeof(int64_t) * 6 * (size_t)std::max(1, c->P));
+	FrontTabs ft;
+	if (!front_tabs(c, &ft)) return PGA_ERR_NOMEM;
+	// The genes' largest keys (what pga_post_front picks the representatives by) ride with this call's clear and with k_post_count -- where a post_front is to be
+	// expected: a context whose last pg_post_process went on with post_apply instead (a sharded run, PANGENE_FRONT=host, a data set with tied isoforms, a verbose
+	// log) leaves them out, and a post_front that comes all the same makes up for it (front_keys)
+	const bool keys = c->front_keys_on;
+	c->front_keys_done = keys;
+	zero_multi(c, c->max_ori, sizeof(int32_t) * (size_t)std::max(1, c->P), c->sums, sizeof(int64_t) * 6 * (size_t)std::max(1, c->P),
+	           keys ? ft.gene_key : nullptr, keys ? 12 * (size_t)std::max(1, c->Q) : 0); // (gene_key and gene_rep1 lie side by side)
 	// (round 6) the sums through LDS where the proteins fit in one or two ranges and a workgroup's stretch is long enough to hold several genomes
 	static const bool pp_atomics = env_has("PANGENE_POST", "atomics"); // (tests: the one-atomic-a-contribution form on every shard)
 	static const bool pp_force = env_has("PANGENE_POST", "lds");       // (tests: the LDS form on small shards too)
@@ -16,20 +35,21 @@ extern "C" int pga_post_partials(pga_ctx_t *c, int32_t **max_ori, int64_t **sums
 		if (p_tiles) {
 			const int PT = (c->P + p_tiles - 1) / p_tiles;
 			const size_t lds = (size_t)PT * 28 + 16;
-			static size_t lds_set = 0;
-			bool ok = true;
-			if (lds > lds_set) { ok = hipFuncSetAttribute(reinterpret_cast<const void *>(k_post_part_lds), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess; if (ok) lds_set = lds; else (void)hipGetLastError(); }
+			bool ok = true; // (the attribute belongs to the device the context runs on: kept per context, and a launch that is refused leaves the step to k_post_part)
+			if (lds > c->lds_post_set) { ok = hipFuncSetAttribute(reinterpret_cast<const void *>(k_post_part_lds), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess; if (ok) c->lds_post_set = lds; else (void)hipGetLastError(); }
 			if (ok) {
 				const int n_chunk = (int)std::max<int64_t>(1, std::min<int64_t>(c->n_cu, c->N / 32768)); // (a stretch of >= 32 k hits: the reduction is what the launch is for)
+				(void)hipGetLastError(); // (what is read below is this launch's)
 				hipLaunchKernelGGL(k_post_part_lds, dim3((unsigned)(n_chunk * p_tiles)), dim3(PP_T), lds, c->st, c->flags, c->pid, c->rank, c->sori, c->sadj, c->nex, c->N, c->P, p_tiles, PT,
 				                   c->max_ori, (unsigned long long *)c->sums);
-				lds_done = true;
+				lds_done = hipGetLastError() == hipSuccess;
+				if (!lds_done) c->lds_post_set = 0;
 			}
 		}
 	}
 	if (c->N && !lds_done) hipLaunchKernelGGL(k_post_part, dim3(nblk(c->N)), dim3(BLOCK), 0, c->st, c->flags, c->pid, c->rank, c->sori, c->sadj, c->nex, c->N, c->P,
 	                             c->max_ori, (unsigned long long *)c->sums);
-	if (c->N && c->P) hipLaunchKernelGGL(k_post_count, dim3(nblk(c->P)), dim3(BLOCK), 0, c->st, (unsigned long long *)c->sums, c->P);
+	if (c->N && c->P) hipLaunchKernelGGL(k_post_count, dim3(nblk(c->P)), dim3(BLOCK), 0, c->st, (unsigned long long *)c->sums, c->P, (const int32_t *)c->prot_gid, c->Q, keys ? ft.gene_key : (unsigned long long *)nullptr);
 	*max_ori = c->max_ori, *sums = c->sums;
 	return 0; // no wait: a consumer that is not on this stream calls pga_sync first
 }
@@ -37,6 +57,7 @@ extern "C" int pga_post_partials(pga_ctx_t *c, int32_t **max_ori, int64_t **sums
 extern "C" int pga_post_apply(pga_ctx_t *c, const uint8_t *prot_rep, const uint8_t *prot_pj, int64_t *n_pseudo)
 {
 	c->yrec_valid = false, c->wrec_valid = false;
+	c->front_keys_on = false; // (the caller picked the representatives itself: the next pga_post_partials need not prepare for a post_front)
 	uint8_t *d = (uint8_t *)c->pool.get(S_MISC, 2 * (size_t)c->P + 16);
 	if (!d) return PGA_ERR_NOMEM;
 	c->walk_valid = false, c->ha_valid = false;
@@ -49,6 +70,38 @@ extern "C" int pga_post_apply(pga_ctx_t *c, const uint8_t *prot_rep, const uint8
 		*n_pseudo = c->h_cnt[2];
 	}
 	return 0;
+}
+
+// pga_post_apply without the host in front of it (include/pangene_hip.h): behind pga_post_partials on the same stream, nothing in between that touches the sums
+extern "C" int pga_post_front(pga_ctx_t *c, double min_cnt, int32_t joint_pseudo, int32_t drop_sgl_exon, const int32_t **host_view)
+{
+	FrontTabs ft;
+	if (host_view == nullptr) return PGA_ERR_ARG;
+	if (!front_tabs(c, &ft)) return PGA_ERR_NOMEM;
+	const size_t P = (size_t)c->P, Q = (size_t)c->Q, words = 16 + 3 * P + Q;
+	if (c->front_live && c->front_epoch == c->sync_epoch) TRY(sync_st(c)); // nobody has waited since the last one was queued: the area is still the device's
+	if (c->h_front_cap < words) {
+		c->h_front = (int32_t *)c->pin.get(sizeof(int32_t) * (words + words / 2) + 256); // (the old piece stays in the arena)
+		if (!c->h_front) { c->h_front_cap = 0; return PGA_ERR_NOMEM; }
+		c->h_front_cap = words + words / 2;
+	}
+	memset(c->h_front, 0, sizeof(int32_t) * 16);
+	if (Q) memset(c->h_front + 16 + 3 * P, 0xff, sizeof(int32_t) * Q); // rep_pid = -1
+	int32_t *hd = nullptr;
+	HIPCHK(hipHostGetDevicePointer((void **)&hd, c->h_front, 0));
+	c->yrec_valid = false, c->wrec_valid = false, c->walk_valid = false, c->ha_valid = false; // (as pga_post_apply)
+	if (!c->front_keys_done) { // pga_post_partials did not expect this call: the genes' keys now (k_post_count once more -- it writes the counts it wrote before)
+		zero_multi(c, ft.gene_key, 12 * (size_t)std::max(1, c->Q));
+		if (c->N && c->P) hipLaunchKernelGGL(k_post_count, dim3(nblk(c->P)), dim3(BLOCK), 0, c->st, (unsigned long long *)c->sums, c->P, (const int32_t *)c->prot_gid, c->Q, ft.gene_key);
+		c->front_keys_done = true;
+	}
+	c->front_keys_on = true;
+	PostFront a = { (const unsigned long long *)c->sums, c->max_ori, c->prot_gid, c->P, c->Q, min_cnt, joint_pseudo ? 1 : 0, drop_sgl_exon ? 1 : 0, ft.gene_key, ft.gene_rep1, ft.rep, ft.pj, hd };
+	if (c->P) hipLaunchKernelGGL(k_post_rep, dim3(nblk(c->P)), dim3(BLOCK), 0, c->st, a);
+	if (c->N) hipLaunchKernelGGL(k_post_apply, dim3(nblk(c->N)), dim3(BLOCK), 0, c->st, c->flags, c->pid, c->nex, c->sdom, c->N, c->max_ori, (const uint8_t *)ft.rep, (const uint8_t *)ft.pj, (int64_t *)nullptr);
+	c->front_live = true, c->front_epoch = c->sync_epoch;
+	*host_view = c->h_front;
+	return 0; // no wait: the view holds what it promises after the caller's next wait for the stream
 }
 
 extern "C" int pga_shadow(pga_ctx_t *c, int32_t cal_dom_sc, int32_t *stats)
@@ -109,13 +162,16 @@ extern "C" int pga_vtx_partials(pga_ctx_t *c, int32_t **cnt, uint64_t **records,
 		{ // (round 6) the genes' counts through LDS on shards whose stretches hold several genomes (PANGENE_POST=atomics / lds as for k_post_part_lds)
 			static const bool vx_atomics = env_has("PANGENE_POST", "atomics"), vx_force = env_has("PANGENE_POST", "lds");
 			const size_t lds = sizeof(int) * 2 * (size_t)std::max(1, Q);
-			static size_t lds_set = 0;
-			bool ok = !vx_atomics && (N >= (1 << 19) || vx_force) && lds <= ((size_t)144 << 10);
-			if (ok && lds > lds_set) { ok = hipFuncSetAttribute(reinterpret_cast<const void *>(k_vtx1_lds), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess; if (ok) lds_set = lds; else (void)hipGetLastError(); }
+			bool ok = !vx_atomics && (N >= (1 << 19) || vx_force) && lds <= ((size_t)144 << 10); // (the attribute per context and the launch checked, as in pga_post_partials)
+			if (ok && lds > c->lds_vtx_set) { ok = hipFuncSetAttribute(reinterpret_cast<const void *>(k_vtx1_lds), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess; if (ok) c->lds_vtx_set = lds; else (void)hipGetLastError(); }
 			if (ok) {
 				const int n_chunk = (int)std::max<int64_t>(1, std::min<int64_t>(2 * c->n_cu, N / 32768));
+				(void)hipGetLastError(); // (what is read below is this launch's)
 				hipLaunchKernelGGL(k_vtx1_lds, dim3((unsigned)n_chunk), dim3(VX_T), lds, c->st, c->flags, c->gnm, c->gid, c->rank, c->pdom, N, Q, c->vtx_cnt, bits, wpg, c->dcnt, c->live_cnt);
-			} else
+				ok = hipGetLastError() == hipSuccess;
+				if (!ok) c->lds_vtx_set = 0;
+			}
+			if (!ok)
 			hipLaunchKernelGGL(k_vtx1, dim3(nblk(N)), dim3(BLOCK), 0, c->st, c->flags, c->gnm, c->gid, c->rank, c->pdom, N, Q, c->vtx_cnt, bits, wpg, c->dcnt, c->live_cnt);
 		}
 		hipLaunchKernelGGL(k_live_sum, dim3(1), dim3(BLOCK), 0, c->st, (const int64_t *)c->live_cnt, c->dcnt);
@@ -125,7 +181,11 @@ extern "C" int pga_vtx_partials(pga_ctx_t *c, int32_t **cnt, uint64_t **records,
 		if (!tile) return PGA_ERR_NOMEM;
 		device_scan<I32>(InDomSet{dom_tab}, OutExclI32{slot}, n_slot, tile, OpSum{}, I32{0}, c->st);
 		hipLaunchKernelGGL(k_vtx_compact, dim3(nblk(n_slot)), dim3(BLOCK), 0, c->st, dom_tab, slot, n_slot, pbits, nw, rec, c->dcnt, c->h_box);
-		TRY(sync_st(c));
+		// Behind a pga_post_front that nobody has waited for since, this is the first wait since stage A was queued: 0.7 ms at configs[1] where the two waits it replaces
+		// took 0.4 each, so it polls for up to 1 ms before it parks.  (Some bench processes spend 0.35 ms a pass longer in the vertex step on the device route, for a
+		// reason that is not known; with the longer poll it was 2 of 8 processes, without it 4 of 8 in the same session, 9 of 21 over two: DESIGN section 9, "slow mode".)
+		const bool behind_front = c->front_live && c->front_epoch == c->sync_epoch;
+		TRY(sync_st(c, behind_front ? 1000.0 : 200.0));
 		if (c->h_cnt[3]) return PGA_ERR_INVARIANT;
 		c->live_hint = c->h_cnt[8];
 		const int64_t n_rec = c->h_cnt[10], n_ovf = c->h_cnt[0];

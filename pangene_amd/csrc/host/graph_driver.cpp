@@ -629,10 +629,12 @@ static int build_backend(const pg_opt_t *opt, pg_data_t *d, DataExt *ext)
 //                 records are neither moved nor refreshed: pg_write_walk reaches them through the file index.
 //   full = true : every per-hit field of the host records, and the records themselves put into cs order, which is how the
 //                 reference leaves them (hit.c:57-63 replaces g->hit on every sort; the BED writers print in array order).
+static int front_settle(pg_data_t *d, DataExt *ext);
 int sync_host(pg_data_t *d, bool full)
 {
 	DataExt *ext = ext_of(d, false);
 	if (ext == nullptr || ext->ctx == nullptr) return g_err;
+	if (front_settle(d, ext) != 0) return g_err; // (the protein and gene fields of a pg_post_process nobody has waited for; a tie repeats it before the state is read)
 	if (!ext->host_stale && !(full && !ext->host_full)) return g_err;
 	Phase ph(PH_SYNC_HOST);
 	const int64_t N = ext->n_hit_local;
@@ -806,6 +808,42 @@ static bool exact_early(const DataExt *ext)
 // ---------------------------------------------------------------------------------------------
 // stage A + B
 // ---------------------------------------------------------------------------------------------
+static int post_host_step(const pg_opt_t *opt, pg_data_t *d, DataExt *ext, int32_t *b_max, int64_t *b_sum);
+static int post_process_impl(const pg_opt_t *opt, pg_data_t *d);
+
+// What the backend's post_front left for the host, into d->prot / d->gene.  The caller has waited for the stream since pg_post_process.
+// Returns 1 when a gene has two proteins at its largest key: the representative the backend took is not necessarily the reference's, nothing is
+// copied, the data set keeps the host route from now on and the caller repeats the run from stage A.
+static int front_fill(pg_data_t *d, DataExt *ext)
+{
+	ext->front_pending = false;
+	const int32_t *v = ext->front_view;
+	const size_t P = (size_t)d->n_prot;
+	if (v[0] != 0) {
+		ext->front_host = true;
+		if (std::getenv("PANGENE_TIMING")) std::fprintf(stderr, "[front] two proteins of a gene share its largest key: pg_post_process again, representatives on the host\n");
+		return 1;
+	}
+	const int32_t *mx = v + 16, *n = mx + P, *avg = n + P, *rep = avg + P;
+	for (size_t i = 0; i < P; ++i) d->prot[i].max_score_ori = mx[i], d->prot[i].n = n[i], d->prot[i].avg_score_adj = avg[i], d->prot[i].rep = 0;
+	for (int32_t g = 0; g < d->n_gene; ++g) {
+		d->gene[g].rep_pid = rep[g];
+		if (rep[g] >= 0) d->prot[rep[g]].rep = 1;
+	}
+	return 0;
+}
+
+// for whoever reads those fields, or the per-hit state, before pg_graph_gen has (sync_host): wait, copy, and on a tie pg_post_process once more
+static int front_settle(pg_data_t *d, DataExt *ext)
+{
+	if (!ext->front_pending) return 0;
+	BE_CALL(ext->be->sync(ext->ctx), "sync");
+	if (front_fill(d, ext) == 0) return 0;
+	const pg_opt_t opt = ext->front_opt;
+	ext->rerun = true;
+	return post_process_impl(&opt, d);
+}
+
 static int post_process_impl(const pg_opt_t *opt, pg_data_t *d)
 {
 	DataExt *ext = ext_of(d, true);
@@ -871,6 +909,38 @@ static int post_process_impl(const pg_opt_t *opt, pg_data_t *d)
 	BE_CALL(be->post_partials(ctx, &b_max, &b_sum), "post_partials");
 	BE_CALL(xreduce(be, ext->ctx, b_max, P, PG_X_I32, PG_X_MAX), "allreduce(max_score_ori)");
 	BE_CALL(xreduce(be, ext->ctx, b_sum, 6 * (int64_t)P, PG_X_I64, PG_X_SUM), "allreduce(protein sums)");
+	// The representatives and the joint-pseudo predicate where the sums are (the backend's post_front: no fetch, no upload, no wait), or on the host
+	// (post_host_step, the general route).  The host keeps the step when the sums were reduced across ranks, when the log wants the number of
+	// pseudogene hits, and on a data set where a gene has two proteins at its largest key (front_host: see front_fill).  PANGENE_FRONT=host: always.
+	ext->front_pending = false;
+	static const bool front_env_host = env_word("PANGENE_FRONT", "host");
+	const char *why_host = be->post_front == nullptr ? "the backend has no post_front" : front_env_host ? "PANGENE_FRONT=host" : sharded() ? "the sums are reduced across ranks"
+	                     : pg_verbose >= 3 ? "the log counts the pseudogene hits" : ext->front_host ? "a gene of this data set has two proteins at its largest key" : nullptr;
+	if (std::getenv("PANGENE_TIMING")) std::fprintf(stderr, "[front] pg_post_process: representatives on the %s%s%s\n", why_host ? "host: " : "device", why_host ? why_host : "", why_host ? "" : " (nothing fetched, no wait)");
+	if (why_host == nullptr) {
+		BE_CALL(be->post_front(ctx, d->n_genome * opt->min_vertex_ratio, !(opt->flag & PG_F_NO_JOINT_PSEUDO), !!(opt->flag & PG_F_DROP_SGL_EXON), &ext->front_view), "post_front");
+		ext->front_pending = true, ext->front_opt = *opt;
+	} else BE_CALL(post_host_step(opt, d, ext, b_max, b_sum), "post_apply");
+	std::vector<int32_t> st2((size_t)nl * 2);
+	BE_CALL(be->shadow(ctx, 0, pg_verbose >= 3 ? st2.data() : nullptr), "shadow"); // graph.c:20-28
+	if (pg_verbose >= 3)
+		for (int32_t k = 0; k < nl; ++k) {
+			const pg_genome_t *g = &d->genome[ext->local_genomes[(size_t)k]];
+			std::fprintf(stderr, "[M::%s::%s] genome[%d]: %s; %d hits remain, of which %d are shadowed\n", __func__, stamp(),
+			             ext->local_genomes[(size_t)k], g->label ? g->label : "-", st2[(size_t)k*2], st2[(size_t)k*2+1]);
+		}
+	ext->host_stale = true;
+	BE_CALL(trace_state(ext, "post_process", 0), "trace");
+	return 0;
+}
+
+// the host's part of pg_post_process between the protein sums and post_apply: pg_cap_score_dom's table, pg_flag_representative's protein part with the
+// reference's unstable sort replayed, the joint-pseudo predicate (the general route: see post_process_impl)
+static int post_host_step(const pg_opt_t *opt, pg_data_t *d, DataExt *ext, int32_t *b_max, int64_t *b_sum)
+{
+	const pga_backend_t *be = ext->be;
+	pga_ctx_t *ctx = ext->ctx;
+	const int32_t P = d->n_prot;
 	static thread_local std::vector<int32_t> mx; // (reused from pass to pass, as gen_vtx's)
 	static thread_local std::vector<int64_t> sm;
 	mx.resize((size_t)P), sm.resize((size_t)P * 6);
@@ -917,17 +987,7 @@ static int post_process_impl(const pg_opt_t *opt, pg_data_t *d)
 	int64_t n_pj = 0;
 	BE_CALL(be->post_apply(ctx, rep.data(), pj.data(), (!(opt->flag & PG_F_NO_JOINT_PSEUDO) && pg_verbose >= 3) ? &n_pj : nullptr), "post_apply");
 	if (!(opt->flag & PG_F_NO_JOINT_PSEUDO) && pg_verbose >= 3)
-		std::fprintf(stderr, "[M::%s::%s] %ld pseudogene hits identified jointly\n", __func__, stamp(), (long)n_pj);
-	std::vector<int32_t> st2((size_t)nl * 2);
-	BE_CALL(be->shadow(ctx, 0, pg_verbose >= 3 ? st2.data() : nullptr), "shadow"); // graph.c:20-28
-	if (pg_verbose >= 3)
-		for (int32_t k = 0; k < nl; ++k) {
-			const pg_genome_t *g = &d->genome[ext->local_genomes[(size_t)k]];
-			std::fprintf(stderr, "[M::%s::%s] genome[%d]: %s; %d hits remain, of which %d are shadowed\n", __func__, stamp(),
-			             ext->local_genomes[(size_t)k], g->label ? g->label : "-", st2[(size_t)k*2], st2[(size_t)k*2+1]);
-		}
-	ext->host_stale = true;
-	BE_CALL(trace_state(ext, "post_process", 0), "trace");
+		std::fprintf(stderr, "[M::%s::%s] %ld pseudogene hits identified jointly\n", "post_process_impl", stamp(), (long)n_pj);
 	return 0;
 }
 
@@ -954,6 +1014,7 @@ static void arc_index(pg_graph_t *q) // graph.c:202-217
 
 // pg_gen_vtx (vertex.c:6-100): counts and sub->dom triples come from the backend, the order-sensitive
 // greedy stays here
+enum { RC_FRONT_TIE = 1001 }; // not an error: front_fill found a tie, pg_graph_gen repeats the run from stage A with the host's representatives
 static int gen_vtx(const pg_opt_t *opt, pg_graph_t *q, DataExt *ext)
 {
 	pg_data_t *d = q->d;
@@ -963,6 +1024,7 @@ static int gen_vtx(const pg_opt_t *opt, pg_graph_t *q, DataExt *ext)
 	int32_t *b_cnt; uint64_t *b_tri; int64_t n_tri;
 	const double tv0 = now_sec();
 	BE_CALL(be->vtx_partials(ext->ctx, &b_cnt, &b_tri, &n_tri), "vtx_partials");
+	if (ext->front_pending && front_fill(d, ext) != 0) return RC_FRONT_TIE; // (vtx_partials has waited for the stream: pg_post_process's protein and gene fields are there)
 	const double tv1 = now_sec();
 	BE_CALL(xreduce(be, ext->ctx, b_cnt, 2 * (int64_t)Q, PG_X_I32, PG_X_SUM), "allreduce(n_dom,n_sub)");
 	static thread_local std::vector<int32_t> cntv; // (these buffers are reused from pass to pass: fresh vectors of a few hundred KB are mmap'ed and page-faulted every time, ~0.1 ms of a 4.6 ms pass)
@@ -1053,9 +1115,11 @@ static int gen_vtx(const pg_opt_t *opt, pg_graph_t *q, DataExt *ext)
 	if (std::getenv("PANGENE_TIMING")) std::fprintf(stderr, "[vtx] partials %.3f ms, fetch %.3f ms (records %ld / %ld), greedy %.3f ms\n", (tv1 - tv0) * 1e3, (tv2 - tv1) * 1e3, (long)n_tri, (long)n_rec, (now_sec() - tv2) * 1e3);
 	// segments by gene id (vertex.c:85-94; keys unique, any sort gives the reference's order)
 	{ // (gene ids are unique and < Q: one placement pass instead of a comparison sort)
-		std::vector<int32_t> at((size_t)Q, -1);
+		static thread_local std::vector<int32_t> at; // (reused from pass to pass, as cntv above)
+		static thread_local std::vector<pg_seg_t> tmp;
+		at.assign((size_t)Q, -1);
 		for (int32_t i = 0; i < q->n_seg; ++i) at[(size_t)q->seg[i].gid] = i;
-		std::vector<pg_seg_t> tmp(q->seg, q->seg + q->n_seg);
+		tmp.assign(q->seg, q->seg + q->n_seg);
 		int32_t k = 0;
 		for (int32_t g = 0; g < Q; ++g) if (at[(size_t)g] >= 0) q->seg[k++] = tmp[(size_t)at[(size_t)g]];
 	}
@@ -1463,7 +1527,11 @@ static int graph_gen_impl(const pg_opt_t *opt, pg_graph_t *q)
 	ext->arc_pending = false;
 	// graph 1: initial vertices (graph.c:284-291)
 	BE_CALL(be->set_filter(ctx, PGA_FLT_PSEUDO), "set_filter");
-	BE_CALL(gen_vtx(opt, q, ext), "gen_vtx");
+	{
+		const int rc = gen_vtx(opt, q, ext);
+		if (rc == RC_FRONT_TIE) return rc; // (not an error: pg_graph_gen repeats the pass)
+		BE_CALL(rc, "gen_vtx");
+	}
 	if (!exact_early(ext)) { Phase ph(PH_EXACT); BE_CALL(exact_sort(ext, 0), "set_head"); } // index 0 of the S1 order, needed from the first sweep of stage C on (see post_process_impl)
 	BE_CALL(flag_vtx(q, ext), "flag_vtx");
 	BE_CALL(trace_state(ext, "gen_vtx+flag_vtx", 0), "trace");
@@ -1668,16 +1736,19 @@ void pg_graph_gen(const pg_opt_t *opt, pg_graph_t *q)
 	double t = now_sec();
 	DataExt *ext = ext_of(q->d, false);
 	if (ext) ext->q_d = q->d;
-	auto run_graph = [&]() { // graph_gen_impl; when the queued branch rounds gave up, once more from stage A with host-driven rounds
-		int rc = graph_gen_impl(opt, q);
-		if (rc == RC_REDO && ext) {
-			if (pg_verbose >= 2) std::fprintf(stderr, "[M::%s::%s] the queued branch rounds met a case they leave to the host: repeating stages A-C with host-driven rounds\n", "pg_graph_gen", stamp());
+	auto run_graph = [&]() { // graph_gen_impl; when it asks for it, once more from stage A: with the host's representatives (RC_FRONT_TIE), with host-driven rounds (RC_REDO)
+		auto again = [&](const char *why) {
+			if (pg_verbose >= 2) std::fprintf(stderr, "[M::%s::%s] %s\n", "pg_graph_gen", stamp(), why);
 			q->n_seg = 0, q->n_arc = 0;
 			std::memset((void *)q->seg, 0, sizeof(pg_seg_t) * (size_t)q->m_seg);
 			ext->rerun = true;
-			rc = post_process_impl(opt, q->d);
-			if (rc == 0) rc = graph_gen_impl(opt, q);
-		}
+			const int rc = post_process_impl(opt, q->d);
+			return rc ? rc : graph_gen_impl(opt, q);
+		};
+		int rc = graph_gen_impl(opt, q);
+		// (front_fill has set ext->front_host: the repeated pg_post_process picks the representatives on the host, and its rounds may still ask for the repeat below)
+		if (rc == RC_FRONT_TIE && ext) rc = again("a gene has two proteins at its largest key: repeating stages A-C with the representatives picked on the host");
+		if (rc == RC_REDO && ext) rc = again("the queued branch rounds met a case they leave to the host: repeating stages A-C with host-driven rounds");
 		return rc;
 	};
 	if (g_err == 0 && run_graph() != 0) q->n_arc = 0;

@@ -198,6 +198,13 @@ struct DataExt {
 	std::vector<std::vector<int32_t>> file_of_host, host_of_file; // per genome whose records were moved into cs order (hits_sorted): host array index <-> file index
 	bool host_order_valid = false;     // the moved records follow the backend's CURRENT cs order
 	bool host_stale = false;           // per-hit flags on the host are older than the backend's
+	// pg_post_process on the backend's post_front: prot[].max_score_ori / n / avg_score_adj / rep and gene[].rep_pid are on their way and reach the host
+	// arrays behind the next wait that happens anyway (pg_gen_vtx's), or when somebody asks first (front_settle, from sync_host); a pg_post_process that comes
+	// before either drops what is pending -- fields and tie flag alike -- because it computes all of it again
+	bool front_pending = false;
+	const int32_t *front_view = nullptr; // the backend's page-locked words (pangene_hip.h: pga_post_front)
+	bool front_host = false;           // this data set has a gene with two proteins at its largest key: only the host's replay of the reference's sort picks its representative -- the host route from now on
+	pg_opt_t front_opt;                // the options of the pg_post_process that is pending (a tie found outside pg_graph_gen repeats it)
 	std::vector<GenomePack> packs;     // per genome (global index); empty buf = not packed (any more)
 	double pack_sec = 0.0;             // wall seconds spent packing (reader threads) since the last upload
 	std::vector<HostSlab> slabs;       // pinned memory the blocks live in (guarded by slab_mu while reader threads pack)
