@@ -6,6 +6,7 @@ nothing in this package knows where it is.)
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 import shlex
@@ -91,16 +92,6 @@ def pan_curves(lib: C.CDLL, presence, n_perm: int = 10, seed: int = 11):
     return out
 
 
-def _curves_args(argv: Sequence[str]):
-    """(orders, seed) of --curves[=INT] / --curves-seed=INT in argv; orders = 0 without --curves."""
-    n, seed = 0, 11
-    for a in argv:
-        if a == "--curves": n = 10
-        elif a.startswith("--curves="): n = int(a.split("=", 1)[1])
-        elif a.startswith("--curves-seed="): seed = int(a.split("=", 1)[1])
-    return n, seed
-
-
 class pg_dist_opt_t(C.Structure):
     """Distance options (include/pangene_amd.h): items (PG_DIST_GENE / PG_DIST_ADJ), metric, PHYLIP layout."""
     _fields_ = [("type", C.c_int32), ("metric", C.c_int32), ("phylip", C.c_int32)]
@@ -154,20 +145,6 @@ def pan_dist(lib: C.CDLL, presence, metric: str = "jaccard"):
     return out if metric == "jaccard" else out.astype(np.int64)
 
 
-def _dist_args(argv: Sequence[str]):
-    """(type, metric) of --dist[=gene|adj] / --dist-metric=STR in argv; type = None without --dist."""
-    t, m = None, "jaccard"
-    for a in argv:
-        if a == "--dist": t = "gene"
-        elif a.startswith("--dist="): t = a.split("=", 1)[1]
-        elif a.startswith("--dist-metric="): m = a.split("=", 1)[1]
-    if t is not None and t not in DIST_TYPES:
-        raise ValueError("--dist must be gene or adj")
-    if m not in DIST_METRICS:
-        raise ValueError("--dist-metric must be jaccard, shared or diff")
-    return t, m
-
-
 class pg_assoc_opt_t(C.Structure):
     """Association options (include/pangene_amd.h): smallest |phi|, smallest min(a, A - a) of a gene, sign (PG_ASSOC_*), pair limit."""
     _fields_ = [("min_phi", C.c_double), ("min_count", C.c_int32), ("sign", C.c_int32), ("max_pair", C.c_int64)]
@@ -212,23 +189,6 @@ def pan_assoc(lib: C.CDLL, presence, min_phi: float = 0.8, min_count: int = 2, s
     D, Vg, Vh = s * A - a * b, a * (A - a), b * (A - b)
     phi = D.astype(np.float64) / np.sqrt(Vg.astype(np.float64) * Vh.astype(np.float64))
     return pairs, phi
-
-
-def _assoc_args(argv: Sequence[str]):
-    """(min_phi, min_count, sign) of --assoc[=FLOAT] / --assoc-min-count=INT / --assoc-sign=STR in argv; min_phi = None without --assoc."""
-    r, c, s = None, 2, "both"
-    for a in argv:
-        if a == "--assoc": r = 0.8
-        elif a.startswith("--assoc="): r = float(a.split("=", 1)[1])
-        elif a.startswith("--assoc-min-count="): c = int(a.split("=", 1)[1])
-        elif a.startswith("--assoc-sign="): s = a.split("=", 1)[1]
-    if r is not None and not 0.0 <= r <= 1.0:
-        raise ValueError("--assoc must be in [0, 1]")
-    if c < 1:
-        raise ValueError("--assoc-min-count must be at least 1")
-    if s not in ASSOC_SIGNS:
-        raise ValueError("--assoc-sign must be pos, neg or both")
-    return r, c, s
 
 
 class pg_trait_opt_t(C.Structure):
@@ -352,36 +312,6 @@ def pan_qtrait(lib: C.CDLL, presence, values, n_perm: int = 1000, seed: int = 11
     if rc != 0:
         raise RuntimeError("pg_pan_qtrait: status %d" % rc)
     return {"N": out[0], "a": out[1], "D": out[2], "k": out[3]}
-
-
-def _qtrait_args(argv: Sequence[str]):
-    """(file, permutations, seed) of --qtrait=FILE / --qtrait-perm=INT / --qtrait-seed=INT in argv; file = None without --qtrait."""
-    f, n, seed, extra = None, 1000, 11, False
-    for a in argv:
-        if a.startswith("--qtrait="): f = a.split("=", 1)[1]
-        elif a.startswith("--qtrait-perm="): n, extra = int(a.split("=", 1)[1]), True
-        elif a.startswith("--qtrait-seed="): seed, extra = int(a.split("=", 1)[1]), True
-    if not 0 <= n <= TRAIT_MAX_PERM:
-        raise ValueError("--qtrait-perm must be in [0, 2^31 - 2]")
-    if extra and f is None:
-        raise ValueError("--qtrait-perm and --qtrait-seed need --qtrait=FILE")
-    return f, n, seed
-
-
-def _trait_args(argv: Sequence[str]):
-    """(file, permutations, seed, lineage) of --trait=FILE / --trait-perm=INT / --trait-seed=INT / --trait-lineage=nj|upgma in argv;
-    file = None without --trait."""
-    f, n, seed, lineage = None, 1000, 11, None
-    for a in argv:
-        if a.startswith("--trait="): f = a.split("=", 1)[1]
-        elif a.startswith("--trait-perm="): n = int(a.split("=", 1)[1])
-        elif a.startswith("--trait-seed="): seed = int(a.split("=", 1)[1])
-        elif a.startswith("--trait-lineage="): lineage = a.split("=", 1)[1]
-    if not 0 <= n <= TRAIT_MAX_PERM:
-        raise ValueError("--trait-perm must be in [0, 2^31 - 2]")
-    if lineage is not None and (lineage not in TRAIT_LINEAGES or f is None):
-        raise ValueError("--trait-lineage must be nj or upgma and needs --trait=FILE")
-    return f, n, seed, lineage
 
 
 class pg_tree_opt_t(C.Structure):
@@ -632,39 +562,21 @@ def pan_permanova_presence(lib: C.CDLL, presence, labels, metric: str = "jaccard
     return _permanova_dict(out), int(F.value)
 
 
-def _permanova_args(argv: Sequence[str]):
-    """(file, type, metric, permutations, seed) of --permanova=FILE / --permanova-type=STR / --permanova-metric=STR / --permanova-perm=INT /
-    --permanova-seed=INT in argv; file = None without --permanova."""
-    f, t, m, n, seed, extra = None, "gene", "jaccard", 1000, 11, False
-    for x in argv:
-        if x.startswith("--permanova="): f = x.split("=", 1)[1]
-        elif x.startswith("--permanova-type="): t, extra = x.split("=", 1)[1], True
-        elif x.startswith("--permanova-metric="): m, extra = x.split("=", 1)[1], True
-        elif x.startswith("--permanova-perm="): n, extra = int(x.split("=", 1)[1]), True
-        elif x.startswith("--permanova-seed="): seed, extra = int(x.split("=", 1)[1]), True
-        elif x.startswith("--permanova"):
-            raise ValueError("unknown option or missing value: " + x)
-    if t not in DIST_TYPES:
-        raise ValueError("--permanova-type must be gene or adj")
-    if m not in TREE_METRICS:
-        raise ValueError("--permanova-metric must be jaccard or diff")
-    if not 0 <= n <= TRAIT_MAX_PERM:
-        raise ValueError("--permanova-perm must be in [0, 2^31 - 2]")
-    if extra and f is None:
-        raise ValueError("--permanova-type, --permanova-metric, --permanova-perm and --permanova-seed need --permanova=FILE")
-    return f, t, m, n, seed
-
-
 class pg_mantel_opt_t(C.Structure):
     """Mantel options (include/pangene_amd.h): the two matrices, the permutations and their seed."""
     _fields_ = [("x_type", C.c_int32), ("x_metric", C.c_int32), ("y_type", C.c_int32), ("y_metric", C.c_int32), ("n_perm", C.c_int32), ("seed", C.c_uint32)]
 
 
+def _spec_ok(spec: str) -> bool:
+    t, colon, m = spec.partition(":")
+    return bool(colon) and t in DIST_TYPES and m in TREE_METRICS
+
+
 def _mantel_spec(spec: str, what: str):
     """(type index, metric index) of gene|adj:jaccard|diff"""
-    t, colon, m = spec.partition(":")
-    if not colon or t not in DIST_TYPES or m not in TREE_METRICS:
+    if not _spec_ok(spec):
         raise ValueError(what + " must be gene|adj:jaccard|diff")
+    t, m = spec.split(":", 1)
     return DIST_TYPES.index(t), DIST_METRICS.index(m)
 
 
@@ -701,30 +613,6 @@ def pan_mantel(lib: C.CDLL, qx, qy, n_perm: int = 1000, seed: int = 11):
     if rc != 0:
         raise RuntimeError("pg_pan_mantel: status %d" % rc)
     return dict(zip(("N", "sx", "sy", "Sa", "Sb", "Saa", "Sbb", "Z", "n_ge", "n_le"), (int(v) for v in out)))
-
-
-def _mantel_args(argv: Sequence[str]):
-    """(asked for, file, x, y, permutations, seed) of --mantel[=FILE] / --mantel-x=SPEC / --mantel-y=SPEC / --mantel-perm=INT /
-    --mantel-seed=INT in argv."""
-    on, f, x, y, n, seed, extra, have_y = False, None, "gene:jaccard", "adj:jaccard", 1000, 11, False, False
-    for a in argv:
-        if a == "--mantel": on = True
-        elif a.startswith("--mantel="): on, f = True, a.split("=", 1)[1]
-        elif a.startswith("--mantel-x="): x, extra = a.split("=", 1)[1], True
-        elif a.startswith("--mantel-y="): y, extra, have_y = a.split("=", 1)[1], True, True
-        elif a.startswith("--mantel-perm="): n, extra = int(a.split("=", 1)[1]), True
-        elif a.startswith("--mantel-seed="): seed, extra = int(a.split("=", 1)[1]), True
-        elif a.startswith("--mantel"):
-            raise ValueError("unknown option or missing value: " + a)
-    _mantel_spec(x, "--mantel-x")
-    _mantel_spec(y, "--mantel-y")
-    if not 0 <= n <= TRAIT_MAX_PERM:
-        raise ValueError("--mantel-perm must be in [0, 2^31 - 2]")
-    if extra and not on:
-        raise ValueError("--mantel-x, --mantel-y, --mantel-perm and --mantel-seed need --mantel")
-    if have_y and f is not None:
-        raise ValueError("--mantel-y cannot be combined with --mantel=FILE")
-    return on, f, x, y, n, seed
 
 
 GAINLOSS_MODES = ("late", "early")
@@ -782,25 +670,6 @@ def pan_gainloss(lib: C.CDLL, presence, rec, method: str, gain: int = 1, loss: i
     out = {k: np.ascontiguousarray(gene[:, i]) for i, k in enumerate(("present", "cost", "gains", "losses", "root"))}
     out.update({"node_" + k: np.ascontiguousarray(node[:, i]) for i, k in enumerate(("present", "gains", "losses"))})
     return out
-
-
-def _gainloss_args(argv: Sequence[str]):
-    """The options of --gainloss[=gene|node] / --gainloss-type= / --gainloss-metric= / --gainloss-method= / --gainloss-gain= /
-    --gainloss-loss= / --gainloss-resolve= / --gainloss-min= in argv as keywords of gainloss_opt; None without --gainloss."""
-    on, extra, kw = False, False, {}
-    names = {"type": "type", "metric": "metric", "method": "method", "gain": "gain", "loss": "loss", "resolve": "mode", "min": "min_changes"}
-    for a in argv:
-        if a == "--gainloss": on = True
-        elif a.startswith("--gainloss="): on, kw["out"] = True, a.split("=", 1)[1]
-        elif a.startswith("--gainloss-") and "=" in a and a[11:].split("=", 1)[0] in names:
-            k, v = a[11:].split("=", 1)
-            kw[names[k]] = int(v) if k in ("gain", "loss", "min") else v
-            extra = True
-        elif a.startswith("--gainloss"):
-            raise ValueError("unknown option or missing value: " + a)
-    if extra and not on:
-        raise ValueError("--gainloss-type, --gainloss-metric, --gainloss-method, --gainloss-gain, --gainloss-loss, --gainloss-resolve and --gainloss-min need --gainloss")
-    return kw if on else None
 
 
 class pg_coevo_opt_t(C.Structure):
@@ -865,85 +734,135 @@ def pan_coevo(lib: C.CDLL, presence, rec, method: str, gain: int = 1, loss: int 
     return events, pairs[:n].copy()
 
 
-def _coevo_args(argv: Sequence[str]):
-    """The options of --coevo[=FLOAT] / --coevo-type= / --coevo-metric= / --coevo-method= / --coevo-gain= / --coevo-loss= /
-    --coevo-resolve= / --coevo-min= / --coevo-sign= / --coevo-max= in argv as keywords of coevo_opt; None without --coevo."""
-    on, extra, kw = False, False, {}
-    names = {"type": "type", "metric": "metric", "method": "method", "gain": "gain", "loss": "loss", "resolve": "mode", "min": "min_events", "sign": "sign",
-             "max": "max_pair"}
-    for a in argv:
-        if a == "--coevo": on = True
-        elif a.startswith("--coevo="): on, kw["min_r"] = True, float(a.split("=", 1)[1])
-        elif a.startswith("--coevo-") and "=" in a and a[8:].split("=", 1)[0] in names:
-            k, v = a[8:].split("=", 1)
-            kw[names[k]] = int(v) if k in ("gain", "loss", "min", "max") else v
-            extra = True
-        elif a.startswith("--coevo"):
-            raise ValueError("unknown option or missing value: " + a)
+# ---- the long options of the analyses, as run() reads them: one table, one reader -------------------------------------------------
+# A row is one --NAME-suffix=VALUE (the head row, without a suffix, is the VALUE of --NAME=VALUE): the keyword of NAME_opt() it fills,
+# the converter (its ValueError is raised where the option stands), and a test of the last value given with the words after the option's
+# name when it fails.  `extra` rows are refused without their --NAME; `phase` 1 rows are read after the others have been checked.
+_Row = collections.namedtuple("_Row", "suffix kw conv ok msg extra phase needs_head no_file", defaults=(str, None, None, False, 0, False, False))
+
+
+def _words(suffix, kw, words, msg, **k):
+    return _Row(suffix, kw, str, lambda v: v in words, msg, **k)
+
+
+def _ints(suffix, kw, lo, hi, msg, **k):
+    return _Row(suffix, kw, int, lambda v: lo <= v <= hi, msg, **k)
+
+
+def _seed32(v):  # digits only, as the command line reads it
+    if not (v.isascii() and v.isdigit() and int(v) <= 0xFFFFFFFF):
+        raise ValueError("--tree-seed must be in [0, 2^32 - 1]")
+    return int(v)
+
+
+def _k_range(v):
+    a, dash, b = v.partition("-")
+    if not a.isdigit() or (dash and not b.isdigit()) or not 2 <= int(a) <= int(b if dash else a) <= TREE_MAX_BOOT:
+        raise ValueError("--cluster must be INT or INT-INT with 2 <= INT")
+    return int(a), int(b if dash else a)
+
+
+# name: of --NAME; opt: the builder NAME_opt(); write: the library's pg_write_NAME; form: --NAME in the messages; bare: what a --NAME without a value sets (None: there is no
+# such thing); head: the row of --NAME=VALUE (None: VALUE is the side file); side: pg_write_NAME takes a file; strict: an unknown
+# --NAME... word is refused (the older analyses let it pass); zero_off: --NAME=0 is no request at all.
+_Analysis = collections.namedtuple("_Analysis", "name opt write form bare head side rows strict zero_off", defaults=(False, False))
+_M_PERM, _M_INT31, _M_TYPE, _M_METRIC = "must be in [0, 2^31 - 2]", "must be in [0, 2^31 - 1]", "must be gene or adj", "must be jaccard or diff"
+_RECON = (_Row("type", "type", extra=True), _Row("metric", "metric", extra=True), _Row("method", "method", extra=True), _Row("gain", "gain", int, extra=True),
+          _Row("loss", "loss", int, extra=True), _Row("resolve", "mode", extra=True))  # gainloss and coevo: gainloss_opt() / coevo_opt() test the values
+
+# in the order in which --X refuses the ones before it (after --matrix and --call)
+_ANALYSES = (
+    _Analysis("curves", curves_opt, "pg_write_curves", "--curves", {"n_perm": 10}, _Row(None, "n_perm", int), False, (_Row("seed", "seed", int),), zero_off=True),
+    _Analysis("dist", dist_opt, "pg_write_dist", "--dist", {"type": "gene"}, _words(None, "type", DIST_TYPES, _M_TYPE), False,
+              (_words("metric", "metric", DIST_METRICS, "must be jaccard, shared or diff"),)),
+    _Analysis("assoc", assoc_opt, "pg_write_assoc", "--assoc", {"min_phi": 0.8}, _Row(None, "min_phi", float, lambda r: 0.0 <= r <= 1.0, "must be in [0, 1]"), False,
+              (_Row("min-count", "min_count", int, lambda c: c >= 1, "must be at least 1"), _words("sign", "sign", ASSOC_SIGNS, "must be pos, neg or both"))),
+    _Analysis("trait", trait_opt, "pg_write_trait", "--trait=FILE", None, None, True,
+              (_ints("perm", "n_perm", 0, TRAIT_MAX_PERM, _M_PERM), _Row("seed", "seed", int),
+               _words("lineage", "lineage", TRAIT_LINEAGES[1:], "must be nj or upgma and needs --trait=FILE", needs_head=True))),  # (one message for both)
+    _Analysis("tree", tree_opt, "pg_write_tree", "--tree", {"type": "gene"}, _words(None, "type", DIST_TYPES, _M_TYPE), False,
+              (_words("metric", "metric", TREE_METRICS, _M_METRIC), _words("method", "method", TREE_METHODS, "must be nj or upgma"),
+               _ints("boot", "n_boot", 0, TREE_MAX_BOOT, _M_INT31, phase=1), _Row("seed", "seed", _seed32, phase=1))),
+    _Analysis("qtrait", qtrait_opt, "pg_write_qtrait", "--qtrait=FILE", None, None, True, (_ints("perm", "n_perm", 0, TRAIT_MAX_PERM, _M_PERM, extra=True), _Row("seed", "seed", int, extra=True))),
+    _Analysis("cluster", cluster_opt, "pg_write_cluster", "--cluster=INT[-INT]", None, _Row(None, ("k_lo", "k_hi"), _k_range), False,
+              (_words("type", "type", DIST_TYPES, _M_TYPE, extra=True), _words("metric", "metric", TREE_METRICS, _M_METRIC, extra=True),
+               _ints("iter", "max_iter", 0, TREE_MAX_BOOT, _M_INT31, extra=True)), strict=True),
+    _Analysis("permanova", permanova_opt, "pg_write_permanova", "--permanova=FILE", None, None, True,
+              (_words("type", "type", DIST_TYPES, _M_TYPE, extra=True), _words("metric", "metric", TREE_METRICS, _M_METRIC, extra=True),
+               _ints("perm", "n_perm", 0, TRAIT_MAX_PERM, _M_PERM, extra=True), _Row("seed", "seed", int, extra=True)), strict=True),
+    _Analysis("mantel", mantel_opt, "pg_write_mantel", "--mantel", {}, None, True,
+              (_Row("x", "x", str, _spec_ok, "must be gene|adj:jaccard|diff", extra=True),
+               _Row("y", "y", str, _spec_ok, "must be gene|adj:jaccard|diff", extra=True, no_file=True),  # (-y and the file both name the second matrix)
+               _ints("perm", "n_perm", 0, TRAIT_MAX_PERM, _M_PERM, extra=True), _Row("seed", "seed", int, extra=True)), strict=True),
+    _Analysis("gainloss", gainloss_opt, "pg_write_gainloss", "--gainloss", {}, _Row(None, "out"), False, _RECON + (_Row("min", "min_changes", int, extra=True),), strict=True),
+    _Analysis("coevo", coevo_opt, "pg_write_coevo", "--coevo", {}, _Row(None, "min_r", float), False,
+              _RECON + (_Row("min", "min_events", int, extra=True), _Row("sign", "sign", extra=True), _Row("max", "max_pair", int, extra=True)), strict=True),
+)
+_HEADS = tuple("--" + a.name for a in _ANALYSES)
+
+
+def _join(words, last):
+    return ", ".join(words[:-1]) + last + words[-1] if len(words) > 1 else words[0]
+
+
+def _one_analysis_args(a: _Analysis, argv: Sequence[str]):
+    """(asked for, keywords of NAME_opt(), side file) of --NAME[=VALUE] and the --NAME-suffix=VALUE of one analysis in argv"""
+    on, extra, side, no_file, kw = False, False, None, None, {}
+    head, rows = "--" + a.name, {"--%s-%s=" % (a.name, r.suffix): r for r in a.rows}
+
+    def put(r, v):
+        v = r.conv(v)
+        kw.update(zip(r.kw, v) if isinstance(r.kw, tuple) else ((r.kw, v),))
+
+    for phase in range(1 + max(r.phase for r in a.rows)):
+        for x in argv:
+            r = rows.get(x[:x.find("=") + 1])
+            if x == head and a.bare is not None:
+                on = True
+                if phase == 0: kw.update(a.bare)
+            elif x.startswith(head + "="):
+                on = True
+                if a.head is None: side = x.split("=", 1)[1]
+                elif phase == 0: put(a.head, x.split("=", 1)[1])
+            elif r is not None:
+                if r.phase == phase:
+                    put(r, x.split("=", 1)[1])
+                    extra, no_file = extra or r.extra, r if r.no_file else no_file
+            elif a.strict and x.startswith(head):  # a bare --NAME that needs a value, --NAME-suffix without one, an unknown --NAME... word
+                raise ValueError("unknown option or missing value: " + x)
+        for r in ((a.head,) if a.head else ()) + a.rows:
+            if r.phase == phase and r.ok is not None and r.kw in kw and not (r.ok(kw[r.kw]) and (on or not r.needs_head)):
+                raise ValueError("%s%s %s" % (head, "-" + r.suffix if r.suffix else "", r.msg))
+    names = [head + "-" + r.suffix for r in a.rows if r.extra]
     if extra and not on:
-        raise ValueError("--coevo-type, --coevo-metric, --coevo-method, --coevo-gain, --coevo-loss, --coevo-resolve, --coevo-min, --coevo-sign and --coevo-max need --coevo")
-    return kw if on else None
+        raise ValueError("%s %s %s" % (_join(names, " and "), "needs" if len(names) == 1 else "need", a.form))
+    if no_file is not None and side is not None:
+        raise ValueError("%s-%s cannot be combined with %s=FILE" % (head, no_file.suffix, head))
+    if a.zero_off and not kw.get(a.head.kw):
+        on = False
+    return on, kw, side
 
 
-def _cluster_args(argv: Sequence[str]):
-    """(k_lo, k_hi, type, metric, iterations) of --cluster=INT[-INT] / --cluster-type=STR / --cluster-metric=STR / --cluster-iter=INT in
-    argv; k_lo = None without --cluster."""
-    lo = hi = None
-    t, m, it, extra = "gene", "jaccard", 1000, False
-    for x in argv:
-        if x.startswith("--cluster="):
-            a, dash, b = x.split("=", 1)[1].partition("-")
-            if not a.isdigit() or (dash and not b.isdigit()):
-                raise ValueError("--cluster must be INT or INT-INT with 2 <= INT")
-            lo, hi = int(a), int(b) if dash else int(a)
-            if not 2 <= lo <= hi <= TREE_MAX_BOOT:
-                raise ValueError("--cluster must be INT or INT-INT with 2 <= INT")
-        elif x.startswith("--cluster-type="): t, extra = x.split("=", 1)[1], True
-        elif x.startswith("--cluster-metric="): m, extra = x.split("=", 1)[1], True
-        elif x.startswith("--cluster-iter="): it, extra = int(x.split("=", 1)[1]), True
-        elif x.startswith("--cluster"):  # a bare --cluster, --cluster-type without a value, an unknown --cluster-* word
-            raise ValueError("unknown option or missing value: " + x)
-    if t not in DIST_TYPES:
-        raise ValueError("--cluster-type must be gene or adj")
-    if m not in TREE_METRICS:
-        raise ValueError("--cluster-metric must be jaccard or diff")
-    if not 0 <= it <= TREE_MAX_BOOT:
-        raise ValueError("--cluster-iter must be in [0, 2^31 - 1]")
-    if extra and lo is None:
-        raise ValueError("--cluster-type, --cluster-metric and --cluster-iter need --cluster=INT[-INT]")
-    return lo, hi, t, m, it
+def _analysis_args(argv: Sequence[str], lib: C.CDLL | None = None):
+    """The analysis argv asks for: (its table entry, the keywords of its NAME_opt(), its side file, NAME_opt(lib, **keywords) when lib is
+    given), or None.  Every analysis is read and checked in the table's order, and --X is refused when anything before it was asked for."""
+    before = ["--matrix", "--call"]
+    any_before = any(x.startswith("--matrix") for x in argv) or "--call" in argv
+    found = None
+    for a in _ANALYSES:
+        on, kw, side = _one_analysis_args(a, argv)
+        if on and any_before:
+            raise ValueError("--%s cannot be combined with %s" % (a.name, _join(before, " or ")))
+        if on:
+            found, any_before = (a, kw, side, a.opt(lib, **kw) if lib is not None else None), True
+        before.append("--" + a.name)
+    return found
 
 
 def _tree_boot_args(argv: Sequence[str]):
     """(replicates, seed) of --tree-boot=INT / --tree-seed=INT in argv"""
-    b, seed = 0, 0
-    for x in argv:
-        if x.startswith("--tree-boot="): b = int(x.split("=", 1)[1])
-        elif x.startswith("--tree-seed="):
-            v = x.split("=", 1)[1]
-            if not (v.isascii() and v.isdigit() and int(v) <= 0xFFFFFFFF):  # digits only, as the command line reads it
-                raise ValueError("--tree-seed must be in [0, 2^32 - 1]")
-            seed = int(v)
-    if not 0 <= b <= TREE_MAX_BOOT:
-        raise ValueError("--tree-boot must be in [0, 2^31 - 1]")
-    return b, seed
-
-
-def _tree_args(argv: Sequence[str]):
-    """(type, metric, method) of --tree[=gene|adj] / --tree-metric=STR / --tree-method=STR in argv; type = None without --tree."""
-    t, m, a = None, "jaccard", "nj"
-    for x in argv:
-        if x == "--tree": t = "gene"
-        elif x.startswith("--tree="): t = x.split("=", 1)[1]
-        elif x.startswith("--tree-metric="): m = x.split("=", 1)[1]
-        elif x.startswith("--tree-method="): a = x.split("=", 1)[1]
-    if t is not None and t not in DIST_TYPES:
-        raise ValueError("--tree must be gene or adj")
-    if m not in TREE_METRICS:
-        raise ValueError("--tree-metric must be jaccard or diff")
-    if a not in TREE_METHODS:
-        raise ValueError("--tree-method must be nj or upgma")
-    return t, m, a
+    kw = _one_analysis_args(next(a for a in _ANALYSES if a.name == "tree"), argv)[1]
+    return kw.get("n_boot", 0), kw.get("seed", 0)
 
 
 # medoid, label, dist, size, sums, rec, rec_cap, n_rec, n_swap, td, converged of pg_pan_medoids / pg_pan_cluster
@@ -1086,7 +1005,7 @@ def parse_args(lib: C.CDLL, argv: Sequence[str]) -> pg_opt_t:
         elif a in ("--bed", "--bed=walk"): opt.flag |= PG_F_WRITE_BED_WALK
         elif a == "--bed=raw": opt.flag |= PG_F_WRITE_BED_RAW
         elif a == "--bed=flag": opt.flag |= PG_F_WRITE_BED_FLAG
-        elif a in ("--matrix", "--matrix=presence", "--matrix=count", "--call") or a.startswith("--curves") or a.startswith("--dist") or a.startswith("--assoc") or a.startswith("--trait") or a.startswith("--qtrait") or a.startswith("--tree") or a.startswith("--cluster") or a.startswith("--permanova") or a.startswith("--mantel") or a.startswith("--gainloss") or a.startswith("--coevo"): pass  # handled by run()
+        elif a in ("--matrix", "--matrix=presence", "--matrix=count", "--call") or a.startswith(_HEADS): pass  # handled by run()
         elif a[:2] in ("-p", "-a", "-f", "-c", "-g", "-r", "-b", "-B", "-y", "-T", "-D", "-C", "-e", "-l", "-m", "-d", "-X", "-I", "-P"):
             v = a[2:] if len(a) > 2 else next(it)
             k = a[1]
@@ -1131,50 +1050,7 @@ def read_files(lib: C.CDLL, opt, d, files: Sequence[str], scan_only: Sequence[bo
 def run(lib: C.CDLL, files: Sequence[str], argv: Sequence[str] = (), scan_only: Sequence[bool] | None = None, batch: bool = True) -> bytes:
     """main.c:117-142 in-process: returns what the command line would print to stdout."""
     opt = parse_args(lib, argv)
-    n_curves, curves_seed = _curves_args(argv)
-    if n_curves and (any(x.startswith("--matrix") for x in argv) or "--call" in argv):
-        raise ValueError("--curves cannot be combined with --matrix or --call")
-    dist_type, dist_metric = _dist_args(argv)
-    if dist_type is not None and (any(x.startswith("--matrix") for x in argv) or "--call" in argv or n_curves):
-        raise ValueError("--dist cannot be combined with --matrix, --call or --curves")
-    assoc_phi, assoc_count, assoc_sign = _assoc_args(argv)
-    if assoc_phi is not None and (any(x.startswith("--matrix") for x in argv) or "--call" in argv or n_curves or dist_type is not None):
-        raise ValueError("--assoc cannot be combined with --matrix, --call, --curves or --dist")
-    trait_fn, trait_n, trait_seed, trait_lineage = _trait_args(argv)
-    if trait_fn is not None and (any(x.startswith("--matrix") for x in argv) or "--call" in argv or n_curves or dist_type is not None or assoc_phi is not None):
-        raise ValueError("--trait cannot be combined with --matrix, --call, --curves, --dist or --assoc")
-    tree_type, tree_metric, tree_method = _tree_args(argv)
-    tree_boot, tree_seed = _tree_boot_args(argv)
-    if tree_type is not None and (any(x.startswith("--matrix") for x in argv) or "--call" in argv or n_curves or dist_type is not None or assoc_phi is not None
-                                  or trait_fn is not None):
-        raise ValueError("--tree cannot be combined with --matrix, --call, --curves, --dist, --assoc or --trait")
-    qtrait_fn, qtrait_n, qtrait_seed = _qtrait_args(argv)
-    if qtrait_fn is not None and (any(x.startswith("--matrix") for x in argv) or "--call" in argv or n_curves or dist_type is not None or assoc_phi is not None
-                                  or trait_fn is not None or tree_type is not None):
-        raise ValueError("--qtrait cannot be combined with --matrix, --call, --curves, --dist, --assoc, --trait or --tree")
-    cl_lo, cl_hi, cl_type, cl_metric, cl_iter = _cluster_args(argv)
-    if cl_lo is not None and (any(x.startswith("--matrix") for x in argv) or "--call" in argv or n_curves or dist_type is not None or assoc_phi is not None
-                              or trait_fn is not None or tree_type is not None or qtrait_fn is not None):
-        raise ValueError("--cluster cannot be combined with --matrix, --call, --curves, --dist, --assoc, --trait, --tree or --qtrait")
-    pm_fn, pm_type, pm_metric, pm_n, pm_seed = _permanova_args(argv)
-    if pm_fn is not None and (any(x.startswith("--matrix") for x in argv) or "--call" in argv or n_curves or dist_type is not None or assoc_phi is not None
-                              or trait_fn is not None or tree_type is not None or qtrait_fn is not None or cl_lo is not None):
-        raise ValueError("--permanova cannot be combined with --matrix, --call, --curves, --dist, --assoc, --trait, --tree, --qtrait or --cluster")
-    mt_on, mt_fn, mt_x, mt_y, mt_n, mt_seed = _mantel_args(argv)
-    if mt_on and (any(x.startswith("--matrix") for x in argv) or "--call" in argv or n_curves or dist_type is not None or assoc_phi is not None
-                  or trait_fn is not None or tree_type is not None or qtrait_fn is not None or cl_lo is not None or pm_fn is not None):
-        raise ValueError("--mantel cannot be combined with --matrix, --call, --curves, --dist, --assoc, --trait, --tree, --qtrait, --cluster or --permanova")
-    gl_kw = _gainloss_args(argv)
-    if gl_kw is not None and (any(x.startswith("--matrix") for x in argv) or "--call" in argv or n_curves or dist_type is not None or assoc_phi is not None
-                              or trait_fn is not None or tree_type is not None or qtrait_fn is not None or cl_lo is not None or pm_fn is not None or mt_on):
-        raise ValueError("--gainloss cannot be combined with --matrix, --call, --curves, --dist, --assoc, --trait, --tree, --qtrait, --cluster, --permanova or --mantel")
-    gl_opt = gainloss_opt(lib, **gl_kw) if gl_kw is not None else None
-    ce_kw = _coevo_args(argv)
-    if ce_kw is not None and (any(x.startswith("--matrix") for x in argv) or "--call" in argv or n_curves or dist_type is not None or assoc_phi is not None
-                              or trait_fn is not None or tree_type is not None or qtrait_fn is not None or cl_lo is not None or pm_fn is not None or mt_on
-                              or gl_kw is not None):
-        raise ValueError("--coevo cannot be combined with --matrix, --call, --curves, --dist, --assoc, --trait, --tree, --qtrait, --cluster, --permanova, --mantel or --gainloss")
-    ce_opt = coevo_opt(lib, **ce_kw) if ce_kw is not None else None
+    what = _analysis_args(argv, lib)
     fd, out = tempfile.mkstemp(prefix="pangene_", suffix=".out")
     os.close(fd)
     lib.pg_set_output(out.encode())
@@ -1198,48 +1074,10 @@ def run(lib: C.CDLL, files: Sequence[str], argv: Sequence[str] = (), scan_only: 
                 lib.pg_write_call(g, C.byref(co))
                 if lib.pg_last_error():
                     raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
-            elif n_curves:
-                lib.pg_write_curves(g, C.byref(curves_opt(lib, n_curves, curves_seed)))
-                if lib.pg_last_error():
-                    raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
-            elif dist_type is not None:
-                lib.pg_write_dist(g, C.byref(dist_opt(lib, dist_type, dist_metric)))
-                if lib.pg_last_error():
-                    raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
-            elif assoc_phi is not None:
-                lib.pg_write_assoc(g, C.byref(assoc_opt(lib, assoc_phi, assoc_count, assoc_sign)))
-                if lib.pg_last_error():
-                    raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
-            elif trait_fn is not None:
-                lib.pg_write_trait(g, trait_fn.encode(), C.byref(trait_opt(lib, trait_n, trait_seed, lineage=trait_lineage)))
-                if lib.pg_last_error():
-                    raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
-            elif qtrait_fn is not None:
-                lib.pg_write_qtrait(g, qtrait_fn.encode(), C.byref(qtrait_opt(lib, qtrait_n, qtrait_seed)))
-                if lib.pg_last_error():
-                    raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
-            elif tree_type is not None:
-                lib.pg_write_tree(g, C.byref(tree_opt(lib, tree_type, tree_metric, tree_method, tree_boot, tree_seed)))
-                if lib.pg_last_error():
-                    raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
-            elif cl_lo is not None:
-                lib.pg_write_cluster(g, C.byref(cluster_opt(lib, cl_lo, cl_hi, cl_type, cl_metric, cl_iter)))
-                if lib.pg_last_error():
-                    raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
-            elif pm_fn is not None:
-                lib.pg_write_permanova(g, pm_fn.encode(), C.byref(permanova_opt(lib, pm_type, pm_metric, pm_n, pm_seed)))
-                if lib.pg_last_error():
-                    raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
-            elif mt_on:
-                lib.pg_write_mantel(g, mt_fn.encode() if mt_fn is not None else None, C.byref(mantel_opt(lib, mt_x, mt_y, mt_n, mt_seed)))
-                if lib.pg_last_error():
-                    raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
-            elif gl_opt is not None:
-                lib.pg_write_gainloss(g, C.byref(gl_opt))
-                if lib.pg_last_error():
-                    raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
-            elif ce_opt is not None:
-                lib.pg_write_coevo(g, C.byref(ce_opt))
+            elif what is not None:
+                a, _, side, o = what
+                file_arg = (side.encode() if side is not None else None,) if a.side else ()  # (pg_write_NAME(g, [file,] options))
+                getattr(lib, a.write)(g, *file_arg, C.byref(o))
                 if lib.pg_last_error():
                     raise RuntimeError("pangene_amd: " + lib.pg_last_error_str().decode())
             elif opt.flag & PG_F_WRITE_BED_WALK: lib.pg_write_bed(d, 1)

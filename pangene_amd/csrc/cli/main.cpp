@@ -182,99 +182,70 @@ static int main_call(int argc, char *argv[])
 	return pg_call_file(argv[optind], &o) == 0 ? 0 : 1;
 }
 
-// `pangene curves`: pan / core / new / unique accumulation curves of the matrix `pangene gfa2matrix` prints for the same GFA
-static int main_curves(int argc, char *argv[])
-{
-	pg_curves_opt_t o;
-	pg_curves_opt_init(&o);
-	int c;
-	while ((c = getopt(argc, argv, "n:s:")) >= 0) {
-		if (c == 'n') o.n_perm = std::atoi(optarg);
-		else if (c == 's') o.seed = (uint32_t)std::strtoul(optarg, nullptr, 10);
-		else return 1;
-	}
-	if (o.n_perm < 1) { std::fprintf(stderr, "ERROR: -n must be at least 1\n"); return 1; }
-	if (argc - optind < 1) {
-		std::printf("Usage: pangene curves [options] <in.gfa>\nOptions:\n  -n INT   orders of the assemblies, the input order first [%d]\n"
-		            "  -s INT   seed of the random orders [%u]\n", o.n_perm, o.seed);
-		return 0;
-	}
-	return pg_curves_file(argv[optind], &o) == 0 ? 0 : 1;
-}
+// ---------------------------------------------------------------------------------------------------------------
+// The analyses: `pangene NAME [options] <in.gfa>` on a GFA file and `pangene --NAME[=X] --NAME-sub=X <in.paf> [...]` on the graph in
+// memory.  Both spellings, their refusals and the dispatch come from ONE table, kAnalyses below: a record per analysis, a row per option.
+// ---------------------------------------------------------------------------------------------------------------
+union AnyOpt { pg_curves_opt_t curves; pg_dist_opt_t dist; pg_assoc_opt_t assoc; pg_trait_opt_t trait; pg_tree_opt_t tree; pg_qtrait_opt_t qtrait;
+	pg_cluster_opt_t cluster; pg_permanova_opt_t permanova; pg_mantel_opt_t mantel; pg_gainloss_opt_t gainloss; pg_coevo_opt_t coevo; };
 
-static int dist_type(const char *s) { return std::strcmp(s, "gene") == 0 ? PG_DIST_GENE : std::strcmp(s, "adj") == 0 ? PG_DIST_ADJ : -1; }
-static int dist_metric(const char *s)
-{
-	return std::strcmp(s, "jaccard") == 0 ? PG_DIST_JACCARD : std::strcmp(s, "shared") == 0 ? PG_DIST_SHARED : std::strcmp(s, "diff") == 0 ? PG_DIST_DIFF : -1;
-}
+struct Word { const char *s; int32_t v; };
+static const Word W_TYPE[] = { { "gene", PG_DIST_GENE }, { "adj", PG_DIST_ADJ }, { nullptr, 0 } };
+static const Word W_DIST_METRIC[] = { { "jaccard", PG_DIST_JACCARD }, { "shared", PG_DIST_SHARED }, { "diff", PG_DIST_DIFF }, { nullptr, 0 } };
+static const Word W_METRIC[] = { { "jaccard", PG_DIST_JACCARD }, { "diff", PG_DIST_DIFF }, { nullptr, 0 } };
+static const Word W_METHOD[] = { { "nj", PG_TREE_NJ }, { "upgma", PG_TREE_UPGMA }, { nullptr, 0 } };
+static const Word W_SIGN[] = { { "both", PG_ASSOC_BOTH }, { "pos", PG_ASSOC_POS }, { "neg", PG_ASSOC_NEG }, { nullptr, 0 } };
+static const Word W_LINEAGE[] = { { "nj", PG_LINEAGE_NJ }, { "upgma", PG_LINEAGE_UPGMA }, { nullptr, 0 } };
+static const Word W_MODE[] = { { "late", PG_GAINLOSS_LATE }, { "early", PG_GAINLOSS_EARLY }, { nullptr, 0 } };
+static const Word W_OUT[] = { { "gene", PG_GAINLOSS_GENE }, { "node", PG_GAINLOSS_NODE }, { nullptr, 0 } };
 
-// `pangene dist`: pairwise distances of the assemblies of a GFA file over their genes or their gene adjacencies
-static int main_dist(int argc, char *argv[])
-{
-	pg_dist_opt_t o;
-	pg_dist_opt_init(&o);
-	int c;
-	while ((c = getopt(argc, argv, "t:m:p")) >= 0) {
-		if (c == 't') { if ((o.type = dist_type(optarg)) < 0) { std::fprintf(stderr, "ERROR: -t must be gene or adj\n"); return 1; } }
-		else if (c == 'm') { if ((o.metric = dist_metric(optarg)) < 0) { std::fprintf(stderr, "ERROR: -m must be jaccard, shared or diff\n"); return 1; } }
-		else if (c == 'p') o.phylip = 1;
-		else return 1;
-	}
-	if (argc - optind < 1) {
-		std::printf("Usage: pangene dist [options] <in.gfa>\nOptions:\n  -t STR   items: gene (gene content) or adj (gene adjacencies of the walks) [gene]\n"
-		            "  -m STR   metric: jaccard, shared or diff [jaccard]\n  -p       relaxed PHYLIP output\n");
-		return 0;
-	}
-	return pg_dist_file(argv[optind], &o) == 0 ? 0 : 1;
-}
+struct Row;
+typedef bool (*Reader)(const char *s, void *field, const Row &r); // false: not a value of this option
+struct Row {
+	char letter;          // of the subcommand (0: none)
+	const char *suffix;   // --NAME-suffix (nullptr: none)
+	Reader read;          // (nullptr ends the rows of an analysis)
+	size_t field;         // offset in the analysis' pg_NAME_opt_t
+	long long lo, hi;     // integer readers: the bounds
+	const Word *words;    // rd_word: the list
+	const char *msg;      // "ERROR: -x <msg>" / "ERROR: --NAME-suffix <msg>"
+	bool extra = false;   // --NAME-suffix without --NAME is refused
+	const char *long_msg = nullptr; // where --NAME says something else than the letter does
+	bool no_file = false; // cannot be combined with the side file
+	bool late = false;    // subcommand, rd_atoi rows (int32 fields) only: lo is checked after the last option, so that a later value mends an earlier one
+};
 
-static int tree_metric(const char *s) { return std::strcmp(s, "jaccard") == 0 ? PG_DIST_JACCARD : std::strcmp(s, "diff") == 0 ? PG_DIST_DIFF : -1; }
-static int tree_method(const char *s) { return std::strcmp(s, "nj") == 0 ? PG_TREE_NJ : std::strcmp(s, "upgma") == 0 ? PG_TREE_UPGMA : -1; }
-static bool tree_boot(const char *s, int32_t &v) // a whole number of replicates
+static int word_of(const Word *w, const char *s) { for (; w->s; ++w) if (std::strcmp(w->s, s) == 0) return w->v; return -1; }
+static bool strict_ll(const char *s, long long lo, long long hi, long long &x) // a whole number in [lo, hi] and nothing after it
 {
-	char *end = nullptr;
-	const long long x = std::strtoll(s, &end, 10);
-	if (end == s || *end != 0 || x < 0 || x > 2147483647ll) return false;
-	v = (int32_t)x;
-	return true;
+	char *e = nullptr;
+	x = std::strtoll(s, &e, 10);
+	return e != s && *e == 0 && x >= lo && x <= hi;
 }
-static bool tree_seed_arg(const char *s, uint32_t &v) // a whole number that fits 32 bits; digits only (strtoull alone would take "-1" and " 7")
+static bool strict_real(const char *s, double &x) { char *e; x = std::strtod(s, &e); return e != s && *e == 0; }
+
+static bool rd_i32(const char *s, void *f, const Row &r) { long long x; if (!strict_ll(s, r.lo, r.hi, x)) return false; *(int32_t *)f = (int32_t)x; return true; }
+static bool rd_i64(const char *s, void *f, const Row &r) { long long x; if (!strict_ll(s, r.lo, r.hi, x)) return false; *(int64_t *)f = x; return true; }
+static bool rd_u32(const char *s, void *f, const Row &) // a whole number that fits 32 bits; digits only (strtoull alone would take "-1" and " 7")
 {
 	char *end = nullptr;
 	if (*s < '0' || *s > '9') return false;
 	const unsigned long long x = std::strtoull(s, &end, 10);
 	if (*end != 0 || end - s > 10 || x > 4294967295ull) return false;
-	v = (uint32_t)x;
+	*(uint32_t *)f = (uint32_t)x;
 	return true;
 }
-
-// `pangene tree`: a neighbour-joining or UPGMA tree of the assemblies of a GFA file from the distances `pangene dist` prints
-static int main_tree(int argc, char *argv[])
-{
-	pg_tree_opt_t o;
-	pg_tree_opt_init(&o);
-	int c;
-	while ((c = getopt(argc, argv, "t:m:a:b:s:")) >= 0) {
-		if (c == 't') { if ((o.type = dist_type(optarg)) < 0) { std::fprintf(stderr, "ERROR: -t must be gene or adj\n"); return 1; } }
-		else if (c == 'm') { if ((o.metric = tree_metric(optarg)) < 0) { std::fprintf(stderr, "ERROR: -m must be jaccard or diff (shared is not a distance)\n"); return 1; } }
-		else if (c == 'a') { if ((o.method = tree_method(optarg)) < 0) { std::fprintf(stderr, "ERROR: -a must be nj or upgma\n"); return 1; } }
-		else if (c == 'b') { if (!tree_boot(optarg, o.n_boot)) { std::fprintf(stderr, "ERROR: -b must be in [0, 2147483647]\n"); return 1; } }
-		else if (c == 's') { if (!tree_seed_arg(optarg, o.seed)) { std::fprintf(stderr, "ERROR: -s must be in [0, 4294967295]\n"); return 1; } }
-		else return 1;
-	}
-	if (argc - optind < 1) {
-		std::printf("Usage: pangene tree [options] <in.gfa>\nOptions:\n  -t STR   items: gene (gene content) or adj (gene adjacencies of the walks) [gene]\n"
-		            "  -m STR   distance: jaccard or diff [jaccard]\n"
-		            "  -a STR   nj (neighbour-joining: unrooted, negative branch lengths are printed as they come) or upgma [nj]\n"
-		            "  -b INT   bootstrap replicates over the items: inner nodes are labelled with their support in per cent [0]\n"
-		            "  -s INT   seed of the bootstrap draws [0]\n");
-		return 0;
-	}
-	return pg_tree_file(argv[optind], &o) == 0 ? 0 : 1;
-}
-
-// "INT" or "INT-INT": a k or a range of k, 2 <= lo <= hi; digits only
-static bool cluster_range(const char *s, int32_t &lo, int32_t &hi)
+// the lax readers of the older options: whatever atoi / atoll / strtoul make of the text ("x" is 0, "3x" is 3)
+static bool rd_atoi(const char *s, void *f, const Row &r) { return (*(int32_t *)f = std::atoi(s)) >= r.lo; }
+static bool rd_atoll(const char *s, void *f, const Row &r) { return (*(int64_t *)f = std::atoll(s)) >= r.lo; }
+static bool rd_strtoul(const char *s, void *f, const Row &) { *(uint32_t *)f = (uint32_t)std::strtoul(s, nullptr, 10); return true; }
+static bool rd_unit(const char *s, void *f, const Row &) { double &x = *(double *)f; return strict_real(s, x) && x >= 0.0 && x <= 1.0; } // a number in [0, 1]
+static bool rd_nonneg(const char *s, void *f, const Row &) { double &x = *(double *)f; return strict_real(s, x) && x >= 0.0; }
+static bool rd_word(const char *s, void *f, const Row &r) { return (*(int32_t *)f = word_of(r.words, s)) >= 0; }
+static bool rd_flag(const char *, void *f, const Row &) { *(int32_t *)f = 1; return true; } // (an option without a value)
+// "INT" or "INT-INT": a k or a range of k, 2 <= lo <= hi; digits only.  Fills the field (k_lo) and the one after it (k_hi).
+static_assert(offsetof(pg_cluster_opt_t, k_hi) == offsetof(pg_cluster_opt_t, k_lo) + sizeof(int32_t), "rd_cluster_range fills k_lo and the int32 after it");
+static bool rd_cluster_range(const char *s, void *f, const Row &)
 {
 	char *end = nullptr;
 	if (*s < '0' || *s > '9') return false;
@@ -286,275 +257,194 @@ static bool cluster_range(const char *s, int32_t &lo, int32_t &hi)
 		b = std::strtoll(t, &end, 10);
 	}
 	if (*end != 0 || a < 2 || b < a || b > 2147483647ll) return false;
-	lo = (int32_t)a, hi = (int32_t)b;
+	((int32_t *)f)[0] = (int32_t)a, ((int32_t *)f)[1] = (int32_t)b;
+	return true;
+}
+// SPEC of mantel: gene|adj + ':' + jaccard|diff.  Fills the field (the type) and the one after it (the metric).
+static_assert(offsetof(pg_mantel_opt_t, x_metric) == offsetof(pg_mantel_opt_t, x_type) + sizeof(int32_t) &&
+              offsetof(pg_mantel_opt_t, y_metric) == offsetof(pg_mantel_opt_t, y_type) + sizeof(int32_t), "rd_mantel_spec fills a type and the int32 after it");
+static bool rd_mantel_spec(const char *s, void *f, const Row &)
+{
+	const char *c = std::strchr(s, ':');
+	if (c == nullptr) return false;
+	const int ty = word_of(W_TYPE, std::string(s, c).c_str()), me = word_of(W_METRIC, c + 1);
+	if (ty < 0 || me < 0) return false;
+	((int32_t *)f)[0] = ty, ((int32_t *)f)[1] = me;
 	return true;
 }
 
-// `pangene cluster`: k-medoids clusters of the assemblies of a GFA file over the distances `pangene dist` prints
-static int main_cluster(int argc, char *argv[])
+// the rows by what reads them
+static constexpr long long INT31 = 2147483647ll;
+static constexpr Row word(char l, const char *suf, size_t f, const Word *w, const char *msg, bool extra = false) { return { l, suf, rd_word, f, 0, 0, w, msg, extra }; }
+static constexpr Row i32(char l, const char *suf, size_t f, long long lo, long long hi, const char *msg, bool extra = false) { return { l, suf, rd_i32, f, lo, hi, nullptr, msg, extra }; }
+static constexpr Row plain(char l, const char *suf, Reader rd, size_t f, const char *msg, bool extra = false, long long lo = 0) { return { l, suf, rd, f, lo, 0, nullptr, msg, extra }; }
+static constexpr Row seed(char l, size_t f, bool extra = false) { return plain(l, "seed", rd_strtoul, f, "", extra); } // (never refused)
+static constexpr Row i64(char l, const char *suf, size_t f, long long lo, long long hi, const char *msg, bool extra = false) { return { l, suf, rd_i64, f, lo, hi, nullptr, msg, extra }; }
+// a lax count of the subcommand alone, at least lo, checked late (Row::late); --NAME=X reads it too, checks at once and says long_msg
+static constexpr Row late_count(char l, size_t f, long long lo, const char *msg, const char *long_msg)
 {
-	pg_cluster_opt_t o;
-	pg_cluster_opt_init(&o);
-	bool have_k = false;
-	int c;
-	while ((c = getopt(argc, argv, "t:m:k:i:")) >= 0) {
-		if (c == 't') { if ((o.type = dist_type(optarg)) < 0) { std::fprintf(stderr, "ERROR: -t must be gene or adj\n"); return 1; } }
-		else if (c == 'm') { if ((o.metric = tree_metric(optarg)) < 0) { std::fprintf(stderr, "ERROR: -m must be jaccard or diff (shared is not a distance)\n"); return 1; } }
-		else if (c == 'k') { if (!(have_k = cluster_range(optarg, o.k_lo, o.k_hi))) { std::fprintf(stderr, "ERROR: -k must be INT or INT-INT with 2 <= INT\n"); return 1; } }
-		else if (c == 'i') { if (!tree_boot(optarg, o.max_iter)) { std::fprintf(stderr, "ERROR: -i must be in [0, 2147483647]\n"); return 1; } }
-		else return 1;
-	}
-	if (argc - optind < 1) {
-		std::printf("Usage: pangene cluster -k INT[-INT] [options] <in.gfa>\nOptions:\n  -k INT[-INT]  clusters: one k, or a range whose k with the largest mean silhouette is printed in full\n"
-		            "  -t STR   items: gene (gene content) or adj (gene adjacencies of the walks) [gene]\n"
-		            "  -m STR   distance: jaccard or diff [jaccard]\n"
-		            "  -i INT   swap iterations per k at the most [1000]\n");
-		return 0;
-	}
-	if (!have_k) { std::fprintf(stderr, "ERROR: pangene cluster needs -k INT[-INT]\n"); return 1; }
-	return pg_cluster_file(argv[optind], &o) == 0 ? 0 : 1;
+	Row r = plain(l, nullptr, rd_atoi, f, msg, false, lo);
+	r.long_msg = long_msg, r.late = true;
+	return r;
+}
+static constexpr Row spec(char l, const char *suf, size_t f, bool no_file) { return { l, suf, rd_mantel_spec, f, 0, 0, nullptr, "must be gene|adj:jaccard|diff", true, nullptr, no_file }; }
+static constexpr const char *M_TYPE = "must be gene or adj";
+static constexpr const char *M_METRIC = "must be jaccard or diff (shared is not a distance)";
+static constexpr const char *M_PERM = "must be in [0, 2147483646]";
+static constexpr const char *M_INT31 = "must be in [0, 2147483647]";
+static constexpr const char *M_COST = "must be in [1, 255]";
+static constexpr const char *M_UNIT = "must be in [0, 1]";
+static constexpr const char *M_MIN1 = "must be at least 1";
+static constexpr const char *M_NONNEG = "must not be negative";
+static constexpr const char *M_SIGN = "must be pos, neg or both";
+static constexpr const char *M_MODE = "must be late or early";
+
+// pg_NAME_opt_init, pg_NAME_file and pg_write_NAME behind one signature; `side` is the trait or matrix file of the analyses that take one
+struct Calls {
+	void (*init)(AnyOpt *o);
+	int (*file)(const char *gfa_fn, const char *side, const AnyOpt *o);
+	void (*write)(pg_graph_t *g, const char *side, const AnyOpt *o);
+};
+template <class O, void (*Init)(O *), int (*File)(const char *, const O *), void (*Write)(pg_graph_t *, const O *)>
+static constexpr Calls calls()
+{
+	return { [](AnyOpt *o) { Init((O *)o); }, [](const char *fn, const char *, const AnyOpt *o) { return File(fn, (const O *)o); },
+	         [](pg_graph_t *g, const char *, const AnyOpt *o) { Write(g, (const O *)o); } };
+}
+template <class O, void (*Init)(O *), int (*File)(const char *, const char *, const O *), void (*Write)(pg_graph_t *, const char *, const O *)>
+static constexpr Calls calls_side()
+{
+	return { [](AnyOpt *o) { Init((O *)o); }, [](const char *fn, const char *side, const AnyOpt *o) { return File(fn, side, (const O *)o); },
+	         [](pg_graph_t *g, const char *side, const AnyOpt *o) { Write(g, side, (const O *)o); } };
 }
 
-static int assoc_sign(const char *s) { return std::strcmp(s, "both") == 0 ? PG_ASSOC_BOTH : std::strcmp(s, "pos") == 0 ? PG_ASSOC_POS : std::strcmp(s, "neg") == 0 ? PG_ASSOC_NEG : -1; }
-static bool assoc_phi(const char *s, double &r) // a number in [0, 1]
-{
-	char *e;
-	r = std::strtod(s, &e);
-	return e != s && *e == 0 && r >= 0.0 && r <= 1.0;
-}
+enum { MAX_ROWS = 11 };
+enum HeadValue { HEAD_FILE, HEAD_ROW0 }; // the value of --NAME=X: the side file, or what the first row reads
+struct Analysis {
+	const char *name;      // the subcommand, and --NAME
+	const char *head_form; // --NAME as the messages write it
+	bool head_required;    // --NAME=X (and the subcommand cannot do without X either), not --NAME[=X]
+	HeadValue head_value;
+	const char *bare;      // what a --NAME without a value stands for, read by row 0 (nullptr: it leaves the value as it is)
+	char file_letter;      // the side file of the subcommand (0: none)
+	bool refusal_is_1;     // the library's "bad argument" (-3) on the PAF route ends with status 1, not 2
+	Calls calls;
+	void (*usage)(const AnyOpt &o); // of the subcommand, the defaults as pg_NAME_opt_init set them
+	Row rows[MAX_ROWS];
+};
 
-// `pangene assoc`: the gene pairs of a GFA file that travel together over the assemblies or exclude each other
-static int main_assoc(int argc, char *argv[])
-{
-	pg_assoc_opt_t o;
-	pg_assoc_opt_init(&o);
-	int c;
-	while ((c = getopt(argc, argv, "r:c:s:x:")) >= 0) {
-		if (c == 'r') { if (!assoc_phi(optarg, o.min_phi)) { std::fprintf(stderr, "ERROR: -r must be in [0, 1]\n"); return 1; } }
-		else if (c == 'c') { if ((o.min_count = std::atoi(optarg)) < 1) { std::fprintf(stderr, "ERROR: -c must be at least 1\n"); return 1; } }
-		else if (c == 's') { if ((o.sign = assoc_sign(optarg)) < 0) { std::fprintf(stderr, "ERROR: -s must be pos, neg or both\n"); return 1; } }
-		else if (c == 'x') { if ((o.max_pair = std::atoll(optarg)) < 0) { std::fprintf(stderr, "ERROR: -x must not be negative\n"); return 1; } }
-		else return 1;
-	}
-	if (argc - optind < 1) {
+// In the order in which --X refuses the ones before it (after --matrix and --call).  Oddities that are behaviour, kept as data:
+// only the rows marked `extra` are refused without their --NAME (--curves-seed, --dist-metric, --assoc-*, --trait-perm, --trait-seed and
+// --tree-* pass); a --NAME without a value after --NAME=X resets X for curves, dist and tree only (`bare`); the seeds and the counts of curves, assoc, trait and qtrait are read laxly; permanova's items are -T, gainloss
+// resolves ties with -r and coevo with -e; a row without a suffix exists for the subcommand only.
+static const Analysis kAnalyses[] = {
+	{ "curves", "--curves", false, HEAD_ROW0, "10", 0, false, calls<pg_curves_opt_t, pg_curves_opt_init, pg_curves_file, pg_write_curves>(),
+	  [](const AnyOpt &o) {
+		std::printf("Usage: pangene curves [options] <in.gfa>\nOptions:\n  -n INT   orders of the assemblies, the input order first [%d]\n"
+		            "  -s INT   seed of the random orders [%u]\n", o.curves.n_perm, o.curves.seed); },
+	  { late_count('n', offsetof(pg_curves_opt_t, n_perm), 1, M_MIN1, "needs at least one order"),
+	    seed('s', offsetof(pg_curves_opt_t, seed)) } },
+	{ "dist", "--dist", false, HEAD_ROW0, "gene", 0, false, calls<pg_dist_opt_t, pg_dist_opt_init, pg_dist_file, pg_write_dist>(),
+	  [](const AnyOpt &) {
+		std::printf("Usage: pangene dist [options] <in.gfa>\nOptions:\n  -t STR   items: gene (gene content) or adj (gene adjacencies of the walks) [gene]\n"
+		            "  -m STR   metric: jaccard, shared or diff [jaccard]\n  -p       relaxed PHYLIP output\n"); },
+	  { word('t', nullptr, offsetof(pg_dist_opt_t, type), W_TYPE, M_TYPE),
+	    word('m', "metric", offsetof(pg_dist_opt_t, metric), W_DIST_METRIC, "must be jaccard, shared or diff"),
+	    plain('p', nullptr, rd_flag, offsetof(pg_dist_opt_t, phylip), "") } },
+	{ "assoc", "--assoc", false, HEAD_ROW0, nullptr, 0, false, calls<pg_assoc_opt_t, pg_assoc_opt_init, pg_assoc_file, pg_write_assoc>(),
+	  [](const AnyOpt &o) {
 		std::printf("Usage: pangene assoc [options] <in.gfa>\nOptions:\n  -r FLOAT  smallest |phi| of a reported pair, in [0, 1], read as per-mille [%g]\n"
 		            "  -c INT    a gene takes part when it is present in >=INT and absent from >=INT assemblies [%d]\n"
 		            "  -s STR    keep pos (co-occurring), neg (avoiding) or both [both]\n"
-		            "  -x INT    give up when more than INT pairs pass [%lld]\n", o.min_phi, o.min_count, (long long)o.max_pair);
-		return 0;
-	}
-	return pg_assoc_file(argv[optind], &o) == 0 ? 0 : 1;
-}
-
-static bool trait_perm(const char *s, int32_t &n) // an integer in [0, 2^31 - 2]
-{
-	char *e;
-	const long long v = std::strtoll(s, &e, 10);
-	if (e == s || *e != 0 || v < 0 || v > 2147483646ll) return false;
-	n = (int32_t)v;
-	return true;
-}
-
-static int trait_lineage(const char *s) { return std::strcmp(s, "nj") == 0 ? PG_LINEAGE_NJ : std::strcmp(s, "upgma") == 0 ? PG_LINEAGE_UPGMA : -1; }
-
-// `pangene trait`: the association of every gene of a GFA file with the binary traits of a trait file
-static int main_trait(int argc, char *argv[])
-{
-	pg_trait_opt_t o;
-	pg_trait_opt_init(&o);
-	const char *fn = nullptr;
-	int c;
-	while ((c = getopt(argc, argv, "t:n:s:c:p:L:")) >= 0) {
-		if (c == 't') fn = optarg;
-		else if (c == 'n') { if (!trait_perm(optarg, o.n_perm)) { std::fprintf(stderr, "ERROR: -n must be in [0, 2147483646]\n"); return 1; } }
-		else if (c == 's') o.seed = (uint32_t)std::strtoul(optarg, nullptr, 10);
-		else if (c == 'c') { if ((o.min_count = std::atoi(optarg)) < 1) { std::fprintf(stderr, "ERROR: -c must be at least 1\n"); return 1; } }
-		else if (c == 'p') { char *e; o.max_p = std::strtod(optarg, &e); if (e == optarg || *e != 0 || !(o.max_p >= 0.0)) { std::fprintf(stderr, "ERROR: -p must be a number >= 0\n"); return 1; } }
-		else if (c == 'L') { if ((o.lineage = trait_lineage(optarg)) < 0) { std::fprintf(stderr, "ERROR: -L must be nj or upgma\n"); return 1; } }
-		else return 1;
-	}
-	if (argc - optind < 1) {
+		            "  -x INT    give up when more than INT pairs pass [%lld]\n", o.assoc.min_phi, o.assoc.min_count, (long long)o.assoc.max_pair); },
+	  { plain('r', nullptr, rd_unit, offsetof(pg_assoc_opt_t, min_phi), M_UNIT),
+	    plain('c', "min-count", rd_atoi, offsetof(pg_assoc_opt_t, min_count), M_MIN1, false, 1),
+	    word('s', "sign", offsetof(pg_assoc_opt_t, sign), W_SIGN, M_SIGN),
+	    plain('x', nullptr, rd_atoll, offsetof(pg_assoc_opt_t, max_pair), M_NONNEG) } },
+	{ "trait", "--trait=FILE", true, HEAD_FILE, nullptr, 't', false, calls_side<pg_trait_opt_t, pg_trait_opt_init, pg_trait_file, pg_write_trait>(),
+	  [](const AnyOpt &o) {
 		std::printf("Usage: pangene trait -t FILE [options] <in.gfa>\nOptions:\n  -t FILE   traits: a header line (any first field, one name per trait), then per line an assembly and 1, 0 or NA per trait\n"
 		            "  -n INT    label permutations per trait; 0: none [%d]\n  -s INT    seed of the permutations [%u]\n"
 		            "  -c INT    a gene is tested when it is present in >=INT and absent from >=INT assemblies [%d]\n"
 		            "  -p FLOAT  print the genes with p_fisher <= FLOAT [%g]\n"
 		            "  -L STR    lineage-aware test: the pairwise comparisons on the nj or upgma tree of all assemblies (gene content, jaccard);\n"
-		            "            adds the columns pairs, supp, opp, p_pair_best and p_pair_worst [none]\n", o.n_perm, o.seed, o.min_count, o.max_p);
-		return 0;
-	}
-	if (fn == nullptr) { std::fprintf(stderr, "ERROR: pangene trait needs -t FILE\n"); return 1; }
-	return pg_trait_file(argv[optind], fn, &o) == 0 ? 0 : 1;
-}
-
-// `pangene qtrait`: the rank-sum test of every gene of a GFA file against the quantitative traits of a trait file
-static int main_qtrait(int argc, char *argv[])
-{
-	pg_qtrait_opt_t o;
-	pg_qtrait_opt_init(&o);
-	const char *fn = nullptr;
-	int c;
-	while ((c = getopt(argc, argv, "t:n:s:c:p:")) >= 0) {
-		if (c == 't') fn = optarg;
-		else if (c == 'n') { if (!trait_perm(optarg, o.n_perm)) { std::fprintf(stderr, "ERROR: -n must be in [0, 2147483646]\n"); return 1; } }
-		else if (c == 's') o.seed = (uint32_t)std::strtoul(optarg, nullptr, 10);
-		else if (c == 'c') { if ((o.min_count = std::atoi(optarg)) < 1) { std::fprintf(stderr, "ERROR: -c must be at least 1\n"); return 1; } }
-		else if (c == 'p') { char *e; o.max_p = std::strtod(optarg, &e); if (e == optarg || *e != 0 || !(o.max_p >= 0.0)) { std::fprintf(stderr, "ERROR: -p must be a number >= 0\n"); return 1; } }
-		else return 1;
-	}
-	if (argc - optind < 1) {
+		            "            adds the columns pairs, supp, opp, p_pair_best and p_pair_worst [none]\n", o.trait.n_perm, o.trait.seed, o.trait.min_count, o.trait.max_p); },
+	  { i32('n', "perm", offsetof(pg_trait_opt_t, n_perm), 0, INT31 - 1, M_PERM),
+	    seed('s', offsetof(pg_trait_opt_t, seed)),
+	    word('L', "lineage", offsetof(pg_trait_opt_t, lineage), W_LINEAGE, "must be nj or upgma", true),
+	    plain('c', nullptr, rd_atoi, offsetof(pg_trait_opt_t, min_count), M_MIN1, false, 1),
+	    plain('p', nullptr, rd_nonneg, offsetof(pg_trait_opt_t, max_p), "must be a number >= 0") } },
+	{ "tree", "--tree", false, HEAD_ROW0, "gene", 0, false, calls<pg_tree_opt_t, pg_tree_opt_init, pg_tree_file, pg_write_tree>(),
+	  [](const AnyOpt &) {
+		std::printf("Usage: pangene tree [options] <in.gfa>\nOptions:\n  -t STR   items: gene (gene content) or adj (gene adjacencies of the walks) [gene]\n"
+		            "  -m STR   distance: jaccard or diff [jaccard]\n"
+		            "  -a STR   nj (neighbour-joining: unrooted, negative branch lengths are printed as they come) or upgma [nj]\n"
+		            "  -b INT   bootstrap replicates over the items: inner nodes are labelled with their support in per cent [0]\n"
+		            "  -s INT   seed of the bootstrap draws [0]\n"); },
+	  { word('t', nullptr, offsetof(pg_tree_opt_t, type), W_TYPE, M_TYPE),
+	    word('m', "metric", offsetof(pg_tree_opt_t, metric), W_METRIC, M_METRIC),
+	    word('a', "method", offsetof(pg_tree_opt_t, method), W_METHOD, "must be nj or upgma"),
+	    i32('b', "boot", offsetof(pg_tree_opt_t, n_boot), 0, INT31, M_INT31),
+	    plain('s', "seed", rd_u32, offsetof(pg_tree_opt_t, seed), "must be in [0, 4294967295]") } },
+	{ "qtrait", "--qtrait=FILE", true, HEAD_FILE, nullptr, 't', false, calls_side<pg_qtrait_opt_t, pg_qtrait_opt_init, pg_qtrait_file, pg_write_qtrait>(),
+	  [](const AnyOpt &o) {
 		std::printf("Usage: pangene qtrait -t FILE [options] <in.gfa>\nOptions:\n  -t FILE   traits: a header line (any first field, one name per trait), then per line an assembly and a number or NA per trait\n"
 		            "  -n INT    permutations of the values per trait; 0: none [%d]\n  -s INT    seed of the permutations [%u]\n"
 		            "  -c INT    a gene is tested when it is present in >=INT and absent from >=INT assemblies [%d]\n"
-		            "  -p FLOAT  print the genes with p_wilcox <= FLOAT [%g]\n", o.n_perm, o.seed, o.min_count, o.max_p);
-		return 0;
-	}
-	if (fn == nullptr) { std::fprintf(stderr, "ERROR: pangene qtrait needs -t FILE\n"); return 1; }
-	return pg_qtrait_file(argv[optind], fn, &o) == 0 ? 0 : 1;
-}
-
-// `pangene permanova`: the two-group PERMANOVA of the assemblies' distances for every binary trait of a trait file
-static int main_permanova(int argc, char *argv[])
-{
-	pg_permanova_opt_t o;
-	pg_permanova_opt_init(&o);
-	const char *fn = nullptr;
-	int c;
-	while ((c = getopt(argc, argv, "t:T:m:n:s:")) >= 0) {
-		if (c == 't') fn = optarg;
-		else if (c == 'T') { if ((o.type = dist_type(optarg)) < 0) { std::fprintf(stderr, "ERROR: -T must be gene or adj\n"); return 1; } }
-		else if (c == 'm') { if ((o.metric = tree_metric(optarg)) < 0) { std::fprintf(stderr, "ERROR: -m must be jaccard or diff (shared is not a distance)\n"); return 1; } }
-		else if (c == 'n') { if (!trait_perm(optarg, o.n_perm)) { std::fprintf(stderr, "ERROR: -n must be in [0, 2147483646]\n"); return 1; } }
-		else if (c == 's') o.seed = (uint32_t)std::strtoul(optarg, nullptr, 10);
-		else return 1;
-	}
-	if (argc - optind < 1) {
+		            "  -p FLOAT  print the genes with p_wilcox <= FLOAT [%g]\n", o.qtrait.n_perm, o.qtrait.seed, o.qtrait.min_count, o.qtrait.max_p); },
+	  { i32('n', "perm", offsetof(pg_qtrait_opt_t, n_perm), 0, INT31 - 1, M_PERM, true),
+	    seed('s', offsetof(pg_qtrait_opt_t, seed), true),
+	    plain('c', nullptr, rd_atoi, offsetof(pg_qtrait_opt_t, min_count), M_MIN1, false, 1),
+	    plain('p', nullptr, rd_nonneg, offsetof(pg_qtrait_opt_t, max_p), "must be a number >= 0") } },
+	{ "cluster", "--cluster=INT[-INT]", true, HEAD_ROW0, nullptr, 0, true, calls<pg_cluster_opt_t, pg_cluster_opt_init, pg_cluster_file, pg_write_cluster>(),
+	  [](const AnyOpt &) {
+		std::printf("Usage: pangene cluster -k INT[-INT] [options] <in.gfa>\nOptions:\n  -k INT[-INT]  clusters: one k, or a range whose k with the largest mean silhouette is printed in full\n"
+		            "  -t STR   items: gene (gene content) or adj (gene adjacencies of the walks) [gene]\n"
+		            "  -m STR   distance: jaccard or diff [jaccard]\n"
+		            "  -i INT   swap iterations per k at the most [1000]\n"); },
+	  { plain('k', nullptr, rd_cluster_range, offsetof(pg_cluster_opt_t, k_lo), "must be INT or INT-INT with 2 <= INT"),
+	    word('t', "type", offsetof(pg_cluster_opt_t, type), W_TYPE, M_TYPE, true),
+	    word('m', "metric", offsetof(pg_cluster_opt_t, metric), W_METRIC, M_METRIC, true),
+	    i32('i', "iter", offsetof(pg_cluster_opt_t, max_iter), 0, INT31, M_INT31, true) } },
+	{ "permanova", "--permanova=FILE", true, HEAD_FILE, nullptr, 't', false, calls_side<pg_permanova_opt_t, pg_permanova_opt_init, pg_permanova_file, pg_write_permanova>(),
+	  [](const AnyOpt &o) {
 		std::printf("Usage: pangene permanova -t FILE [options] <in.gfa>\nOptions:\n  -t FILE   traits: a header line (any first field, one name per trait), then per line an assembly and 1, 0 or NA per trait\n"
 		            "  -T STR    items: gene (gene content) or adj (gene adjacencies of the walks) [gene]\n"
 		            "  -m STR    distance: jaccard or diff [jaccard]\n"
-		            "  -n INT    label permutations per trait; 0: none [%d]\n  -s INT    seed of the permutations [%u]\n", o.n_perm, o.seed);
-		return 0;
-	}
-	if (fn == nullptr) { std::fprintf(stderr, "ERROR: pangene permanova needs -t FILE\n"); return 1; }
-	return pg_permanova_file(argv[optind], fn, &o) == 0 ? 0 : 1;
-}
-
-// SPEC of `pangene mantel`: gene|adj + ':' + jaccard|diff
-static bool mantel_spec(const char *s, int32_t &type, int32_t &metric)
-{
-	const char *c = std::strchr(s, ':');
-	if (c == nullptr) return false;
-	const std::string t(s, c);
-	const int ty = dist_type(t.c_str()), me = tree_metric(c + 1);
-	if (ty < 0 || me < 0) return false;
-	type = ty, metric = me;
-	return true;
-}
-
-// `pangene mantel`: the Mantel test of two distance matrices of the assemblies of a GFA file, or of one of them and a matrix file
-static int main_mantel(int argc, char *argv[])
-{
-	pg_mantel_opt_t o;
-	pg_mantel_opt_init(&o);
-	const char *fn = nullptr;
-	bool have_y = false;
-	int c;
-	while ((c = getopt(argc, argv, "x:y:f:n:s:")) >= 0) {
-		if (c == 'x') { if (!mantel_spec(optarg, o.x_type, o.x_metric)) { std::fprintf(stderr, "ERROR: -x must be gene|adj:jaccard|diff\n"); return 1; } }
-		else if (c == 'y') { have_y = true; if (!mantel_spec(optarg, o.y_type, o.y_metric)) { std::fprintf(stderr, "ERROR: -y must be gene|adj:jaccard|diff\n"); return 1; } }
-		else if (c == 'f') fn = optarg;
-		else if (c == 'n') { if (!trait_perm(optarg, o.n_perm)) { std::fprintf(stderr, "ERROR: -n must be in [0, 2147483646]\n"); return 1; } }
-		else if (c == 's') o.seed = (uint32_t)std::strtoul(optarg, nullptr, 10);
-		else return 1;
-	}
-	if (argc - optind < 1) {
+		            "  -n INT    label permutations per trait; 0: none [%d]\n  -s INT    seed of the permutations [%u]\n", o.permanova.n_perm, o.permanova.seed); },
+	  { word('T', "type", offsetof(pg_permanova_opt_t, type), W_TYPE, M_TYPE, true),
+	    word('m', "metric", offsetof(pg_permanova_opt_t, metric), W_METRIC, M_METRIC, true),
+	    i32('n', "perm", offsetof(pg_permanova_opt_t, n_perm), 0, INT31 - 1, M_PERM, true),
+	    seed('s', offsetof(pg_permanova_opt_t, seed), true) } },
+	{ "mantel", "--mantel", false, HEAD_FILE, nullptr, 'f', false, calls_side<pg_mantel_opt_t, pg_mantel_opt_init, pg_mantel_file, pg_write_mantel>(),
+	  [](const AnyOpt &o) {
 		std::printf("Usage: pangene mantel [options] <in.gfa>\nOptions:\n  -x SPEC   the first matrix: gene (gene content) or adj (gene adjacencies of the walks), ':', jaccard or diff [gene:jaccard]\n"
 		            "  -y SPEC   the second matrix [adj:jaccard]\n"
 		            "  -f FILE   the second matrix from FILE instead: the table or the PHYLIP form `pangene dist` prints\n"
-		            "  -n INT    permutations of the assemblies; 0: none [%d]\n  -s INT    seed of the permutations [%u]\n", o.n_perm, o.seed);
-		return 0;
-	}
-	if (have_y && fn != nullptr) { std::fprintf(stderr, "ERROR: -y cannot be combined with -f\n"); return 1; }
-	return pg_mantel_file(argv[optind], fn, &o) == 0 ? 0 : 1;
-}
-
-static bool gainloss_cost(const char *s, int32_t &v) // an integer in [1, 255]
-{
-	char *e;
-	const long long x = std::strtoll(s, &e, 10);
-	if (e == s || *e != 0 || x < 1 || x > 255) return false;
-	v = (int32_t)x;
-	return true;
-}
-static int gainloss_mode(const char *s) { return std::strcmp(s, "late") == 0 ? PG_GAINLOSS_LATE : std::strcmp(s, "early") == 0 ? PG_GAINLOSS_EARLY : -1; }
-static int gainloss_out(const char *s) { return std::strcmp(s, "gene") == 0 ? PG_GAINLOSS_GENE : std::strcmp(s, "node") == 0 ? PG_GAINLOSS_NODE : -1; }
-
-// `pangene gainloss`: the gains and losses of every item of a GFA file on the tree `pangene tree` builds over its assemblies
-static int main_gainloss(int argc, char *argv[])
-{
-	pg_gainloss_opt_t o;
-	pg_gainloss_opt_init(&o);
-	int c;
-	while ((c = getopt(argc, argv, "t:m:a:g:l:r:o:c:")) >= 0) {
-		if (c == 't') { if ((o.type = dist_type(optarg)) < 0) { std::fprintf(stderr, "ERROR: -t must be gene or adj\n"); return 1; } }
-		else if (c == 'm') { if ((o.metric = tree_metric(optarg)) < 0) { std::fprintf(stderr, "ERROR: -m must be jaccard or diff (shared is not a distance)\n"); return 1; } }
-		else if (c == 'a') { if ((o.method = tree_method(optarg)) < 0) { std::fprintf(stderr, "ERROR: -a must be upgma or nj\n"); return 1; } }
-		else if (c == 'g') { if (!gainloss_cost(optarg, o.gain)) { std::fprintf(stderr, "ERROR: -g must be in [1, 255]\n"); return 1; } }
-		else if (c == 'l') { if (!gainloss_cost(optarg, o.loss)) { std::fprintf(stderr, "ERROR: -l must be in [1, 255]\n"); return 1; } }
-		else if (c == 'r') { if ((o.mode = gainloss_mode(optarg)) < 0) { std::fprintf(stderr, "ERROR: -r must be late or early\n"); return 1; } }
-		else if (c == 'o') { if ((o.out = gainloss_out(optarg)) < 0) { std::fprintf(stderr, "ERROR: -o must be gene or node\n"); return 1; } }
-		else if (c == 'c') { if (!tree_boot(optarg, o.min_changes)) { std::fprintf(stderr, "ERROR: -c must be in [0, 2147483647]\n"); return 1; } }
-		else return 1;
-	}
-	if (argc - optind < 1) {
+		            "  -n INT    permutations of the assemblies; 0: none [%d]\n  -s INT    seed of the permutations [%u]\n", o.mantel.n_perm, o.mantel.seed); },
+	  { spec('x', "x", offsetof(pg_mantel_opt_t, x_type), false),
+	    spec('y', "y", offsetof(pg_mantel_opt_t, y_type), true), // (-y and the file both name the second matrix)
+	    i32('n', "perm", offsetof(pg_mantel_opt_t, n_perm), 0, INT31 - 1, M_PERM, true),
+	    seed('s', offsetof(pg_mantel_opt_t, seed), true) } },
+	{ "gainloss", "--gainloss", false, HEAD_ROW0, nullptr, 0, false, calls<pg_gainloss_opt_t, pg_gainloss_opt_init, pg_gainloss_file, pg_write_gainloss>(),
+	  [](const AnyOpt &o) {
 		std::printf("Usage: pangene gainloss [options] <in.gfa>\nOptions:\n  -t STR   items: gene (gene content) or adj (gene adjacencies of the walks) [gene]\n"
 		            "  -m STR   distance of the tree: jaccard or diff [jaccard]\n"
 		            "  -a STR   tree: upgma, or nj rooted at its closing join, read as ((x, y), z): gains and losses depend on that reading [upgma]\n"
 		            "  -g INT   cost of a gain, 1 to 255 [%d]\n  -l INT   cost of a loss, 1 to 255 [%d]\n"
 		            "  -r STR   on a tie a change sits towards the tips (late) or towards the root (early) [late]\n"
 		            "  -o STR   table: gene (per item: Present Cost Changes Gains Losses Root) or node (per branch: Leaves Present Gains Losses) [gene]\n"
-		            "  -c INT   -o gene: print the items with at least INT changes [%d]\n", o.gain, o.loss, o.min_changes);
-		return 0;
-	}
-	return pg_gainloss_file(argv[optind], &o) == 0 ? 0 : 1;
-}
-
-static bool coevo_min(const char *s, int32_t &v) // an integer in [1, 2^31 - 1]
-{
-	char *e;
-	const long long x = std::strtoll(s, &e, 10);
-	if (e == s || *e != 0 || x < 1 || x > 2147483647LL) return false;
-	v = (int32_t)x;
-	return true;
-}
-static bool coevo_max(const char *s, int64_t &v) // a whole number
-{
-	char *e;
-	const long long x = std::strtoll(s, &e, 10);
-	if (e == s || *e != 0 || x < 0) return false;
-	v = x;
-	return true;
-}
-
-// `pangene coevo`: the item pairs of a GFA file whose gains and losses fall on the same branches of the tree `pangene tree` builds
-static int main_coevo(int argc, char *argv[])
-{
-	pg_coevo_opt_t o;
-	pg_coevo_opt_init(&o);
-	int c;
-	while ((c = getopt(argc, argv, "t:m:a:g:l:e:r:c:s:x:")) >= 0) {
-		if (c == 't') { if ((o.type = dist_type(optarg)) < 0) { std::fprintf(stderr, "ERROR: -t must be gene or adj\n"); return 1; } }
-		else if (c == 'm') { if ((o.metric = tree_metric(optarg)) < 0) { std::fprintf(stderr, "ERROR: -m must be jaccard or diff (shared is not a distance)\n"); return 1; } }
-		else if (c == 'a') { if ((o.method = tree_method(optarg)) < 0) { std::fprintf(stderr, "ERROR: -a must be upgma or nj\n"); return 1; } }
-		else if (c == 'g') { if (!gainloss_cost(optarg, o.gain)) { std::fprintf(stderr, "ERROR: -g must be in [1, 255]\n"); return 1; } }
-		else if (c == 'l') { if (!gainloss_cost(optarg, o.loss)) { std::fprintf(stderr, "ERROR: -l must be in [1, 255]\n"); return 1; } }
-		else if (c == 'e') { if ((o.mode = gainloss_mode(optarg)) < 0) { std::fprintf(stderr, "ERROR: -e must be late or early\n"); return 1; } }
-		else if (c == 'r') { if (!assoc_phi(optarg, o.min_r)) { std::fprintf(stderr, "ERROR: -r must be in [0, 1]\n"); return 1; } }
-		else if (c == 'c') { if (!coevo_min(optarg, o.min_events)) { std::fprintf(stderr, "ERROR: -c must be at least 1\n"); return 1; } }
-		else if (c == 's') { if ((o.sign = assoc_sign(optarg)) < 0) { std::fprintf(stderr, "ERROR: -s must be pos, neg or both\n"); return 1; } }
-		else if (c == 'x') { if (!coevo_max(optarg, o.max_pair)) { std::fprintf(stderr, "ERROR: -x must not be negative\n"); return 1; } }
-		else return 1;
-	}
-	if (argc - optind < 1) {
+		            "  -c INT   -o gene: print the items with at least INT changes [%d]\n", o.gainloss.gain, o.gainloss.loss, o.gainloss.min_changes); },
+	  { word('o', nullptr, offsetof(pg_gainloss_opt_t, out), W_OUT, "must be gene or node"),
+	    word('t', "type", offsetof(pg_gainloss_opt_t, type), W_TYPE, M_TYPE, true),
+	    word('m', "metric", offsetof(pg_gainloss_opt_t, metric), W_METRIC, M_METRIC, true),
+	    word('a', "method", offsetof(pg_gainloss_opt_t, method), W_METHOD, "must be upgma or nj", true),
+	    i32('g', "gain", offsetof(pg_gainloss_opt_t, gain), 1, 255, M_COST, true),
+	    i32('l', "loss", offsetof(pg_gainloss_opt_t, loss), 1, 255, M_COST, true),
+	    word('r', "resolve", offsetof(pg_gainloss_opt_t, mode), W_MODE, M_MODE, true),
+	    i32('c', "min", offsetof(pg_gainloss_opt_t, min_changes), 0, INT31, M_INT31, true) } },
+	{ "coevo", "--coevo", false, HEAD_ROW0, nullptr, 0, false, calls<pg_coevo_opt_t, pg_coevo_opt_init, pg_coevo_file, pg_write_coevo>(),
+	  [](const AnyOpt &o) {
 		std::printf("Usage: pangene coevo [options] <in.gfa>\nOptions:\n  -t STR    items: gene (gene content) or adj (gene adjacencies of the walks) [gene]\n"
 		            "  -m STR    distance of the tree: jaccard or diff [jaccard]\n"
 		            "  -a STR    tree: upgma, or nj rooted at its closing join, read as ((x, y), z): the events depend on that reading [upgma]\n"
@@ -563,10 +453,136 @@ static int main_coevo(int argc, char *argv[])
 		            "  -r FLOAT  smallest |r| of a reported pair, in [0, 1], read as per-mille [%g]\n"
 		            "  -c INT    an item takes part with at least INT gains and losses; with 1 every pair of strain-specific genes of one assembly scores 1 [%d]\n"
 		            "  -s STR    keep pos (same direction), neg (opposite direction) or both [both]\n"
-		            "  -x INT    give up when more than INT pairs pass [%lld]\n", o.gain, o.loss, o.min_r, o.min_events, (long long)o.max_pair);
-		return 0;
+		            "  -x INT    give up when more than INT pairs pass [%lld]\n", o.coevo.gain, o.coevo.loss, o.coevo.min_r, o.coevo.min_events, (long long)o.coevo.max_pair); },
+	  { plain('r', nullptr, rd_unit, offsetof(pg_coevo_opt_t, min_r), M_UNIT),
+	    word('t', "type", offsetof(pg_coevo_opt_t, type), W_TYPE, M_TYPE, true),
+	    word('m', "metric", offsetof(pg_coevo_opt_t, metric), W_METRIC, M_METRIC, true),
+	    word('a', "method", offsetof(pg_coevo_opt_t, method), W_METHOD, "must be upgma or nj", true),
+	    i32('g', "gain", offsetof(pg_coevo_opt_t, gain), 1, 255, M_COST, true),
+	    i32('l', "loss", offsetof(pg_coevo_opt_t, loss), 1, 255, M_COST, true),
+	    word('e', "resolve", offsetof(pg_coevo_opt_t, mode), W_MODE, M_MODE, true),
+	    i32('c', "min", offsetof(pg_coevo_opt_t, min_events), 1, INT31, M_MIN1, true),
+	    word('s', "sign", offsetof(pg_coevo_opt_t, sign), W_SIGN, M_SIGN, true),
+	    i64('x', "max", offsetof(pg_coevo_opt_t, max_pair), 0, LLONG_MAX, M_NONNEG, true) } },
+};
+enum { N_ANALYSES = sizeof(kAnalyses) / sizeof(kAnalyses[0]) };
+
+static void *field_of(AnyOpt &o, const Row &r) { return (char *)&o + r.field; }
+
+// `pangene NAME [options] <in.gfa>`
+static int main_analysis(const Analysis &a, int argc, char *argv[])
+{
+	AnyOpt o;
+	a.calls.init(&o);
+	char letters[2 * MAX_ROWS + 3], *p = letters;
+	if (a.file_letter) *p++ = a.file_letter, *p++ = ':';
+	for (const Row *r = a.rows; r->read; ++r) if (r->letter) { *p++ = r->letter; if (r->read != rd_flag) *p++ = ':'; }
+	*p = 0;
+	const char *side = nullptr;
+	const Row *no_file = nullptr;
+	bool have_row0 = false;
+	int c;
+	while ((c = getopt(argc, argv, letters)) >= 0) {
+		if (c == a.file_letter) { side = optarg; continue; }
+		const Row *r = a.rows;
+		while (r->read && r->letter != c) ++r;
+		if (r->read == nullptr) return 1; // (getopt has said what is wrong)
+		if (r->no_file) no_file = r;
+		const bool ok = r->read(optarg, field_of(o, *r), *r);
+		if (!ok && !r->late) { std::fprintf(stderr, "ERROR: -%c %s\n", c, r->msg); return 1; }
+		if (r == a.rows) have_row0 = ok;
 	}
-	return pg_coevo_file(argv[optind], &o) == 0 ? 0 : 1;
+	for (const Row *r = a.rows; r->read; ++r)
+		if (r->late && *(const int32_t *)field_of(o, *r) < r->lo) { std::fprintf(stderr, "ERROR: -%c %s\n", r->letter, r->msg); return 1; }
+	if (argc - optind < 1) { a.usage(o); return 0; }
+	if (a.head_required && !(a.head_value == HEAD_FILE ? side != nullptr : have_row0)) {
+		std::fprintf(stderr, "ERROR: pangene %s needs -%c %s\n", a.name, a.head_value == HEAD_FILE ? a.file_letter : a.rows[0].letter, std::strchr(a.head_form, '=') + 1);
+		return 1;
+	}
+	if (no_file && side) { std::fprintf(stderr, "ERROR: -%c cannot be combined with -%c\n", no_file->letter, a.file_letter); return 1; }
+	return a.calls.file(argv[optind], side, &o) == 0 ? 0 : 1;
+}
+
+// `pangene --NAME[=X] --NAME-suffix=X ...`: what the options of one analysis have said so far.  Every analysis keeps its own, as a
+// --NAME-suffix may come before its --NAME or, for the rows that are not `extra`, without it.
+struct Parsed { AnyOpt opt; const char *side = nullptr; bool asked = false, extra = false; const Row *no_file = nullptr; };
+
+// the codes getopt_long returns for them: LONG_BASE + analysis * LONG_STRIDE for --NAME, + 1 + row for --NAME-suffix
+enum { LONG_BASE = 1000, LONG_STRIDE = MAX_ROWS + 1, N_FIXED_LONG = 8 };
+static struct option g_long[N_FIXED_LONG + N_ANALYSES * LONG_STRIDE + 1];
+static char g_long_name[N_ANALYSES * MAX_ROWS][32];
+
+static void long_options_init() // the reference's own options around the table's, in the order of the usage text
+{
+	static const struct option first[] = { { "bed", optional_argument, nullptr, 301 }, { "ori-sc", no_argument, nullptr, 302 }, { "matrix", optional_argument, nullptr, 303 },
+		{ "call", no_argument, nullptr, 305 } };
+	static const struct option last[] = { { "gpus", required_argument, nullptr, 304 }, { "procs", required_argument, nullptr, 304 }, { "version", no_argument, nullptr, 401 },
+		{ nullptr, 0, nullptr, 0 } };
+	struct option *lo = g_long;
+	int n_name = 0;
+	for (const struct option &f : first) *lo++ = f;
+	for (int i = 0; i < N_ANALYSES; ++i) {
+		const Analysis &a = kAnalyses[i];
+		*lo++ = { a.name, a.head_required ? required_argument : optional_argument, nullptr, LONG_BASE + i * LONG_STRIDE };
+		for (int k = 0; a.rows[k].read; ++k) {
+			if (a.rows[k].suffix == nullptr) continue;
+			std::snprintf(g_long_name[n_name], sizeof(g_long_name[0]), "%s-%s", a.name, a.rows[k].suffix);
+			*lo++ = { g_long_name[n_name++], required_argument, nullptr, LONG_BASE + i * LONG_STRIDE + 1 + k };
+		}
+	}
+	for (const struct option &l : last) *lo++ = l;
+}
+
+static bool long_option(int code, const char *arg, Parsed *parsed) // false: refused, and said why
+{
+	const int i = (code - LONG_BASE) / LONG_STRIDE, k = (code - LONG_BASE) % LONG_STRIDE - 1;
+	const Analysis &a = kAnalyses[i];
+	Parsed &p = parsed[i];
+	const Row *r = k < 0 ? a.rows : &a.rows[k];
+	if (k < 0) { // --NAME[=X]
+		p.asked = true;
+		if (a.head_value == HEAD_FILE) p.side = arg;
+		if (a.head_value == HEAD_FILE) return true;
+		if (arg == nullptr && (arg = a.bare) == nullptr) return true; // (a later --curves, --dist or --tree without a value is the default again; --assoc, --gainloss and --coevo keep what an earlier one said)
+	} else {
+		if (r->extra) p.extra = true;
+		if (r->no_file) p.no_file = r;
+	}
+	if (r->read(arg, field_of(p.opt, *r), *r)) return true;
+	std::fprintf(stderr, "ERROR: --%s%s%s %s\n", a.name, k < 0 ? "" : "-", k < 0 ? "" : r->suffix, r->long_msg ? r->long_msg : r->msg);
+	return false;
+}
+
+// After parsing: --X cannot be combined with anything before it in the table (--matrix and --call come first), and the `extra` rows need
+// their --X.  One analysis after the other, so that of two mistakes the one reported is the one that always was.
+static bool check_analyses(const Parsed *parsed, bool matrix, bool call, int &which) // false: refused, and said why; which: the one asked for, or -1
+{
+	const char *before[2 + N_ANALYSES] = { "matrix", "call" }; // (--matrix --call together pass, and the matrix is printed)
+	int n_before = 2;
+	bool any = matrix || call;
+	which = -1;
+	for (int i = 0; i < N_ANALYSES; ++i) {
+		const Analysis &a = kAnalyses[i];
+		const Parsed &p = parsed[i];
+		if (p.asked && any) {
+			std::fprintf(stderr, "ERROR: --%s cannot be combined with", a.name);
+			for (int k = 0; k < n_before; ++k) std::fprintf(stderr, "%s--%s", k == 0 ? " " : k == n_before - 1 ? " or " : ", ", before[k]);
+			std::fputc('\n', stderr);
+			return false;
+		}
+		if (p.extra && !p.asked) {
+			int n = 0, k = 0;
+			for (const Row *r = a.rows; r->read; ++r) n += r->extra;
+			std::fprintf(stderr, "ERROR:");
+			for (const Row *r = a.rows; r->read; ++r) if (r->extra) { std::fprintf(stderr, "%s--%s-%s", k == 0 ? " " : k == n - 1 ? " and " : ", ", a.name, r->suffix); ++k; }
+			std::fprintf(stderr, " %s %s\n", n == 1 ? "needs" : "need", a.head_form);
+			return false;
+		}
+		if (p.no_file && p.side) { std::fprintf(stderr, "ERROR: --%s-%s cannot be combined with --%s=FILE\n", a.name, p.no_file->suffix, a.name); return false; }
+		if (p.asked) which = i, any = true;
+		before[n_before++] = a.name;
+	}
+	return true;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -577,16 +593,8 @@ static int main_coevo(int argc, char *argv[])
 // tests) it is a shared-memory region mapped before the fork.  Rank 0 prints the graph; every rank writes the lines of its own
 // genomes to a temporary file that rank 0 copies to stdout in rank order.
 // ---------------------------------------------------------------------------------------------------------------
-struct Output { int matrix = 0; bool call = false; int curves = 0; uint32_t curves_seed = 11; int dist = -1, dist_metric = 0; // curves: orders (0: none); dist: PG_DIST_* (-1: none)
-	bool assoc = false; double assoc_phi = 0.8; int assoc_count = 2, assoc_sign = 0;
-	const char *trait = nullptr; int32_t trait_perm = 1000; uint32_t trait_seed = 11; int trait_lineage = 0;
-	const char *qtrait = nullptr; int32_t qtrait_perm = 1000; uint32_t qtrait_seed = 11;
-	int tree = -1, tree_metric = 0, tree_method = 0; int32_t tree_boot = 0; uint32_t tree_seed = 0; // tree: PG_DIST_GENE / PG_DIST_ADJ (-1: none)
-	int32_t cluster_lo = 0, cluster_hi = 0, cluster_iter = 1000; int cluster_type = 0, cluster_metric = 0; // cluster_lo: 0 = none
-	const char *permanova = nullptr; int permanova_type = 0, permanova_metric = 0; int32_t permanova_perm = 1000; uint32_t permanova_seed = 11;
-	bool mantel = false; const char *mantel_file = nullptr; pg_mantel_opt_t mantel_opt;
-	bool gainloss = false; pg_gainloss_opt_t gainloss_opt;
-	bool coevo = false; pg_coevo_opt_t coevo_opt; };
+// what to print instead of the graph: the matrix, the bubbles, or one analysis with its options and its side file
+struct Output { int matrix = 0; bool call = false; const Analysis *analysis = nullptr; AnyOpt opt; const char *side = nullptr; }; // matrix: 1 presence, 2 counts
 
 static int run_path(pg_opt_t &opt, int n_files, char **files, const uint8_t *ids_only, const Output &o, bool graph_lines, bool own_lines, int device = -1)
 {
@@ -617,73 +625,9 @@ static int run_path(pg_opt_t &opt, int n_files, char **files, const uint8_t *ids
 		if (pg_last_error()) rc = 2;
 		else if (o.matrix) pg_write_matrix(g, o.matrix == 2);
 		else if (o.call) { pg_call_opt_t co; pg_call_opt_init(&co); pg_write_call(g, &co); if (pg_last_error()) rc = 2; }
-		else if (o.curves) {
-			pg_curves_opt_t co;
-			pg_curves_opt_init(&co);
-			co.n_perm = o.curves, co.seed = o.curves_seed;
-			pg_write_curves(g, &co);
-			if (pg_last_error()) rc = 2;
-		}
-		else if (o.dist >= 0) {
-			pg_dist_opt_t dop;
-			pg_dist_opt_init(&dop);
-			dop.type = o.dist, dop.metric = o.dist_metric;
-			pg_write_dist(g, &dop);
-			if (pg_last_error()) rc = 2;
-		}
-		else if (o.assoc) {
-			pg_assoc_opt_t ao;
-			pg_assoc_opt_init(&ao);
-			ao.min_phi = o.assoc_phi, ao.min_count = o.assoc_count, ao.sign = o.assoc_sign;
-			pg_write_assoc(g, &ao);
-			if (pg_last_error()) rc = 2;
-		}
-		else if (o.trait) {
-			pg_trait_opt_t to;
-			pg_trait_opt_init(&to);
-			to.n_perm = o.trait_perm, to.seed = o.trait_seed, to.lineage = o.trait_lineage;
-			pg_write_trait(g, o.trait, &to);
-			if (pg_last_error()) rc = 2;
-		}
-		else if (o.qtrait) {
-			pg_qtrait_opt_t qo;
-			pg_qtrait_opt_init(&qo);
-			qo.n_perm = o.qtrait_perm, qo.seed = o.qtrait_seed;
-			pg_write_qtrait(g, o.qtrait, &qo);
-			if (pg_last_error()) rc = 2;
-		}
-		else if (o.tree >= 0) {
-			pg_tree_opt_t tro;
-			pg_tree_opt_init(&tro);
-			tro.type = o.tree, tro.metric = o.tree_metric, tro.method = o.tree_method, tro.n_boot = o.tree_boot, tro.seed = o.tree_seed;
-			pg_write_tree(g, &tro);
-			if (pg_last_error()) rc = 2;
-		}
-		else if (o.cluster_lo) {
-			pg_cluster_opt_t clo;
-			pg_cluster_opt_init(&clo);
-			clo.type = o.cluster_type, clo.metric = o.cluster_metric, clo.k_lo = o.cluster_lo, clo.k_hi = o.cluster_hi, clo.max_iter = o.cluster_iter;
-			pg_write_cluster(g, &clo);
-			if (pg_last_error()) rc = pg_last_error() == -3 ? 1 : 2; // -3, PGA_ERR_ARG: a k outside [2, assemblies - 1] or fewer than 3 assemblies -- a refusal, as on `pangene cluster`
-		}
-		else if (o.permanova) {
-			pg_permanova_opt_t po;
-			pg_permanova_opt_init(&po);
-			po.type = o.permanova_type, po.metric = o.permanova_metric, po.n_perm = o.permanova_perm, po.seed = o.permanova_seed;
-			pg_write_permanova(g, o.permanova, &po);
-			if (pg_last_error()) rc = 2;
-		}
-		else if (o.mantel) {
-			pg_write_mantel(g, o.mantel_file, &o.mantel_opt);
-			if (pg_last_error()) rc = 2;
-		}
-		else if (o.gainloss) {
-			pg_write_gainloss(g, &o.gainloss_opt);
-			if (pg_last_error()) rc = 2;
-		}
-		else if (o.coevo) {
-			pg_write_coevo(g, &o.coevo_opt);
-			if (pg_last_error()) rc = 2;
+		else if (o.analysis) {
+			o.analysis->calls.write(g, o.side, &o.opt);
+			if (pg_last_error()) rc = o.analysis->refusal_is_1 && pg_last_error() == -3 ? 1 : 2; // (cluster's -3, PGA_ERR_ARG: a k outside [2, assemblies - 1] or fewer than 3 assemblies -- a refusal, as on `pangene cluster`)
 		}
 		else if (opt.flag & PG_F_WRITE_BED_WALK) { if (own_lines) pg_write_bed(d, 1); }
 		else if (opt.flag & PG_F_WRITE_BED_FLAG) { if (own_lines) pg_write_bed(d, 0); }
@@ -742,19 +686,8 @@ static std::vector<int> partition_files(int W, int n_files, char **files)
 
 static int run_sharded(pg_opt_t &opt, int W, int n_files, char **files, const Output &o)
 {
-	if (o.matrix) { std::fprintf(stderr, "ERROR: --matrix needs every genome in one process; run it without --gpus\n"); return 1; }
-	if (o.call) { std::fprintf(stderr, "ERROR: --call needs every genome in one process; run it without --gpus\n"); return 1; }
-	if (o.curves) { std::fprintf(stderr, "ERROR: --curves needs every genome in one process; run it without --gpus\n"); return 1; }
-	if (o.dist >= 0) { std::fprintf(stderr, "ERROR: --dist needs every genome in one process; run it without --gpus\n"); return 1; }
-	if (o.assoc) { std::fprintf(stderr, "ERROR: --assoc needs every genome in one process; run it without --gpus\n"); return 1; }
-	if (o.trait) { std::fprintf(stderr, "ERROR: --trait needs every genome in one process; run it without --gpus\n"); return 1; }
-	if (o.qtrait) { std::fprintf(stderr, "ERROR: --qtrait needs every genome in one process; run it without --gpus\n"); return 1; }
-	if (o.tree >= 0) { std::fprintf(stderr, "ERROR: --tree needs every genome in one process; run it without --gpus\n"); return 1; }
-	if (o.cluster_lo) { std::fprintf(stderr, "ERROR: --cluster needs every genome in one process; run it without --gpus\n"); return 1; }
-	if (o.permanova) { std::fprintf(stderr, "ERROR: --permanova needs every genome in one process; run it without --gpus\n"); return 1; }
-	if (o.mantel) { std::fprintf(stderr, "ERROR: --mantel needs every genome in one process; run it without --gpus\n"); return 1; }
-	if (o.gainloss) { std::fprintf(stderr, "ERROR: --gainloss needs every genome in one process; run it without --gpus\n"); return 1; }
-	if (o.coevo) { std::fprintf(stderr, "ERROR: --coevo needs every genome in one process; run it without --gpus\n"); return 1; }
+	const char *whole = o.matrix ? "matrix" : o.call ? "call" : o.analysis ? o.analysis->name : nullptr;
+	if (whole) { std::fprintf(stderr, "ERROR: --%s needs every genome in one process; run it without --gpus\n", whole); return 1; }
 	const bool dev = pg_backend_is_device() != 0;
 	typedef int (*uid_fn)(void *); typedef int (*init_fn)(int32_t, int32_t, const void *); typedef int (*fin_fn)(void);
 	uid_fn rccl_uid = nullptr; init_fn rccl_init = nullptr; fin_fn rccl_fin = nullptr;
@@ -896,83 +829,16 @@ int main(int argc, char *argv[])
 {
 	if (argc >= 2 && std::strcmp(argv[1], "gfa2matrix") == 0) return main_gfa2matrix(argc - 1, argv + 1);
 	if (argc >= 2 && std::strcmp(argv[1], "call") == 0) return main_call(argc - 1, argv + 1);
-	if (argc >= 2 && std::strcmp(argv[1], "curves") == 0) return main_curves(argc - 1, argv + 1);
-	if (argc >= 2 && std::strcmp(argv[1], "dist") == 0) return main_dist(argc - 1, argv + 1);
-	if (argc >= 2 && std::strcmp(argv[1], "assoc") == 0) return main_assoc(argc - 1, argv + 1);
-	if (argc >= 2 && std::strcmp(argv[1], "trait") == 0) return main_trait(argc - 1, argv + 1);
-	if (argc >= 2 && std::strcmp(argv[1], "qtrait") == 0) return main_qtrait(argc - 1, argv + 1);
-	if (argc >= 2 && std::strcmp(argv[1], "tree") == 0) return main_tree(argc - 1, argv + 1);
-	if (argc >= 2 && std::strcmp(argv[1], "cluster") == 0) return main_cluster(argc - 1, argv + 1);
-	if (argc >= 2 && std::strcmp(argv[1], "permanova") == 0) return main_permanova(argc - 1, argv + 1);
-	if (argc >= 2 && std::strcmp(argv[1], "mantel") == 0) return main_mantel(argc - 1, argv + 1);
-	if (argc >= 2 && std::strcmp(argv[1], "gainloss") == 0) return main_gainloss(argc - 1, argv + 1);
-	if (argc >= 2 && std::strcmp(argv[1], "coevo") == 0) return main_coevo(argc - 1, argv + 1);
-	int matrix = 0, n_gpus = 1; // matrix: 1 presence, 2 counts
-	bool call = false;
-	int curves = 0; // orders of --curves (0: not asked for)
-	uint32_t curves_seed = 11;
-	int dist = -1, dist_metric_v = PG_DIST_JACCARD; // --dist: PG_DIST_* (-1: not asked for)
-	bool assoc = false; // --assoc
-	double assoc_phi_v = 0.8;
-	int assoc_count = 2, assoc_sign_v = PG_ASSOC_BOTH;
-	const char *trait = nullptr; // --trait=FILE
-	int32_t trait_perm_v = 1000;
-	uint32_t trait_seed = 11;
-	int trait_lineage_v = 0; // --trait-lineage: PG_LINEAGE_*
-	const char *qtrait = nullptr; // --qtrait=FILE
-	int32_t qtrait_perm_v = 1000;
-	uint32_t qtrait_seed = 11;
-	bool qtrait_extra = false; // a --qtrait-* option was given
-	int tree = -1, tree_metric_v = PG_DIST_JACCARD, tree_method_v = PG_TREE_NJ; // --tree: PG_DIST_GENE / PG_DIST_ADJ (-1: not asked for)
-	int32_t tree_boot_v = 0;
-	uint32_t tree_seed = 0;
-	int32_t cluster_lo = 0, cluster_hi = 0, cluster_iter_v = 1000; // --cluster: the range of k (0: not asked for)
-	int cluster_type_v = PG_DIST_GENE, cluster_metric_v = PG_DIST_JACCARD;
-	bool cluster_extra = false; // a --cluster-* option was given
-	const char *permanova = nullptr; // --permanova=FILE
-	int permanova_type_v = PG_DIST_GENE, permanova_metric_v = PG_DIST_JACCARD;
-	int32_t permanova_perm_v = 1000;
-	uint32_t permanova_seed = 11;
-	bool permanova_extra = false; // a --permanova-* option was given
-	bool mantel = false, mantel_extra = false, mantel_y = false; // --mantel[=FILE]; a --mantel-* option was given; --mantel-y was
-	const char *mantel_file = nullptr;
-	pg_mantel_opt_t mantel_opt;
-	pg_mantel_opt_init(&mantel_opt);
-	bool gainloss = false, gainloss_extra = false; // --gainloss[=gene|node]; a --gainloss-* option was given
-	pg_gainloss_opt_t gainloss_opt;
-	pg_gainloss_opt_init(&gainloss_opt);
-	bool coevo = false, coevo_extra = false; // --coevo[=FLOAT]; a --coevo-* option was given
-	pg_coevo_opt_t coevo_opt;
-	pg_coevo_opt_init(&coevo_opt);
-	static const struct option lopts[] = {
-		{ "bed", optional_argument, nullptr, 301 }, { "ori-sc", no_argument, nullptr, 302 }, { "matrix", optional_argument, nullptr, 303 }, { "call", no_argument, nullptr, 305 },
-		{ "curves", optional_argument, nullptr, 306 }, { "curves-seed", required_argument, nullptr, 307 },
-		{ "dist", optional_argument, nullptr, 308 }, { "dist-metric", required_argument, nullptr, 309 },
-		{ "assoc", optional_argument, nullptr, 310 }, { "assoc-min-count", required_argument, nullptr, 311 }, { "assoc-sign", required_argument, nullptr, 312 },
-		{ "trait", required_argument, nullptr, 313 }, { "trait-perm", required_argument, nullptr, 314 }, { "trait-seed", required_argument, nullptr, 315 },
-		{ "trait-lineage", required_argument, nullptr, 321 },
-		{ "qtrait", required_argument, nullptr, 322 }, { "qtrait-perm", required_argument, nullptr, 323 }, { "qtrait-seed", required_argument, nullptr, 324 },
-		{ "tree", optional_argument, nullptr, 316 }, { "tree-metric", required_argument, nullptr, 317 }, { "tree-method", required_argument, nullptr, 318 },
-		{ "tree-boot", required_argument, nullptr, 319 }, { "tree-seed", required_argument, nullptr, 320 },
-		{ "cluster", required_argument, nullptr, 325 }, { "cluster-type", required_argument, nullptr, 326 }, { "cluster-metric", required_argument, nullptr, 327 },
-		{ "cluster-iter", required_argument, nullptr, 328 },
-		{ "permanova", required_argument, nullptr, 329 }, { "permanova-type", required_argument, nullptr, 330 }, { "permanova-metric", required_argument, nullptr, 331 },
-		{ "permanova-perm", required_argument, nullptr, 332 }, { "permanova-seed", required_argument, nullptr, 333 },
-		{ "mantel", optional_argument, nullptr, 334 }, { "mantel-x", required_argument, nullptr, 335 }, { "mantel-y", required_argument, nullptr, 336 },
-		{ "mantel-perm", required_argument, nullptr, 337 }, { "mantel-seed", required_argument, nullptr, 338 },
-		{ "gainloss", optional_argument, nullptr, 339 }, { "gainloss-type", required_argument, nullptr, 340 }, { "gainloss-metric", required_argument, nullptr, 341 },
-		{ "gainloss-method", required_argument, nullptr, 342 }, { "gainloss-gain", required_argument, nullptr, 343 }, { "gainloss-loss", required_argument, nullptr, 344 },
-		{ "gainloss-resolve", required_argument, nullptr, 345 }, { "gainloss-min", required_argument, nullptr, 346 },
-		{ "coevo", optional_argument, nullptr, 347 }, { "coevo-type", required_argument, nullptr, 348 }, { "coevo-metric", required_argument, nullptr, 349 },
-		{ "coevo-method", required_argument, nullptr, 350 }, { "coevo-gain", required_argument, nullptr, 351 }, { "coevo-loss", required_argument, nullptr, 352 },
-		{ "coevo-resolve", required_argument, nullptr, 353 }, { "coevo-min", required_argument, nullptr, 354 }, { "coevo-sign", required_argument, nullptr, 355 },
-		{ "coevo-max", required_argument, nullptr, 356 },
-		{ "gpus", required_argument, nullptr, 304 }, { "procs", required_argument, nullptr, 304 },
-		{ "version", no_argument, nullptr, 401 }, { nullptr, 0, nullptr, 0 } };
+	for (const Analysis &a : kAnalyses) if (argc >= 2 && std::strcmp(argv[1], a.name) == 0) return main_analysis(a, argc - 1, argv + 1);
+	int n_gpus = 1;
+	Output o;
+	Parsed parsed[N_ANALYSES];
+	for (int i = 0; i < N_ANALYSES; ++i) kAnalyses[i].calls.init(&parsed[i].opt);
+	long_options_init();
 	pg_opt_t opt;
 	pg_opt_init(&opt);
 	int c;
-	while ((c = getopt_long(argc, argv, "d:e:l:f:g:p:b:B:y:Fr:c:a:wv:GD:C:T:X:I:P:m:JOSE", lopts, nullptr)) >= 0) {
+	while ((c = getopt_long(argc, argv, "d:e:l:f:g:p:b:B:y:Fr:c:a:wv:GD:C:T:X:I:P:m:JOSE", g_long, nullptr)) >= 0) {
 		switch (c) {
 		case 'd': opt.gene_delim = *optarg; break;
 		case 'X': opt.excl = pg_read_list_dict(optarg); break;
@@ -1008,236 +874,19 @@ int main(int argc, char *argv[])
 			else { std::fprintf(stderr, "ERROR: unrecognized --bed argument. Should be 'raw' or 'walk'.\n"); return 1; }
 			break;
 		case 302: opt.flag |= PG_F_ORI_FOR_BRANCH; break;
-		case 303: matrix = (optarg && std::strcmp(optarg, "count") == 0) ? 2 : 1; break;
+		case 303: o.matrix = (optarg && std::strcmp(optarg, "count") == 0) ? 2 : 1; break;
 		case 304: n_gpus = std::atoi(optarg); break;
-		case 305: call = true; break;
-		case 306:
-			curves = optarg ? std::atoi(optarg) : 10;
-			if (curves < 1) { std::fprintf(stderr, "ERROR: --curves needs at least one order\n"); return 1; }
-			break;
-		case 307: curves_seed = (uint32_t)std::strtoul(optarg, nullptr, 10); break;
-		case 308:
-			dist = optarg ? dist_type(optarg) : PG_DIST_GENE;
-			if (dist < 0) { std::fprintf(stderr, "ERROR: --dist must be gene or adj\n"); return 1; }
-			break;
-		case 309:
-			dist_metric_v = dist_metric(optarg);
-			if (dist_metric_v < 0) { std::fprintf(stderr, "ERROR: --dist-metric must be jaccard, shared or diff\n"); return 1; }
-			break;
-		case 310:
-			assoc = true;
-			if (optarg && !assoc_phi(optarg, assoc_phi_v)) { std::fprintf(stderr, "ERROR: --assoc must be in [0, 1]\n"); return 1; }
-			break;
-		case 311:
-			if ((assoc_count = std::atoi(optarg)) < 1) { std::fprintf(stderr, "ERROR: --assoc-min-count must be at least 1\n"); return 1; }
-			break;
-		case 312:
-			if ((assoc_sign_v = assoc_sign(optarg)) < 0) { std::fprintf(stderr, "ERROR: --assoc-sign must be pos, neg or both\n"); return 1; }
-			break;
-		case 313: trait = optarg; break;
-		case 314:
-			if (!trait_perm(optarg, trait_perm_v)) { std::fprintf(stderr, "ERROR: --trait-perm must be in [0, 2147483646]\n"); return 1; }
-			break;
-		case 315: trait_seed = (uint32_t)std::strtoul(optarg, nullptr, 10); break;
-		case 316:
-			tree = optarg ? dist_type(optarg) : PG_DIST_GENE;
-			if (tree < 0) { std::fprintf(stderr, "ERROR: --tree must be gene or adj\n"); return 1; }
-			break;
-		case 317:
-			if ((tree_metric_v = tree_metric(optarg)) < 0) { std::fprintf(stderr, "ERROR: --tree-metric must be jaccard or diff (shared is not a distance)\n"); return 1; }
-			break;
-		case 318:
-			if ((tree_method_v = tree_method(optarg)) < 0) { std::fprintf(stderr, "ERROR: --tree-method must be nj or upgma\n"); return 1; }
-			break;
-		case 319:
-			if (!tree_boot(optarg, tree_boot_v)) { std::fprintf(stderr, "ERROR: --tree-boot must be in [0, 2147483647]\n"); return 1; }
-			break;
-		case 320:
-			if (!tree_seed_arg(optarg, tree_seed)) { std::fprintf(stderr, "ERROR: --tree-seed must be in [0, 4294967295]\n"); return 1; }
-			break;
-		case 321:
-			if ((trait_lineage_v = trait_lineage(optarg)) < 0) { std::fprintf(stderr, "ERROR: --trait-lineage must be nj or upgma\n"); return 1; }
-			break;
-		case 322: qtrait = optarg; break;
-		case 323:
-			qtrait_extra = true;
-			if (!trait_perm(optarg, qtrait_perm_v)) { std::fprintf(stderr, "ERROR: --qtrait-perm must be in [0, 2147483646]\n"); return 1; }
-			break;
-		case 324: qtrait_extra = true, qtrait_seed = (uint32_t)std::strtoul(optarg, nullptr, 10); break;
-		case 325:
-			if (!cluster_range(optarg, cluster_lo, cluster_hi)) { std::fprintf(stderr, "ERROR: --cluster must be INT or INT-INT with 2 <= INT\n"); return 1; }
-			break;
-		case 326:
-			cluster_extra = true;
-			if ((cluster_type_v = dist_type(optarg)) < 0) { std::fprintf(stderr, "ERROR: --cluster-type must be gene or adj\n"); return 1; }
-			break;
-		case 327:
-			cluster_extra = true;
-			if ((cluster_metric_v = tree_metric(optarg)) < 0) { std::fprintf(stderr, "ERROR: --cluster-metric must be jaccard or diff (shared is not a distance)\n"); return 1; }
-			break;
-		case 328:
-			cluster_extra = true;
-			if (!tree_boot(optarg, cluster_iter_v)) { std::fprintf(stderr, "ERROR: --cluster-iter must be in [0, 2147483647]\n"); return 1; }
-			break;
-		case 329: permanova = optarg; break;
-		case 330:
-			permanova_extra = true;
-			if ((permanova_type_v = dist_type(optarg)) < 0) { std::fprintf(stderr, "ERROR: --permanova-type must be gene or adj\n"); return 1; }
-			break;
-		case 331:
-			permanova_extra = true;
-			if ((permanova_metric_v = tree_metric(optarg)) < 0) { std::fprintf(stderr, "ERROR: --permanova-metric must be jaccard or diff (shared is not a distance)\n"); return 1; }
-			break;
-		case 332:
-			permanova_extra = true;
-			if (!trait_perm(optarg, permanova_perm_v)) { std::fprintf(stderr, "ERROR: --permanova-perm must be in [0, 2147483646]\n"); return 1; }
-			break;
-		case 333: permanova_extra = true, permanova_seed = (uint32_t)std::strtoul(optarg, nullptr, 10); break;
-		case 334: mantel = true, mantel_file = optarg; break;
-		case 335:
-			mantel_extra = true;
-			if (!mantel_spec(optarg, mantel_opt.x_type, mantel_opt.x_metric)) { std::fprintf(stderr, "ERROR: --mantel-x must be gene|adj:jaccard|diff\n"); return 1; }
-			break;
-		case 336:
-			mantel_extra = mantel_y = true;
-			if (!mantel_spec(optarg, mantel_opt.y_type, mantel_opt.y_metric)) { std::fprintf(stderr, "ERROR: --mantel-y must be gene|adj:jaccard|diff\n"); return 1; }
-			break;
-		case 337:
-			mantel_extra = true;
-			if (!trait_perm(optarg, mantel_opt.n_perm)) { std::fprintf(stderr, "ERROR: --mantel-perm must be in [0, 2147483646]\n"); return 1; }
-			break;
-		case 338: mantel_extra = true, mantel_opt.seed = (uint32_t)std::strtoul(optarg, nullptr, 10); break;
-		case 339:
-			gainloss = true;
-			if (optarg && (gainloss_opt.out = gainloss_out(optarg)) < 0) { std::fprintf(stderr, "ERROR: --gainloss must be gene or node\n"); return 1; }
-			break;
-		case 340:
-			gainloss_extra = true;
-			if ((gainloss_opt.type = dist_type(optarg)) < 0) { std::fprintf(stderr, "ERROR: --gainloss-type must be gene or adj\n"); return 1; }
-			break;
-		case 341:
-			gainloss_extra = true;
-			if ((gainloss_opt.metric = tree_metric(optarg)) < 0) { std::fprintf(stderr, "ERROR: --gainloss-metric must be jaccard or diff (shared is not a distance)\n"); return 1; }
-			break;
-		case 342:
-			gainloss_extra = true;
-			if ((gainloss_opt.method = tree_method(optarg)) < 0) { std::fprintf(stderr, "ERROR: --gainloss-method must be upgma or nj\n"); return 1; }
-			break;
-		case 343:
-			gainloss_extra = true;
-			if (!gainloss_cost(optarg, gainloss_opt.gain)) { std::fprintf(stderr, "ERROR: --gainloss-gain must be in [1, 255]\n"); return 1; }
-			break;
-		case 344:
-			gainloss_extra = true;
-			if (!gainloss_cost(optarg, gainloss_opt.loss)) { std::fprintf(stderr, "ERROR: --gainloss-loss must be in [1, 255]\n"); return 1; }
-			break;
-		case 345:
-			gainloss_extra = true;
-			if ((gainloss_opt.mode = gainloss_mode(optarg)) < 0) { std::fprintf(stderr, "ERROR: --gainloss-resolve must be late or early\n"); return 1; }
-			break;
-		case 346:
-			gainloss_extra = true;
-			if (!tree_boot(optarg, gainloss_opt.min_changes)) { std::fprintf(stderr, "ERROR: --gainloss-min must be in [0, 2147483647]\n"); return 1; }
-			break;
-		case 347:
-			coevo = true;
-			if (optarg && !assoc_phi(optarg, coevo_opt.min_r)) { std::fprintf(stderr, "ERROR: --coevo must be in [0, 1]\n"); return 1; }
-			break;
-		case 348:
-			coevo_extra = true;
-			if ((coevo_opt.type = dist_type(optarg)) < 0) { std::fprintf(stderr, "ERROR: --coevo-type must be gene or adj\n"); return 1; }
-			break;
-		case 349:
-			coevo_extra = true;
-			if ((coevo_opt.metric = tree_metric(optarg)) < 0) { std::fprintf(stderr, "ERROR: --coevo-metric must be jaccard or diff (shared is not a distance)\n"); return 1; }
-			break;
-		case 350:
-			coevo_extra = true;
-			if ((coevo_opt.method = tree_method(optarg)) < 0) { std::fprintf(stderr, "ERROR: --coevo-method must be upgma or nj\n"); return 1; }
-			break;
-		case 351:
-			coevo_extra = true;
-			if (!gainloss_cost(optarg, coevo_opt.gain)) { std::fprintf(stderr, "ERROR: --coevo-gain must be in [1, 255]\n"); return 1; }
-			break;
-		case 352:
-			coevo_extra = true;
-			if (!gainloss_cost(optarg, coevo_opt.loss)) { std::fprintf(stderr, "ERROR: --coevo-loss must be in [1, 255]\n"); return 1; }
-			break;
-		case 353:
-			coevo_extra = true;
-			if ((coevo_opt.mode = gainloss_mode(optarg)) < 0) { std::fprintf(stderr, "ERROR: --coevo-resolve must be late or early\n"); return 1; }
-			break;
-		case 354:
-			coevo_extra = true;
-			if (!coevo_min(optarg, coevo_opt.min_events)) { std::fprintf(stderr, "ERROR: --coevo-min must be at least 1\n"); return 1; }
-			break;
-		case 355:
-			coevo_extra = true;
-			if ((coevo_opt.sign = assoc_sign(optarg)) < 0) { std::fprintf(stderr, "ERROR: --coevo-sign must be pos, neg or both\n"); return 1; }
-			break;
-		case 356:
-			coevo_extra = true;
-			if (!coevo_max(optarg, coevo_opt.max_pair)) { std::fprintf(stderr, "ERROR: --coevo-max must not be negative\n"); return 1; }
-			break;
+		case 305: o.call = true; break;
 		case 401: std::puts(PG_VERSION); return 0;
-		default: break;
+		default:
+			if (c >= LONG_BASE && !long_option(c, optarg, parsed)) return 1;
+			break;
 		}
 	}
 	if (argc - optind < 1) return usage(stderr, &opt);
-	if (curves && (matrix || call)) { std::fprintf(stderr, "ERROR: --curves cannot be combined with --matrix or --call\n"); return 1; }
-	if (dist >= 0 && (matrix || call || curves)) { std::fprintf(stderr, "ERROR: --dist cannot be combined with --matrix, --call or --curves\n"); return 1; }
-	if (assoc && (matrix || call || curves || dist >= 0)) { std::fprintf(stderr, "ERROR: --assoc cannot be combined with --matrix, --call, --curves or --dist\n"); return 1; }
-	if (trait && (matrix || call || curves || dist >= 0 || assoc)) { std::fprintf(stderr, "ERROR: --trait cannot be combined with --matrix, --call, --curves, --dist or --assoc\n"); return 1; }
-	if (trait_lineage_v && !trait) { std::fprintf(stderr, "ERROR: --trait-lineage needs --trait=FILE\n"); return 1; }
-	if (tree >= 0 && (matrix || call || curves || dist >= 0 || assoc || trait)) { std::fprintf(stderr, "ERROR: --tree cannot be combined with --matrix, --call, --curves, --dist, --assoc or --trait\n"); return 1; }
-	if (qtrait && (matrix || call || curves || dist >= 0 || assoc || trait || tree >= 0)) { std::fprintf(stderr, "ERROR: --qtrait cannot be combined with --matrix, --call, --curves, --dist, --assoc, --trait or --tree\n"); return 1; }
-	if (qtrait_extra && !qtrait) { std::fprintf(stderr, "ERROR: --qtrait-perm and --qtrait-seed need --qtrait=FILE\n"); return 1; }
-	if (cluster_lo && (matrix || call || curves || dist >= 0 || assoc || trait || tree >= 0 || qtrait)) {
-		std::fprintf(stderr, "ERROR: --cluster cannot be combined with --matrix, --call, --curves, --dist, --assoc, --trait, --tree or --qtrait\n");
-		return 1;
-	}
-	if (cluster_extra && !cluster_lo) { std::fprintf(stderr, "ERROR: --cluster-type, --cluster-metric and --cluster-iter need --cluster=INT[-INT]\n"); return 1; }
-	if (permanova && (matrix || call || curves || dist >= 0 || assoc || trait || tree >= 0 || qtrait || cluster_lo)) {
-		std::fprintf(stderr, "ERROR: --permanova cannot be combined with --matrix, --call, --curves, --dist, --assoc, --trait, --tree, --qtrait or --cluster\n");
-		return 1;
-	}
-	if (permanova_extra && !permanova) { std::fprintf(stderr, "ERROR: --permanova-type, --permanova-metric, --permanova-perm and --permanova-seed need --permanova=FILE\n"); return 1; }
-	if (mantel && (matrix || call || curves || dist >= 0 || assoc || trait || tree >= 0 || qtrait || cluster_lo || permanova)) {
-		std::fprintf(stderr, "ERROR: --mantel cannot be combined with --matrix, --call, --curves, --dist, --assoc, --trait, --tree, --qtrait, --cluster or --permanova\n");
-		return 1;
-	}
-	if (mantel_extra && !mantel) { std::fprintf(stderr, "ERROR: --mantel-x, --mantel-y, --mantel-perm and --mantel-seed need --mantel\n"); return 1; }
-	if (mantel_y && mantel_file) { std::fprintf(stderr, "ERROR: --mantel-y cannot be combined with --mantel=FILE\n"); return 1; }
-	if (gainloss && (matrix || call || curves || dist >= 0 || assoc || trait || tree >= 0 || qtrait || cluster_lo || permanova || mantel)) {
-		std::fprintf(stderr, "ERROR: --gainloss cannot be combined with --matrix, --call, --curves, --dist, --assoc, --trait, --tree, --qtrait, --cluster, --permanova or --mantel\n");
-		return 1;
-	}
-	if (gainloss_extra && !gainloss) {
-		std::fprintf(stderr, "ERROR: --gainloss-type, --gainloss-metric, --gainloss-method, --gainloss-gain, --gainloss-loss, --gainloss-resolve and --gainloss-min need --gainloss\n");
-		return 1;
-	}
-	if (coevo && (matrix || call || curves || dist >= 0 || assoc || trait || tree >= 0 || qtrait || cluster_lo || permanova || mantel || gainloss)) {
-		std::fprintf(stderr, "ERROR: --coevo cannot be combined with --matrix, --call, --curves, --dist, --assoc, --trait, --tree, --qtrait, --cluster, --permanova, --mantel or --gainloss\n");
-		return 1;
-	}
-	if (coevo_extra && !coevo) {
-		std::fprintf(stderr, "ERROR: --coevo-type, --coevo-metric, --coevo-method, --coevo-gain, --coevo-loss, --coevo-resolve, --coevo-min, --coevo-sign and --coevo-max need --coevo\n");
-		return 1;
-	}
-	Output o;
-	o.coevo = coevo, o.coevo_opt = coevo_opt;
-	o.gainloss = gainloss, o.gainloss_opt = gainloss_opt;
-	o.mantel = mantel, o.mantel_file = mantel_file, o.mantel_opt = mantel_opt;
-	o.permanova = permanova, o.permanova_type = permanova_type_v, o.permanova_metric = permanova_metric_v, o.permanova_perm = permanova_perm_v, o.permanova_seed = permanova_seed;
-	o.cluster_lo = cluster_lo, o.cluster_hi = cluster_hi, o.cluster_iter = cluster_iter_v, o.cluster_type = cluster_type_v, o.cluster_metric = cluster_metric_v;
-	o.qtrait = qtrait, o.qtrait_perm = qtrait_perm_v, o.qtrait_seed = qtrait_seed;
-	o.tree = tree, o.tree_metric = tree_metric_v, o.tree_method = tree_method_v, o.tree_boot = tree_boot_v, o.tree_seed = tree_seed;
-	o.trait = trait, o.trait_perm = trait_perm_v, o.trait_seed = trait_seed, o.trait_lineage = trait_lineage_v;
-	o.assoc = assoc, o.assoc_phi = assoc_phi_v, o.assoc_count = assoc_count, o.assoc_sign = assoc_sign_v;
-	o.curves = curves, o.curves_seed = curves_seed;
-	o.dist = dist, o.dist_metric = dist_metric_v;
-	o.matrix = matrix;
-	o.call = call;
+	int which;
+	if (!check_analyses(parsed, o.matrix != 0, o.call, which)) return 1;
+	if (which >= 0) o.analysis = &kAnalyses[which], o.opt = parsed[which].opt, o.side = parsed[which].side;
 	int rc;
 	if (n_gpus > 1) {
 		rc = run_sharded(opt, n_gpus, argc - optind, argv + optind, o);
