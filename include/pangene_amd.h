@@ -569,6 +569,42 @@ void    pg_write_coevo(pg_graph_t *g, const pg_coevo_opt_t *o);
 int64_t pg_pan_coevo(const uint8_t *presence, int32_t n_item, int32_t n_asm, const int64_t *rec, int32_t method, const pg_coevo_opt_t *o, int32_t *events_out,
                      int32_t *pair_out, int64_t cap);
 
+/* Phylogenetic signal: does an item's presence follow the assemblies' tree?  The permutation tail probability of the parsimony length
+ * (Faith & Cranston 1991) with the retention index beside it.  DESIGN.md section 8 "Phylogenetic signal" holds the definition.  Items,
+ * tree and costs are those of pg_gainloss_* (type, metric, method, gain, loss); Cost = min(C0, C1) at the root does not depend on the
+ * tie rule.  An item is tested when min(Present, A - Present) >= min_count; the classes are the distinct values of Present over the
+ * tested items.  Replicate (n, p), p = 1 .. n_perm: with o_p the order every other permutation command uses for (A, seed, p), assembly x
+ * is present iff o_p[x] < n; cost(n, p) is the Wagner cost of that tip set.  Per item n_le = #{p : cost(Present, p) <= Cost}, n_ge the
+ * same with >=, p_signal = (1 + n_le) / (1 + n_perm) (small: fewer changes than chance, vertical), p_scatter = (1 + n_ge) / (1 + n_perm)
+ * (small: more changes than chance), q_signal = Benjamini-Hochberg over p_signal of the tested items.  Per class Expect = the mean of
+ * cost(n, p) over p.  MaxCost = min(n gain, (A - n) loss), the cost on an unresolved tree; RI = (MaxCost - Cost) / (MaxCost - min(gain,
+ * loss)), NA when the denominator is 0.  Integers up to the printed ratios.
+ * Output, tab-separated: "Gene Present Cost MaxCost Expect RI n_le n_ge p_signal p_scatter q_signal", one line per tested item in item
+ * order with min(p_signal, p_scatter) <= max_p (q is computed before that filter); Expect %.3f, RI %.4f, the p and q values %.6f.
+ * n_perm = 0 runs no permutation and prints NA for Expect, n_le, n_ge and the three p / q columns.  No assemblies, no items or no tested
+ * item: the header only.  It is a parsimony reading; under NJ it depends on the rooting; the tips are treated as exchangeable.
+ * pg_phylosig_file: 0, -1 (the GFA file cannot be opened) or -2; pg_write_phylosig: errors go to pg_last_error.
+ * pg_pan_phylosig: any presence matrix [n_item][n_asm] and any tree as for pg_pan_gainloss; of the options gain, loss, n_perm, seed and
+ * min_count are read.  Fills out_i32[n_item][5] = present, cost, tested (0 / 1), n_le, n_ge (0 and 0 for an item that is not tested) and
+ * out_sum_i64[n_asm + 1], indexed by n: the sum over p of cost(n, p), 0 for a class that did not run.  Returns 0 or a negative PGA_ERR_*;
+ * errors and limits as for pg_pan_gainloss.  The permutation step comes from the backend's pga_pan_phylosig.
+ * sizeof(pg_phylosig_opt_t) is 40. */
+typedef struct {
+	int32_t type;        /* PG_DIST_GENE or PG_DIST_ADJ [gene] */
+	int32_t metric;      /* PG_DIST_JACCARD or PG_DIST_DIFF [jaccard] */
+	int32_t method;      /* PG_TREE_NJ or PG_TREE_UPGMA [upgma] */
+	int32_t gain, loss;  /* the cost of a gain and of a loss, 1 .. 255 [1, 1] */
+	int32_t n_perm;      /* permutations, 0 .. 2^31 - 2; 0: none [1000] */
+	uint32_t seed;       /* of the permutations [11] */
+	int32_t min_count;   /* an item is tested when it is present in >= min_count and absent from >= min_count assemblies; >= 1 [2] */
+	double  max_p;       /* the table keeps the items with min(p_signal, p_scatter) <= max_p [1.0: all] */
+} pg_phylosig_opt_t;
+void pg_phylosig_opt_init(pg_phylosig_opt_t *o);
+int  pg_phylosig_file(const char *gfa_fn, const pg_phylosig_opt_t *o);
+void pg_write_phylosig(pg_graph_t *g, const pg_phylosig_opt_t *o);
+int  pg_pan_phylosig(const uint8_t *presence, int32_t n_item, int32_t n_asm, const int64_t *rec, int32_t method, const pg_phylosig_opt_t *o, int32_t *out_i32,
+                     int64_t *out_sum_i64);
+
 /* Last error of the path (0 = none).  The reference aborts on invariant violations; this library
  * records a status instead, prints one line to stderr, and leaves the graph empty. */
 int         pg_last_error(void);

@@ -94,7 +94,7 @@ typedef struct {
  * Device layout limits (PGA_ERR_RANGE otherwise): coordinates inside a block < 2^31 (contigs beyond that arrive as virtual contigs,
  * see pga_genome_block_t; what remains out of reach is a single cluster of overlapping hits spanning 2^30 bp), < 2^30 hits and < 2^31
  * exons per shard, < 2^20 genes, < 2^24 genomes. */
-#define PGA_ABI_VERSION 21u /* bumped whenever a struct of this header or the order of pga_backend_t changes; pga_create refuses another */
+#define PGA_ABI_VERSION 22u /* bumped whenever a struct of this header or the order of pga_backend_t changes; pga_create refuses another */
 typedef struct {
 	uint32_t abi_version;        /* = PGA_ABI_VERSION of the header the caller was compiled against (PGA_ERR_ARG otherwise) */
 	int32_t n_genome;            /* genomes in this shard (may include genomes with 0 hits) */
@@ -615,6 +615,39 @@ typedef struct { const int32_t *events; int64_t n_pair; const int32_t *pair; } p
 int pga_pan_coevo(const pga_coevo_in_t *in, pga_coevo_out_t *out);
 int32_t pga_coevo_chunk(int32_t n_leaf);
 
+/* Phylogenetic signal (include/pangene_amd.h pg_pan_phylosig, pangene phylosig; DESIGN.md section 8 "Phylogenetic signal"): the
+ * permutation tail of the parsimony cost.  Context-free.  The tree is pan_gainloss's postfix program; the null distribution of an item
+ * depends only on its number of carriers, so the replicates are classes x permutations.  Replicate (n, p), p = 1 .. n_perm: with o_p the
+ * order pgx::fisher_yates_order(n_leaf, seed, p) gives, assembly x is present iff o_p[x] < n; cost(n, p) = min(C0, C1) at the root of
+ * pan_gainloss's up pass over that tip set.
+ * In:  op[2 n_leaf - 1], checked as pan_gainloss checks it (malformed: PGA_ERR_ARG, a stack need above 16: PGA_ERR_RANGE); leaf[n_leaf]
+ *      = the assembly of the k-th push, a permutation of 0 .. n_leaf - 1 (PGA_ERR_ARG otherwise); cls[n_cls] strictly ascending, each in
+ *      1 .. n_leaf - 1 (PGA_ERR_ARG otherwise); item_cls[n_item] an index into cls (PGA_ERR_ARG otherwise); item_cost[n_item] the
+ *      observed cost.  cost_rows, rank_rows: NULL, or -- for tests only -- room for the first batch's costs, int32 [n_cls][nb], and
+ *      orders, uint16 [n_leaf][nbs]: rank_rows[x * nbs + q] = o_(1 + q)[x], nb = min(n_perm, pga_phylosig_batch(n_cls)), nbs = nb rounded
+ *      up to a multiple of 64; the columns past nb hold an order nobody reads.
+ * Out: n_le[n_item] = #{p : cost(cls[item_cls[i]], p) <= item_cost[i]}, n_ge[n_item] the same with >=, sum[n_cls] = the sum over p of
+ *      cost(cls[c], p).  The arrays are page-locked, belong to the backend and stay valid until its next pan_phylosig.  n_cls, n_item or
+ *      n_perm = 0: zeros, nothing is launched.
+ * The permutations go through in batches of pga_phylosig_batch(n_cls): PANGENE_PHYLOSIG_BATCH rounded up to a multiple of 64, or the
+ * largest multiple of 64 up to 4 096 for which n_cls x batch x 4 bytes stay within 256 MiB, never less than 64.
+ * Limits (PGA_ERR_RANGE otherwise, before anything is launched): n_leaf <= 65 535, a stack need <= 16, 1 <= gain, loss <= 255,
+ * n_perm <= 2^31 - 2, n_item <= 16 777 215. */
+typedef struct {
+	const uint8_t *op;
+	const int32_t *leaf;
+	int32_t n_leaf, gain, loss;
+	int32_t n_cls; const int32_t *cls;
+	int32_t n_item; const int32_t *item_cls;
+	const int32_t *item_cost;
+	int32_t n_perm; uint32_t seed;
+	int32_t *cost_rows;
+	uint16_t *rank_rows;
+} pga_phylosig_in_t;
+typedef struct { const int32_t *n_le, *n_ge; const int64_t *sum; } pga_phylosig_out_t;
+int pga_pan_phylosig(const pga_phylosig_in_t *in, pga_phylosig_out_t *out);
+int32_t pga_phylosig_batch(int32_t n_cls);
+
 /* the same ABI as a table, so the host driver is written once */
 struct pga_branch_par_s; struct pga_loop_xchg_s;
 typedef struct {
@@ -686,6 +719,7 @@ typedef struct {
 	int  (*pan_gainloss)(const pga_gainloss_in_t *, pga_gainloss_out_t *); /* may be NULL: the host driver then runs the same step itself */
 	int  (*pan_coevo)(const pga_coevo_in_t *, pga_coevo_out_t *); /* may be NULL: the host driver then runs the same step itself */
 	int  (*post_front)(pga_ctx_t *, double, int32_t, int32_t, const int32_t **); /* may be NULL: the host driver then computes the representatives itself and calls post_apply */
+	int  (*pan_phylosig)(const pga_phylosig_in_t *, pga_phylosig_out_t *); /* may be NULL: the host driver then runs the same step itself */
 } pga_backend_t;
 
 const pga_backend_t *pga_backend(void);

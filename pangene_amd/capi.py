@@ -734,6 +734,61 @@ def pan_coevo(lib: C.CDLL, presence, rec, method: str, gain: int = 1, loss: int 
     return events, pairs[:n].copy()
 
 
+class pg_phylosig_opt_t(C.Structure):
+    """Phylogenetic signal options (include/pangene_amd.h): the items, the tree and the costs as for gainloss, then the permutations, their
+    seed, the smallest count of a tested item and the filter of the table."""
+    _fields_ = [("type", C.c_int32), ("metric", C.c_int32), ("method", C.c_int32), ("gain", C.c_int32), ("loss", C.c_int32), ("n_perm", C.c_int32),
+                ("seed", C.c_uint32), ("min_count", C.c_int32), ("max_p", C.c_double)]
+
+
+def phylosig_opt(lib: C.CDLL, type: str = "gene", metric: str = "jaccard", method: str = "upgma", gain: int = 1, loss: int = 1, n_perm: int = 1000,
+                 seed: int = 11, min_count: int = 2, max_p: float = 1.0) -> pg_phylosig_opt_t:
+    if type not in DIST_TYPES:
+        raise ValueError("type must be gene or adj")
+    if metric not in TREE_METRICS:
+        raise ValueError("metric must be jaccard or diff")
+    if method not in TREE_METHODS:
+        raise ValueError("method must be upgma or nj")
+    if not (1 <= int(gain) <= 255 and 1 <= int(loss) <= 255):
+        raise ValueError("gain and loss must be in [1, 255]")
+    if not 0 <= int(n_perm) <= TRAIT_MAX_PERM:
+        raise ValueError("n_perm must be in [0, 2^31 - 2]")
+    if not 0 <= int(seed) <= 0xFFFFFFFF:
+        raise ValueError("seed must be in [0, 2^32 - 1]")
+    if not 1 <= int(min_count) <= TREE_MAX_BOOT:
+        raise ValueError("min_count must be in [1, 2^31 - 1]")
+    if not float(max_p) >= 0.0:
+        raise ValueError("max_p must be a number >= 0")
+    o = pg_phylosig_opt_t()
+    lib.pg_phylosig_opt_init(C.byref(o))
+    o.type, o.metric, o.method = DIST_TYPES.index(type), DIST_METRICS.index(metric), TREE_METHODS.index(method)
+    o.gain, o.loss, o.n_perm, o.seed, o.min_count, o.max_p = int(gain), int(loss), int(n_perm), int(seed), int(min_count), float(max_p)
+    return o
+
+
+def pan_phylosig(lib: C.CDLL, presence, rec, method: str, gain: int = 1, loss: int = 1, n_perm: int = 1000, seed: int = 11, min_count: int = 2):
+    """The permutation tail of the parsimony cost of the items of an item x assembly presence matrix (bool numpy array or torch tensor,
+    shape (M, A)) on the tree of the records rec (as for pan_gainloss) through pg_pan_phylosig: a dict of numpy arrays: present, cost,
+    tested, n_le and n_ge, int32 (M,), per item; sum, int64 (A + 1,), indexed by the class size n (0 for a class that did not run)."""
+    import numpy as np
+    p = _presence(presence)
+    M, A = p.shape
+    m = TREE_METHODS.index(method)
+    rec = np.ascontiguousarray(rec if rec is not None else np.zeros((0, 6)), dtype=np.int64).reshape(-1, 6)
+    if A >= 3 and rec.shape[0] != A - 2 + m:
+        raise ValueError("rec must hold %d records for %d assemblies and %s" % (A - 2 + m, A, method))
+    o = phylosig_opt(lib, method=method, gain=gain, loss=loss, n_perm=n_perm, seed=seed, min_count=min_count)
+    item = np.zeros((M, 5), dtype=np.int32)
+    total = np.zeros(A + 1, dtype=np.int64)
+    rc = lib.pg_pan_phylosig(p.ctypes.data_as(C.POINTER(C.c_uint8)), M, A, rec.ctypes.data_as(C.POINTER(C.c_int64)), m, C.byref(o),
+                             item.ctypes.data_as(C.POINTER(C.c_int32)), total.ctypes.data_as(C.POINTER(C.c_int64)))
+    if rc != 0:
+        raise RuntimeError("pg_pan_phylosig: status %d" % rc)
+    out = {k: np.ascontiguousarray(item[:, i]) for i, k in enumerate(("present", "cost", "tested", "n_le", "n_ge"))}
+    out["sum"] = total
+    return out
+
+
 # ---- the long options of the analyses, as run() reads them: one table, one reader -------------------------------------------------
 # A row is one --NAME-suffix=VALUE (the head row, without a suffix, is the VALUE of --NAME=VALUE): the keyword of NAME_opt() it fills,
 # the converter (its ValueError is raised where the option stands), and a test of the last value given with the words after the option's
@@ -768,7 +823,7 @@ def _k_range(v):
 _Analysis = collections.namedtuple("_Analysis", "name opt write form bare head side rows strict zero_off", defaults=(False, False))
 _M_PERM, _M_INT31, _M_TYPE, _M_METRIC = "must be in [0, 2^31 - 2]", "must be in [0, 2^31 - 1]", "must be gene or adj", "must be jaccard or diff"
 _RECON = (_Row("type", "type", extra=True), _Row("metric", "metric", extra=True), _Row("method", "method", extra=True), _Row("gain", "gain", int, extra=True),
-          _Row("loss", "loss", int, extra=True), _Row("resolve", "mode", extra=True))  # gainloss and coevo: gainloss_opt() / coevo_opt() test the values
+          _Row("loss", "loss", int, extra=True), _Row("resolve", "mode", extra=True))  # gainloss, coevo and (without resolve) phylosig: NAME_opt() tests the values
 
 # in the order in which --X refuses the ones before it (after --matrix and --call)
 _ANALYSES = (
@@ -797,6 +852,8 @@ _ANALYSES = (
     _Analysis("gainloss", gainloss_opt, "pg_write_gainloss", "--gainloss", {}, _Row(None, "out"), False, _RECON + (_Row("min", "min_changes", int, extra=True),), strict=True),
     _Analysis("coevo", coevo_opt, "pg_write_coevo", "--coevo", {}, _Row(None, "min_r", float), False,
               _RECON + (_Row("min", "min_events", int, extra=True), _Row("sign", "sign", extra=True), _Row("max", "max_pair", int, extra=True)), strict=True),
+    _Analysis("phylosig", phylosig_opt, "pg_write_phylosig", "--phylosig", {}, _ints(None, "n_perm", 0, TRAIT_MAX_PERM, _M_PERM), False,
+              _RECON[:5] + (_Row("seed", "seed", int, extra=True), _Row("min", "min_count", int, extra=True), _Row("max-p", "max_p", float, extra=True)), strict=True),
 )
 _HEADS = tuple("--" + a.name for a in _ANALYSES)
 
@@ -924,6 +981,10 @@ _API = {
     "pg_coevo_file": (C.c_int, [C.c_char_p, C.c_void_p]),
     "pg_write_coevo": (None, [C.c_void_p, C.c_void_p]),
     "pg_pan_coevo": (C.c_int64, [C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int64]),
+    "pg_phylosig_opt_init": (None, [C.c_void_p]),
+    "pg_phylosig_file": (C.c_int, [C.c_char_p, C.c_void_p]),
+    "pg_write_phylosig": (None, [C.c_void_p, C.c_void_p]),
+    "pg_pan_phylosig": (C.c_int, [C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "pg_pan_qtrait": (C.c_int, [C.POINTER(C.c_uint8), C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]),
     "pg_pan_trait": (C.c_int, [C.POINTER(C.c_uint8), C.POINTER(C.c_int8), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]),
     "pg_pan_pairs": (C.c_int, [C.POINTER(C.c_uint8), C.POINTER(C.c_int8), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int32)]),

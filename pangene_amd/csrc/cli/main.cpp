@@ -187,7 +187,7 @@ static int main_call(int argc, char *argv[])
 // memory.  Both spellings, their refusals and the dispatch come from ONE table, kAnalyses below: a record per analysis, a row per option.
 // ---------------------------------------------------------------------------------------------------------------
 union AnyOpt { pg_curves_opt_t curves; pg_dist_opt_t dist; pg_assoc_opt_t assoc; pg_trait_opt_t trait; pg_tree_opt_t tree; pg_qtrait_opt_t qtrait;
-	pg_cluster_opt_t cluster; pg_permanova_opt_t permanova; pg_mantel_opt_t mantel; pg_gainloss_opt_t gainloss; pg_coevo_opt_t coevo; };
+	pg_cluster_opt_t cluster; pg_permanova_opt_t permanova; pg_mantel_opt_t mantel; pg_gainloss_opt_t gainloss; pg_coevo_opt_t coevo; pg_phylosig_opt_t phylosig; };
 
 struct Word { const char *s; int32_t v; };
 static const Word W_TYPE[] = { { "gene", PG_DIST_GENE }, { "adj", PG_DIST_ADJ }, { nullptr, 0 } };
@@ -336,7 +336,7 @@ struct Analysis {
 // In the order in which --X refuses the ones before it (after --matrix and --call).  Oddities that are behaviour, kept as data:
 // only the rows marked `extra` are refused without their --NAME (--curves-seed, --dist-metric, --assoc-*, --trait-perm, --trait-seed and
 // --tree-* pass); a --NAME without a value after --NAME=X resets X for curves, dist and tree only (`bare`); the seeds and the counts of curves, assoc, trait and qtrait are read laxly; permanova's items are -T, gainloss
-// resolves ties with -r and coevo with -e; a row without a suffix exists for the subcommand only.
+// resolves ties with -r and coevo with -e, phylosig has no tie rule; a row without a suffix exists for the subcommand only.
 static const Analysis kAnalyses[] = {
 	{ "curves", "--curves", false, HEAD_ROW0, "10", 0, false, calls<pg_curves_opt_t, pg_curves_opt_init, pg_curves_file, pg_write_curves>(),
 	  [](const AnyOpt &o) {
@@ -464,6 +464,30 @@ static const Analysis kAnalyses[] = {
 	    i32('c', "min", offsetof(pg_coevo_opt_t, min_events), 1, INT31, M_MIN1, true),
 	    word('s', "sign", offsetof(pg_coevo_opt_t, sign), W_SIGN, M_SIGN, true),
 	    i64('x', "max", offsetof(pg_coevo_opt_t, max_pair), 0, LLONG_MAX, M_NONNEG, true) } },
+	// (its lines in usage() wait for the next recording of the command-line transcript, which pins that text: the subcommand's own usage names both spellings)
+	{ "phylosig", "--phylosig", false, HEAD_ROW0, nullptr, 0, false, calls<pg_phylosig_opt_t, pg_phylosig_opt_init, pg_phylosig_file, pg_write_phylosig>(),
+	  [](const AnyOpt &o) {
+		std::printf("Usage: pangene phylosig [options] <in.gfa>\n       pangene --phylosig[=INT] [--phylosig-NAME=VALUE ...] <in.paf> [...]   (INT: -n; NAME in parentheses below)\nOptions:\n"
+		            "  -t STR    (type) items: gene (gene content) or adj (gene adjacencies of the walks) [gene]\n"
+		            "  -m STR    (metric) distance of the tree: jaccard or diff [jaccard]\n"
+		            "  -a STR    (method) tree: upgma, or nj rooted at its closing join, read as ((x, y), z): the costs depend on that reading unless -g and -l are equal [upgma]\n"
+		            "  -g INT    (gain) cost of a gain, 1 to 255 [%d]\n  -l INT    (loss) cost of a loss, 1 to 255 [%d]\n"
+		            "  -n INT    (--phylosig=INT) permutations of the tips: per item the random tip sets of its size on the same tree; 0: none [%d]\n"
+		            "  -s INT    (seed) seed of the permutations [%u]\n"
+		            "  -c INT    (min) an item is tested when it is present in >=INT and absent from >=INT assemblies [%d]\n"
+		            "  -p FLOAT  (max-p) print the items with min(p_signal, p_scatter) <= FLOAT [%g]\n"
+		            "Columns: p_signal is small when the item changes less often on the tree than chance (inherited down the lineages),\n"
+		            "         p_scatter when more often (scattered over the tree); RI is the retention index\n",
+		            o.phylosig.gain, o.phylosig.loss, o.phylosig.n_perm, o.phylosig.seed, o.phylosig.min_count, o.phylosig.max_p); },
+	  { i32('n', nullptr, offsetof(pg_phylosig_opt_t, n_perm), 0, INT31 - 1, M_PERM),
+	    word('t', "type", offsetof(pg_phylosig_opt_t, type), W_TYPE, M_TYPE, true),
+	    word('m', "metric", offsetof(pg_phylosig_opt_t, metric), W_METRIC, M_METRIC, true),
+	    word('a', "method", offsetof(pg_phylosig_opt_t, method), W_METHOD, "must be upgma or nj", true),
+	    i32('g', "gain", offsetof(pg_phylosig_opt_t, gain), 1, 255, M_COST, true),
+	    i32('l', "loss", offsetof(pg_phylosig_opt_t, loss), 1, 255, M_COST, true),
+	    plain('s', "seed", rd_u32, offsetof(pg_phylosig_opt_t, seed), "must be in [0, 4294967295]", true),
+	    i32('c', "min", offsetof(pg_phylosig_opt_t, min_count), 1, INT31, M_MIN1, true),
+	    plain('p', "max-p", rd_nonneg, offsetof(pg_phylosig_opt_t, max_p), "must be a number >= 0", true) } },
 };
 enum { N_ANALYSES = sizeof(kAnalyses) / sizeof(kAnalyses[0]) };
 
@@ -543,7 +567,7 @@ static bool long_option(int code, const char *arg, Parsed *parsed) // false: ref
 		p.asked = true;
 		if (a.head_value == HEAD_FILE) p.side = arg;
 		if (a.head_value == HEAD_FILE) return true;
-		if (arg == nullptr && (arg = a.bare) == nullptr) return true; // (a later --curves, --dist or --tree without a value is the default again; --assoc, --gainloss and --coevo keep what an earlier one said)
+		if (arg == nullptr && (arg = a.bare) == nullptr) return true; // (a later --curves, --dist or --tree without a value is the default again; --assoc, --gainloss, --coevo and --phylosig keep what an earlier one said)
 	} else {
 		if (r->extra) p.extra = true;
 		if (r->no_file) p.no_file = r;

@@ -50,3 +50,19 @@ __device__ __forceinline__ void perm_wave_rows(int32_t elems, int32_t n_swap, ui
 	const int32_t n_row = (int32_t)min((int64_t)WAVE, (int64_t)nb - q0);
 	for (int32_t q = 0; q < n_row; ++q) row_out(mine + q, q0 + q, l);
 }
+
+// The same rows written out element-major: out[k * stride + q], q = 64 blockIdx.x + l -- which is the wave's own layout, so the
+// write-out is a copy of the block, a lane moving its own elements (no exchange across lanes, no barrier), 128 contiguous bytes of uint16
+// per element and wave.  out has ceil(nb / 64) * 64 columns: the lanes past nb write the permutation nobody reads.
+template <class T, int32_t LDS_ELEMS, bool USE_LDS, class Fill, class Swap>
+__device__ __forceinline__ void perm_wave_block(int32_t elems, int32_t n_swap, uint32_t seed, uint32_t p0, T *work, Fill fill, Swap swap, T *out, size_t stride)
+{
+	__shared__ T sh[USE_LDS ? LDS_ELEMS * WAVE : 1];
+	const int32_t l = (int32_t)threadIdx.x;
+	const int64_t q0 = (int64_t)blockIdx.x * WAVE;
+	T *mine = USE_LDS ? sh : work + (size_t)blockIdx.x * (size_t)elems * WAVE;
+	for (int32_t k = 0; k < elems; ++k) mine[k * WAVE + l] = fill(k);
+	perm_swaps(n_swap, seed, p0 + (uint32_t)(q0 + l), [&](int32_t i, int32_t j) { swap(mine + l, i, j); });
+	T *col = out + (size_t)(q0 + l);
+	for (int32_t k = 0; k < elems; ++k) col[(size_t)k * stride] = mine[k * WAVE + l];
+}

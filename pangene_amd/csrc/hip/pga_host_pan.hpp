@@ -8,7 +8,7 @@
 
 constexpr int PAN_MAX_DEV = 22, PAN_MAX_HOST = 3; // buffers a pool has room for
 
-enum PanEntry { PAN_CURVES, PAN_DIST, PAN_ASSOC, PAN_TRAIT, PAN_JOIN, PAN_BOOT, PAN_PAIRS, PAN_QTRAIT, PAN_MEDOIDS, PAN_PERMANOVA, PAN_MANTEL, PAN_GAINLOSS, PAN_COEVO, PAN_N_ENTRY };
+enum PanEntry { PAN_CURVES, PAN_DIST, PAN_ASSOC, PAN_TRAIT, PAN_JOIN, PAN_BOOT, PAN_PAIRS, PAN_QTRAIT, PAN_MEDOIDS, PAN_PERMANOVA, PAN_MANTEL, PAN_GAINLOSS, PAN_COEVO, PAN_PHYLOSIG, PAN_N_ENTRY };
 
 namespace {
 struct PanDev {
@@ -55,7 +55,7 @@ struct PanDev {
 	}
 };
 PanDev g_pan[PAN_N_ENTRY] = {{"pga_pan_curves"}, {"pga_pan_shared"}, {"pga_pan_assoc"}, {"pga_pan_trait"}, {"pga_pan_join"}, {"pga_pan_boot"}, {"pga_pan_pairs"},
-                            {"pga_pan_qtrait"}, {"pga_pan_medoids"}, {"pga_pan_permanova"}, {"pga_pan_mantel"}, {"pga_pan_gainloss"}, {"pga_pan_coevo"}};
+                            {"pga_pan_qtrait"}, {"pga_pan_medoids"}, {"pga_pan_permanova"}, {"pga_pan_mantel"}, {"pga_pan_gainloss"}, {"pga_pan_coevo"}, {"pga_pan_phylosig"}};
 }
 
 static void pan_release_all()
@@ -75,7 +75,7 @@ static int64_t pan_env(const char *name, int64_t def, int64_t max)
 	return def;
 }
 
-// The batch driver of the permutation entries (trait, qtrait, permanova, mantel).  n permutations go through in batches of
+// The batch driver of the permutation entries (trait, qtrait, permanova, mantel, phylosig).  n permutations go through in batches of
 // B = min(batch, max(n, 1)) rows made by a one-wave kernel of k_perm.hpp, whose 64 rows per workgroup live in LDS (lds) or in a scratch
 // buffer of work(elems) elements:  for (PermBatches b(n, batch, lds); b.more(); b.next()) with b.p0(), b.nb(), b.first().
 constexpr int32_t PAN_MAX_PERM = 2147483646; // 2^31 - 2

@@ -1,6 +1,9 @@
 // pan_common.hpp -- what the pan commands (curves.cpp, dist.cpp, assoc.cpp, trait.cpp, tree.cpp) share on the host: packing a matrix
-// into bit rows, the random orders, the buffered writer of their tables.  Included at the end of pg_internal.hpp.
+// into bit rows, the random orders, Benjamini-Hochberg q values, the buffered writer of their tables.  Included at the end of pg_internal.hpp.
 #pragma once
+#include <algorithm>
+#include <numeric>
+#include <vector>
 
 namespace pgx {
 
@@ -60,6 +63,21 @@ struct OutBuf {
 	void flush_if_full() { if (s.size() >= (1u << 20)) std::fwrite(s.data(), 1, s.size(), out_stream()), s.clear(); }
 	void finish() { std::fwrite(s.data(), 1, s.size(), out_stream()), s.clear(); std::fflush(out_stream()); }
 };
+
+// Benjamini-Hochberg q of p (in row order): sorted ascending, ties by row; q_(i) = min over j >= i of p_(j) m / j, capped at 1
+inline void bh_q(const std::vector<double> &p, std::vector<double> &q)
+{
+	const size_t m = p.size();
+	q.assign(m, 0.0);
+	std::vector<size_t> idx(m);
+	std::iota(idx.begin(), idx.end(), (size_t)0);
+	std::stable_sort(idx.begin(), idx.end(), [&](size_t x, size_t y) { return p[x] < p[y]; }); // ties by row
+	double run = 1.0;
+	for (size_t j = m; j >= 1; --j) {
+		run = std::min(run, p[idx[j - 1]] * (double)m / (double)j);
+		q[idx[j - 1]] = run;
+	}
+}
 
 inline int cannot_open(const char *fn) { std::fprintf(stderr, "Error: cannot open %s\n", fn ? fn : "-"); return -1; }
 

@@ -11,6 +11,22 @@ constexpr int32_t GAINLOSS_MAX_LEAF = 65535, GAINLOSS_MAX_ITEM = 16777215, GAINL
 
 inline uint32_t item_bit(const uint32_t *bits, size_t W, int32_t a, int32_t i) { return bits[(size_t)a * W + (size_t)(i >> 5)] >> (i & 31) & 1u; }
 
+// The way up of one item or replicate: C[2 v + s] = the cheapest cost of the subtree of node v with v in state s.  The leaves' entries
+// 0 .. A - 1 are set; the joins follow bottom-up in join order.  Shared with pan_phylosig.hpp.
+inline void wagner_up(const std::vector<int32_t> &kid, int32_t A, int32_t g, int32_t l, int32_t *C)
+{
+	const int32_t w[2] = {g, l};
+	for (size_t t = 0; t < kid.size() / 2; ++t)
+		for (int32_t s = 0; s < 2; ++s) {
+			int32_t sum = 0;
+			for (int32_t c = 0; c < 2; ++c) {
+				const int32_t *cc = C + 2 * (size_t)kid[2 * t + (size_t)c];
+				sum += std::min(cc[s], cc[1 - s] + w[s]);
+			}
+			C[2 * ((size_t)A + t) + (size_t)s] = sum;
+		}
+}
+
 // The backend's step on the host, by the definition and over the tree itself (no program, no reordering): per item every node's
 // (C0, C1) bottom-up in join order, then the states top-down from the root, a join before its children.  bits[A][W], kid as pairs_tree
 // makes it; gene[M][4] = cost, gains, losses, root; node[2 A - 1][3] in node id order.  A >= 1.  states: nullptr, or receives
@@ -28,15 +44,7 @@ void gainloss_host(const uint32_t *bits, int32_t M, int32_t A, const std::vector
 			const uint32_t b = item_bit(bits, W, x, i);
 			C[2 * (size_t)x + b] = 0, C[2 * (size_t)x + (1 - b)] = g + l;
 		}
-		for (size_t t = 0; t < n_join; ++t)
-			for (int32_t s = 0; s < 2; ++s) {
-				int32_t sum = 0;
-				for (int32_t c = 0; c < 2; ++c) {
-					const int32_t *cc = C.data() + 2 * (size_t)kid[2 * t + (size_t)c];
-					sum += std::min(cc[s], cc[1 - s] + w[s]);
-				}
-				C[2 * ((size_t)A + t) + (size_t)s] = sum;
-			}
+		wagner_up(kid, A, g, l, C.data());
 		const size_t root = n_node - 1;
 		state[root] = C[2 * root + 1] < C[2 * root];
 		int32_t gains = 0, losses = 0;

@@ -323,21 +323,6 @@ int read_qtraits(const char *fn, const std::vector<std::string> &asm_name, QTrai
 	                       [&](size_t j, size_t c, const std::string &v) { return qtrait_value(v, tr.val[j * A + c]); });
 }
 
-// Benjamini-Hochberg q of p (in row order): sorted ascending, ties by row; q_(i) = min over j >= i of p_(j) m / j, capped at 1
-void bh_q(const std::vector<double> &p, std::vector<double> &q)
-{
-	const size_t m = p.size();
-	q.assign(m, 0.0);
-	std::vector<size_t> idx(m);
-	std::iota(idx.begin(), idx.end(), (size_t)0);
-	std::stable_sort(idx.begin(), idx.end(), [&](size_t x, size_t y) { return p[x] < p[y]; }); // ties by row
-	double run = 1.0;
-	for (size_t j = m; j >= 1; --j) {
-		run = std::min(run, p[idx[j - 1]] * (double)m / (double)j);
-		q[idx[j - 1]] = run;
-	}
-}
-
 // PANGENE_TRAIT_TIMING=1: one line on stderr per call
 void report_time(const char *route, int32_t G, int32_t A, size_t T, int32_t n, double t_all)
 {

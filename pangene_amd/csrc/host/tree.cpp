@@ -7,6 +7,7 @@
 //   pan_mantel.hpp     pangene mantel
 //   pan_gainloss.hpp   pangene gainloss (with pan_treeprog.hpp: the records as a tree and as the backend's program, shared with trait.cpp)
 //   pan_coevo.hpp      pangene coevo (the reconstruction and the program are pan_gainloss.hpp's)
+//   pan_phylosig.hpp   pangene phylosig (the observed costs and the way up are pan_gainloss.hpp's)
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -26,3 +27,4 @@ using namespace pgx;
 #include "pan_mantel.hpp"
 #include "pan_gainloss.hpp"
 #include "pan_coevo.hpp"
+#include "pan_phylosig.hpp"
