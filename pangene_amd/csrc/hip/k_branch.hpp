@@ -237,21 +237,34 @@ __device__ __noinline__ bool nl_hazard(const NLocalHz &z, int cc, int iv1, int i
 // Tried the other way too, four pairs a group in flight with their loads batched: k_n_local 31 -> 43 us at configs[1]; more waves beat longer ones.)
 constexpr int nl_lanes_for(int GL) { return GL <= 256 ? 16 : GL <= 640 ? 32 : 64; }
 
+// seg_shift >= 0 (the residual list of a lazy round, BrLazy below): the list is BR_RSEG segments of 1 << seg_shift pairs, np_dev[s * BR_RSTRIDE] the
+// length of segment s; wave w of the launch (a multiple of BR_RSEG waves) takes segment w % BR_RSEG.  A segment beyond its room holds stretches
+// nobody wrote and is left out as a whole (the round is void: k_br_finish raises the flag).
+// bid / nb: the workgroup's number and their count (the kernel's own, or those of the leading workgroups of k_mark_hits_nl, k_genes.hpp).
+constexpr int BR_RSEG = 32, BR_RSTRIDE = 512; // (the lengths 4 KB apart: one atomic a vertex on ONE word cost the decision 12 us a round at configs[1])
+struct NLocalArgs { const int32_t *pairs; int64_t n_cap; const int64_t *np_dev; int GL; const void *rp_in; int local_dist, local_count, frag_mode; int32_t *cnt; NLocalHz hz; int seg_shift; };
 template <int FORM, int NL_LANES>
-__global__ __launch_bounds__(BLOCK) void k_n_local(const int32_t *pairs, int64_t n_cap, const int64_t *np_dev, int GL, const void *rp_in,
-                                                     int local_dist, int local_count, int frag_mode, int32_t *cnt, NLocalHz hz, Gate gate)
+__device__ __forceinline__ void n_local_body(const NLocalArgs &a, const unsigned bid, const unsigned nb)
 {
 	constexpr int NL_PAIRS = WAVE / NL_LANES;
 	constexpr unsigned long long NL_MASK = NL_LANES == 64 ? ~0ull : ((1ull << (NL_LANES & 63)) - 1);
-	if (gate_closed(gate)) return;
+	const int32_t *pairs = a.pairs; const int GL = a.GL; const void *rp_in = a.rp_in; const int local_dist = a.local_dist, local_count = a.local_count, frag_mode = a.frag_mode;
+	int32_t *cnt = a.cnt; const NLocalHz hz = a.hz;
 	const int lane = threadIdx.x & 63, grp = lane / NL_LANES, sub = lane & (NL_LANES - 1);
-	int64_t n_pair = np_dev ? *np_dev : n_cap; // the count may still be on its way to the host: it is read here
-	if (n_pair > n_cap) return; // more pairs than the list holds: some stretches of it were never written, and the host repeats the step with room
-	const int64_t stride = (int64_t)gridDim.x * (BLOCK / WAVE) * NL_PAIRS;
-	for (int64_t k0 = ((int64_t)blockIdx.x * (BLOCK / WAVE) + (threadIdx.x >> 6)) * NL_PAIRS; k0 < n_pair; k0 += stride) {
-		const int64_t k = k0 + grp;
-		const bool have = k < n_pair;
-		const int64_t kk = have ? k : n_pair - 1;
+	int64_t wid = (int64_t)bid * (BLOCK / WAVE) + (threadIdx.x >> 6), nw = (int64_t)nb * (BLOCK / WAVE), base = 0;
+	int64_t n_pair = (a.np_dev && a.seg_shift < 0) ? *a.np_dev : a.n_cap; // the count may still be on its way to the host: it is read here
+	if (a.seg_shift >= 0) { // this wave's segment, and its share of it
+		const int s = (int)(wid % BR_RSEG);
+		n_pair = a.np_dev[s * BR_RSTRIDE], base = (int64_t)s << a.seg_shift;
+		if (n_pair > ((int64_t)1 << a.seg_shift)) return;
+		wid /= BR_RSEG, nw /= BR_RSEG;
+	}
+	else if (n_pair > a.n_cap) return; // more pairs than the list holds: some stretches of it were never written, and the host repeats the step with room
+	const int64_t stride = nw * NL_PAIRS;
+	for (int64_t k0 = wid * NL_PAIRS; k0 < n_pair; k0 += stride) {
+		const bool have = k0 + grp < n_pair;
+		const int64_t k = base + k0 + grp;
+		const int64_t kk = have ? k : base + n_pair - 1;
 		const int64_t g1 = (int64_t)pairs[2 * kk] * GL, g2 = (int64_t)pairs[2 * kk + 1] * GL;
 		int c = 0;
 		bool open = have; // still searching (uniform over the sixteen lanes of the pair)
@@ -296,6 +309,13 @@ __global__ __launch_bounds__(BLOCK) void k_n_local(const int32_t *pairs, int64_t
 		}
 		if (have && sub == 0) cnt[k] = c;
 	}
+}
+template <int FORM, int NL_LANES>
+__global__ __launch_bounds__(BLOCK) void k_n_local(const int32_t *pairs, int64_t n_cap, const int64_t *np_dev, int GL, const void *rp_in,
+                                                     int local_dist, int local_count, int frag_mode, int32_t *cnt, NLocalHz hz, Gate gate, int seg_shift = -1)
+{
+	if (gate_closed(gate)) return;
+	n_local_body<FORM, NL_LANES>(NLocalArgs{pairs, n_cap, np_dev, GL, rp_in, local_dist, local_count, frag_mode, cnt, hz, seg_shift}, blockIdx.x, gridDim.x);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -367,7 +387,8 @@ __global__ __launch_bounds__(BLOCK) void k_deg(const int32_t *vs, const int32_t 
 }
 
 // number of pg_n_local calls of vertex v: n_max * n_weak (branch.c:70-75) + n(n-1)/2 (branch.c:83-88)
-__device__ __forceinline__ int br_count_one(const int v, const int32_t *vs, const int32_t *ve, const int32_t *s1, const double bd)
+// lazy (BrLazy below): a vertex the lane form takes lists row 0 of part 2 only, n - 1 pairs; the count must match the form the vertex will take
+__device__ __forceinline__ int br_count_one(const int v, const int32_t *vs, const int32_t *ve, const int32_t *s1, const double bd, const bool lazy = false)
 {
 	const int a0 = vs[v], n = ve[v] - a0;
 	if (n < 2) return 0;
@@ -377,13 +398,14 @@ __device__ __forceinline__ int br_count_one(const int v, const int32_t *vs, cons
 		n_max += s1[a0 + i] == max_s1;
 		n_weak += (1.0 - (double)s1[a0 + i] / max_s1) > bd; // branch.c:71-72
 	}
-	return n_max * n_weak + n * (n - 1) / 2;
+	return n_max * n_weak + (lazy && n <= WAVE ? n - 1 : n * (n - 1) / 2);
 }
-__global__ __launch_bounds__(BLOCK) void k_br_count(int n_vtx, const int32_t *vs, const int32_t *ve, const int32_t *s1, double bd, int32_t *pc, Gate gate)
+__global__ __launch_bounds__(BLOCK) void k_br_count(int n_vtx, const int32_t *vs, const int32_t *ve, const int32_t *s1, double bd, int32_t *pc, Gate gate, int64_t *res_len = nullptr /* lazy: the residual list's lengths, started again here */)
 {
 	const int v = blockIdx.x * BLOCK + threadIdx.x;
 	if (v >= n_vtx || gate_closed(gate)) return;
-	pc[v] = br_count_one(v, vs, ve, s1, bd);
+	if (v == 0 && res_len) for (int k = 0; k < BR_RSEG; ++k) res_len[k * BR_RSTRIDE] = 0;
+	pc[v] = br_count_one(v, vs, ve, s1, bd, res_len != nullptr);
 }
 
 // Exclusive prefix sums of the vertices' pair counts in ONE workgroup: a graph has thousands of vertices, not millions, and the
@@ -509,10 +531,22 @@ __device__ void br_vertex_wide(const int lane, int a0, int n, const int32_t *s1,
 // One WAVE per oriented vertex; lane j holds arc j (score, target gene, group mark) in registers and arcs are
 // broadcast with shuffles, so the O(n^2) pair loops of branch.c:70-90 touch memory only for the pair list
 // (coalesced stores, MODE 1) or the all-reduced counts (coalesced loads, MODE 2).
+//
+// The lazy form (the unsharded queued loop, lane form only).  Part 2 only computes n_dist_loci, and branch.c:86 reads a pair's answer only while j has
+// no group yet: once row 0 has put an arc into group 1 no later row's answer about it is read.  So the main list carries part 1 and row 0 (n - 1 pairs);
+// the decision settles row 0 and, where arcs are left without a group (about one vertex in ten), lists every (i, j) with 1 <= i < j for those j in a
+// RESIDUAL list (one atomic a vertex on its length); k_n_local runs over that list and k_br_finish replays the rows i >= 1 in order.
+struct BrLazy {
+	int on;
+	int32_t *rpairs; int seg_shift; // the residual list: BR_RSEG segments of 1 << seg_shift pairs (a vertex takes segment v % BR_RSEG)
+	int64_t *rlen;                  // [BR_RSEG * BR_RSTRIDE] their lengths (started again by the round's count kernel) -- beyond the room: what the round needed
+	int32_t *roff;                  // [n_vtx] where a vertex's stretch begins in the whole list, or -1: no stretch (written for every vertex of the lane form)
+	unsigned long long *rmask;      // [n_vtx] the arcs without a group after row 0
+};
 template <int MODE>
 __device__ __forceinline__ void br_wave_body(const int v, const int lane, uint16_t *s_grp /* MODE 2: the workgroup's */, const int64_t k0 /* poff[v] */, const int32_t *vs, const int32_t *ve, const int32_t *s1g, const int32_t *agidg, double bd,
                                              int32_t *pairs, int64_t pair_cap, const int32_t *pcnt, const int32_t *cnt, double bdist, double bcut,
-                                             uint8_t *weak, int32_t *grpg, int32_t *ndl, int64_t *dcnt, uint8_t *vwk)
+                                             uint8_t *weak, int32_t *grpg, int32_t *ndl, int64_t *dcnt, uint8_t *vwk, const BrLazy lz = BrLazy{0, nullptr, 0, nullptr, nullptr, nullptr})
 {
 	const int a0 = vs[v], n = ve[v] - a0;
 	if (n < 2) { if (MODE == 2 && lane == 0) ndl[v] = 0; return; } // (every n_dist_loci entry is written: nothing to clear beforehand)
@@ -559,6 +593,43 @@ __device__ __forceinline__ void br_wave_body(const int v, const int lane, uint16
 	}
 	// part 2 (branch.c:82-90): all i<j pairs, row i starts after i*n - i(i+1)/2 earlier pairs
 	const int64_t k2 = k0 + (int64_t)n_max * __popcll(m_weak);
+	if (lz.on) { // row 0 only: the pair (0, j) at k2 + j - 1
+		const int64_t k = k2 + (lane - 1);
+		if (MODE == 1) {
+			const int gid_0 = __builtin_amdgcn_readlane(my_gid, 0);
+			if (lane > 0 && in) pairs[2 * k] = gid_0, pairs[2 * k + 1] = my_gid;
+			return;
+		}
+		const bool un = lane > 0 && in && !(cnt[k] > 0); // arc 0 opens group 1, every j local with it joins
+		const unsigned long long m_un = __ballot(un);
+		int n_group = 1, off = -1;
+		if (m_un) {
+			// the stretch: for every j without a group (ascending) the rows 1 .. j - 1, the same gene order as the full list (agid[i] first)
+			const int mine = un ? lane - 1 : 0;
+			const int incl = wave_scan_incl(I32{mine}, OpSum{}, lane).v, tot = __builtin_amdgcn_readlane(incl, 63);
+			if (tot == 0) n_group = 2; // arc 1 alone is left: it opens group 2 and no row is asked anything
+			else {
+				const int seg = v & (BR_RSEG - 1);
+				long long base = 0;
+				if (lane == 0) base = (long long)atomicAdd((unsigned long long *)(lz.rlen + seg * BR_RSTRIDE), (unsigned long long)tot);
+				base = __shfl(base, 0, WAVE);
+				n_group = 0; // (k_br_finish writes it; a segment beyond its room voids the round -- k_br_finish raises the flag from the lengths)
+				if (base + tot <= ((long long)1 << lz.seg_shift)) {
+					base += (long long)seg << lz.seg_shift;
+					off = (int)base;
+					const int my_off = incl - mine;
+					for (unsigned long long m = m_un; m; m &= m - 1) {
+						const int j = __ffsll((long long)m) - 1; // wave-uniform
+						const int gid_j = __builtin_amdgcn_readlane(my_gid, j), off_j = __builtin_amdgcn_readlane(my_off, j);
+						const int64_t q = base + off_j + (lane - 1);
+						if (lane >= 1 && lane < j) lz.rpairs[2 * q] = my_gid, lz.rpairs[2 * q + 1] = gid_j;
+					}
+				}
+			}
+		}
+		if (lane == 0) ndl[v] = n_group, lz.roff[v] = off, lz.rmask[v] = m_un;
+		return;
+	}
 	int grp = 0, n_group = 0;
 	for (int i = 0; i < n; ++i) {
 		const int64_t k = k2 + (int64_t)i * n - (int64_t)i * (i + 1) / 2 + (lane - i - 1);
@@ -577,13 +648,46 @@ template <int MODE>
 __global__ __launch_bounds__(BLOCK) void k_br_wave(int n_vtx, const int32_t *vs, const int32_t *ve, const int32_t *s1g, const int32_t *agidg, double bd,
                                                      const int32_t *poff, int32_t *pairs, int64_t pair_cap /* MODE 1: room in pairs[] */, const int32_t *pcnt /* MODE 1: pairs of each vertex */, const int32_t *cnt, double bdist, double bcut,
                                                      uint8_t *weak, int32_t *grpg, int32_t *ndl, int64_t *dcnt, uint8_t *vwk /* MODE 2: vertex has a weak arc */,
-                                                     const int64_t *np_dev = nullptr /* MODE 2: the number of pairs, when the list has a capacity (pair_cap) */, Gate gate = Gate{nullptr, 0})
+                                                     const int64_t *np_dev = nullptr /* MODE 2: the number of pairs, when the list has a capacity (pair_cap) */, Gate gate = Gate{nullptr, 0},
+                                                     BrLazy lz = BrLazy{0, nullptr, 0, nullptr, nullptr, nullptr})
 {
 	__shared__ uint16_t s_grp[MODE == 2 ? (BLOCK / WAVE) * BR_WIDE_CAP : 1];
 	const int v = blockIdx.x * (BLOCK / WAVE) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
 	if (v >= n_vtx || gate_closed(gate)) return;
 	if (MODE == 2 && np_dev && *np_dev > pair_cap) return; // the list overflowed: there are no counts to read, the host repeats the step with room
-	br_wave_body<MODE>(v, lane, s_grp, poff[v], vs, ve, s1g, agidg, bd, pairs, pair_cap, pcnt, cnt, bdist, bcut, weak, grpg, ndl, dcnt, vwk);
+	br_wave_body<MODE>(v, lane, s_grp, poff[v], vs, ve, s1g, agidg, bd, pairs, pair_cap, pcnt, cnt, bdist, bcut, weak, grpg, ndl, dcnt, vwk, lz);
+}
+
+// The finish of a lazy round (branch.c:83-90 from row 1 on) for the vertices that have a stretch of the residual list: one wave a vertex, lane j holds
+// arc j's group mark; the rows run in order, each consults the residual counts only of the j still without a group at that moment, and the group
+// numbers are handed out in the reference's order.  rcnt[]: k_n_local's counts over the residual list.  Vertex 0's wave also keeps the books of the
+// list: the longest segment of the run (dcnt[18]) and the sticky flag when one did not fit (its vertices have no stretch: the run is repeated with room).
+__global__ __launch_bounds__(BLOCK) void k_br_finish(int n_vtx, const int32_t *vs, const int32_t *ve, const int32_t *rcnt, BrLazy lz, int32_t *ndl, int64_t *dcnt, const int64_t *np_dev, int64_t pair_cap, Gate gate)
+{
+	const int v = blockIdx.x * (BLOCK / WAVE) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+	if (v >= n_vtx || gate_closed(gate)) return;
+	if (np_dev && *np_dev > pair_cap) return; // the main list overflowed: the decision did not run (k_br_wave<2>), roff / rmask are not this round's
+	if (v == 0) { // the longest segment: what a list with room for the round needs is BR_RSEG times that
+		const int64_t l64 = lane < BR_RSEG ? lz.rlen[lane * BR_RSTRIDE] : 0;
+		const int64_t len = wave_max((int)(l64 < 0x7fffffff ? l64 : 0x7fffffff));
+		if (lane == 0) { if (len > dcnt[18]) dcnt[18] = len; if (len > ((int64_t)1 << lz.seg_shift)) dcnt[11] = 1; }
+	}
+	const int n = ve[v] - vs[v];
+	if (n < 2 || n > WAVE) return; // (not the lane form: the vertex listed every pair)
+	const int off = lz.roff[v];
+	if (off < 0) return;
+	const unsigned long long m_un = lz.rmask[v];
+	const bool in = lane < n, un = (m_un >> lane) & 1;
+	const int mine = un ? lane - 1 : 0;
+	const int my_off = wave_scan_incl(I32{mine}, OpSum{}, lane).v - mine;
+	int grp = in && !un ? 1 : 0, n_group = 1;
+	for (int i = 1; i < n; ++i) {
+		if (__ballot(in && grp == 0) == 0) break; // every arc has its group: the rows left open none
+		int gi = __builtin_amdgcn_readlane(grp, i);
+		if (gi == 0) { gi = ++n_group; if (lane == i) grp = gi; }
+		if (lane > i && un && grp == 0 && rcnt[(int64_t)off + my_off + (i - 1)] > 0) grp = gi;
+	}
+	if (lane == 0) ndl[v] = n_group;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -602,6 +706,7 @@ struct LoopFront {
 	const uint32_t *flags; const int32_t *goff; int32_t *rx;                                 // ranks
 	void *rp_out; int64_t n_ent; int clear_bytes;                                            // clear (0: none, 8 / 16: record size)
 	Gate gate;
+	int64_t *res_len; // lazy rounds (BrLazy): the residual list's lengths, started again here; NULL: every pair is listed
 };
 __global__ __launch_bounds__(RK_T) void k_loop_front1(LoopFront a)
 {
@@ -610,7 +715,8 @@ __global__ __launch_bounds__(RK_T) void k_loop_front1(LoopFront a)
 	const int b = blockIdx.x, tid = threadIdx.x;
 	if (b < a.nbc) {
 		const int v = b * RK_T + tid, lane = tid & 63, w = tid >> 6;
-		const int pc = v < a.n_vtx ? br_count_one(v, a.vs, a.ve, a.s1, a.bd) : 0;
+		if (v < BR_RSEG && a.res_len) a.res_len[v * BR_RSTRIDE] = 0;
+		const int pc = v < a.n_vtx ? br_count_one(v, a.vs, a.ve, a.s1, a.bd, a.res_len != nullptr) : 0;
 		const I32 incl = wave_scan_incl(I32{pc}, OpSum{}, lane);
 		if (lane == 63) wtot[0][w] = incl.v;
 		__syncthreads();
@@ -627,7 +733,7 @@ __global__ __launch_bounds__(RK_T) void k_loop_front1(LoopFront a)
 	}
 }
 struct LoopFront2 {
-	int nb_rep, n_vtx, nbc; const int32_t *vs, *ve, *s1, *agid; double bd; int32_t *poff; const int32_t *btot, *pc; int32_t *pairs; int64_t pair_cap; int64_t *dcnt;
+	int nb_rep, n_vtx, nbc; const int32_t *vs, *ve, *s1, *agid; double bd; int32_t *poff; const int32_t *btot, *pc; int32_t *pairs; int64_t pair_cap; int64_t *dcnt; int lazy;
 };
 template <int FORM, bool CLEARED>
 __global__ __launch_bounds__(BLOCK) void k_loop_front2(RepFill rf, LoopFront2 a)
@@ -644,7 +750,7 @@ __global__ __launch_bounds__(BLOCK) void k_loop_front2(RepFill rf, LoopFront2 a)
 		const int tot = wave_sum(part);
 		if (lane == 0) { a.dcnt[15] = tot; if (tot > a.pair_cap) { a.dcnt[11] = 1; if (tot > a.dcnt[16]) a.dcnt[16] = tot; } } // ([16]: the longest list that did not fit -- pga_branch_loop's next attempt makes room)
 	}
-	br_wave_body<1>(v, lane, nullptr, k0, a.vs, a.ve, a.s1, a.agid, a.bd, a.pairs, a.pair_cap, a.pc, nullptr, 0.0, 0.0, nullptr, nullptr, nullptr, a.dcnt, nullptr);
+	br_wave_body<1>(v, lane, nullptr, k0, a.vs, a.ve, a.s1, a.agid, a.bd, a.pairs, a.pair_cap, a.pc, nullptr, 0.0, 0.0, nullptr, nullptr, nullptr, a.dcnt, nullptr, BrLazy{a.lazy, nullptr, 0, nullptr, nullptr, nullptr});
 }
 
 // pg_flt_high_occ's three tests (graph.c:226-258) for every segment of the round, from what the round left on the device:

@@ -621,13 +621,16 @@ __global__ __launch_bounds__(BLOCK) void k_xs_compact(const int4 *gmeta, const i
 // ------------------------------------------------------------------------------------------------
 // pg_mark_branch_flt_hit (branch.c:108-145): a hit is marked by the weak arcs among its own two half-arcs
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(BLOCK) void k_mark_hits_z(const int32_t *zx, const int32_t *zy, const int32_t *zg, const uint32_t *hfk, const uint32_t *hbk, uint32_t tag, int n, const int32_t *g2s,
-                                                        const uint64_t *ax, const uint8_t *aw, const int32_t *vs, const int32_t *ve, const uint8_t *vwk,
-                                                        uint32_t *flags, int64_t *cnt, int then_filter, Gate gate, int32_t *stamp /* Gate::w of the loop, or NULL */, int round)
+struct MarkHitsZ {
+	const int32_t *zx, *zy, *zg; const uint32_t *hfk, *hbk; uint32_t tag; int n; const int32_t *g2s;
+	const uint64_t *ax; const uint8_t *aw; const int32_t *vs, *ve; const uint8_t *vwk;
+	uint32_t *flags; int64_t *cnt; int then_filter; Gate gate; int32_t *stamp /* Gate::w of the loop, or NULL */; int round;
+};
+__device__ __forceinline__ void mark_hits_z_body(const MarkHitsZ &a, const int z)
 {
-	int z = blockIdx.x * BLOCK + threadIdx.x;
+	const int32_t *zx = a.zx, *zy = a.zy, *zg = a.zg, *g2s = a.g2s, *vs = a.vs, *ve = a.ve; const uint32_t *hfk = a.hfk, *hbk = a.hbk; const uint32_t tag = a.tag; const int n = a.n;
+	const uint64_t *ax = a.ax; const uint8_t *aw = a.aw, *vwk = a.vwk; uint32_t *flags = a.flags; int64_t *cnt = a.cnt; const int then_filter = a.then_filter, round = a.round; int32_t *stamp = a.stamp;
 	bool marked = false;
-	if (gate_closed(gate)) return; // (uniform; a round that counts for the log never comes with a gate)
 	if (z < n) {
 		const uint32_t kb = hbk[z], kf = hfk[z]; // 16 bytes a hit, all independent loads
 		const int y = zy[z], g = zg[z];
@@ -661,4 +664,19 @@ __global__ __launch_bounds__(BLOCK) void k_mark_hits_z(const int32_t *zx, const 
 		const unsigned long long mk = __ballot(marked);
 		if (mk && (threadIdx.x & 63) == (unsigned)__ffsll((long long)mk) - 1) atomicAdd((unsigned long long *)cnt, (unsigned long long)__popcll(mk));
 	}
+}
+__global__ __launch_bounds__(BLOCK) void k_mark_hits_z(MarkHitsZ a)
+{
+	if (gate_closed(a.gate)) return; // (uniform; a round that counts for the log never comes with a gate)
+	mark_hits_z_body(a, blockIdx.x * BLOCK + threadIdx.x);
+}
+// The same with pg_n_local over the residual list of a lazy branch round (k_branch.hpp: BrLazy) as the launch's leading nb_nl workgroups: the marking
+// reads weak_br and the vertices' weak marks, which the decision has completed, and not n_dist_loci, which waits for these counts -- two chains that
+// share nothing, side by side (the list is short: a launch of its own is all launch).  Both run under the gate of the round's branch steps.
+template <int FORM, int NL_LANES>
+__global__ __launch_bounds__(BLOCK) void k_mark_hits_nl(MarkHitsZ a, NLocalArgs nl, int nb_nl)
+{
+	if (gate_closed(a.gate)) return;
+	if ((int)blockIdx.x < nb_nl) { n_local_body<FORM, NL_LANES>(nl, blockIdx.x, (unsigned)nb_nl); return; }
+	mark_hits_z_body(a, (blockIdx.x - nb_nl) * BLOCK + threadIdx.x);
 }

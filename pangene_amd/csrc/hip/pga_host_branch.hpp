@@ -57,20 +57,28 @@ static int rep_pos_impl(pga_ctx *c, RepDefer *df)
 extern "C" int pga_rep_pos(pga_ctx_t *c) { return rep_pos_impl(c, nullptr); }
 
 // n = number of pairs, or (np_dev != NULL) the capacity of d_pairs with the actual number in device memory
-static int n_local_dev(pga_ctx *c, const int32_t *d_pairs, int64_t n, const int64_t *np_dev, int32_t local_dist, int32_t local_count, int32_t frag_mode, int32_t **cnt)
+// (cnt_slot / seen / seg_shift: the residual list of a lazy round has counts and lengths of its own; ride: nothing is launched -- the arguments and the
+// number of workgroups for the launch that carries them, k_mark_hits_nl)
+struct NLocalRide { NLocalArgs a; unsigned nb; int lanes; };
+static int mark_hits_resident(pga_ctx *c, int64_t *n_marked, int32_t then_filter, const NLocalRide *ride); // (below)
+static int n_local_dev(pga_ctx *c, const int32_t *d_pairs, int64_t n, const int64_t *np_dev, int32_t local_dist, int32_t local_count, int32_t frag_mode, int32_t **cnt, int cnt_slot = S_NLCNT, int64_t seen = -1, int seg_shift = -1,
+                       NLocalRide *ride = nullptr)
 {
-	int32_t *d_cnt = (int32_t *)c->pool.get(S_NLCNT, sizeof(int32_t) * (size_t)n + 16);
+	int32_t *d_cnt = (int32_t *)c->pool.get(cnt_slot, sizeof(int32_t) * (size_t)n + 16);
 	int4 *rp = (int4 *)c->pool.get(S_RP_SEG, 0);
 	if (!d_cnt || !rp) return PGA_ERR_NOMEM;
 	*cnt = d_cnt;
 	NLocalHz hz = { (const int32_t *)c->pool.get(S_RP_IV, 0), c->ctg_base, c->dcnt, (int32_t *)c->pool.get(S_HZLIST, sizeof(int32_t) * PGA_HAZARD_CAP) };
 	if (!hz.iv || !hz.list) return PGA_ERR_NOMEM;
 	// the grid follows the last known number of pairs (the kernel strides over whatever there is)
-	const int64_t est = np_dev ? (c->br_np_seen > 0 ? c->br_np_seen : std::min<int64_t>(n, 1 << 18)) : n;
+	if (seen < 0) seen = c->br_np_seen;
+	const int64_t est = np_dev ? (seen > 0 ? seen : std::min<int64_t>(n, 1 << 18)) : n;
 	static const int lanes_env = [] { const char *e = getenv("PANGENE_NL_LANES"); return e ? atoi(e) : 0; }(); // (measurements: 16 / 32 / 64 whatever the number of genomes)
 	const int lanes = (lanes_env == 16 || lanes_env == 32 || lanes_env == 64) ? lanes_env : nl_lanes_for(c->n_genome);
-	const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(nblk(est, BLOCK / WAVE * (WAVE / lanes)), 1 << 20));
-#define NL_LAUNCH(FORM, LANES) hipLaunchKernelGGL((k_n_local<FORM, LANES>), dim3(grid), dim3(BLOCK), 0, c->st, d_pairs, n, np_dev, c->n_genome, (const void *)rp, local_dist, local_count, frag_mode, d_cnt, hz, c->gate)
+	unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(nblk(est, BLOCK / WAVE * (WAVE / lanes)), 1 << 20));
+	if (seg_shift >= 0) grid = (grid + 7u) & ~7u; // (a multiple of BR_RSEG waves: every segment gets the same number)
+	if (ride) { *ride = NLocalRide{ NLocalArgs{d_pairs, n, np_dev, c->n_genome, (const void *)rp, local_dist, local_count, frag_mode, d_cnt, hz, seg_shift}, n ? grid : 0u, lanes }; return 0; }
+#define NL_LAUNCH(FORM, LANES) hipLaunchKernelGGL((k_n_local<FORM, LANES>), dim3(grid), dim3(BLOCK), 0, c->st, d_pairs, n, np_dev, c->n_genome, (const void *)rp, local_dist, local_count, frag_mode, d_cnt, hz, c->gate, seg_shift)
 #define NL_FORM(FORM) do { if (lanes == 16) NL_LAUNCH(FORM, 16); else if (lanes == 32) NL_LAUNCH(FORM, 32); else NL_LAUNCH(FORM, 64); } while (0)
 	if (n && c->rp_form == RP_COMPACT) NL_FORM(RP_COMPACT);
 	else if (n && c->rp_form == RP_WIDE) NL_FORM(RP_WIDE);
@@ -124,7 +132,7 @@ static int branch_enumerate(pga_ctx *c, int32_t **cnt, const RepDefer *df = null
 	if (df) { // the records of pg_gen_rep_pos and the pair list in one launch (k_loop_front1 ran: ranks, counts, offsets inside each workgroup of 1 024 vertices)
 		const int32_t *pc = (const int32_t *)c->pool.get(S_BR_PC, 0);
 		const unsigned nb_rep = df->rode >= 2 ? 0u : df->nb; // (the records rode with the arc round's gene kernel: the pair list alone)
-		const LoopFront2 a = { (int)nb_rep, n_vtx, (n_vtx + RK_T - 1) / RK_T, vs, ve, s1, agid, c->br_par.diff, poff, pc + loop_btot_at(n_vtx), pc, pairs, c->br_cap, c->dcnt };
+		const LoopFront2 a = { (int)nb_rep, n_vtx, (n_vtx + RK_T - 1) / RK_T, vs, ve, s1, agid, c->br_par.diff, poff, pc + loop_btot_at(n_vtx), pc, pairs, c->br_cap, c->dcnt, c->br_lazy ? 1 : 0 };
 		const dim3 grid(nb_rep + nblk(n_vtx, BLOCK / WAVE));
 		const int form = c->rp_form;
 		if (df->cleared) {
@@ -138,8 +146,54 @@ static int branch_enumerate(pga_ctx *c, int32_t **cnt, const RepDefer *df = null
 		}
 	} else
 	hipLaunchKernelGGL((k_br_wave<1>), dim3(nblk(n_vtx, BLOCK / WAVE)), dim3(BLOCK), 0, c->st, n_vtx, vs, ve, s1, agid, c->br_par.diff, poff, pairs, c->br_cap, (const int32_t *)c->pool.get(S_BR_PC, 0),
-	                   (const int32_t *)nullptr, 0.0, 0.0, (uint8_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, c->dcnt, (uint8_t *)nullptr, (const int64_t *)nullptr, c->gate);
+	                   (const int32_t *)nullptr, 0.0, 0.0, (uint8_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, c->dcnt, (uint8_t *)nullptr, (const int64_t *)nullptr, c->gate, BrLazy{c->br_lazy ? 1 : 0, nullptr, 0, nullptr, nullptr, nullptr});
 	return n_local_dev(c, pairs, c->br_cap, c->dcnt + 15, c->br_par.local_dist, c->br_par.local_count, c->br_par.frag_mode, cnt);
+}
+
+// The lazy form of a round (k_branch.hpp: BrLazy): the lengths of the residual list's segments (the round's count kernel starts them again), or NULL ...
+static inline int64_t *br_res_len(pga_ctx *c) { return c->br_lazy ? (int64_t *)c->pool.get(S_BR_RLEN, sizeof(int64_t) * BR_RSEG * BR_RSTRIDE) : (int64_t *)nullptr; }
+// ... what the decision needs besides the main list ...
+static int br_lazy_args(pga_ctx *c, int n_vtx, BrLazy *lz)
+{
+	*lz = BrLazy{0, nullptr, 0, nullptr, nullptr, nullptr};
+	if (!c->br_lazy) return 0;
+	int shift = 0;
+	while (((int64_t)BR_RSEG << shift) < c->br_rcap) ++shift;
+	c->br_rcap = (int64_t)BR_RSEG << shift; // (the room is BR_RSEG segments of a power of two)
+	lz->on = 1, lz->seg_shift = shift;
+	lz->rlen = br_res_len(c);
+	lz->rpairs = (int32_t *)c->pool.get(S_RPAIRS, sizeof(int32_t) * 2 * (size_t)c->br_rcap + 16);
+	lz->roff = (int32_t *)c->pool.get(S_BR_ROFF, sizeof(int32_t) * (size_t)n_vtx + 16);
+	lz->rmask = (unsigned long long *)c->pool.get(S_BR_RMASK, sizeof(unsigned long long) * (size_t)n_vtx + 16);
+	return (lz->rpairs && lz->rlen && lz->roff && lz->rmask) ? 0 : PGA_ERR_NOMEM;
+}
+// ... and what follows it: pg_n_local over the residual list (its length in device memory, as the main list's) and the rows from 1 on (k_br_finish)
+// (ride: the counts travel in the launch of pg_mark_branch_flt_hit, which the caller queues between the two)
+static int branch_residual_counts(pga_ctx *c, const BrLazy &lz, NLocalRide *ride)
+{
+	int32_t *rcnt;
+	return lz.on ? n_local_dev(c, lz.rpairs, c->br_rcap, lz.rlen, c->br_par.local_dist, c->br_par.local_count, c->br_par.frag_mode, &rcnt, S_RNLCNT, std::min<int64_t>(c->br_rcap, std::max<int64_t>(c->br_res_seen, 1 << 12)), lz.seg_shift, ride) : 0;
+}
+static int branch_finish(pga_ctx *c, const BrLazy &lz, int n_vtx, int32_t *ndl)
+{
+	if (!lz.on) return 0;
+	const int32_t *rcnt = (const int32_t *)c->pool.get(S_RNLCNT, 0);
+	if (!rcnt) return PGA_ERR_NOMEM;
+	hipLaunchKernelGGL(k_br_finish, dim3(nblk(n_vtx, BLOCK / WAVE)), dim3(BLOCK), 0, c->st, n_vtx, (const int32_t *)c->pool.get(S_BR_VS, 0), (const int32_t *)c->pool.get(S_BR_VE, 0), rcnt, lz, ndl, c->dcnt, (const int64_t *)(c->dcnt + 15), (int64_t)c->br_cap, c->gate);
+	return 0;
+}
+static int branch_residual(pga_ctx *c, const BrLazy &lz, int n_vtx, int32_t *ndl)
+{
+	TRY(branch_residual_counts(c, lz, nullptr));
+	return branch_finish(c, lz, n_vtx, ndl);
+}
+// the residual list's room (BR_RSEG segments; seen / need: BR_RSEG times the longest segment): what earlier runs over the data set needed with a margin,
+// never less than a floor (64 k pairs: 0.75 MB with the counts; a segment of 2 048 then holds the 1 953 pairs of the largest stretch of the lane form)
+static inline bool loop_res_cap_forced(const pga_ctx *c) { return getenv("PANGENE_LOOP_RES_CAP") != nullptr && !c->loop_room_given; }
+static void br_res_room(pga_ctx *c)
+{
+	c->br_rcap = std::max<int64_t>(c->br_rcap, std::max<int64_t>((int64_t)1 << 16, c->br_res_seen + c->br_res_seen / 4));
+	if (loop_res_cap_forced(c)) c->br_rcap = std::max<long long>(1, atoll(getenv("PANGENE_LOOP_RES_CAP"))); // (tests: a first attempt with this little room -> status 4 -> a second one with what was needed)
 }
 
 static int branch_pairs_impl(pga_ctx *c, const uint64_t *arc_x, const int32_t *arc_s1, int64_t n_arc, const int32_t *seg_gid, int32_t n_seg,
@@ -174,12 +228,12 @@ static int branch_pairs_impl(pga_ctx *c, const uint64_t *arc_x, const int32_t *a
 		const RepFill &rf = df->rf;
 		const int64_t n_clear = (df->cleared && !df->rode) ? rf.n_ent : 0;
 		const int gl = df->rode ? 0 : rf.GL; // (the ranks and the clear rode with the arc round's walk: the pair counts alone)
-		const LoopFront a = { n_vtx, nbc, gl, vs, ve, s1, branch_diff, pc, poff, pc + loop_btot_at(n_vtx), rf.flags, rf.goff, df->rx, rf.rp_out, n_clear, c->rp_form == RP_COMPACT ? 8 : 16, c->gate };
+		const LoopFront a = { n_vtx, nbc, gl, vs, ve, s1, branch_diff, pc, poff, pc + loop_btot_at(n_vtx), rf.flags, rf.goff, df->rx, rf.rp_out, n_clear, c->rp_form == RP_COMPACT ? 8 : 16, c->gate, br_res_len(c) };
 		hipLaunchKernelGGL(k_loop_front1, dim3((unsigned)(nbc + gl + (n_clear + RK_T - 1) / RK_T)), dim3(RK_T), 0, c->st, a);
 		if (c->br_cap < 4 * (int64_t)n_vtx && !loop_cap_forced(c)) c->br_cap = 4 * (int64_t)n_vtx;
 		return branch_enumerate(c, cnt, df);
 	}
-	hipLaunchKernelGGL(k_br_count, dim3(nblk(n_vtx)), dim3(BLOCK), 0, c->st, n_vtx, vs, ve, s1, branch_diff, pc, c->gate);
+	hipLaunchKernelGGL(k_br_count, dim3(nblk(n_vtx)), dim3(BLOCK), 0, c->st, n_vtx, vs, ve, s1, branch_diff, pc, c->gate, br_res_len(c));
 	if (one_wg) hipLaunchKernelGGL(k_pair_offsets, dim3(1), dim3(PO_THREADS), 0, c->st, (const int32_t *)pc, n_vtx, poff, c->dcnt, c->h_box, n_pairs ? -1ll : loop_cap_forced(c) ? (long long)c->br_cap : (long long)std::max<int64_t>(c->br_cap, 4 * (int64_t)n_vtx), c->gate); // offsets, and dcnt[15] = number of pairs
 	else {
 		I32 *tile = (I32 *)c->pool.get(S_TILE, tile_buf_bytes(n_vtx));
@@ -470,8 +524,15 @@ extern "C" int pga_branch_loop(pga_ctx_t *c, int32_t n_round, const pga_branch_p
 	// in the header of the round's all-gather (k_xs_compact writes the word whether its gate is open or not) and k_xs_sum_rank stamps the round on every rank when any rank marked; a rank's own arc
 	// round follows its own hits (nothing changed here: its slot stands as it is, k_xs_compact leaves), the collectives are queued all the same.
 	const bool gated = !no_skip && (int64_t)c->round_tag + n_round + 4 < (int64_t)HA_TAG_MAX;
-	struct GateScope { pga_ctx *c; ~GateScope() { c->gate = Gate{nullptr, 0}, c->loop_gated = false, c->in_loop = false, c->ride_want = 0, c->ride_done = 0; } } gate_scope{c}; // (every way out of this function leaves the launches open)
+	struct GateScope { pga_ctx *c; ~GateScope() { c->gate = Gate{nullptr, 0}, c->loop_gated = false, c->in_loop = false, c->br_lazy = false, c->ride_want = 0, c->ride_done = 0; } } gate_scope{c}; // (every way out of this function leaves the launches open)
 	c->loop_gated = gated, c->in_loop = true;
+	// The lazy form (k_branch.hpp: BrLazy): the unsharded queue with the fused front lists part 1 and row 0 of part 2 and asks about the rest only where
+	// row 0 left arcs without a group.  Sharded rounds all-reduce the main list's counts at a capacity all ranks share and keep every pair; so do the
+	// host-driven entry points and PANGENE_LOOP_FUSE=0.  PANGENE_BR_LAZY=0: every pair everywhere (read at every call: one process can run both forms).
+	c->br_lazy = !env_has("PANGENE_BR_LAZY", "0") && x == nullptr && !env_has("PANGENE_LOOP_FUSE", "0");
+	if (c->br_lazy) br_res_room(c);
+	BrLazy lz;
+	TRY(br_lazy_args(c, n_vtx, &lz));
 	// Riders (pga_host_arcs.hpp): an arc round that a branch round of this queue follows carries the front half of that round's pg_gen_rep_pos in its own
 	// launches -- the ranks (and the clear) with the walk, the records with the gene kernel; both run under the arc round's gate, which is the gate of
 	// that branch round's front (something changed in round r).  PANGENE_LOOP_RIDE=0: nothing rides, 1: the ranks only, 2 (default): both.  Not with
@@ -485,7 +546,7 @@ extern "C" int pga_branch_loop(pga_ctx_t *c, int32_t n_round, const pga_branch_p
 		if (maxg <= (1 << 15)) ride = ride_env, c->ride_cpg = (int)std::max<int64_t>(1, (maxg + RK_CHUNK - 1) / RK_CHUNK);
 	}
 	const uint32_t tag_before = c->round_tag;
-	HIPCHK(hipMemsetAsync(c->dcnt + 16, 0, sizeof(int64_t), c->st)); // the longest pair list that did not fit (k_loop_front2 / k_pair_offsets)
+	HIPCHK(hipMemsetAsync(c->dcnt + 16, 0, 3 * sizeof(int64_t), c->st)); // [16] the longest pair list that did not fit (k_loop_front2 / k_pair_offsets); [18] the longest segment of a residual list in this run (k_br_finish)
 	if (gated) HIPCHK(hipMemsetAsync(c->loopctl, 0xff, 4 * sizeof(int32_t), c->st)); // -1: nothing has happened yet; round 0 runs (its branch steps ask for a change in round -1 or later)
 	// Live lists inside the queue.  pg_flt_high_occ's first rounds delete segments wholesale on many-genome shards (1 250 bacterial
 	// genomes: 98.5 % of the hits are without flt before the test of round 1, 38.5 % after it), so on shards where a wait is small beside a round
@@ -513,9 +574,15 @@ extern "C" int pga_branch_loop(pga_ctx_t *c, int32_t n_round, const pga_branch_p
 			int32_t *sg = (int32_t *)c->pool.get(S_BR_SEGGID, 0), *dg = (int32_t *)c->pool.get(S_DEG, 0), *seg_cnt = (int32_t *)c->pool.get(S_SEGCNT, 0);
 			if (!aw || !vwk || !s1 || !agid || !vs || !ve || !poff || !grp || !sg || !dg || !seg_cnt) return PGA_ERR_NOMEM;
 			hipLaunchKernelGGL((k_br_wave<2>), dim3(nblk(n_vtx, BLOCK / WAVE)), dim3(BLOCK), 0, c->st, n_vtx, vs, ve, s1, agid, par->branch_diff, poff, (int32_t *)nullptr, (int64_t)c->br_cap, (const int32_t *)nullptr, (const int32_t *)c->pool.get(S_NLCNT, 0),
-			                   par->branch_diff_dist, par->branch_diff_cut, aw, grp, ndl, (int64_t *)nullptr, vwk, c->dcnt + 15, c->gate);
-			// pg_mark_branch_flt_hit + PG_SET_FILTER(weak_br == 2) (branch.c:108-145, graph.c:309): with the numbering the arcs were made with
-			TRY(pga_mark_hits(c, nullptr, nullptr, 0, nullptr, 1));
+			                   par->branch_diff_dist, par->branch_diff_cut, aw, grp, ndl, (int64_t *)nullptr, vwk, c->dcnt + 15, c->gate, lz);
+			// pg_mark_branch_flt_hit + PG_SET_FILTER(weak_br == 2) (branch.c:108-145, graph.c:309): with the numbering the arcs were made with.
+			// (lazy: the residual list's counts ride in its launch as leading workgroups -- PANGENE_BR_LAZY_RIDE=0: in a launch of their own in
+			// front of it --, then the rows from 1 on; ndl is complete behind them)
+			NLocalRide nlr;
+			const bool nl_rides = lz.on && c->NL > 0 && !env_has("PANGENE_BR_LAZY_RIDE", "0");
+			TRY(branch_residual_counts(c, lz, nl_rides ? &nlr : nullptr));
+			TRY(mark_hits_resident(c, nullptr, 1, nl_rides ? &nlr : nullptr));
+			TRY(branch_finish(c, lz, n_vtx, ndl));
 			c->gate = gated ? Gate{c->loopctl, r} : Gate{nullptr, 0}; // from here on: something changed in THIS round
 			if (r > 0) { // pg_flt_high_occ + pg_hard_delete + PG_SET_FILTER(vtx == 0) (graph.c:219-263, 312): the thresholds tighten every round, so this test always runs
 				hipLaunchKernelGGL(k_round_del, dim3(nblk(S)), dim3(BLOCK), 0, c->st, S, (const int32_t *)ndl, max_tot_cnt[r], max_degree[r], max_dist_loci[r], (const int32_t *)sg, c->g2s, vs, ve, dg, seg_cnt, vwk, alive,
@@ -577,15 +644,15 @@ extern "C" int pga_branch_loop(pga_ctx_t *c, int32_t n_round, const pga_branch_p
 		if (!h_ctl) return PGA_ERR_NOMEM;
 		HIPCHK(hipMemcpyAsync(h_ctl, c->loopctl, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, c->st));
 	}
-	const size_t fetch_need = (((size_t)S + 128 + (par->final_on ? 4 * sizeof(int32_t) * (size_t)S + 64 : 0) + 15) & ~(size_t)15) + 64 + 16;
+	const size_t fetch_need = (((size_t)S + 128 + (par->final_on ? 4 * sizeof(int32_t) * (size_t)S + 64 : 0) + 15) & ~(size_t)15) + 64 + 32;
 	if (c->h_fetch_cap < fetch_need) {
 		c->h_fetch = c->pin.get(fetch_need + fetch_need / 2 + 512);
 		if (!c->h_fetch) return PGA_ERR_NOMEM;
 		c->h_fetch_cap = fetch_need + fetch_need / 2 + 512;
 	}
 	HIPCHK(hipMemcpyAsync(c->h_fetch, alive, (size_t)S, hipMemcpyDeviceToHost, c->st));
-	int64_t *h_need = (int64_t *)((char *)c->h_fetch + fetch_need - 16); // (the last 16 bytes of what was asked for)
-	HIPCHK(hipMemcpyAsync(h_need, c->dcnt + 16, sizeof(int64_t), hipMemcpyDeviceToHost, c->st));
+	int64_t *h_need = (int64_t *)((char *)c->h_fetch + fetch_need - 32); // (the last 32 bytes of what was asked for: dcnt[16 .. 18])
+	HIPCHK(hipMemcpyAsync(h_need, c->dcnt + 16, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, c->st));
 	int32_t *h_fin = (int32_t *)((char *)c->h_fetch + (((size_t)S + 127) & ~(size_t)63)); // (final_on) the last arc round's segment counters, the last branch step's n_dist_loci
 	if (par->final_on) {
 		HIPCHK(hipMemcpyAsync(h_fin, (const int32_t *)c->pool.get(S_SEGCNT, 0), sizeof(int32_t) * (size_t)n_vtx, hipMemcpyDeviceToHost, c->st));
@@ -608,6 +675,10 @@ extern "C" int pga_branch_loop(pga_ctx_t *c, int32_t n_round, const pga_branch_p
 	}
 	c->br_np_seen = std::max<int64_t>(c->br_np_seen, c->h_cnt[15]);
 	if (getenv("PANGENE_TIMING")) fprintf(stderr, "[pga_branch_loop] counters after %d rounds: invariant %lld, table overflows (last round) %lld, sticky %lld, pairs (last round) %lld of capacity %lld\n", n_round, (long long)c->h_cnt[3], (long long)c->h_cnt[9], (long long)c->h_cnt[11], (long long)c->h_cnt[15], (long long)c->br_cap);
+	const int64_t res_need = h_need[2] * BR_RSEG; // (every segment as long as the longest)
+	if (c->br_lazy && getenv("PANGENE_TIMING")) fprintf(stderr, "[pga_branch_loop] lazy rounds: the longest segment of a residual list %lld of capacity %lld (%d segments)\n", (long long)h_need[2], (long long)(c->br_rcap / BR_RSEG), BR_RSEG);
+	const bool res_over = c->br_lazy && res_need > c->br_rcap; // (read before the scope's end clears br_lazy)
+	if (c->br_lazy) c->br_res_seen = std::max<int64_t>(c->br_res_seen, res_need);
 	if (x && par->final_on) c->cur_tab = L.merged, c->cur_tab_n = c->h_cnt[10], c->table_sparse = false; // the merged table of the last queued arc round is the graph's (pga_arc_table)
 	if (x) {
 		const int32_t *f = (const int32_t *)h_x;
@@ -633,6 +704,8 @@ extern "C" int pga_branch_loop(pga_ctx_t *c, int32_t n_round, const pga_branch_p
 		const int64_t need = *h_need;
 		if (getenv("PANGENE_TIMING")) fprintf(stderr, "[pga_branch_loop] the longest pair list that did not fit: %lld (capacity %lld)\n", (long long)need, (long long)c->br_cap);
 		if (need > c->br_cap && c->h_cnt[9] == 0 && need + need / 4 <= ((int64_t)1 << 27)) { c->br_cap = need + need / 4, c->loop_room_given = true; return 4; }
+		// the same for the residual list of the lazy rounds (the main list fitted: the decision ran and counted what it needed)
+		if (need <= c->br_cap && res_over && c->h_cnt[9] == 0 && res_need + res_need / 4 <= ((int64_t)1 << 27)) { c->br_rcap = res_need + res_need / 4, c->loop_room_given = true; return 4; }
 		return 1;
 	}
 	memcpy(seg_alive, c->h_fetch, (size_t)S);
@@ -642,21 +715,40 @@ extern "C" int pga_branch_loop(pga_ctx_t *c, int32_t n_round, const pga_branch_p
 	return 0;
 }
 
+// the arcs (and their weak_br) left resident by the round: every hit looks at its own two half-arcs (k_genes.hpp).  ride: pg_n_local over the residual
+// list of a lazy branch round in the same launch (pga_branch_loop; needs c->NL > 0 and no n_marked: the same gate for both)
+static int mark_hits_resident(pga_ctx *c, int64_t *n_marked, int32_t then_filter, const NLocalRide *ride)
+{
+	TRY(ensure_half_arcs(c, c->ha_ori < 0 ? 0 : c->ha_ori));
+	const uint64_t *ax = (const uint64_t *)c->pool.get(S_ARCX, 0); const uint8_t *aw = (const uint8_t *)c->pool.get(S_ARCW, 0);
+	const int32_t *vs = (const int32_t *)c->pool.get(S_BR_VS, 0), *ve = (const int32_t *)c->pool.get(S_BR_VE, 0);
+	const uint8_t *vwk = (const uint8_t *)c->pool.get(S_VWK, 0);
+	if (!ax || !aw || !vs || !ve || !vwk) return PGA_ERR_NOMEM;
+	if (n_marked) HIPCHK(hipMemsetAsync(c->dcnt + 2, 0, sizeof(int64_t), c->st));
+	const MarkHitsZ a = { c->zx, c->zy, c->zg, c->hfk, c->hbk, c->round_tag, c->NL, c->g2s, ax, aw, vs, ve, vwk, c->flags,
+	                      n_marked ? c->dcnt + 2 : (int64_t *)nullptr, then_filter, n_marked ? Gate{nullptr, 0} : c->gate, c->gate.w ? c->loopctl : (int32_t *)nullptr, c->loop_round };
+	if (ride && ride->nb && c->NL && !n_marked) {
+		const dim3 grid(ride->nb + nblk(c->NL));
+#define MH_LAUNCH(FORM, LANES) hipLaunchKernelGGL((k_mark_hits_nl<FORM, LANES>), grid, dim3(BLOCK), 0, c->st, a, ride->a, (int)ride->nb)
+#define MH_FORM(FORM) do { if (ride->lanes == 16) MH_LAUNCH(FORM, 16); else if (ride->lanes == 32) MH_LAUNCH(FORM, 32); else MH_LAUNCH(FORM, 64); } while (0)
+		if (c->rp_form == RP_COMPACT) MH_FORM(RP_COMPACT);
+		else if (c->rp_form == RP_WIDE) MH_FORM(RP_WIDE);
+		else MH_FORM(RP_FULL);
+#undef MH_FORM
+#undef MH_LAUNCH
+	}
+	else if (c->NL) hipLaunchKernelGGL(k_mark_hits_z, dim3(nblk(c->NL)), dim3(BLOCK), 0, c->st, a);
+	if (then_filter) c->walk_valid = false, c->ha_valid = false; // else: weak_br does not enter the walkable test, the half-arcs stay valid
+	return 0;
+}
+
 extern "C" int pga_mark_hits(pga_ctx_t *c, const uint64_t *arc_x, const uint8_t *arc_weak, int64_t n_arc, int64_t *n_marked, int32_t then_filter)
 {
 	const int N = c->N;
 	if (n_marked) *n_marked = 0;
 	if (N == 0) return 0;
-	if (arc_x == nullptr) { // the arcs (and their weak_br) left resident by the round: every hit looks at its own two half-arcs (k_genes.hpp)
-		TRY(ensure_half_arcs(c, c->ha_ori < 0 ? 0 : c->ha_ori));
-		const uint64_t *ax = (const uint64_t *)c->pool.get(S_ARCX, 0); const uint8_t *aw = (const uint8_t *)c->pool.get(S_ARCW, 0);
-		const int32_t *vs = (const int32_t *)c->pool.get(S_BR_VS, 0), *ve = (const int32_t *)c->pool.get(S_BR_VE, 0);
-		const uint8_t *vwk = (const uint8_t *)c->pool.get(S_VWK, 0);
-		if (!ax || !aw || !vs || !ve || !vwk) return PGA_ERR_NOMEM;
-		if (n_marked) HIPCHK(hipMemsetAsync(c->dcnt + 2, 0, sizeof(int64_t), c->st));
-		if (c->NL) hipLaunchKernelGGL(k_mark_hits_z, dim3(nblk(c->NL)), dim3(BLOCK), 0, c->st, c->zx, c->zy, c->zg, c->hfk, c->hbk, c->round_tag, c->NL, c->g2s, ax, aw, vs, ve, vwk, c->flags,
-		                   n_marked ? c->dcnt + 2 : (int64_t *)nullptr, then_filter, n_marked ? Gate{nullptr, 0} : c->gate, c->gate.w ? c->loopctl : (int32_t *)nullptr, c->loop_round);
-		if (then_filter) c->walk_valid = false, c->ha_valid = false; // else: weak_br does not enter the walkable test, the half-arcs stay valid
+	if (arc_x == nullptr) {
+		TRY(mark_hits_resident(c, n_marked, then_filter, nullptr));
 	} else {
 		uint64_t *ax = (uint64_t *)c->pool.get(S_ARCX, sizeof(uint64_t) * (size_t)n_arc + 16);
 		uint8_t *aw = (uint8_t *)c->pool.get(S_ARCW, (size_t)n_arc + 16);

@@ -220,3 +220,85 @@ extern "C" int pga_selftest_post_rep(const int64_t *sums, const int32_t *max_ori
 	(void)hipFree(d_sums); (void)hipFree(d_key); (void)hipFree(d_mx); (void)hipFree(d_gid); (void)hipFree(d_rep1); (void)hipFree(d_words); (void)hipFree(d_rep);
 	return 0;
 }
+
+// pg_mark_branch_flt_arc's device chain on a given arc table and a given position-record table (tests/test_branch_lazy_gpu.py): counts -> offsets ->
+// list -> k_n_local -> decision (-> residual list -> k_n_local -> k_br_finish when lazy), the kernels and host steps pga_branch_loop queues, without a
+// context of a data set.  vs / ve [n_vtx]: the arc range of every vertex; s1 / agid [n_arc]: rounded score and target gene of every arc; rp [4 Q GL]:
+// the full-form records {contig, rank, cm, interval} of (gene, genome), contig -1 = absent.  lazy: 0 every pair, 1 the lazy form; res_cap: room of
+// the residual list on the first attempt (<= 0: the floor; shared out over BR_RSEG segments) -- a list beyond it ends in the repeat with room, as pga_branch_loop's status 4 does;
+// gate_closed: every launch finds its gate closed (the outputs stay as the caller filled them).  aw [n_arc], ndl [n_vtx], vwk [n_vtx]: in / out;
+// lens[4]: the main list's length, the residual list's, attempts made, the sticky flag of the LAST attempt.
+extern "C" int pga_selftest_branch(const int32_t *vs, const int32_t *ve, const int32_t *s1, const int32_t *agid, int32_t n_vtx, int64_t n_arc, const int32_t *rp, int32_t Q, int32_t GL,
+                                   double bd, double bdist, double bcut, int32_t local_dist, int32_t local_count, int32_t lazy, int64_t res_cap, int32_t gate_closed,
+                                   uint8_t *aw, int32_t *ndl, uint8_t *vwk, int64_t *lens)
+{
+	int ndev = 0;
+	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return PGA_ERR_NO_DEVICE;
+	if (n_vtx <= 0 || n_vtx > PO_THREADS * PO_MAX_ITEMS || n_arc <= 0 || Q <= 0 || GL <= 0 || !vs || !ve || !s1 || !agid || !rp || !aw || !ndl || !vwk || !lens) return PGA_ERR_ARG;
+	for (int v = 0; v < n_vtx; ++v) if (vs[v] < 0 || ve[v] < vs[v] || ve[v] > n_arc) return PGA_ERR_ARG;
+	for (int64_t i = 0; i < n_arc; ++i) if (agid[i] < 0 || agid[i] >= Q || s1[i] <= 0) return PGA_ERR_ARG;
+	pga_ctx c; // a bare context: stream, counters, pool
+	HIPCHK(hipStreamCreateWithFlags(&c.st, hipStreamNonBlocking));
+	TRY(dalloc(&c, &c.dcnt, 24)); TRY(dalloc(&c, &c.loopctl, 4)); TRY(dalloc_commit(&c));
+	HIPCHK(hipHostMalloc((void **)&c.h_cnt, 24 * sizeof(int64_t), hipHostMallocDefault));
+	HIPCHK(hipHostGetDevicePointer((void **)&c.h_box, c.h_cnt, 0));
+	c.n_genome = GL, c.Q = Q, c.rp_form = RP_FULL;
+	c.br_n = n_arc, c.br_S = n_vtx / 2, c.br_np = -1;
+	c.br_par.diff = bd, c.br_par.local_dist = local_dist, c.br_par.local_count = local_count, c.br_par.frag_mode = 0;
+	auto up = [&](int slot, const void *src, size_t bytes) -> void * { void *d = c.pool.get(slot, bytes + 16); if (d && hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, c.st) != hipSuccess) d = nullptr; return d; };
+	int32_t *d_vs = (int32_t *)up(S_BR_VS, vs, sizeof(int32_t) * (size_t)n_vtx), *d_ve = (int32_t *)up(S_BR_VE, ve, sizeof(int32_t) * (size_t)n_vtx);
+	int32_t *d_s1 = (int32_t *)up(S_BR_S1, s1, sizeof(int32_t) * (size_t)n_arc), *d_gid = (int32_t *)up(S_BR_GID, agid, sizeof(int32_t) * (size_t)n_arc);
+	void *d_rp = up(S_RP_SEG, rp, sizeof(int4) * (size_t)Q * (size_t)GL);
+	uint8_t *d_aw = (uint8_t *)up(S_ARCW, aw, (size_t)n_arc), *d_vwk = (uint8_t *)up(S_VWK, vwk, (size_t)n_vtx);
+	int32_t *d_ndl = (int32_t *)up(S_BR_NDL, ndl, sizeof(int32_t) * (size_t)n_vtx);
+	int32_t *pc = (int32_t *)c.pool.get(S_BR_PC, sizeof(int32_t) * (loop_btot_at(n_vtx) + 64) + 16), *poff = (int32_t *)c.pool.get(S_BR_POFF, sizeof(int32_t) * (size_t)n_vtx + 16);
+	int32_t *grp = (int32_t *)c.pool.get(S_BR_GRP, sizeof(int32_t) * (size_t)n_arc + 16);
+	int rc = (d_vs && d_ve && d_s1 && d_gid && d_rp && d_aw && d_vwk && d_ndl && pc && poff && grp && c.pool.get(S_RP_IV, 16)) ? 0 : PGA_ERR_NOMEM;
+	if (rc == 0 && (hipMemsetAsync(c.dcnt, 0, 24 * sizeof(int64_t), c.st) != hipSuccess || hipMemsetAsync(c.loopctl, 0xff, 4 * sizeof(int32_t), c.st) != hipSuccess)) rc = PGA_ERR_NO_DEVICE;
+	// the worst case of the main list, so that only the residual list can run out of room: n^2 pairs a vertex (branch.c:70-88)
+	int64_t worst = 16;
+	for (int v = 0; v < n_vtx; ++v) worst += (int64_t)(ve[v] - vs[v]) * (ve[v] - vs[v]);
+	c.br_cap = worst;
+	c.gate = gate_closed ? Gate{c.loopctl, 0} : Gate{nullptr, 0}; // (loopctl = {-1, -1, ..}: nothing has happened in round 0 or later)
+	c.br_lazy = lazy != 0;
+	c.br_rcap = res_cap > 0 ? res_cap : (int64_t)1 << 16;
+	if (rc == 0 && c.br_lazy && (!br_res_len(&c) || hipMemsetAsync(br_res_len(&c), 0, sizeof(int64_t) * BR_RSEG * BR_RSTRIDE, c.st) != hipSuccess)) rc = PGA_ERR_NOMEM; // (a closed gate starts nothing)
+	int attempt = 0;
+	for (; rc == 0; ++attempt) {
+		BrLazy lz;
+		if ((rc = br_lazy_args(&c, n_vtx, &lz)) != 0) break;
+		(void)hipMemsetAsync(c.dcnt + 11, 0, sizeof(int64_t), c.st);
+		(void)hipMemsetAsync(c.dcnt + 15, 0, 4 * sizeof(int64_t), c.st);
+		hipLaunchKernelGGL(k_br_count, dim3(nblk(n_vtx)), dim3(BLOCK), 0, c.st, n_vtx, (const int32_t *)d_vs, (const int32_t *)d_ve, (const int32_t *)d_s1, bd, pc, c.gate, br_res_len(&c));
+		hipLaunchKernelGGL(k_pair_offsets, dim3(1), dim3(PO_THREADS), 0, c.st, (const int32_t *)pc, n_vtx, poff, c.dcnt, c.h_box, (long long)c.br_cap, c.gate);
+		int32_t *cnt;
+		if ((rc = branch_enumerate(&c, &cnt)) != 0) break;
+		hipLaunchKernelGGL((k_br_wave<2>), dim3(nblk(n_vtx, BLOCK / WAVE)), dim3(BLOCK), 0, c.st, n_vtx, (const int32_t *)d_vs, (const int32_t *)d_ve, (const int32_t *)d_s1, (const int32_t *)d_gid, bd, (const int32_t *)poff, (int32_t *)nullptr, (int64_t)c.br_cap,
+		                   (const int32_t *)nullptr, (const int32_t *)cnt, bdist, bcut, d_aw, grp, d_ndl, (int64_t *)nullptr, d_vwk, (const int64_t *)(c.dcnt + 15), c.gate, lz);
+		if ((rc = branch_residual(&c, lz, n_vtx, d_ndl)) != 0) break;
+		if (hipMemcpyAsync(c.h_cnt, c.dcnt, 24 * sizeof(int64_t), hipMemcpyDeviceToHost, c.st) != hipSuccess || hipStreamSynchronize(c.st) != hipSuccess) { rc = PGA_ERR_NO_DEVICE; break; }
+		if (c.h_cnt[11] && c.br_lazy && c.h_cnt[18] * BR_RSEG > c.br_rcap && attempt == 0) { // the residual list did not fit: the repeat with room (the arcs' marks start again, as the caller's next run does)
+			c.br_rcap = c.h_cnt[18] * BR_RSEG + c.h_cnt[18] * BR_RSEG / 4;
+			(void)hipMemcpyAsync(d_aw, aw, (size_t)n_arc, hipMemcpyHostToDevice, c.st); (void)hipMemcpyAsync(d_vwk, vwk, (size_t)n_vtx, hipMemcpyHostToDevice, c.st);
+			(void)hipMemcpyAsync(d_ndl, ndl, sizeof(int32_t) * (size_t)n_vtx, hipMemcpyHostToDevice, c.st);
+			continue;
+		}
+		++attempt;
+		break;
+	}
+	if (rc == 0) {
+		lens[0] = c.h_cnt[15], lens[1] = 0, lens[2] = attempt, lens[3] = c.h_cnt[11];
+		int64_t seg_len[BR_RSEG] = { 0 };
+		if (c.br_lazy && hipMemcpy2D(seg_len, sizeof(int64_t), br_res_len(&c), sizeof(int64_t) * BR_RSTRIDE, sizeof(int64_t), BR_RSEG, hipMemcpyDeviceToHost) != hipSuccess) rc = PGA_ERR_NO_DEVICE;
+		for (int k = 0; k < BR_RSEG; ++k) lens[1] += seg_len[k];
+		if (hipMemcpy(aw, d_aw, (size_t)n_arc, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(vwk, d_vwk, (size_t)n_vtx, hipMemcpyDeviceToHost) != hipSuccess ||
+		    hipMemcpy(ndl, d_ndl, sizeof(int32_t) * (size_t)n_vtx, hipMemcpyDeviceToHost) != hipSuccess) rc = PGA_ERR_NO_DEVICE;
+	}
+	(void)hipStreamSynchronize(c.st);
+	(void)hipHostFree(c.h_cnt); c.h_cnt = nullptr, c.h_box = nullptr;
+	c.pool.release();
+	for (void *q : c.owned) (void)hipFree(q);
+	dev_big_free(c.arena, c.arena_cap), c.arena = nullptr;
+	(void)hipStreamDestroy(c.st); c.st = nullptr;
+	return rc;
+}
