@@ -177,6 +177,15 @@ extern "C" int pga_selftest_stage_a(pga_ctx_t *c, pga_selftest_stage_a_t *out) /
 	return 0;
 }
 
+// which builds of the sweep and of stage A's filters a context takes (tests/test_sweep_gpu.py, tests/support/sweep_direct.py): out[6] =
+// {lists_in_lds, density_known, any_multi, exon_regular, gf_ok, gf_k32}.  Reads only; not part of pangene_hip.h.
+extern "C" int pga_selftest_sweep_route(pga_ctx_t *c, int32_t *out)
+{
+	if (c == nullptr || out == nullptr) return PGA_ERR_ARG;
+	out[0] = c->lists_in_lds, out[1] = c->density_known, out[2] = c->any_multi, out[3] = c->exon_regular, out[4] = c->gf_ok, out[5] = c->gf_k32;
+	return 0;
+}
+
 // the roundings of a final arc record on the device (k_genes.hpp: arc_final_hi): out[4 n] = {avg_dist, s1, s2, 0} of every in[i]
 extern "C" int pga_selftest_arc_final(const pga_arc_part_t *in, int64_t n, int32_t *out)
 {

@@ -89,12 +89,14 @@ class Genome:
 
 
 class Shard:
-    """genomes -> pga_shard_t (self.c); max_cs / max_cm: what every block DECLARES (None: what its hits have)"""
+    """genomes -> pga_shard_t (self.c); max_cs / max_cm: what every block DECLARES (None: what its hits have); prot_gid / gene_pref: the tables
+    (None: drawn, N_PROT proteins of N_GENE genes); par: (min_ov_ratio, check_strand)"""
 
-    def __init__(self, name, genomes, rng, max_cs=None, max_cm=None):
+    def __init__(self, name, genomes, rng, max_cs=None, max_cm=None, prot_gid=None, gene_pref=None, par=(0.5, 0)):
         self.name, self.genomes = name, genomes
-        self.prot_gid = rng.integers(0, N_GENE, N_PROT).astype(np.int32)
-        self.gene_pref = (rng.random(N_GENE) < 0.3).astype(np.uint8)
+        self.prot_gid = rng.integers(0, N_GENE, N_PROT).astype(np.int32) if prot_gid is None else np.ascontiguousarray(prot_gid, np.int32)
+        self.gene_pref = (rng.random(N_GENE) < 0.3).astype(np.uint8) if gene_pref is None else np.ascontiguousarray(gene_pref, np.uint8)
+        self.P, self.Q = len(self.prot_gid), len(self.gene_pref)
         self.goff = np.concatenate([[0], np.cumsum([g.n for g in genomes])]).astype(np.int64)
         self.eoff = np.concatenate([[0], np.cumsum([g.n_exon for g in genomes])]).astype(np.int64)
         self.ctg_base = np.concatenate([[0], np.cumsum([g.n_ctg for g in genomes])]).astype(np.int64)
@@ -106,12 +108,12 @@ class Shard:
             d_cs = max_cs if max_cs is not None else (int(g.cs.max()) if g.n else 0)
             d_cm = max_cm if max_cm is not None else (int(g.cm.max()) if g.n else 0)
             assert g.n == 0 or (g.cs.max() <= d_cs and g.cm.max() <= d_cm)
-            self._blocks[k] = Block(g.n, g.n_exon, g.n_ctg, d_cs, d_cm, int(g.sadj.max()) if g.n else 0, 0, int((g.nex != 1).any()) if g.n else 0,
+            self._blocks[k] = Block(g.n, g.n_exon, g.n_ctg, d_cs, d_cm, int(g.sadj.max()) if g.n else 0, int((g.sadj < 0).any()) if g.n else 0, int((g.nex != 1).any()) if g.n else 0,
                                     w.ctypes.data, w.size, None, None)
         self._gg = np.arange(self.G, dtype=np.int32)
-        self.c = CShard(abi_version(), self.G, self.G, self._gg.ctypes.data, N_PROT, N_GENE, self.N, self.E, C.addressof(self._blocks),
+        self.c = CShard(abi_version(), self.G, self.G, self._gg.ctypes.data, self.P, self.Q, self.N, self.E, C.addressof(self._blocks),
                         self.prot_gid.ctypes.data, self.gene_pref.ctypes.data)
-        self.par = Par(0.5, 0, 0)
+        self.par = Par(par[0], par[1], 0)
         self.key_bits = (bits_for(max(b.max_cs for b in self._blocks)), bits_for(max(b.max_cm for b in self._blocks)), bits_for(max(1, max(g.n_ctg for g in genomes)) - 1))
 
 
