@@ -704,11 +704,13 @@ int pgo_arc_merge(pga_ctx_t *c, const pga_arc_part_t *gathered, const int64_t *c
  * ones among them receive consecutive values of the running counter r in whatever order they end up, so the r of a representative
  * is only known up to the interval [r - nb, r + na] (nb / na = walkable members of its tie group before / after it in the canonical
  * order); pgo_n_local raises the hazard when that matters.  Two walkable hits of ONE gene inside a tie group (possible with -S:
- * opposite strands) make the representative itself order-dependent (branch.c:22-23: the last one wins): hazard at once. */
+ * opposite strands) make the representative itself order-dependent (branch.c:22-23: the last one wins): hazard at once -- ONE event
+ * for the tie group of the representative (pangene_hip.h: "tie groups holding two walkable hits of one gene"), not one per hit of it. */
 int pgo_rep_pos(pga_ctx_t *c)
 {
 	int64_t Q = c->n_gene, i, n = Q * c->n_genome;
-	int32_t j;
+	int32_t j, g;
+	uint8_t *hzf = CALLOC(uint8_t, Q > 0 ? Q : 1); /* the representative of (gene, this genome) stands in a tie group with another walkable hit of its gene */
 	if (c->rp_x == 0) c->rp_x = MALLOC(int64_t, n), c->rp_y = MALLOC(int64_t, n), c->rp_iv = MALLOC(int32_t, n);
 	for (i = 0; i < n; ++i) c->rp_x[i] = -1, c->rp_y[i] = 0, c->rp_iv[i] = 0;
 	for (j = 0; j < c->n_genome; ++j) {
@@ -721,13 +723,17 @@ int pgo_rep_pos(pga_ctx_t *c)
 				if (!(c->flags[p] & (PGA_F_FLT | PGA_F_SHADOW))) ++nb, same_gene |= c->gid[p] == c->gid[i];
 			for (p = i + 1; p < c->off[j + 1] && c->cid[p] == c->cid[i] && c->cs[p] == c->cs[i]; ++p)
 				if (!(c->flags[p] & (PGA_F_FLT | PGA_F_SHADOW))) ++na, same_gene |= c->gid[p] == c->gid[i];
-			if (same_gene || nb > 0xffff || na > 0xffff) c->hz.h2_cs_tie++, hz_note(c, j, c->cid[i]), nb = na = 0;
+			hzf[c->gid[i]] = same_gene || nb > 0xffff || na > 0xffff; /* (a later walkable hit of the gene replaces the representative and this with it) */
+			if (hzf[c->gid[i]]) nb = na = 0;
 			c->rp_x[j * Q + c->gid[i]] = (int64_t)c->cid[i] << 32 | r;
 			c->rp_y[j * Q + c->gid[i]] = c->cm[i];
 			c->rp_iv[j * Q + c->gid[i]] = nb << 16 | na;
 			++r;
 		}
+		for (g = 0; g < Q; ++g)
+			if (hzf[g]) { c->hz.h2_cs_tie++; hz_note(c, j, (int32_t)(c->rp_x[j * Q + g] >> 32)); hzf[g] = 0; }
 	}
+	free(hzf);
 	return PGA_OK;
 }
 

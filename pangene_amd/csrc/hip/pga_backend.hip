@@ -51,6 +51,10 @@ static long long xloop_cap(int which)
 // debugging aid: PANGENE_POISON=1 fills every fresh device / pinned allocation with a pattern, so that a read of memory nobody
 // wrote shows up the same way in every run (recycled memory otherwise holds whatever the previous context left there)
 static bool poison_on() { static const bool f = getenv("PANGENE_POISON") != nullptr; return f; }
+// The fill of a fresh device allocation.  hipMemset runs on the null stream and may return before it is done; the contexts' streams do not
+// wait for the null stream (hipStreamNonBlocking), so without the wait the pattern could land on top of what a context's first kernels
+// have already written there -- counters cleared a moment ago, on the smallest shards -- and send a later kernel out of bounds.
+static void poison_fill(void *p, size_t bytes) { if (hipMemset(p, 0x5a, bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) fprintf(stderr, "[W::pga] PANGENE_POISON: the fill of %zu bytes failed\n", bytes); }
 
 #define F_HEAD 0x80000000u   // static: first hit of its genome in X order (index-0 quirk, overlap.c:108)
 #define F_MULTI 0x40000000u  // static: the hit has more than one exon (lets the sweep skip the exon records)

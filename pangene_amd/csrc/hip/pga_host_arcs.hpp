@@ -160,6 +160,7 @@ static int ensure_half_arcs(pga_ctx *c, int use_ori)
 	else if (c->NL) hipLaunchKernelGGL(k_walk<1>, dim3(nb), dim3(BLOCK), 0, c->st, wk, rd);
 	if (c->timing_rounds) time_mark(c, &tw, 6, true);
 	c->ha_valid = true, c->ha_ori = use_ori;
+	if (four || c->NL) c->walk_ipt = four ? 4 : 1;
 	return 0;
 }
 

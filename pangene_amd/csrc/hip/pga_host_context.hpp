@@ -95,7 +95,7 @@ struct DevPool { // persistent, grow-only device temporaries keyed by slot
 			if (p[slot] && own[slot]) (void)hipFree(p[slot]);
 			size_t want = (bytes + bytes / 4 + 256 + 255) & ~(size_t)255;
 			if (arena && arena_off + want <= arena_cap) { p[slot] = arena + arena_off, arena_off += want, own[slot] = 0; }
-			else if (hipMalloc(&p[slot], want) == hipSuccess) { own[slot] = 1; if (poison_on()) (void)hipMemset(p[slot], 0x5a, want); }
+			else if (hipMalloc(&p[slot], want) == hipSuccess) { own[slot] = 1; if (poison_on()) poison_fill(p[slot], want); }
 			else { p[slot] = nullptr; cap[slot] = 0; own[slot] = 0; return nullptr; }
 			cap[slot] = want;
 		}
@@ -233,6 +233,7 @@ struct pga_ctx {
 	int4 *wrec = 0; bool wrec_valid = false; // the walk's 32-byte records in cm order (k_pack_wrec): they carry the gene-major position, so a new index or a new cm order makes them stale
 	uint32_t *hfk = 0, *hbk = 0; int4 *hfp = 0, *hbp = 0; // half-arc key words and payloads
 	bool z_valid = false, ha_valid = false; uint32_t round_tag = 0; int ha_ori = -1;
+	int walk_ipt = 0; // positions a thread of the k_walk that ran last (1 or 4; 0: none yet) -- for pga_selftest_arc_route
 	Gate gate = Gate{nullptr, 0};     // what the launches of the moment carry (pga_branch_loop sets it per phase; open everywhere else)
 	int32_t *loopctl = nullptr;       // [4] device: Gate::w[0..1], [2] = tag of the last arc round of the loop that ran
 	int loop_round = 0;               // the round the launches of the moment belong to (stamps)
@@ -278,7 +279,7 @@ static int dalloc_commit(pga_ctx *c)
 {
 	size_t tot = 0;
 	if (getenv("PANGENE_NO_ARENA")) { // debugging aid: one allocation per array (out-of-bounds accesses then land in padding)
-		for (auto &e : c->plan) { void *q = nullptr; if (hipMalloc(&q, e.second) != hipSuccess) return PGA_ERR_NOMEM; *e.first = q; c->owned.push_back(q); if (poison_on()) (void)hipMemset(q, 0x5a, e.second); }
+		for (auto &e : c->plan) { void *q = nullptr; if (hipMalloc(&q, e.second) != hipSuccess) return PGA_ERR_NOMEM; *e.first = q; c->owned.push_back(q); if (poison_on()) poison_fill(q, e.second); }
 		c->plan.clear();
 		return 0;
 	}
@@ -287,7 +288,7 @@ static int dalloc_commit(pga_ctx *c)
 	void *base = dev_big_alloc(tot ? tot : 256, &got);
 	if (base == nullptr) return PGA_ERR_NOMEM;
 	c->arena = base, c->arena_cap = got;
-	if (poison_on()) (void)hipMemset(base, 0x5a, tot ? tot : 256);
+	if (poison_on()) poison_fill(base, tot ? tot : 256);
 	size_t off = 0;
 	for (auto &e : c->plan) *e.first = (char *)base + off, off += e.second;
 	c->plan.clear();

@@ -186,6 +186,22 @@ extern "C" int pga_selftest_sweep_route(pga_ctx_t *c, int32_t *out)
 	return 0;
 }
 
+// which route the arc and branch rounds of a context took (tests/test_arcs_gpu.py, tests/support/arcs_direct.py): out[8] = {n_big = ga_ctl[0] as the
+// last arc round left it (the genes k_gene_arcs_wave_t handed on), the genes that overflowed their table in the last round as mailed, table_sparse,
+// live_on, NL, rp_form, positions a thread of the walk that ran (1 or 4; 0: none), lds_vtx_set != 0}.  Waits for the stream; reads only; not part of
+// pangene_hip.h.
+extern "C" int pga_selftest_arc_route(pga_ctx_t *c, int32_t *out)
+{
+	if (c == nullptr || out == nullptr) return PGA_ERR_ARG;
+	TRY(sync_st(c));
+	int32_t n_big = 0;
+	if (c->ga_ctl) HIPCHK(hipMemcpy(&n_big, c->ga_ctl, sizeof(int32_t), hipMemcpyDeviceToHost));
+	// (a round of pga_arc_round_local leaves its own count behind the counters and degrees it mails, where later mail does not reach it: out[1] is valid
+	// directly behind such a round only -- after pga_arc_round, a forced sort path or an exchange round the slot is stale or holds something else)
+	out[0] = n_big, out[1] = c->h_round ? c->h_round[4 * (size_t)c->n_seg] : (int32_t)c->h_cnt[9], out[2] = c->table_sparse, out[3] = c->live_on, out[4] = c->NL, out[5] = c->rp_form, out[6] = c->walk_ipt, out[7] = c->lds_vtx_set != 0;
+	return 0;
+}
+
 // the roundings of a final arc record on the device (k_genes.hpp: arc_final_hi): out[4 n] = {avg_dist, s1, s2, 0} of every in[i]
 extern "C" int pga_selftest_arc_final(const pga_arc_part_t *in, int64_t n, int32_t *out)
 {

@@ -173,7 +173,7 @@ static int create_impl(pga_ctx *c, const pga_shard_t *sh)
 		void *a = getenv("PANGENE_NO_ARENA") == nullptr ? dev_big_alloc(want, &got) : nullptr;
 		if (a) { // else: slot by slot
 			c->pool.arena = (char *)a, c->pool.arena_cap = got, c->pool.arena_off = 0;
-			if (poison_on()) (void)hipMemset(a, 0x5a, got);
+			if (poison_on()) poison_fill(a, got);
 		}
 	}
 	const double t1 = now();

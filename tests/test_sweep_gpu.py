@@ -8,8 +8,9 @@ hit, filtered ones included: the public flag bits, rank, score_dom, pid_dom, pid
 of pga_ingest and pga_shadow, n_pseudo, max_ori, sums, and the hazard counters and hazard segments.  The hook pga_selftest_sweep_route
 (pga_host_selftest.hpp) says which builds ran, and the child asserts that they are the ones its environment asks for.
 
-Not covered here: the sweeps of the arc rounds with weak_br set (the weak bits come from pga_mark_hits) and over the live lists (pga_branch_loop) --
-MODE 0 runs with weak_br = 0 and over the full records only -- and everything from pga_vtx_partials on."""
+Not covered here: the sweeps of the arc rounds with weak_br set and over the live lists -- MODE 0 runs with weak_br = 0 and over the full records only --
+and everything from pga_vtx_partials on: tests/test_arcs_gpu.py, whose second arc round sweeps with weak_br set, under PANGENE_LIVE_LISTS=1 over the
+members' lists.  What is left: the sweeps queued by pga_branch_loop."""
 import os
 import subprocess
 import sys
