@@ -782,6 +782,68 @@ __global__ __launch_bounds__(BLOCK) void k_round_del(int S, const int32_t *ndl, 
 	if (gmeta) gmeta[s] = make_int4(0, 0, 0, 0); // (sharded rounds compact the genes' stretches: this one has none from now on)
 }
 
+// The two in ONE launch (pga_branch_loop, PANGENE_LOOP_LEAN bit 4: rounds r > 0 of the lazy form).  A workgroup is four waves = the vertices 4b .. 4b + 3 = the
+// segments 2b and 2b + 1, and everything k_round_del reads or writes belongs to its own segment: after the waves' part (k_br_finish's, under the gate
+// of the branch steps and the overflow test; its early returns are branches here, every thread reaches the barrier) two threads apply k_round_del's
+// body to the two segments.  The four n_dist_loci travel through LDS; a wave that did not compute its vertex's loads what the decision (or an earlier
+// round) left.  The delete part is not gated and runs whether or not the pair list overflowed, as the launch of its own does.
+// The gate word and the stamp are one word: a deletion stamps stamp[0] = round, which is what the gate of the finish part (min = round - 1) reads, so in a
+// round whose branch steps found their gate closed a workgroup that starts after another one's deletion finds it open.  That is harmless: its waves then
+// replay the rows from the roff / rmask / rcnt / rlen of the last round whose steps did run, and nothing those rows read has changed since (that is what a
+// closed gate says; this round's deletions touch only their own segments' entries, read in front of the barrier by their own workgroup alone) -- the same
+// n_dist_loci, the same dcnt[18] and dcnt[11] as are there already.  Each wave reads the gate ONCE (lane 0, broadcast): its branches are uniform whatever
+// other workgroups write meanwhile.
+struct RoundDel { int S, max_tot_cnt, max_degree, max_dist_loci; const int32_t *seg_gid; int32_t *g2s, *vs, *ve, *deg, *seg_cnt; uint8_t *vwk, *alive; int4 *gmeta; int32_t *stamp; int round; };
+__global__ __launch_bounds__(BLOCK) void k_br_finish_del(int n_vtx, const int32_t *rcnt, BrLazy lz, int32_t *ndl, int64_t *dcnt, const int64_t *np_dev, int64_t pair_cap, Gate gate, RoundDel d)
+{
+	__shared__ int32_t s_ndl[BLOCK / WAVE];
+	const int w = threadIdx.x >> 6, v = blockIdx.x * (BLOCK / WAVE) + w, lane = threadIdx.x & 63;
+	int fin_l0 = 0;
+	if (lane == 0) fin_l0 = (!gate_closed(gate) && !(np_dev && *np_dev > pair_cap)) ? 1 : 0;
+	const bool fin = __builtin_amdgcn_readfirstlane(fin_l0) != 0; // (lane 0 is the first active lane: every thread of the workgroup is here)
+	if (v < n_vtx) { // (wave-uniform, as every branch below)
+		int g = -1; // n_dist_loci when this wave settles it
+		if (fin) {
+			if (v == 0) { // the books of the residual list (k_br_finish)
+				const int64_t l64 = lane < BR_RSEG ? lz.rlen[lane * BR_RSTRIDE] : 0;
+				const int64_t len = wave_max((int)(l64 < 0x7fffffff ? l64 : 0x7fffffff));
+				if (lane == 0) { if (len > dcnt[18]) dcnt[18] = len; if (len > ((int64_t)1 << lz.seg_shift)) dcnt[11] = 1; }
+			}
+			const int n = d.ve[v] - d.vs[v];
+			const int off = (n >= 2 && n <= WAVE) ? lz.roff[v] : -1;
+			if (off >= 0) {
+				const unsigned long long m_un = lz.rmask[v];
+				const bool in = lane < n, un = (m_un >> lane) & 1;
+				const int mine = un ? lane - 1 : 0;
+				const int my_off = wave_scan_incl(I32{mine}, OpSum{}, lane).v - mine;
+				int grp = in && !un ? 1 : 0, n_group = 1;
+				for (int i = 1; i < n; ++i) {
+					if (__ballot(in && grp == 0) == 0) break;
+					int gi = __builtin_amdgcn_readlane(grp, i);
+					if (gi == 0) { gi = ++n_group; if (lane == i) grp = gi; }
+					if (lane > i && un && grp == 0 && rcnt[(int64_t)off + my_off + (i - 1)] > 0) grp = gi;
+				}
+				g = n_group;
+				if (lane == 0) ndl[v] = g;
+			}
+		}
+		if (lane == 0) s_ndl[w] = g >= 0 ? g : ndl[v];
+	}
+	__syncthreads();
+	const int s = blockIdx.x * (BLOCK / WAVE / 2) + (int)threadIdx.x;
+	if (threadIdx.x >= BLOCK / WAVE / 2 || s >= d.S || !d.alive[s]) return;
+	const int l0 = s_ndl[2 * threadIdx.x], l1 = s_ndl[2 * threadIdx.x + 1], S = d.S;
+	if (!(d.seg_cnt[S + s] > d.max_tot_cnt || d.deg[2 * s] > d.max_degree || d.deg[2 * s + 1] > d.max_degree || (l0 > l1 ? l0 : l1) > d.max_dist_loci)) return; // k_round_filter's tests
+	d.alive[s] = 0;
+	if (d.stamp) d.stamp[0] = d.round;
+	d.g2s[d.seg_gid[s]] = -1;
+	d.vs[2 * s] = d.ve[2 * s] = d.vs[2 * s + 1] = d.ve[2 * s + 1] = 0;
+	d.deg[2 * s] = d.deg[2 * s + 1] = 0;
+	d.seg_cnt[s] = d.seg_cnt[S + s] = 0;
+	d.vwk[2 * s] = d.vwk[2 * s + 1] = 0;
+	if (d.gmeta) d.gmeta[s] = make_int4(0, 0, 0, 0);
+}
+
 __device__ __forceinline__ int arc_weak(const uint64_t *ax, const uint8_t *aw, int64_t n, uint64_t x) // pg_get_arc, pgpriv.h:99-107
 {
 	int64_t lo = 0, hi = n;

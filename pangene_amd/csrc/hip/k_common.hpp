@@ -132,6 +132,18 @@ __global__ __launch_bounds__(BLOCK) void k_zero_multi(ZeroList z)
 	}
 }
 
+// the same with a byte value per buffer (pga_branch_loop's head: `alive` = 1, counters = 0, the gates' words = 0xff)
+struct FillList { void *p[4]; unsigned long long dwords[4]; uint32_t word[4]; };
+__global__ __launch_bounds__(BLOCK) void k_fill_multi(FillList z)
+{
+	unsigned long long i = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x;
+#pragma unroll
+	for (int k = 0; k < 4; ++k) {
+		if (i < z.dwords[k]) { ((uint32_t *)z.p[k])[i] = z.word[k]; return; }
+		i -= z.dwords[k];
+	}
+}
+
 __device__ __forceinline__ int genome_of(const int32_t *goff, int n_genome, int i) // last g with goff[g] <= i
 {
 	int lo = 0, hi = n_genome;

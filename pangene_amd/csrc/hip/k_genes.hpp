@@ -292,9 +292,12 @@ struct GeneArcs {
 	uint64_t *ax; int32_t *s1, *agid; uint8_t *aw; int32_t *vs, *ve, *deg; uint8_t *vwk;
 	int32_t *h_round;                   // pinned host memory (or NULL): seg_cnt[2S] then deg[2S] for the host, written straight from here
 	int32_t *big_list;                  // [Q] the genes left to the workgroup kernel, in the order the first kernel's workgroups gave up on them
-	int32_t *big_ctl;                   // [2] their number; how many of them have been taken (both cleared by the k_sweep_slow in front of every arc round)
+	int32_t *big_ctl;                   // [2] their number; how many of them have been taken (both cleared by the k_sweep_slow in front of every arc round, or by the sweep itself where none follows it)
 	int64_t *dcnt;                      // [3] invariant, [9] genes that overflowed GA_CAP
 	Gate gate; int32_t *tag_out;        // (pga_branch_loop) the round may have nothing to do; tag_out: where a round that does run leaves its tag
+	// (pga_branch_loop, PANGENE_LOOP_LEAN bit 2) no k_gene_arcs_big follows: a gene the wave kernel gives up on is not listed -- it raises the sticky
+	// flag (dcnt[11]) and counts into dcnt[17], the queue is repeated with the second kernel --, and the wave kernel leaves the tag itself
+	int big_off;
 };
 
 
@@ -473,6 +476,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(7))) void k_
 {
 	__shared__ GeneTable<CAP, HITS> T;
 	if (gate_closed(a.gate)) return;
+	if (a.big_off && a.tag_out && blockIdx.x == 0 && threadIdx.x == 0) *a.tag_out = (int32_t)a.tag; // (what k_gene_arcs_big's first thread does otherwise)
 	if ((int)blockIdx.x >= a.Q) { // (only with ride_form >= 0)
 		const int t = ((int)blockIdx.x - a.Q) * NT + (int)threadIdx.x;
 		switch (ride_form) {
@@ -494,7 +498,14 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(7))) void k_
 	}
 	const int cl = a.cap_log2 < CAP_LOG2 ? a.cap_log2 : CAP_LOG2;
 	const bool done = z1 - z0 <= HITS && gene_arcs_one<NT, CAP, HITS>(a, T, g, sid, tid, cl);
-	if (tid == 0 && !done) a.big_list[atomicAdd(&a.big_ctl[0], 1)] = g; // many hits, or many neighbours: the second kernel takes it
+	if (tid == 0 && !done) {
+		if (!a.big_off) a.big_list[atomicAdd(&a.big_ctl[0], 1)] = g; // many hits, or many neighbours: the second kernel takes it
+		else { // nobody behind this kernel: the run is void and repeated with the second kernel (what the rest of the queue finds here meanwhile: a vertex without arcs)
+			a.dcnt[11] = 1, atomicAdd((unsigned long long *)&a.dcnt[17], 1ull);
+			a.gmeta[sid] = make_int4(0, 0, 0, 0);
+			a.vs[2 * sid] = a.ve[2 * sid] = a.vs[2 * sid + 1] = a.ve[2 * sid + 1] = 0, a.deg[2 * sid] = a.deg[2 * sid + 1] = 0;
+		}
+	}
 }
 
 // (512 threads a gene: the LDS tables allow three of these workgroups on a CU whatever their width -- 12 waves of 256 threads, 24 of 512; 328 -> 258 us

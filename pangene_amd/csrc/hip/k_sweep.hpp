@@ -68,7 +68,13 @@ struct SweepView {
 	// in X order, pm recomputed over them -- and reach the per-hit state (flag word, pid_dom) at the hit's X position through xmap; NULL: A / B / C
 	// are the X-order records themselves.  A filtered hit takes no part in any pair (overlap.c:112,127), so the pairs are the same.
 	const int32_t *xmap;
+	// The lean forms of the MODE-0 sweep (sweep_tile's LEAN; pga_branch_loop, PANGENE_LOOP_LEAN bits 1 and 8; never with xmap):
+	int64_t *lean_cnt;   // [0] the longest slow list of a MODE-0 sweep in this run (sticky; the host decides the form of later sweeps by it), [1] open hits evaluated by the sweeps themselves
+	long long *next_cnt; int32_t *clear2; // LEAN & 1: what k_sweep_slow's first thread clears -- the NEXT sweep's counter, the gene kernels' hand-out counters -- falls to this kernel's
+	const int32_t *g2s;  // LEAN & 2: gene -> segment, for k_flag_vtx's transform of every flag word the tile stages
 };
+// graph.c:61-69 + PG_SET_FILTER(vtx == 0) on one flag word (k_flag_vtx with then_filter, k_flag_vtx_z): idempotent
+__device__ __forceinline__ uint32_t sw_flag_vtx(uint32_t f, int sid) { return sid >= 0 ? (f | PGA_F_VTX) : ((f & ~PGA_F_VTX) | PGA_F_FLT); }
 #define SW_X(v, h) ((v).xmap ? (v).xmap[h] : (h)) /* where the state of the hit at (compact) position h lives */
 
 // pg_hit_overlap (overlap.c:6-42) step by step as the reference takes them: for shards with an exon list that is not sorted and disjoint
@@ -290,9 +296,53 @@ __device__ __forceinline__ void sw_finish(const SweepView &v, int h, uint32_t fl
 	}
 }
 
-template <int MODE, bool STAGE_C, bool LISTS_IN_LDS>
+// One hit against all its partners in global memory, in both directions (the plain thread-per-hit formulation of the sweep): k_sweep_slow's work for a
+// listed hit, and what a lane of the LEAN & 1 sweep does itself for a hit whose partners reach beyond its window.  G2S (LEAN & 2): the partners' flag
+// words pass through sw_flag_vtx first -- their owners may not have stored the transformed word yet.
+template <int MODE, bool G2S>
+__device__ __forceinline__ void sweep_slow_one(const SweepView &v, const int h, const uint32_t fl)
+{
+	SwHit t;
+	const int4 ch = v.C[h];
+	{
+		const int4 a = sw_scse(v.A[h]), b = v.B[h];
+		t.sg = a.x, t.cs = a.y, t.ce = a.z, t.gid = b.y, t.cds = b.z, t.rank = ch.x, t.nex = ch.y, t.offx = ch.z;
+		t.weak = (int)((fl & PGA_F_WEAK_MASK) >> PGA_F_WEAK_SHIFT), t.fl = fl;
+		t.sc = (uint32_t)b.x;
+	}
+	SwBest r = { false, false, 0, -1, 0, -1, 0, -1 };
+	// partners before h: every j with ce_j > cs_h.  pm (running max of ce) is non-decreasing inside a contig, so the
+	// walk stops at the first j whose pm is <= cs_h.
+	for (int j = h - 1; j >= 0; --j) {
+		const int4 a = sw_scse(v.A[j]);
+		if (a.x != t.sg || a.w <= t.cs) break;
+		const int4 b = v.B[j];
+		uint32_t fp = v.flags[MODE == 0 ? SW_X(v, j) : j];
+		if (G2S) fp = sw_flag_vtx(fp, v.g2s[b.y]);
+		sw_pair<MODE, true>(v, t, r, a, fp, b, v.C[j], j, a.z > t.cs);
+	}
+	// partners after h: every i with cs_i < ce_h
+	for (int i = h + 1; i < v.n; ++i) {
+		const int4 a = sw_scse(v.A[i]);
+		if (a.x != t.sg || a.y >= t.ce) break;
+		const int4 b = v.B[i];
+		uint32_t fp = v.flags[MODE == 0 ? SW_X(v, i) : i];
+		if (G2S) fp = sw_flag_vtx(fp, v.g2s[b.y]);
+		sw_pair<MODE, false>(v, t, r, a, fp, b, v.C[i], i, true);
+	}
+	sw_finish<MODE>(v, h, fl, r.lose, r.best > 0, r.pid, r.ov, t.cds, r.cds, ch.w, (MODE == 1 || MODE == 3) && r.best > 0 ? v.C[r.j].w : 0, r.iso);
+}
+
+// LEAN (MODE 0 without xmap only; 0: the kernel as it was, and every other mode's): bit 0 -- a lane that finds its hit open evaluates it itself
+// (sweep_slow_one) instead of listing it, and no k_sweep_slow follows; that is as race-free as the halo reads: a MODE-0 sweep changes only the shadow bit
+// of a flag word (sw_finish), partners' words are read while their owners may be rewriting that bit anyway, and sw_pair looks at a partner's flt, rev and
+// weak bits, never at its shadow bit.  Bit 1 -- k_flag_vtx's transform (sw_flag_vtx) on every flag word the tile stages, stored for the tile's own hits:
+// the transform is idempotent, so a neighbour that reads a word before or after its owner's store stages the same value.
+template <int MODE, bool STAGE_C, bool LISTS_IN_LDS, int LEAN = 0>
 __device__ __forceinline__ void sweep_tile(const SweepView &v)
 {
+	static_assert(LEAN == 0 || MODE == 0, "the lean forms are the arc rounds' sweeps'");
+	if ((LEAN & 1) && blockIdx.x == 0 && threadIdx.x == 0) { *v.next_cnt = 0; if (v.clear2) v.clear2[0] = 0, v.clear2[1] = 0; } // (k_sweep_slow's resets, before the gate test: the two-counter protocol holds for any sequence of the two forms)
 	if (gate_closed(v.gate)) return; // (k_sweep_slow then finds an empty list and only resets the next sweep's counter)
 	static_assert(2 * SW_HALO == 64 && SW_NW == 4 && SW_LDS <= 1024 && 64 + 2 * SW_HALO <= 128 && SW_WCAP >= 64 + 3 * SW_HALO, "the slots past SW_TILE are staged one array per wave; window-relative slot ids are packed in 7 bits, winner slots in 10; a level of the pair list has at most 64 + SW_HALO entries");
 	constexpr bool STAGE_ORI = (MODE == 1 || MODE == 3) && !STAGE_C; // score_dom needs score_ori: out of the C records when they are staged, else staged alone
@@ -328,12 +378,26 @@ __device__ __forceinline__ void sweep_tile(const SweepView &v)
 			a = v.A[g], b = v.B[g], f = v.flags[MODE == 0 ? SW_X(v, g) : g];
 			if (STAGE_C) c = v.C[g];
 			if (STAGE_ORI) so = v.sori[g];
+			if (LEAN & 2) { // (own hits: the slots SW_HALO .. SW_HALO + SW_TILE - 1; this thread stages those below SW_TILE)
+				const uint32_t nf = sw_flag_vtx(f, v.g2s[b.y]);
+				if (nf != f && tid >= SW_HALO) v.flags[g] = nf;
+				f = nf;
+			}
 		}
 		// the 2 * SW_HALO slots past SW_TILE: one array per wave, so that no wave has more to stage than the others
 		const int l2 = SW_TILE + lane, g2 = base + l2;
 		const bool in2 = lane < 2 * SW_HALO && g2 >= 0 && g2 < v.n;
 		if (wave == 0) sA[l2] = in2 ? v.A[g2] : make_int4(0, -2, 0, 0);
 		else if (wave == 1) sB[l2] = in2 ? v.B[g2] : make_int4(0, 0, 0, 0);
+		else if (wave == 2 && (LEAN & 2)) {
+			uint32_t f2 = PGA_F_FLT;
+			if (in2) {
+				const uint32_t f0 = v.flags[g2];
+				f2 = sw_flag_vtx(f0, v.g2s[((const int32_t *)&v.B[g2])[1]]);
+				if (f2 != f0 && lane < SW_HALO) v.flags[g2] = f2; // (the last SW_HALO own hits are staged here)
+			}
+			sF[l2] = f2;
+		}
 		else if (wave == 2) sF[l2] = in2 ? v.flags[MODE == 0 ? SW_X(v, g2) : g2] : PGA_F_FLT;
 		else if (STAGE_C) sC[l2] = in2 ? v.C[g2] : make_int4(0, 0, 0, 0);
 		else if (STAGE_ORI) sOri[l2] = in2 ? v.sori[g2] : 0;
@@ -553,7 +617,11 @@ __device__ __forceinline__ void sweep_tile(const SweepView &v)
 			// partners outside the window?  (pm = running max of ce is non-decreasing inside a contig)
 			const int4 w0 = sA[lo - SW_HALO], w1 = sA[wend - 1];
 			const bool open = (w0.y == a.y && w0.w > a.x) || (w1.y == a.y && w1.x < a.z);
-			if (open) {
+			if (open && (LEAN & 1)) { // rare (the host picks this form where no sweep of the upload listed a hit): evaluated here and now
+				const unsigned long long at = atomicAdd((unsigned long long *)v.slow_cnt, 1ull); // (nobody reads a list: the counter only says how many there were)
+				atomicMax((unsigned long long *)&v.lean_cnt[0], at + 1ull), atomicAdd((unsigned long long *)&v.lean_cnt[1], 1ull);
+				sweep_slow_one<MODE, (LEAN & 2) != 0>(v, h, fl);
+			} else if (open) {
 				const unsigned long long at = atomicAdd((unsigned long long *)v.slow_cnt, 1ull);
 				v.slow_list[at] = h;
 			} else {
@@ -594,6 +662,9 @@ __device__ __forceinline__ void sweep_tile(const SweepView &v)
 
 template <int MODE, bool STAGE_C>
 __global__ __launch_bounds__(SW_TILE) void k_sweep(SweepView v) { sweep_tile<MODE, STAGE_C, true>(v); }
+// the lean forms of the arc rounds' sweep (sweep_tile: LEAN = 1 open hits evaluated in place, 2 k_flag_vtx's transform while staging, 3 both)
+template <bool STAGE_C, int LEAN>
+__global__ __launch_bounds__(SW_TILE) void k_sweep_rounds(SweepView v) { sweep_tile<0, STAGE_C, true, LEAN>(v); }
 // the sweeps of stage A and pg_post_process on a shard of multi-exon hits that rarely overlap: the exon lists stay in global memory
 template <int MODE>
 __global__ __launch_bounds__(SW_TILE) void k_sweep_lean(SweepView v) { sweep_tile<MODE, true, false>(v); }
@@ -619,32 +690,12 @@ template <int MODE>
 __global__ __launch_bounds__(BLOCK) void k_sweep_slow(SweepView v, long long *next_cnt, int32_t *clear2 = nullptr /* two more words to clear: the hand-out counters of the gene kernels behind the arc rounds' sweep */)
 {
 	const long long n_slow = *v.slow_cnt;
-	if (blockIdx.x == 0 && threadIdx.x == 0) { *next_cnt = 0; if (clear2) clear2[0] = 0, clear2[1] = 0; } // the counter the NEXT sweep will use (ping-pong; nobody reads it now)
+	if (blockIdx.x == 0 && threadIdx.x == 0) {
+		*next_cnt = 0; if (clear2) clear2[0] = 0, clear2[1] = 0; // the counter the NEXT sweep will use (ping-pong; nobody reads it now)
+		if (MODE == 0 && n_slow > v.lean_cnt[0]) v.lean_cnt[0] = n_slow; // (the longest list of the run: the host picks the form of later sweeps by it, sweep_tile's LEAN)
+	}
 	for (long long q = blockIdx.x * (long long)BLOCK + threadIdx.x; q < n_slow; q += (long long)gridDim.x * BLOCK) {
 		const int h = v.slow_list[q];
-		const uint32_t fl = v.flags[MODE == 0 ? SW_X(v, h) : h];
-		SwHit t;
-		const int4 ch = v.C[h];
-		{
-			const int4 a = sw_scse(v.A[h]), b = v.B[h];
-			t.sg = a.x, t.cs = a.y, t.ce = a.z, t.gid = b.y, t.cds = b.z, t.rank = ch.x, t.nex = ch.y, t.offx = ch.z;
-			t.weak = (int)((fl & PGA_F_WEAK_MASK) >> PGA_F_WEAK_SHIFT), t.fl = fl;
-			t.sc = (uint32_t)b.x;
-		}
-		SwBest r = { false, false, 0, -1, 0, -1, 0, -1 };
-		// partners before h: every j with ce_j > cs_h.  pm (running max of ce) is non-decreasing inside a contig, so the
-		// walk stops at the first j whose pm is <= cs_h.
-		for (int j = h - 1; j >= 0; --j) {
-			const int4 a = sw_scse(v.A[j]);
-			if (a.x != t.sg || a.w <= t.cs) break;
-			sw_pair<MODE, true>(v, t, r, a, v.flags[MODE == 0 ? SW_X(v, j) : j], v.B[j], v.C[j], j, a.z > t.cs);
-		}
-		// partners after h: every i with cs_i < ce_h
-		for (int i = h + 1; i < v.n; ++i) {
-			const int4 a = sw_scse(v.A[i]);
-			if (a.x != t.sg || a.y >= t.ce) break;
-			sw_pair<MODE, false>(v, t, r, a, v.flags[MODE == 0 ? SW_X(v, i) : i], v.B[i], v.C[i], i, true);
-		}
-		sw_finish<MODE>(v, h, fl, r.lose, r.best > 0, r.pid, r.ov, t.cds, r.cds, ch.w, (MODE == 1 || MODE == 3) && r.best > 0 ? v.C[r.j].w : 0, r.iso);
+		sweep_slow_one<MODE, false>(v, h, v.flags[MODE == 0 ? SW_X(v, h) : h]);
 	}
 }

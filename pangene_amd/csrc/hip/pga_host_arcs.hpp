@@ -203,8 +203,13 @@ static int arc_round_genes(pga_ctx *c, int use_ori, int32_t **seg_cnt_out, int32
 	int32_t *big = (int32_t *)c->pool.get(S_BIGLIST, sizeof(int32_t) * (size_t)std::max(1, c->Q));
 	if (!big) return PGA_ERR_NOMEM;
 	static const int cap_log2 = [] { const char *e = getenv("PANGENE_GENE_TABLE_LOG2"); const int v = e ? atoi(e) : 9; return v < 1 ? 1 : v > 9 ? 9 : v; }();
+	// (pga_branch_loop, PANGENE_LOOP_LEAN bit 2) Optimistic: where a gene has on average at most half the hits the wave kernel gives up at, and no gene of
+	// this upload has needed the second kernel, it is not launched; a gene that needs it after all voids the run on the device (dcnt[17]) and the queue is
+	// repeated with it (status 4).  configs[1]: 191 hits a gene, the largest 381; the 12.1 M-hit shard: 2 400 a gene -- it keeps the launch.
+	const bool big_off = (c->lean & 2) && !c->ga_big_keep && (int64_t)N <= (int64_t)c->Q * GA_WAVE_HITS / 2;
+	if (c->lean & 2) c->lean_big_skipped = big_off ? 1 : 0;
 	GeneArcs ga = { c->zy, c->zoff, c->hfk, c->hbk, c->hfp, c->hbp, c->g2s, c->Q, S, c->round_tag, cap_log2, seg_cnt, t.sg, stage, gmeta,
-	                t.ax, t.s1, t.agid, t.aw, t.vs, t.ve, t.dg, t.vwk, h_round_dev, big, c->ga_ctl, c->dcnt, c->gate, (c->gate.w || c->loop_gated) ? c->loopctl + 2 : (int32_t *)nullptr };
+	                t.ax, t.s1, t.agid, t.aw, t.vs, t.ve, t.dg, t.vwk, h_round_dev, big, c->ga_ctl, c->dcnt, c->gate, (c->gate.w || c->loop_gated) ? c->loopctl + 2 : (int32_t *)nullptr, big_off ? 1 : 0 };
 	// (round 6, measured side by side at configs[1] / human 47 x 20 k, ms per pass: <128 threads, 128 keys, 512 hits> 5.26 / 5.11 -- kept; <64, 64, 256> 5.83 / 4.98;
 	// <128, 64, 256> 5.65 / 5.08; <64, 128, 512> 5.49 / 5.13; <64, 32, 256> 5.90 / 5.05: smaller tables put more genes on a CU and send more of them to the second kernel)
 	RepFill rf = {}; int ride_form = -1; unsigned nb_genes = (unsigned)c->Q;
@@ -216,7 +221,7 @@ static int arc_round_genes(pga_ctx *c, int use_ori, int32_t **seg_cnt_out, int32
 		c->ride_done = 2;
 	}
 	hipLaunchKernelGGL((k_gene_arcs_wave_t<GA_WAVE_NT, GA_CAP_WAVE, GA_WAVE_HITS, 7>), dim3(nb_genes), dim3(GA_WAVE_NT), 0, c->st, ga, rf, ride_form);
-	hipLaunchKernelGGL(k_gene_arcs_big, dim3((unsigned)std::min(c->Q, 8 * c->n_cu)), dim3(GA_BIG_NT), 0, c->st, ga);
+	if (!big_off) hipLaunchKernelGGL(k_gene_arcs_big, dim3((unsigned)std::min(c->Q, 8 * c->n_cu)), dim3(GA_BIG_NT), 0, c->st, ga);
 	if (c->timing_rounds) time_mark(c, &tr, 5, true);
 	if (mail) hipLaunchKernelGGL(k_mail_round, dim3(1), dim3(64), 0, c->st, c->dcnt, c->h_box, h_round_dev ? h_round_dev + 4 * (size_t)S : (int32_t *)nullptr); // invariant / overflow counters for the host; the overflow counter starts again
 	return 0;

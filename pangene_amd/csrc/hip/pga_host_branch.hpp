@@ -434,6 +434,15 @@ extern "C" int pga_arc_round_x(pga_ctx_t *c, int32_t use_ori, int32_t n_seg, con
 	return 0;
 }
 
+// what a pga_branch_loop did with PANGENE_LOOP_LEAN (pga_selftest_loop_route says what the eight words are): of a context, and of the last call of the process
+static int32_t g_loop_route[10] = { 0, 0, 0, 0, 0, -1, 0, 0, 0, 0 };
+static std::mutex g_loop_route_mu; // (contexts may run on threads of their own)
+static void loop_route_of(const pga_ctx *c, int32_t *out)
+{
+	out[0] = c->lean_parts, out[1] = c->lean_inline_sweeps, out[2] = (int32_t)std::min<int64_t>(c->lean_inline_hits, INT32_MAX), out[3] = c->lean_big_skipped, out[4] = c->lean_gene_repeat;
+	out[5] = (int32_t)std::min<int64_t>(c->slow_seen, INT32_MAX), out[6] = c->ga_big_keep, out[7] = c->lean_flag_sweeps, out[8] = c->lean_S, out[9] = 0;
+}
+
 extern "C" int pga_branch_loop(pga_ctx_t *c, int32_t n_round, const pga_branch_par_t *par, const int32_t *max_tot_cnt, const int32_t *max_degree,
                                const int32_t *max_dist_loci, uint8_t *seg_alive, const pga_loop_xchg_t *x, int32_t *seg_cnt_host, int32_t *ndl_host)
 {
@@ -445,7 +454,15 @@ extern "C" int pga_branch_loop(pga_ctx_t *c, int32_t n_round, const pga_branch_p
 	uint8_t *alive = (uint8_t *)c->pool.get(S_MISC, (size_t)S + 64);
 	int32_t *ndl = (int32_t *)c->pool.get(S_BR_NDL, sizeof(int32_t) * (size_t)n_vtx + 16);
 	if (!alive || !ndl) return PGA_ERR_NOMEM;
-	HIPCHK(hipMemsetAsync(alive, 1, (size_t)S, c->st));
+	// The lean form (x == nullptr; PANGENE_LOOP_LEAN, a bit mask read at every call, default: every part): 1 the MODE-0 sweeps evaluate their open hits
+	// themselves where no sweep of the upload had any (launch_sweep), 2 no k_gene_arcs_big where no gene can need it (arc_round_genes), 4 k_br_finish and
+	// k_round_del in one launch (k_br_finish_del), 8 k_flag_vtx inside the sweep that follows it.  0: every launch as before.
+	// Not the sharded form, not timed rounds (PANGENE_TIME_ROUNDS), not PANGENE_LOOP_FUSE=0: every launch as it was.
+	const int lean = (x != nullptr || c->timing_rounds || env_has("PANGENE_LOOP_FUSE", "0")) ? 0 : [] { const char *e = getenv("PANGENE_LOOP_LEAN"); return e && *e ? atoi(e) & 15 : 15; }();
+	c->lean_parts = lean, c->lean_inline_sweeps = 0, c->lean_big_skipped = 0, c->lean_S = S, c->lean_flag_sweeps = 0; // (lean_gene_repeat counts over the upload)
+	// (lean: the three clears of the head -- alive, dcnt[16 .. 18] and [20], the gates' words, which nobody reads unless the rounds are gated -- in one launch)
+	if (lean) fill_multi(c, { FillReq{alive, (size_t)S, 1}, FillReq{c->dcnt + 16, 3 * sizeof(int64_t), 0}, FillReq{c->loopctl, 4 * sizeof(int32_t), 0xff}, FillReq{c->dcnt + 20, sizeof(int64_t), 0} });
+	else HIPCHK(hipMemsetAsync(alive, 1, (size_t)S, c->st));
 	const int64_t br_cap_before = c->br_cap;
 	LoopX L = { x, 0, 0, 0, nullptr, 0, nullptr, nullptr, nullptr };
 	if (x == nullptr) { // Room for the pair lists of every round (nobody can ask for more on the way): a vertex with n out-arcs lists at most n^2
@@ -524,7 +541,7 @@ extern "C" int pga_branch_loop(pga_ctx_t *c, int32_t n_round, const pga_branch_p
 	// in the header of the round's all-gather (k_xs_compact writes the word whether its gate is open or not) and k_xs_sum_rank stamps the round on every rank when any rank marked; a rank's own arc
 	// round follows its own hits (nothing changed here: its slot stands as it is, k_xs_compact leaves), the collectives are queued all the same.
 	const bool gated = !no_skip && (int64_t)c->round_tag + n_round + 4 < (int64_t)HA_TAG_MAX;
-	struct GateScope { pga_ctx *c; ~GateScope() { c->gate = Gate{nullptr, 0}, c->loop_gated = false, c->in_loop = false, c->br_lazy = false, c->ride_want = 0, c->ride_done = 0; } } gate_scope{c}; // (every way out of this function leaves the launches open)
+	struct GateScope { pga_ctx *c; ~GateScope() { c->gate = Gate{nullptr, 0}, c->loop_gated = false, c->in_loop = false, c->br_lazy = false, c->ride_want = 0, c->ride_done = 0, c->lean = 0, c->flag_in_sweep = false; } } gate_scope{c}; // (every way out of this function leaves the launches open)
 	c->loop_gated = gated, c->in_loop = true;
 	// The lazy form (k_branch.hpp: BrLazy): the unsharded queue with the fused front lists part 1 and row 0 of part 2 and asks about the rest only where
 	// row 0 left arcs without a group.  Sharded rounds all-reduce the main list's counts at a capacity all ranks share and keep every pair; so do the
@@ -546,14 +563,16 @@ extern "C" int pga_branch_loop(pga_ctx_t *c, int32_t n_round, const pga_branch_p
 		if (maxg <= (1 << 15)) ride = ride_env, c->ride_cpg = (int)std::max<int64_t>(1, (maxg + RK_CHUNK - 1) / RK_CHUNK);
 	}
 	const uint32_t tag_before = c->round_tag;
-	HIPCHK(hipMemsetAsync(c->dcnt + 16, 0, 3 * sizeof(int64_t), c->st)); // [16] the longest pair list that did not fit (k_loop_front2 / k_pair_offsets); [18] the longest segment of a residual list in this run (k_br_finish)
-	if (gated) HIPCHK(hipMemsetAsync(c->loopctl, 0xff, 4 * sizeof(int32_t), c->st)); // -1: nothing has happened yet; round 0 runs (its branch steps ask for a change in round -1 or later)
+	// [16] the longest pair list that did not fit (k_loop_front2 / k_pair_offsets); [17] genes the wave kernel gave up on with nobody behind it (lean part 2); [18] the longest segment of a residual list in this run (k_br_finish)
+	if (!lean) HIPCHK(hipMemsetAsync(c->dcnt + 16, 0, 3 * sizeof(int64_t), c->st)); // (lean: cleared at the head, and nothing in between touches them)
+	if (gated && !lean) HIPCHK(hipMemsetAsync(c->loopctl, 0xff, 4 * sizeof(int32_t), c->st)); // -1: nothing has happened yet; round 0 runs (its branch steps ask for a change in round -1 or later)
 	// Live lists inside the queue.  pg_flt_high_occ's first rounds delete segments wholesale on many-genome shards (1 250 bacterial
 	// genomes: 98.5 % of the hits are without flt before the test of round 1, 38.5 % after it), so on shards where a wait is small beside a round
 	// the loop asks after the deletions of rounds 1, 2, 4 and 8 how many hits are left (k_flag_vtx counts them) and, when a quarter of what the
 	// lists hold has gone, builds them again before the round's pg_gen_arc.  PANGENE_LIVE_LISTS=0: never; =2: ask in every round, whatever the size.
 	static const int live_env = [] { const char *e = getenv("PANGENE_LIVE_LISTS"); return e ? atoi(e) : -1; }();
 	const bool live_ask = live_env != 0 && (live_env == 2 || N >= (1 << 21));
+	c->lean = lean; // (from here on: the rounds of the queue; the pre_on block above keeps every launch)
 	for (int r = 0; r < n_round; ++r) {
 		c->loop_round = r;
 		bool rebuilt = false;
@@ -582,15 +601,27 @@ extern "C" int pga_branch_loop(pga_ctx_t *c, int32_t n_round, const pga_branch_p
 			const bool nl_rides = lz.on && c->NL > 0 && !env_has("PANGENE_BR_LAZY_RIDE", "0");
 			TRY(branch_residual_counts(c, lz, nl_rides ? &nlr : nullptr));
 			TRY(mark_hits_resident(c, nullptr, 1, nl_rides ? &nlr : nullptr));
-			TRY(branch_finish(c, lz, n_vtx, ndl));
+			const bool tail_fused = (c->lean & 4) && lz.on && r > 0; // (PANGENE_LOOP_LEAN bit 4: the rows from 1 on and the deletions in one launch, k_br_finish_del)
+			const Gate gate_steps = c->gate;
+			if (!tail_fused) TRY(branch_finish(c, lz, n_vtx, ndl));
 			c->gate = gated ? Gate{c->loopctl, r} : Gate{nullptr, 0}; // from here on: something changed in THIS round
 			if (r > 0) { // pg_flt_high_occ + pg_hard_delete + PG_SET_FILTER(vtx == 0) (graph.c:219-263, 312): the thresholds tighten every round, so this test always runs
+				int4 *gm_del = (x || par->final_on) ? (int4 *)c->pool.get(S_GMETA, 0) : (int4 *)nullptr; // (whoever compacts the genes' stretches afterwards must find a deleted one empty)
+				if (tail_fused) {
+					const int32_t *rcnt = (const int32_t *)c->pool.get(S_RNLCNT, 0);
+					if (!rcnt) return PGA_ERR_NOMEM;
+					const RoundDel rd = { S, max_tot_cnt[r], max_degree[r], max_dist_loci[r], sg, c->g2s, vs, ve, dg, seg_cnt, vwk, alive, gm_del, gated ? c->loopctl : (int32_t *)nullptr, r };
+					hipLaunchKernelGGL(k_br_finish_del, dim3(nblk(n_vtx, BLOCK / WAVE)), dim3(BLOCK), 0, c->st, n_vtx, rcnt, lz, ndl, c->dcnt, (const int64_t *)(c->dcnt + 15), (int64_t)c->br_cap, gate_steps, rd);
+				} else
 				hipLaunchKernelGGL(k_round_del, dim3(nblk(S)), dim3(BLOCK), 0, c->st, S, (const int32_t *)ndl, max_tot_cnt[r], max_degree[r], max_dist_loci[r], (const int32_t *)sg, c->g2s, vs, ve, dg, seg_cnt, vwk, alive,
-				                   (x || par->final_on) ? (int4 *)c->pool.get(S_GMETA, 0) : (int4 *)nullptr, // (whoever compacts the genes' stretches afterwards must find a deleted one empty)
-				                   gated ? c->loopctl : (int32_t *)nullptr, r);
+				                   gm_del, gated ? c->loopctl : (int32_t *)nullptr, r);
 				const bool ask = live_ask && (live_env == 2 || r == 1 || r == 2 || r == 4 || r == 8) && (r + 1 < n_round || par->final_on);
 				if (ask) HIPCHK(hipMemsetAsync(c->live_cnt, 0, sizeof(int64_t) * LIVE_CNT_N, c->st));
 				static const bool fv_x = env_has("PANGENE_FLAG_VTX", "x"); // (tests: every hit in every round, as before)
+				// (PANGENE_LOOP_LEAN bit 8) without live lists and without the count, where the round's arc round follows: no launch -- its sweep, the next
+				// reader of the flag words, applies the transform to every word it stages and stores its own hits' (launch_sweep, sweep_tile's LEAN & 2)
+				if ((c->lean & 8) && !ask && !c->live_on && !fv_x && (r + 1 < n_round || par->final_on)) c->flag_in_sweep = true;
+				else
 				if (c->live_on && c->z_valid && !fv_x && (int64_t)c->NL * 5 < (int64_t)N) // few members: along the index (40 bytes a member against 8 a hit)
 					hipLaunchKernelGGL(k_flag_vtx_z, dim3(nblk(std::max(c->NL, 1))), dim3(BLOCK), 0, c->st, c->flags, (const int32_t *)c->zx, (const int32_t *)c->zg, c->NL, (const int32_t *)c->g2s, c->gate, ask ? c->live_cnt : (int64_t *)nullptr);
 				else
@@ -644,15 +675,15 @@ extern "C" int pga_branch_loop(pga_ctx_t *c, int32_t n_round, const pga_branch_p
 		if (!h_ctl) return PGA_ERR_NOMEM;
 		HIPCHK(hipMemcpyAsync(h_ctl, c->loopctl, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, c->st));
 	}
-	const size_t fetch_need = (((size_t)S + 128 + (par->final_on ? 4 * sizeof(int32_t) * (size_t)S + 64 : 0) + 15) & ~(size_t)15) + 64 + 32;
+	const size_t fetch_need = (((size_t)S + 128 + (par->final_on ? 4 * sizeof(int32_t) * (size_t)S + 64 : 0) + 15) & ~(size_t)15) + 64 + 48;
 	if (c->h_fetch_cap < fetch_need) {
 		c->h_fetch = c->pin.get(fetch_need + fetch_need / 2 + 512);
 		if (!c->h_fetch) return PGA_ERR_NOMEM;
 		c->h_fetch_cap = fetch_need + fetch_need / 2 + 512;
 	}
 	HIPCHK(hipMemcpyAsync(c->h_fetch, alive, (size_t)S, hipMemcpyDeviceToHost, c->st));
-	int64_t *h_need = (int64_t *)((char *)c->h_fetch + fetch_need - 32); // (the last 32 bytes of what was asked for: dcnt[16 .. 18])
-	HIPCHK(hipMemcpyAsync(h_need, c->dcnt + 16, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, c->st));
+	int64_t *h_need = (int64_t *)((char *)c->h_fetch + fetch_need - 48); // (the last 48 bytes of what was asked for: dcnt[16 .. 20])
+	HIPCHK(hipMemcpyAsync(h_need, c->dcnt + 16, 5 * sizeof(int64_t), hipMemcpyDeviceToHost, c->st)); // ([19]: the longest slow list of a MODE-0 sweep in this run, [20]: open hits the sweeps of this call evaluated themselves -- launch_sweep)
 	int32_t *h_fin = (int32_t *)((char *)c->h_fetch + (((size_t)S + 127) & ~(size_t)63)); // (final_on) the last arc round's segment counters, the last branch step's n_dist_loci
 	if (par->final_on) {
 		HIPCHK(hipMemcpyAsync(h_fin, (const int32_t *)c->pool.get(S_SEGCNT, 0), sizeof(int32_t) * (size_t)n_vtx, hipMemcpyDeviceToHost, c->st));
@@ -675,6 +706,11 @@ extern "C" int pga_branch_loop(pga_ctx_t *c, int32_t n_round, const pga_branch_p
 	}
 	c->br_np_seen = std::max<int64_t>(c->br_np_seen, c->h_cnt[15]);
 	if (getenv("PANGENE_TIMING")) fprintf(stderr, "[pga_branch_loop] counters after %d rounds: invariant %lld, table overflows (last round) %lld, sticky %lld, pairs (last round) %lld of capacity %lld\n", n_round, (long long)c->h_cnt[3], (long long)c->h_cnt[9], (long long)c->h_cnt[11], (long long)c->h_cnt[15], (long long)c->br_cap);
+	c->slow_seen = std::max<int64_t>(c->slow_seen, h_need[3]); // (what launch_sweep decides by from now on)
+	c->lean_inline_hits = (lean & 1) ? h_need[4] : 0;
+	struct RouteSnap { const pga_ctx *c; ~RouteSnap() { std::lock_guard<std::mutex> lk(g_loop_route_mu); const int32_t n = g_loop_route[9]; loop_route_of(c, g_loop_route); g_loop_route[9] = n + 1; } } route_snap{c}; // (whatever the status: pga_selftest_loop_route)
+	if (lean && getenv("PANGENE_TIMING")) fprintf(stderr, "[pga_branch_loop] lean parts %d: %d sweeps evaluated their open hits themselves (the longest slow list since the upload: %lld), k_gene_arcs_big %s\n", lean, c->lean_inline_sweeps,
+	                                              (long long)c->slow_seen, c->lean_big_skipped ? "not launched" : "launched");
 	const int64_t res_need = h_need[2] * BR_RSEG; // (every segment as long as the longest)
 	if (c->br_lazy && getenv("PANGENE_TIMING")) fprintf(stderr, "[pga_branch_loop] lazy rounds: the longest segment of a residual list %lld of capacity %lld (%d segments)\n", (long long)h_need[2], (long long)(c->br_rcap / BR_RSEG), BR_RSEG);
 	const bool res_over = c->br_lazy && res_need > c->br_rcap; // (read before the scope's end clears br_lazy)
@@ -698,6 +734,15 @@ extern "C" int pga_branch_loop(pga_ctx_t *c, int32_t n_round, const pga_branch_p
 	}
 	else if (c->h_cnt[11]) {
 		if (c->h_cnt[3]) return PGA_ERR_INVARIANT;
+		// (lean, bit 2) a gene the wave kernel gave up on in an arc round without k_gene_arcs_big behind it: from now on this upload keeps that launch, and
+		// the queue runs again -- status 4 as for a list beyond its room (whatever else the void run met, the repeat meets again)
+		if (c->lean_big_skipped && h_need[1] != 0 && c->h_cnt[9] == 0) {
+			if (getenv("PANGENE_TIMING")) fprintf(stderr, "[pga_branch_loop] lean: %lld gene(s) needed k_gene_arcs_big in a round without it -- the queue is repeated with it\n", (long long)h_need[1]);
+			c->ga_big_keep = true, ++c->lean_gene_repeat;
+			if (*h_need > c->br_cap && *h_need + *h_need / 4 <= ((int64_t)1 << 27)) c->br_cap = *h_need + *h_need / 4, c->loop_room_given = true; // (a list that did not fit either: one repeat for both)
+			if (res_over && res_need + res_need / 4 <= ((int64_t)1 << 27)) c->br_rcap = res_need + res_need / 4, c->loop_room_given = true;
+			return 4;
+		}
 		// A pair list beyond its capacity and nothing else (no hub gene beyond its LDS table): the next attempt gets the room -- status 4, the caller runs the
 		// queue again (round 6: a shard of 10 000 genomes lists 10^7 pairs in round 0, before pg_flt_high_occ has seen the graph; the queue gave
 		// up for good and every pass of configs[3] at full size ran its fifteen rounds host-driven).  Lists beyond 2^26 pairs: status 1 as before.

@@ -46,6 +46,7 @@ static int make_sweep_view(pga_ctx *c, SweepView *v)
 	v->literal = c->exon_regular && getenv("PANGENE_MERGE_LITERAL") == nullptr ? 0 : 1;
 	v->gate = c->gate;
 	v->xmap = nullptr;
+	v->lean_cnt = c->dcnt + 19, v->next_cnt = nullptr, v->clear2 = nullptr, v->g2s = nullptr;
 	v->slow_cnt = nullptr, v->slow_list = (int32_t *)c->pool.get(S_SLOW, sizeof(int32_t) * (size_t)c->N);
 	v->hz_list = (int32_t *)c->pool.get(S_HZLIST, sizeof(int32_t) * PGA_HAZARD_CAP);
 	if (!v->slow_list || !v->hz_list) return PGA_ERR_NOMEM;
@@ -89,6 +90,19 @@ template <int MODE> static int launch_sweep(pga_ctx *c, int timed_which)
 	static_assert(MODE == 0 || MODE == 1 || MODE == 3, "sweep modes");
 	static const bool no_compact = env_has("PANGENE_LIVE", "fullsweep"); // (tests: live lists, but the sweeps over every record)
 	if (MODE == 0 && c->live_on && c->z_valid && !no_compact) v.A = c->cA, v.B = c->cB, v.C = c->cC, v.n = c->NL, v.xmap = c->cx; // the sweeps of the rounds: the members' records (see SweepView::xmap; z_valid: a cs override under -S drops the lists -- until they are built again the compact records are not what the X order holds)
+	// The lean forms of a MODE-0 sweep over the X-order records (k_sweep_rounds).  1: no hit of any MODE-0 sweep of this upload had partners beyond its wave's
+	// window, as far as the host has seen (pga_branch_loop fetches dcnt[19] with its own wait; until then, and on a pile-rich shard, the list form with its
+	// balanced k_sweep_slow) -- the open test is static in the A records, so the rare hit that is open after all is evaluated by its own lane.  Either form
+	// is correct on any input.  PANGENE_SWEEP_INLINE (tests; read at every call): 1 every such sweep takes this form, 0 none.  2: pga_branch_loop left the
+	// k_flag_vtx of its round to this sweep (flag_in_sweep).
+	int lean_form = 0;
+	if (MODE == 0) {
+		const char *e = getenv("PANGENE_SWEEP_INLINE");
+		if (v.xmap == nullptr && ((e && *e) ? *e == '1' : ((c->lean & 1) && c->slow_seen == 0))) lean_form |= 1;
+		if (c->flag_in_sweep && v.xmap == nullptr) lean_form |= 2, ++c->lean_flag_sweeps;
+		else if (c->flag_in_sweep) hipLaunchKernelGGL(k_flag_vtx, dim3(nblk(c->N)), dim3(BLOCK), 0, c->st, c->flags, c->gid, c->N, c->g2s, 1, c->gate, (int64_t *)nullptr); // (never: the loop keeps its launch with live lists)
+		c->flag_in_sweep = false;
+	}
 	const int n_sw = v.n; // (0: one workgroup of sentinels -- the k_sweep_slow behind it still has counters to clear)
 	const bool timed = (timed_which == 0 || timed_which == 1) && c->timing_on; // (the stage-C sweeps are not timed one by one: two events per launch cost ~10 us of queue time)
 	if (timed) {
@@ -107,6 +121,14 @@ template <int MODE> static int launch_sweep(pga_ctx *c, int timed_which)
 		// a timed launch carries its own start/stop events: they take the dispatch's begin and end time stamps, i.e. the
 		// duration of k_sweep itself, the figure rocprofv3 --kernel-trace reports for it
 		hipEvent_t ea = timed && reps == 1 ? t.a : nullptr, eb = timed && reps == 1 ? t.b : nullptr;
+		long long *next_cnt = (long long *)(c->dcnt + 12 + ((c->sweep_seq + 1) & 1));
+		if (MODE == 0 && lean_form) { // (sweep_tile's LEAN: 1 no k_sweep_slow behind it, 2 the k_flag_vtx in front of it left out by pga_branch_loop)
+			v.next_cnt = next_cnt, v.clear2 = c->ga_ctl, v.g2s = c->g2s;
+#define SW_LEAN(L) do { if (c->any_multi) hipExtLaunchKernelGGL((k_sweep_rounds<true, L>), dim3(nt), dim3(SW_TILE), 0, c->st, ea, eb, 0, v); else hipExtLaunchKernelGGL((k_sweep_rounds<false, L>), dim3(nt), dim3(SW_TILE), 0, c->st, ea, eb, 0, v); } while (0)
+			if (lean_form == 1) SW_LEAN(1); else if (lean_form == 2) SW_LEAN(2); else SW_LEAN(3);
+#undef SW_LEAN
+			if (lean_form & 1) { ++c->lean_inline_sweeps, ++c->sweep_seq; continue; }
+		} else
 		if (c->any_multi && MODE != 0 && !c->lists_in_lds) hipExtLaunchKernelGGL((k_sweep_lean<MODE == 0 ? 1 : MODE>), dim3(nt), dim3(SW_TILE), 0, c->st, ea, eb, 0, v);
 		else if (c->any_multi) hipExtLaunchKernelGGL((k_sweep<MODE, true>), dim3(nt), dim3(SW_TILE), 0, c->st, ea, eb, 0, v);
 		else hipExtLaunchKernelGGL((k_sweep<MODE, false>), dim3(nt), dim3(SW_TILE), 0, c->st, ea, eb, 0, v);
@@ -191,6 +213,16 @@ static void zero_multi(pga_ctx *c, void *p0, size_t b0, void *p1 = nullptr, size
 	ZeroList z = { { p0, p1, p2, p3 }, { (b0 + 3) / 4, (b1 + 3) / 4, (b2 + 3) / 4, (b3 + 3) / 4 } };
 	const unsigned long long tot = z.dwords[0] + z.dwords[1] + z.dwords[2] + z.dwords[3];
 	if (tot) hipLaunchKernelGGL(k_zero_multi, dim3((unsigned)((tot + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->st, z);
+}
+
+// the same with a byte value per buffer (up to four; a NULL buffer or no bytes: left out)
+struct FillReq { void *p; size_t bytes; uint8_t v; };
+static void fill_multi(pga_ctx *c, const FillReq (&r)[4])
+{
+	FillList z;
+	unsigned long long tot = 0;
+	for (int k = 0; k < 4; ++k) z.p[k] = r[k].p, z.dwords[k] = r[k].p ? (r[k].bytes + 3) / 4 : 0, z.word[k] = 0x01010101u * r[k].v, tot += z.dwords[k];
+	if (tot) hipLaunchKernelGGL(k_fill_multi, dim3((unsigned)((tot + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->st, z);
 }
 
 template <class T> static int upload(pga_ctx *c, T *dst, const T *src, size_t n)

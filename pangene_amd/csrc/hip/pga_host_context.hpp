@@ -241,6 +241,13 @@ struct pga_ctx {
 	bool loop_room_given = false;     // pga_branch_loop returned status 4 once on this context (tests: PANGENE_LOOP_PAIR_CAP applies until then)
 	bool loop_gated = false;          // pga_branch_loop runs with gates: an arc round that runs leaves its tag in loopctl[2], whether its own gate is open or not
 	int32_t *h_loopctl = nullptr;     // pinned mirror of loopctl (bump-allocated once per context)
+	// The lean form of the unsharded queued rounds (pga_branch_loop: PANGENE_LOOP_LEAN, a bit mask read at every call).  lean: the parts on for the
+	// launches of the moment (0 outside the queue's rounds); slow_seen: the longest slow list of any MODE-0 sweep since the upload as the host knows it
+	// (dcnt[19], fetched with the loop's own wait; -1: not seen yet -- the sweeps keep the list form); ga_big_keep: a gene needed k_gene_arcs_big on
+	// this upload (learnt through a status-4 repeat).  lean_*: what the last pga_branch_loop did, for pga_selftest_loop_route.
+	int lean = 0; int64_t slow_seen = -1; bool ga_big_keep = false;
+	bool flag_in_sweep = false; // (bit 8) the loop queued no k_flag_vtx for the round's deletions: the MODE-0 sweep launched next applies it while staging (launch_sweep)
+	int lean_parts = 0, lean_inline_sweeps = 0, lean_big_skipped = 0, lean_gene_repeat = 0, lean_S = 0, lean_flag_sweeps = 0; int64_t lean_inline_hits = 0;
 	int32_t *h_ov = nullptr; size_t h_ov_cap = 0; // pinned: position / file-index lists of an order override, two halves used in turn
 	hipEvent_t ov_ev[2] = { nullptr, nullptr }; bool ov_ev_used[2] = { false, false }; unsigned ov_seq = 0; // a half is free again when the copy out of it has happened
 	bool zposy_stale = false; // the gene-major index stands but the cm order (or the X numbering) changed: the walk's records have to be packed again (ensure_z)

@@ -202,6 +202,25 @@ extern "C" int pga_selftest_arc_route(pga_ctx_t *c, int32_t *out)
 	return 0;
 }
 
+// What the last pga_branch_loop of the context did with PANGENE_LOOP_LEAN (read-only; ten words): out[0] the parts that were on (the bit mask; 0: every launch as
+// before), [1] sweeps of that call that evaluated their open hits themselves, [2] how many open hits those evaluated, [3] k_gene_arcs_big was left out,
+// [4] status-4 repeats for a gene that needed it, counted over the upload, [5] the longest slow list of a MODE-0 sweep since the upload as the host
+// knows it (-1: not seen yet), [6] the upload keeps k_gene_arcs_big from now on, [7] sweeps of that call that applied the round's k_flag_vtx while staging (bit 8), [8] the segments that call ran over, [9] calls of pga_branch_loop in this process that got as far as their wait.
+// c == NULL: the last such call of the process, whatever its context (a run through the pg_* entry points has no handle on the context).
+extern "C" int pga_selftest_loop_route(pga_ctx_t *c, int32_t *out)
+{
+	if (out == nullptr) return PGA_ERR_ARG;
+	std::lock_guard<std::mutex> lk(g_loop_route_mu);
+	if (c) { // (with the context at hand: [1] and [2] count the sweeps since that call began as well -- pga_shadow with PANGENE_SWEEP_INLINE=1)
+		TRY(sync_st(c));
+		int64_t n_inline = 0;
+		HIPCHK(hipMemcpy(&n_inline, c->dcnt + 20, sizeof(int64_t), hipMemcpyDeviceToHost));
+		loop_route_of(c, out), out[2] = (int32_t)std::min<int64_t>(n_inline, INT32_MAX), out[9] = g_loop_route[9];
+	}
+	else memcpy(out, g_loop_route, sizeof(g_loop_route));
+	return 0;
+}
+
 // the roundings of a final arc record on the device (k_genes.hpp: arc_final_hi): out[4 n] = {avg_dist, s1, s2, 0} of every in[i]
 extern "C" int pga_selftest_arc_final(const pga_arc_part_t *in, int64_t n, int32_t *out)
 {

@@ -326,7 +326,7 @@ extern "C" int pga_begin(pga_ctx_t *c)
 		HIPCHK(hipEventCreate(&c->span_a));
 		HIPCHK(hipEventRecord(c->span_a, c->st));
 	}
-	HIPCHK(hipMemsetAsync(c->dcnt, 0, 16 * sizeof(int64_t), c->st));
+	HIPCHK(hipMemsetAsync(c->dcnt, 0, 24 * sizeof(int64_t), c->st)); // (beyond the mailbox's sixteen: [19] the longest slow list of a MODE-0 sweep in this run, launch_sweep)
 	if (c->Q) hipLaunchKernelGGL(k_fill_i32, dim3(nblk(c->Q)), dim3(BLOCK), 0, c->st, c->g2s, (int64_t)c->Q, -1);
 	c->n_seg = 0;
 	if (N == 0) return sync_st(c);

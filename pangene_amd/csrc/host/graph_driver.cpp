@@ -1748,7 +1748,9 @@ void pg_graph_gen(const pg_opt_t *opt, pg_graph_t *q)
 		int rc = graph_gen_impl(opt, q);
 		// (front_fill has set ext->front_host: the repeated pg_post_process picks the representatives on the host, and its rounds may still ask for the repeat below)
 		if (rc == RC_FRONT_TIE && ext) rc = again("a gene has two proteins at its largest key: repeating stages A-C with the representatives picked on the host");
-		if (rc == RC_REDO && ext) rc = again("the queued branch rounds met a case they leave to the host: repeating stages A-C with host-driven rounds");
+		// (more than once: the backend's status 4 repeats the queue with what the void run taught it -- room for a list, the gene kernel a lean round left
+		// out -- and the repeated queue may still meet a case for the host-driven rounds; the third status 4 switches the queue off, see branch_loop)
+		for (int k = 0; rc == RC_REDO && ext && k < 4; ++k) rc = again("the queued branch rounds met a case they leave to the host or ask for once more: repeating stages A-C");
 		return rc;
 	};
 	if (g_err == 0 && run_graph() != 0) q->n_arc = 0;
