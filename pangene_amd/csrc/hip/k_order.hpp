@@ -93,11 +93,15 @@ __global__ __launch_bounds__(BLOCK) void k_ov_gather(PermArrays p, const int32_t
 }
 
 __global__ __launch_bounds__(BLOCK) void k_ov_scatter(PermArrays p, const int32_t *ov_pos, const int32_t *ov_file, int64_t t, const int32_t *tmp,
-                                                        const int32_t *gnm, const int32_t *goff, int32_t *inv, int32_t *zx, int32_t *zpos /* or NULL */)
+                                                        const int32_t *gnm, const int32_t *goff, int32_t *inv, int32_t *zx, int32_t *zpos /* or NULL */, int32_t *headpos)
 {
 	int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
 	if (i >= t) return;
 	int pos = ov_pos[i];
+	// The mark goes to the genome's first position below, so k_set_head must find it there.  A mark that pga_set_head had put on another hit of this
+	// contig is cleared with the contig's other flag words.  Naming a hit of a LATER contig in pga_set_head is outside the ABI (head_file is the hit at
+	// array index 0 of the cs order, which lies in the genome's first contig): such a mark would not be cleared here.
+	if (pos == goff[gnm[pos]]) headpos[gnm[pos]] = pos;
 	inv[ov_file[i]] = pos; // (k_ov_gather, the launch before, was the last reader of the old entries)
 	if (zpos) { const int z = tmp[(int64_t)(OV_PLANES + 12) * t + i]; zpos[pos] = z; if (z >= 0) zx[z] = pos; } // (z < 0: not in the index -- live lists)
 #pragma unroll

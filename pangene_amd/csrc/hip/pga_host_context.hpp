@@ -250,6 +250,7 @@ struct pga_ctx {
 	int lean_parts = 0, lean_inline_sweeps = 0, lean_big_skipped = 0, lean_gene_repeat = 0, lean_S = 0, lean_flag_sweeps = 0; int64_t lean_inline_hits = 0;
 	int32_t *h_ov = nullptr; size_t h_ov_cap = 0; // pinned: position / file-index lists of an order override, two halves used in turn
 	hipEvent_t ov_ev[2] = { nullptr, nullptr }; bool ov_ev_used[2] = { false, false }; unsigned ov_seq = 0; // a half is free again when the copy out of it has happened
+	int32_t ov_route[8] = { -1, 0, 0, 0, 0, 0, 0, 0 }; // what the last override decided (pga_selftest_order): which, T, z_keep, wrec_ok, partial, live, h_ov grew, ov_seq
 	bool zposy_stale = false; // the gene-major index stands but the cm order (or the X numbering) changed: the walk's records have to be packed again (ensure_z)
 	const pga_arc_part_t *cur_tab = nullptr; int64_t cur_tab_n = 0; // the table of pga_arc_set_current
 	bool table_sparse = false; // the current arc table lives in the genes' stretches (arc_round_genes) and has not been compacted

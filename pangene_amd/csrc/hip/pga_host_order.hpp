@@ -21,6 +21,11 @@ extern "C" int pga_override_order(pga_ctx_t *c, int32_t which, int32_t n_seg, co
 	// (round 5 packed the whole shard again after every override that found no walk standing: 13 of 145 us per pass of the full-size configs[4] set).
 	const bool wrec_ok = c->wrec_valid && z_keep && !c->zposy_stale && n_seg > 0;
 	const bool partial = c->ha_valid && wrec_ok && c->vfirst == nullptr && seg_off[n_seg] * 8 <= (int64_t)N;
+	const bool live = c->live_on && z_keep; // the lists stand and have to follow the override (an index that is dropped is built again, lists and all)
+	{ // the route of this call, for pga_selftest_order (plain words: nothing is launched, nothing waits)
+		int32_t *r = c->ov_route;
+		r[0] = which, r[1] = n_seg > 0 ? (int32_t)std::min<int64_t>(seg_off[n_seg], INT32_MAX) : 0, r[2] = z_keep, r[3] = wrec_ok, r[4] = partial, r[5] = live, r[6] = 0, r[7] = (int32_t)c->ov_seq;
+	}
 	c->walk_valid = false, c->ha_valid = false, c->yrec_valid = false, c->wrec_valid = false;
 	if (!z_keep) c->z_valid = false;
 	if (n_seg <= 0 || N == 0) return 0;
@@ -39,7 +44,6 @@ extern "C" int pga_override_order(pga_ctx_t *c, int32_t which, int32_t n_seg, co
 		}
 		return 0;
 	};
-	const bool live = c->live_on && z_keep; // the lists stand and have to follow the override (an index that is dropped is built again, lists and all)
 	// positions and file indices of the overridden hits, built in page-locked memory (a real DMA; from a std::vector the runtime stages)
 	// (nothing waits at the end of an override any more -- sixty-six of them per pass each found the device still at the round queued
 	// before -- so the lists must not be overwritten while their copy is under way: two halves, an event each)
@@ -50,8 +54,10 @@ extern "C" int pga_override_order(pga_ctx_t *c, int32_t which, int32_t n_seg, co
 		c->h_ov = (int32_t *)c->pin.get(2 * cap);
 		if (!c->h_ov) return PGA_ERR_NOMEM;
 		c->h_ov_cap = cap, c->ov_ev_used[0] = c->ov_ev_used[1] = false;
+		c->ov_route[6] = 1;
 	}
 	const int half = (int)(c->ov_seq++ & 1u);
+	c->ov_route[7] = (int32_t)c->ov_seq;
 	if (!c->ov_ev[half]) HIPCHK(hipEventCreateWithFlags(&c->ov_ev[half], hipEventDisableTiming));
 	if (c->ov_ev_used[half]) HIPCHK(hipEventSynchronize(c->ov_ev[half]));
 	int32_t *pos = (int32_t *)((char *)c->h_ov + (size_t)half * c->h_ov_cap), *fil = pos + T, *fst = fil + T;
@@ -85,7 +91,7 @@ extern "C" int pga_override_order(pga_ctx_t *c, int32_t which, int32_t n_seg, co
 	PermArrays p = { { c->fidx, c->pid, c->gid, c->cm, c->nex, c->sadj, c->rank, c->sdom, c->pdom, c->pdom0, (int32_t *)c->flags, c->sori }, { c->recA, c->recB, c->recC } };
 	static_assert(OV_FLAGS == 10, "the flag word's place in PermArrays");
 	hipLaunchKernelGGL(k_ov_gather, dim3(nblk(T)), dim3(BLOCK), 0, c->st, p, d_pos, d_fil, T, c->inv, tmp, remap, z_keep ? (const int32_t *)c->zpos : (const int32_t *)nullptr);
-	hipLaunchKernelGGL(k_ov_scatter, dim3(nblk(T)), dim3(BLOCK), 0, c->st, p, d_pos, d_fil, T, tmp, c->gnm, c->goff, c->inv, c->zx, z_keep ? c->zpos : (int32_t *)nullptr);
+	hipLaunchKernelGGL(k_ov_scatter, dim3(nblk(T)), dim3(BLOCK), 0, c->st, p, d_pos, d_fil, T, tmp, c->gnm, c->goff, c->inv, c->zx, z_keep ? c->zpos : (int32_t *)nullptr, c->headpos);
 	hipLaunchKernelGGL(k_ov_remap_y, dim3(nblk(T)), dim3(BLOCK), 0, c->st, c->yperm, d_pos, T, remap);
 	if (live) hipLaunchKernelGGL(k_ovl_remap_ylist, dim3(nblk(T)), dim3(BLOCK), 0, c->st, c->ylist_buf, (const int32_t *)d_lpos, T, (const int32_t *)remap);
 	if (z_keep) c->zposy_stale = true;

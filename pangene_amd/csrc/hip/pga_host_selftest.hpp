@@ -202,6 +202,37 @@ extern "C" int pga_selftest_arc_route(pga_ctx_t *c, int32_t *out)
 	return 0;
 }
 
+// what the order overrides keep current beside the arrays pga_selftest_stage_a exports (tests/test_order_gpu.py, tests/support/order_direct.py): inv, the
+// gene-major index's zpos / zx, and under live lists lx, the members' list in cm order and their compact records; with the route of the context's last
+// pga_override_order = {which, T, z_keep, wrec_ok, partial, live, h_ov grew, ov_seq}.  Waits for the stream; reads only; not part of pangene_hip.h.
+typedef struct {
+	int32_t *inv, *zpos, *zx;      /* [N] each (zx: the first NL entries mean something) */
+	int32_t *lx;                   /* [N + 1] */
+	int32_t *ylist;                /* [N]: the first NL entries of what the walk reads */
+	int32_t *cA, *cB, *cC, *cx;    /* [4 N] [4 N] [4 N] [N]: the first NL entries */
+	int32_t NL, live_on, z_valid, inv_valid, wrec_valid, ha_valid, zposy_stale; /* out */
+	int32_t route[8];              /* out */
+	uint32_t f_member;             /* out: the value of the internal bit "in the live lists" */
+} pga_selftest_order_t;
+extern "C" int pga_selftest_order(pga_ctx_t *c, pga_selftest_order_t *out) // any pointer may be NULL
+{
+	if (c == nullptr || out == nullptr) return PGA_ERR_ARG;
+	TRY(sync_st(c));
+	const size_t N = (size_t)c->N, NL = (size_t)c->NL;
+	auto fetch = [&](void *dst, const void *src, size_t bytes) { return (dst == nullptr || src == nullptr || bytes == 0 || hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) == hipSuccess) ? 0 : PGA_ERR_NO_DEVICE; };
+	TRY(fetch(out->inv, c->inv, sizeof(int32_t) * N)); TRY(fetch(out->zpos, c->zpos, sizeof(int32_t) * N)); TRY(fetch(out->zx, c->zx, sizeof(int32_t) * N));
+	if (N) TRY(fetch(out->lx, c->lx, sizeof(int32_t) * (N + 1)));
+	TRY(fetch(out->ylist, c->ylist, sizeof(int32_t) * std::min(N, NL)));
+	if (c->live_on) {
+		TRY(fetch(out->cA, c->cA, sizeof(int4) * std::min(N, NL))); TRY(fetch(out->cB, c->cB, sizeof(int4) * std::min(N, NL))); TRY(fetch(out->cC, c->cC, sizeof(int4) * std::min(N, NL)));
+		TRY(fetch(out->cx, c->cx, sizeof(int32_t) * std::min(N, NL)));
+	}
+	out->NL = c->NL, out->live_on = c->live_on, out->z_valid = c->z_valid, out->inv_valid = c->inv_valid, out->wrec_valid = c->wrec_valid, out->ha_valid = c->ha_valid, out->zposy_stale = c->zposy_stale;
+	memcpy(out->route, c->ov_route, sizeof(out->route));
+	out->f_member = F_MEMBER;
+	return 0;
+}
+
 // What the last pga_branch_loop of the context did with PANGENE_LOOP_LEAN (read-only; ten words): out[0] the parts that were on (the bit mask; 0: every launch as
 // before), [1] sweeps of that call that evaluated their open hits themselves, [2] how many open hits those evaluated, [3] k_gene_arcs_big was left out,
 // [4] status-4 repeats for a gene that needed it, counted over the upload, [5] the longest slow list of a MODE-0 sweep since the upload as the host

@@ -335,8 +335,10 @@ BRANCH_DEG = (2, 3, 63, 64, 65)
 BRANCH_S = (1000, 1000, 981, 980, 979, 951, 950, 949, 501, 500, 499, 100)  # the hub hit's score = the arc's s1: 1 - s1 / 1000 around .02, .05 and .5
 
 
-def branch():
+def branch(name="branch", cm_tie=False):
+    """cm_tie (order_ref's `marks`; it draws what `branch` draws): the hub's hit and its target stand on one cm, 1 000 bp apart, wherever no third hit lies between them"""
     b = _Build("branch", 6)
+    b.name = name
     ga, gb = b.g[3], b.g[4]
     Zg = b.genes.new()
     hubs = {}
@@ -351,9 +353,13 @@ def branch():
             if k % 12 in (3, 4) and n > 3:  # a hub hit that will carry weak_br = 1, over a weaker hit of another gene: the second round's sweep shadows the HUB hit
                 kk = ga.put(V, 0, s, sadj=2000)
                 ga.put(Zg, 0, sadj=1000, cm=ga.h[kk][1] + 10)
+                kk = -1
             else:
-                ga.put(V, 0, s)
-            ga.put(T[k], int(b.rng.integers(0, 2)))
+                kk = ga.put(V, 0, s)
+            if cm_tie and kk >= 0:
+                ga.put(T[k], int(b.rng.integers(0, 2)), cm=ga.h[kk][1], cs=ga.at, ce=ga.at + 100)
+            else:
+                ga.put(T[k], int(b.rng.integers(0, 2)))
         # a second genome in which every third target stands next to the best-scoring one: local there, nowhere comparable otherwise
         gb.ctg()
         gb.put(T[0], 0)

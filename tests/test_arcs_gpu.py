@@ -7,7 +7,7 @@ graph.c:103-169 and branch.c:6-46).  One child process per environment (tests/su
 assertions from the hook pga_selftest_arc_route of pga_host_selftest.hpp).
 
 Not covered here: the queued loop pga_branch_loop with its riders and k_arc_final (tests/test_loop_tail_gpu.py, tests/test_branch_lazy_gpu.py hold it
-against these host-driven rounds), k_walk_list / pga_override_order, the sharded exchange kernels."""
+against these host-driven rounds), the sharded exchange kernels (k_walk_list / pga_override_order: tests/test_order_gpu.py)."""
 import os
 import subprocess
 import sys
