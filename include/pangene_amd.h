@@ -605,6 +605,44 @@ void pg_write_phylosig(pg_graph_t *g, const pg_phylosig_opt_t *o);
 int  pg_pan_phylosig(const uint8_t *presence, int32_t n_item, int32_t n_asm, const int64_t *rec, int32_t method, const pg_phylosig_opt_t *o, int32_t *out_i32,
                      int64_t *out_sum_i64);
 
+/* Principal coordinates of the assemblies: classical scaling (cmdscale of R, pcoa of ape and scikit-bio) of one distance matrix, the
+ * plot that shows the groups pg_cluster_* names and pg_permanova_* tests.  DESIGN.md section 8 "Principal coordinates" holds the
+ * definition.  Input: a fixed-point matrix q over N assemblies, symmetric, zero diagonal, entries in [0, 2^29), F fraction bits,
+ * d = q 2^-F.  A = -1/2 d o d entrywise, B = J A J with J = I - 11'/N, B = V L V'.  The axes are the n_axis ALGEBRAICALLY largest
+ * eigenvalues l_1 >= ... (diff and plain Jaccard are not Euclidean: B then has negative eigenvalues, which are never axes); axis a is
+ * reported when l_a > 1e-9 l_1, so fewer than n_axis axes may come back; an n_axis above N - 1 is N - 1.  Coordinates x_ia = v_ia
+ * sqrt(l_a); sign: the component of v_a largest in size is positive, the first one on an exact tie (near-ties are decided by rounding:
+ * compare after aligning the signs).  trace(B) = T / (2 N) 4^-F with T = the sum of q_ij^2 over i != j, an exact 128-bit sum converted
+ * with one long double division; Explained = l_a / trace(B), whose denominator is the sum of ALL eigenvalues, the negative ones
+ * included, so that it can overstate an axis' share for a metric that is not Euclidean.  The eigenpairs come from the backend's
+ * pga_pan_pcoa: Lanczos with full reorthogonalisation, start vectors from the counter (seed, i); it stops when every wanted pair has a
+ * residual <= 1e-10 l_1 or after 256 vectors (PANGENE_PCOA_STEPS lowers that for tests), and then says converged 0, prints the residuals
+ * and leaves a note on stderr; that is no error.  Floating point: two builds agree within tolerances, not byte for byte; the same call
+ * on the same build returns the same bits.
+ * Output, tab-separated: one line "# items T / metric M / N / Fbits / trace / steps / restarts / converged" as name-value fields, then
+ * "EV Axis Eigenvalue Explained Cumulative Residual" and one EV line per axis, then "PC Asm PC1 .. PCk" and one PC line per assembly;
+ * numbers %.6g, Explained and Cumulative %.4f.  N < 3 or no distance above zero: the # line, a note on stderr and no table.
+ * pg_pcoa_file: 0, -1 (the GFA file cannot be opened) or -2 (the backend's status is on stderr); pg_write_pcoa: the same for the graph
+ * in memory; errors go to pg_last_error.
+ * pg_pan_pcoa: any such matrix, int32 [n][n], with fbits fraction bits (PGA_ERR_ARG when it is not symmetric, has a diagonal entry that
+ * is not zero or a negative entry, PGA_ERR_RANGE for an entry of 2^29 or more, for n > 16 384 and for an n_axis outside 1 .. 16); of the
+ * options n_axis and seed are read.  Fills eig[n_axis], resid[n_axis], coord[n][n_axis] (row-major; the columns past the axes returned
+ * are zero), trace and info[4] = axes returned, steps, converged, restarts, and returns 0 or a negative PGA_ERR_*.
+ * pg_pan_pcoa_presence: the same for an item x assembly presence matrix [n_item][n_asm] and the distance `metric` of the options;
+ * frac_bits receives F.  sizeof(pg_pcoa_opt_t) is 16. */
+typedef struct {
+	int32_t  type;    /* PG_DIST_GENE or PG_DIST_ADJ [gene] */
+	int32_t  metric;  /* PG_DIST_JACCARD or PG_DIST_DIFF [jaccard] */
+	int32_t  n_axis;  /* axes, 1 .. 16 [3] */
+	uint32_t seed;    /* of the start vectors [0] */
+} pg_pcoa_opt_t;
+void pg_pcoa_opt_init(pg_pcoa_opt_t *o);
+int  pg_pcoa_file(const char *gfa_fn, const pg_pcoa_opt_t *o);
+void pg_write_pcoa(pg_graph_t *g, const pg_pcoa_opt_t *o);
+int  pg_pan_pcoa(const int32_t *q, int32_t n, int32_t fbits, const pg_pcoa_opt_t *o, double *eig, double *resid, double *coord, double *trace, int32_t *info);
+int  pg_pan_pcoa_presence(const uint8_t *presence, int32_t n_item, int32_t n_asm, const pg_pcoa_opt_t *o, double *eig, double *resid, double *coord, double *trace,
+                          int32_t *info, int32_t *frac_bits);
+
 /* Last error of the path (0 = none).  The reference aborts on invariant violations; this library
  * records a status instead, prints one line to stderr, and leaves the graph empty. */
 int         pg_last_error(void);

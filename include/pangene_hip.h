@@ -94,7 +94,7 @@ typedef struct {
  * Device layout limits (PGA_ERR_RANGE otherwise): coordinates inside a block < 2^31 (contigs beyond that arrive as virtual contigs,
  * see pga_genome_block_t; what remains out of reach is a single cluster of overlapping hits spanning 2^30 bp), < 2^30 hits and < 2^31
  * exons per shard, < 2^20 genes, < 2^24 genomes. */
-#define PGA_ABI_VERSION 22u /* bumped whenever a struct of this header or the order of pga_backend_t changes; pga_create refuses another */
+#define PGA_ABI_VERSION 23u /* bumped whenever a struct of this header or the order of pga_backend_t changes; pga_create refuses another */
 typedef struct {
 	uint32_t abi_version;        /* = PGA_ABI_VERSION of the header the caller was compiled against (PGA_ERR_ARG otherwise) */
 	int32_t n_genome;            /* genomes in this shard (may include genomes with 0 hits) */
@@ -648,6 +648,34 @@ typedef struct { const int32_t *n_le, *n_ge; const int64_t *sum; } pga_phylosig_
 int pga_pan_phylosig(const pga_phylosig_in_t *in, pga_phylosig_out_t *out);
 int32_t pga_phylosig_batch(int32_t n_cls);
 
+/* Principal coordinates (include/pangene_amd.h pg_pan_pcoa, pangene pcoa; DESIGN.md section 8 "Principal coordinates"): the n_axis
+ * algebraically largest eigenpairs of B = J A J, A = -1/2 d o d, d = q 2^-fbits, J = I - 11'/n, by Lanczos with full
+ * reorthogonalisation in the centred subspace.  Context-free.  B is never formed: for x orthogonal to 1, B x = A x - mean(A x) 1, and
+ * A x comes from q itself, -1/2 d^2 formed in fp64 on the fly.  The first floating-point entry: every sum has a fixed reduction tree,
+ * there is no floating-point atomic, and the same call on the same build returns the same bits.
+ * In:  q[n][n], symmetric, zero diagonal, 0 <= q < 2^29 (the caller's promise: pg_pan_pcoa checks it); seed of the counter-based start
+ *      vectors; max_step: the vectors the iteration may use in all, 1 .. 256 (<= 0: 256).  x_test, y_test, n_test: NULL, NULL, 0, or --
+ *      for tests only -- n_test <= 8 columns x_test[n][n_test] (row-major) and room for y_test[n][n_test], which receives
+ *      A x - the column means (= B x for columns orthogonal to 1) from the product kernel before the iteration starts.
+ * Out: n_axis = min(asked, n - 1, the Ritz values there are) pairs in descending order of the eigenvalue: eig[n_axis], resid[n_axis] (the
+ *      residual norm |beta s| of each pair), vec[n][n_axis] (row-major, unit columns orthogonal to 1, no sign convention); n_step (the
+ *      vectors used), n_restart (the restarts after an invariant subspace was locked) and converged (every returned pair has a residual
+ *      <= 1e-10 times the largest eigenvalue).  The arrays are page-locked, belong to the backend and stay valid until its next pan_pcoa.
+ *      Running into max_step is not an error: converged is 0 and the residuals say how far the pairs are.
+ * Limits: n >= 1, fbits in [0, 30] (PGA_ERR_ARG otherwise); n <= 16 384 and 1 <= n_axis <= 16 (PGA_ERR_RANGE, before anything is
+ * launched); an n_axis above n - 1 is n - 1.  n_test in [0, 8] (PGA_ERR_ARG otherwise). */
+typedef struct {
+	const int32_t *q;
+	int32_t n, fbits, n_axis;
+	uint32_t seed;
+	int32_t max_step;
+	const double *x_test;
+	double *y_test;
+	int32_t n_test;
+} pga_pcoa_in_t;
+typedef struct { const double *eig, *resid, *vec; int32_t n_axis, n_step, n_restart, converged; } pga_pcoa_out_t;
+int pga_pan_pcoa(const pga_pcoa_in_t *in, pga_pcoa_out_t *out);
+
 /* the same ABI as a table, so the host driver is written once */
 struct pga_branch_par_s; struct pga_loop_xchg_s;
 typedef struct {
@@ -720,6 +748,7 @@ typedef struct {
 	int  (*pan_coevo)(const pga_coevo_in_t *, pga_coevo_out_t *); /* may be NULL: the host driver then runs the same step itself */
 	int  (*post_front)(pga_ctx_t *, double, int32_t, int32_t, const int32_t **); /* may be NULL: the host driver then computes the representatives itself and calls post_apply */
 	int  (*pan_phylosig)(const pga_phylosig_in_t *, pga_phylosig_out_t *); /* may be NULL: the host driver then runs the same step itself */
+	int  (*pan_pcoa)(const pga_pcoa_in_t *, pga_pcoa_out_t *); /* may be NULL: the host driver then runs a second implementation (Jacobi on the dense B) */
 } pga_backend_t;
 
 const pga_backend_t *pga_backend(void);

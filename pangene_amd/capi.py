@@ -789,6 +789,78 @@ def pan_phylosig(lib: C.CDLL, presence, rec, method: str, gain: int = 1, loss: i
     return out
 
 
+class pg_pcoa_opt_t(C.Structure):
+    """Principal coordinates options (include/pangene_amd.h): items, distance, axes and the seed of the start vectors."""
+    _fields_ = [("type", C.c_int32), ("metric", C.c_int32), ("n_axis", C.c_int32), ("seed", C.c_uint32)]
+
+
+PCOA_MAX_AXIS = 16
+
+
+def pcoa_opt(lib: C.CDLL, type: str = "gene", metric: str = "jaccard", n_axis: int = 3, seed: int = 0) -> pg_pcoa_opt_t:
+    if type not in DIST_TYPES:
+        raise ValueError("type must be gene or adj")
+    if metric not in TREE_METRICS:
+        raise ValueError("metric must be jaccard or diff (shared is not a distance)")
+    if not 1 <= int(n_axis) <= PCOA_MAX_AXIS:
+        raise ValueError("n_axis must be in [1, 16]")
+    if not 0 <= int(seed) <= 0xFFFFFFFF:
+        raise ValueError("seed must be in [0, 2^32 - 1]")
+    o = pg_pcoa_opt_t()
+    lib.pg_pcoa_opt_init(C.byref(o))
+    o.type, o.metric, o.n_axis, o.seed = DIST_TYPES.index(type), DIST_METRICS.index(metric), int(n_axis), int(seed)
+    return o
+
+
+def _pcoa_out(n, k):
+    import numpy as np
+    out = {"eig": np.zeros(k), "resid": np.zeros(k), "coord": np.zeros((n, k)), "trace": C.c_double(0.0), "info": np.zeros(4, dtype=np.int32)}
+    ptr = [out[key].ctypes.data_as(C.POINTER(C.c_double)) for key in ("eig", "resid", "coord")] + [C.byref(out["trace"]), out["info"].ctypes.data_as(C.POINTER(C.c_int32))]
+    return out, ptr
+
+
+def _pcoa_dict(out):
+    axes, steps, converged, restarts = (int(v) for v in out["info"])
+    return {"axes": axes, "steps": steps, "converged": converged, "restarts": restarts, "trace": float(out["trace"].value), "eig": out["eig"][:axes].copy(),
+            "resid": out["resid"][:axes].copy(), "coord": out["coord"][:, :axes].copy()}
+
+
+def pan_pcoa(lib: C.CDLL, q, fbits: int = 20, n_axis: int = 3, seed: int = 0):
+    """Principal coordinates of a fixed-point distance matrix (int32 numpy array or torch tensor, shape (n, n), symmetric, zero diagonal,
+    entries in [0, 2^29), fbits fraction bits) through pg_pan_pcoa: a dict with axes (the axes returned: those above 1e-9 of the first),
+    steps, converged, restarts, trace, and float64 arrays eig (axes,), resid (axes,) and coord (n, axes).  Fewer than 3 assemblies or no
+    distance above zero: no axes."""
+    import numpy as np
+    if hasattr(q, "detach"):  # torch tensor, on any device
+        q = q.detach().cpu().numpy()
+    q = np.ascontiguousarray(q, dtype=np.int32)
+    if q.ndim != 2 or q.shape[0] != q.shape[1]:
+        raise ValueError("q must be a square matrix")
+    o = pg_pcoa_opt_t()
+    lib.pg_pcoa_opt_init(C.byref(o))
+    o.n_axis, o.seed = int(n_axis), int(seed) & 0xFFFFFFFF  # (the library checks n_axis: PGA_ERR_RANGE)
+    n, k = q.shape[0], max(int(n_axis), 1)
+    out, ptr = _pcoa_out(n, k)
+    rc = lib.pg_pan_pcoa(q.ctypes.data_as(C.POINTER(C.c_int32)), n, int(fbits), C.byref(o), *ptr)
+    if rc != 0:
+        raise RuntimeError("pg_pan_pcoa: status %d" % rc)
+    return _pcoa_dict(out)
+
+
+def pan_pcoa_presence(lib: C.CDLL, presence, metric: str = "jaccard", n_axis: int = 3, seed: int = 0):
+    """The same for an item x assembly presence matrix (bool numpy array or torch tensor, shape (M, A)) through pg_pan_pcoa_presence:
+    (the dict pan_pcoa returns, F) with the distances of `metric` in units of 2^-F."""
+    p = _presence(presence)
+    M, A = p.shape
+    o = pcoa_opt(lib, metric=metric, n_axis=n_axis, seed=seed)
+    out, ptr = _pcoa_out(A, int(n_axis))
+    F = C.c_int32(0)
+    rc = lib.pg_pan_pcoa_presence(p.ctypes.data_as(C.POINTER(C.c_uint8)), M, A, C.byref(o), *ptr, C.byref(F))
+    if rc != 0:
+        raise RuntimeError("pg_pan_pcoa_presence: status %d" % rc)
+    return _pcoa_dict(out), int(F.value)
+
+
 # ---- the long options of the analyses, as run() reads them: one table, one reader -------------------------------------------------
 # A row is one --NAME-suffix=VALUE (the head row, without a suffix, is the VALUE of --NAME=VALUE): the keyword of NAME_opt() it fills,
 # the converter (its ValueError is raised where the option stands), and a test of the last value given with the words after the option's
@@ -854,6 +926,9 @@ _ANALYSES = (
               _RECON + (_Row("min", "min_events", int, extra=True), _Row("sign", "sign", extra=True), _Row("max", "max_pair", int, extra=True)), strict=True),
     _Analysis("phylosig", phylosig_opt, "pg_write_phylosig", "--phylosig", {}, _ints(None, "n_perm", 0, TRAIT_MAX_PERM, _M_PERM), False,
               _RECON[:5] + (_Row("seed", "seed", int, extra=True), _Row("min", "min_count", int, extra=True), _Row("max-p", "max_p", float, extra=True)), strict=True),
+    _Analysis("pcoa", pcoa_opt, "pg_write_pcoa", "--pcoa", {}, _ints(None, "n_axis", 1, PCOA_MAX_AXIS, "must be in [1, 16]"), False,
+              (_words("type", "type", DIST_TYPES, _M_TYPE, extra=True), _words("metric", "metric", TREE_METRICS, _M_METRIC, extra=True), _Row("seed", "seed", int, extra=True)),
+              strict=True),
 )
 _HEADS = tuple("--" + a.name for a in _ANALYSES)
 
@@ -985,6 +1060,13 @@ _API = {
     "pg_phylosig_file": (C.c_int, [C.c_char_p, C.c_void_p]),
     "pg_write_phylosig": (None, [C.c_void_p, C.c_void_p]),
     "pg_pan_phylosig": (C.c_int, [C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "pg_pcoa_opt_init": (None, [C.c_void_p]),
+    "pg_pcoa_file": (C.c_int, [C.c_char_p, C.c_void_p]),
+    "pg_write_pcoa": (None, [C.c_void_p, C.c_void_p]),
+    "pg_pan_pcoa": (C.c_int, [C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                              C.POINTER(C.c_int32)]),
+    "pg_pan_pcoa_presence": (C.c_int, [C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                       C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "pg_pan_qtrait": (C.c_int, [C.POINTER(C.c_uint8), C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]),
     "pg_pan_trait": (C.c_int, [C.POINTER(C.c_uint8), C.POINTER(C.c_int8), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]),
     "pg_pan_pairs": (C.c_int, [C.POINTER(C.c_uint8), C.POINTER(C.c_int8), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int32)]),

@@ -187,7 +187,7 @@ static int main_call(int argc, char *argv[])
 // memory.  Both spellings, their refusals and the dispatch come from ONE table, kAnalyses below: a record per analysis, a row per option.
 // ---------------------------------------------------------------------------------------------------------------
 union AnyOpt { pg_curves_opt_t curves; pg_dist_opt_t dist; pg_assoc_opt_t assoc; pg_trait_opt_t trait; pg_tree_opt_t tree; pg_qtrait_opt_t qtrait;
-	pg_cluster_opt_t cluster; pg_permanova_opt_t permanova; pg_mantel_opt_t mantel; pg_gainloss_opt_t gainloss; pg_coevo_opt_t coevo; pg_phylosig_opt_t phylosig; };
+	pg_cluster_opt_t cluster; pg_permanova_opt_t permanova; pg_mantel_opt_t mantel; pg_gainloss_opt_t gainloss; pg_coevo_opt_t coevo; pg_phylosig_opt_t phylosig; pg_pcoa_opt_t pcoa; };
 
 struct Word { const char *s; int32_t v; };
 static const Word W_TYPE[] = { { "gene", PG_DIST_GENE }, { "adj", PG_DIST_ADJ }, { nullptr, 0 } };
@@ -488,6 +488,21 @@ static const Analysis kAnalyses[] = {
 	    plain('s', "seed", rd_u32, offsetof(pg_phylosig_opt_t, seed), "must be in [0, 4294967295]", true),
 	    i32('c', "min", offsetof(pg_phylosig_opt_t, min_count), 1, INT31, M_MIN1, true),
 	    plain('p', "max-p", rd_nonneg, offsetof(pg_phylosig_opt_t, max_p), "must be a number >= 0", true) } },
+	// (like phylosig: not in usage() until the transcript is recorded again)
+	{ "pcoa", "--pcoa", false, HEAD_ROW0, nullptr, 0, false, calls<pg_pcoa_opt_t, pg_pcoa_opt_init, pg_pcoa_file, pg_write_pcoa>(),
+	  [](const AnyOpt &o) {
+		std::printf("Usage: pangene pcoa [options] <in.gfa>\n       pangene --pcoa[=INT] [--pcoa-NAME=VALUE ...] <in.paf> [...]   (INT: -k; NAME in parentheses below)\nOptions:\n"
+		            "  -t STR   (type) items: gene (gene content) or adj (gene adjacencies of the walks) [gene]\n"
+		            "  -m STR   (metric) distance: jaccard or diff [jaccard]\n"
+		            "  -k INT   (--pcoa=INT) axes, 1 to 16; an axis is printed when its eigenvalue is above 1e-9 of the first [%d]\n"
+		            "  -s INT   (seed) seed of the start vectors of the iteration [%u]\n"
+		            "Principal coordinates (classical scaling) of the assemblies: EV lines, one per axis, then PC lines, one per assembly.\n"
+		            "Explained = eigenvalue / trace, and the trace sums all eigenvalues, the negative ones included: for a distance that is\n"
+		            "not Euclidean (diff, plain jaccard) it can overstate an axis' share.\n", o.pcoa.n_axis, o.pcoa.seed); },
+	  { i32('k', nullptr, offsetof(pg_pcoa_opt_t, n_axis), 1, 16, "must be in [1, 16]"),
+	    word('t', "type", offsetof(pg_pcoa_opt_t, type), W_TYPE, M_TYPE, true),
+	    word('m', "metric", offsetof(pg_pcoa_opt_t, metric), W_METRIC, M_METRIC, true),
+	    plain('s', "seed", rd_u32, offsetof(pg_pcoa_opt_t, seed), "must be in [0, 4294967295]", true) } },
 };
 enum { N_ANALYSES = sizeof(kAnalyses) / sizeof(kAnalyses[0]) };
 
@@ -567,7 +582,7 @@ static bool long_option(int code, const char *arg, Parsed *parsed) // false: ref
 		p.asked = true;
 		if (a.head_value == HEAD_FILE) p.side = arg;
 		if (a.head_value == HEAD_FILE) return true;
-		if (arg == nullptr && (arg = a.bare) == nullptr) return true; // (a later --curves, --dist or --tree without a value is the default again; --assoc, --gainloss, --coevo and --phylosig keep what an earlier one said)
+		if (arg == nullptr && (arg = a.bare) == nullptr) return true; // (a later --curves, --dist or --tree without a value is the default again; --assoc, --gainloss, --coevo, --phylosig and --pcoa keep what an earlier one said)
 	} else {
 		if (r->extra) p.extra = true;
 		if (r->no_file) p.no_file = r;

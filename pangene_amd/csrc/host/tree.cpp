@@ -8,6 +8,7 @@
 //   pan_gainloss.hpp   pangene gainloss (with pan_treeprog.hpp: the records as a tree and as the backend's program, shared with trait.cpp)
 //   pan_coevo.hpp      pangene coevo (the reconstruction and the program are pan_gainloss.hpp's)
 //   pan_phylosig.hpp   pangene phylosig (the observed costs and the way up are pan_gainloss.hpp's)
+//   pan_pcoa.hpp       pangene pcoa (floating point: the exact trace uses pan_permanova.hpp's ratio)
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -28,3 +29,4 @@ using namespace pgx;
 #include "pan_gainloss.hpp"
 #include "pan_coevo.hpp"
 #include "pan_phylosig.hpp"
+#include "pan_pcoa.hpp"
