@@ -643,6 +643,49 @@ int  pg_pan_pcoa(const int32_t *q, int32_t n, int32_t fbits, const pg_pcoa_opt_t
 int  pg_pan_pcoa_presence(const uint8_t *presence, int32_t n_item, int32_t n_asm, const pg_pcoa_opt_t *o, double *eig, double *resid, double *coord, double *trace,
                           int32_t *info, int32_t *frac_bits);
 
+/* Gene-trait tests adjusted for population structure: the Rao score test of every gene against a trait, with the principal coordinates
+ * of pg_pcoa_* as covariates -- what a fixed-effects GWAS does with its principal components.  DESIGN.md section 8 "Structure-adjusted
+ * association" holds the definition.  A screening test: one null fit per trait, one matrix product for all genes, no per-gene fit.
+ * For a trait, N = the assemblies with a value and Z = [1, z_1 .. z_k] over them: the n_axis axes pcoa_core returns for ALL assemblies
+ * (distance of `type` and `metric`, start vectors from `seed`), each divided by sqrt(eigenvalue / assemblies); fewer when fewer come
+ * back, none for n_axis = 0.  Null model: PG_GLM_BINARY, logistic regression of y on Z by Newton steps from (logit mean(y), 0 ..),
+ * the step halved up to 10 times while the log-likelihood falls, converged when the largest change of a coefficient is <= 1e-9, at
+ * most 30 iterations; Fit 0 (a note, no gene lines) when the cap is reached, when any |eta_i| > 30 at convergence (separation) or when
+ * the Cholesky factorisation fails; r = y - mu, w = mu (1 - mu).  PG_GLM_QUANT, least squares: s2 = RSS / (N - k - 1), r = (y - mu) / s2,
+ * w = 1 / s2.  A trait with N < k + 3 or one value only is skipped with a note.  Per gene with presence x over the N assemblies:
+ * a = sum x, U = x.r, s_w = x.w, b = (s_w, x.(w z_1) ..), V = s_w - |L^-1 b|^2 with L the Cholesky factor of Z'WZ.  A gene is eligible
+ * when min(a, N - a) >= min_count, collinear when V <= 1e-8 s_w (printed with NA, left out of q and Lambda); otherwise Beta = U / V (the
+ * exact least-squares coefficient for quant, the ONE-STEP estimate for binary), SE = 1 / sqrt(V), Z = U / sqrt(V), p = erfc(|Z| /
+ * sqrt 2), q = Benjamini-Hochberg per trait over the tested genes, Lambda = median(Z^2) / 0.4549364 per trait.
+ * Output, tab-separated, numbers %.6g: "# items / metric / A / Fbits / axes / family / converged" as name-value fields; "T Trait N
+ * Cases|Mean Iter Fit Tested Collinear Lambda" and one T line per trait that was not skipped; "G Trait Gene N a Beta SE Z p q" and one G
+ * line per eligible gene with p <= max_p (and per collinear one).  Floating point: two builds agree within tolerances, not byte for
+ * byte; the same call on the same build returns the same bits.
+ * pg_glm_file: 0, -1 (the GFA file cannot be opened), -2 (the backend's status is on stderr) or -3 (the trait file was turned down);
+ * pg_write_glm: the same for the graph in memory; errors go to pg_last_error.
+ * pg_pan_glm: any presence matrix uint8 [n_gene][n_asm], values double [n_trait][n_asm] (NaN = missing; 0 and 1 for PG_GLM_BINARY) and
+ * explicit covariates double [n_asm][n_cov] (NULL with n_cov = 0), used as they are; of the options min_count is read.  Fills
+ * out[n_trait][n_gene][4] = a, U, V, s_w (a = -1 and zeros for a gene that is not eligible or a trait without a fit) and
+ * info[n_trait][4] = N, iterations, fit, tested, and returns 0 or a negative PGA_ERR_*: PGA_ERR_RANGE for n_cov > 13 or n_asm > 16 384,
+ * PGA_ERR_ARG for an infinite value, a binary value that is not 0 or 1, or a covariate that is not finite.
+ * sizeof(pg_glm_opt_t) is 32. */
+#define PG_GLM_BINARY 0
+#define PG_GLM_QUANT  1
+typedef struct {
+	int32_t  type;      /* of the distance: PG_DIST_GENE or PG_DIST_ADJ [gene] (the items tested are the genes) */
+	int32_t  metric;    /* PG_DIST_JACCARD or PG_DIST_DIFF [jaccard] */
+	int32_t  family;    /* PG_GLM_BINARY or PG_GLM_QUANT [binary] */
+	int32_t  n_axis;    /* axes used as covariates, 0 .. 13; 0: intercept only [3] */
+	uint32_t seed;      /* of the start vectors of the axes [0] */
+	int32_t  min_count; /* a gene is tested when min(a, N - a) >= min_count [1] */
+	double   max_p;     /* genes with p <= max_p are printed [1] */
+} pg_glm_opt_t;
+void pg_glm_opt_init(pg_glm_opt_t *o);
+int  pg_glm_file(const char *gfa_fn, const char *trait_fn, const pg_glm_opt_t *o);
+void pg_write_glm(pg_graph_t *g, const char *trait_fn, const pg_glm_opt_t *o);
+int  pg_pan_glm(const uint8_t *presence, const double *values, int32_t n_gene, int32_t n_asm, int32_t n_trait, const double *covariates, int32_t n_cov, int32_t family,
+                const pg_glm_opt_t *o, double *out, int32_t *info);
+
 /* Last error of the path (0 = none).  The reference aborts on invariant violations; this library
  * records a status instead, prints one line to stderr, and leaves the graph empty. */
 int         pg_last_error(void);

@@ -94,7 +94,7 @@ typedef struct {
  * Device layout limits (PGA_ERR_RANGE otherwise): coordinates inside a block < 2^31 (contigs beyond that arrive as virtual contigs,
  * see pga_genome_block_t; what remains out of reach is a single cluster of overlapping hits spanning 2^30 bp), < 2^30 hits and < 2^31
  * exons per shard, < 2^20 genes, < 2^24 genomes. */
-#define PGA_ABI_VERSION 23u /* bumped whenever a struct of this header or the order of pga_backend_t changes; pga_create refuses another */
+#define PGA_ABI_VERSION 24u /* bumped whenever a struct of this header or the order of pga_backend_t changes; pga_create refuses another */
 typedef struct {
 	uint32_t abi_version;        /* = PGA_ABI_VERSION of the header the caller was compiled against (PGA_ERR_ARG otherwise) */
 	int32_t n_genome;            /* genomes in this shard (may include genomes with 0 hits) */
@@ -676,6 +676,29 @@ typedef struct {
 typedef struct { const double *eig, *resid, *vec; int32_t n_axis, n_step, n_restart, converged; } pga_pcoa_out_t;
 int pga_pan_pcoa(const pga_pcoa_in_t *in, pga_pcoa_out_t *out);
 
+/* Structure-adjusted association (include/pangene_amd.h pg_pan_glm, pangene glm; DESIGN.md section 8 "Structure-adjusted association"):
+ * the score statistics of every gene against every trait whose null model the host has fitted.  Context-free.  Floating point, fp64
+ * throughout: S = X . cols on the fp64 matrix cores (v_mfma_f64_16x16x4_f64), no floating-point atomic, partial sums of fixed segments
+ * added in a fixed order; the same call on the same build returns the same bits.
+ * In:  bits[n_gene][W], gene-major, W = ceil(n_asm / 32), the bits past n_asm zero (the caller's promise).  cols[n_trait][n_asm][16]:
+ *      per trait and assembly 16 doubles (128 bytes) -- column 0 valid (1.0 or 0.0), 1 r, 2 w, 3 .. 2 + n_cov w z_j, the rest zero, the
+ *      whole row zero for an assembly without a value: that is how a missing value is handled, the bit rows are never compacted.
+ *      chol[n_trait][(n_cov + 1)^2]: the Cholesky factor L of Z'WZ, row-major, lower triangle.  sums_test: NULL, or -- for tests only --
+ *      room for [n_trait][n_gene][16] doubles, which receive the raw sums S.
+ * Out: a[n_trait][n_gene] = S_0 (the carriers among the assemblies with a value, an exact integer), u = S_1, sw = S_2 and
+ *      v = sw - |L^-1 (S_2 .. S_{2 + n_cov})|^2 by forward substitution in ascending order.  The arrays are page-locked, belong to the
+ *      backend and stay valid until its next pan_glm.
+ * Limits: counts >= 0 (PGA_ERR_ARG otherwise); n_asm <= 16 384, n_cov <= 13, n_gene < 2^24, n_trait <= 4 096 (PGA_ERR_RANGE, before
+ * anything is launched). */
+typedef struct {
+	const uint32_t *bits;
+	const double *cols, *chol;
+	int32_t n_gene, n_asm, n_trait, n_cov;
+	double *sums_test;
+} pga_glm_in_t;
+typedef struct { const int32_t *a; const double *u, *v, *sw; } pga_glm_out_t;
+int pga_pan_glm(const pga_glm_in_t *in, pga_glm_out_t *out);
+
 /* the same ABI as a table, so the host driver is written once */
 struct pga_branch_par_s; struct pga_loop_xchg_s;
 typedef struct {
@@ -749,6 +772,7 @@ typedef struct {
 	int  (*post_front)(pga_ctx_t *, double, int32_t, int32_t, const int32_t **); /* may be NULL: the host driver then computes the representatives itself and calls post_apply */
 	int  (*pan_phylosig)(const pga_phylosig_in_t *, pga_phylosig_out_t *); /* may be NULL: the host driver then runs the same step itself */
 	int  (*pan_pcoa)(const pga_pcoa_in_t *, pga_pcoa_out_t *); /* may be NULL: the host driver then runs a second implementation (Jacobi on the dense B) */
+	int  (*pan_glm)(const pga_glm_in_t *, pga_glm_out_t *); /* may be NULL: the host driver then runs a second implementation (the set bits walked in fp64) */
 } pga_backend_t;
 
 const pga_backend_t *pga_backend(void);

@@ -861,6 +861,80 @@ def pan_pcoa_presence(lib: C.CDLL, presence, metric: str = "jaccard", n_axis: in
     return _pcoa_dict(out), int(F.value)
 
 
+class pg_glm_opt_t(C.Structure):
+    """Structure-adjusted association options (include/pangene_amd.h): the distance of the axes, the family, the axes, their seed, the filters."""
+    _fields_ = [("type", C.c_int32), ("metric", C.c_int32), ("family", C.c_int32), ("n_axis", C.c_int32), ("seed", C.c_uint32), ("min_count", C.c_int32),
+                ("max_p", C.c_double)]
+
+
+GLM_FAMILIES = ("binary", "quant")
+GLM_MAX_AXIS = 13
+
+
+def glm_opt(lib: C.CDLL, family: str = "binary", n_axis: int = 3, type: str = "gene", metric: str = "jaccard", seed: int = 0, min_count: int = 1,
+            max_p: float = 1.0) -> pg_glm_opt_t:
+    if family not in GLM_FAMILIES:
+        raise ValueError("family must be binary or quant")
+    if not 0 <= int(n_axis) <= GLM_MAX_AXIS:
+        raise ValueError("n_axis must be in [0, 13]")
+    if type not in DIST_TYPES:
+        raise ValueError("type must be gene or adj")
+    if metric not in TREE_METRICS:
+        raise ValueError("metric must be jaccard or diff (shared is not a distance)")
+    if not 0 <= int(seed) <= 0xFFFFFFFF:
+        raise ValueError("seed must be in [0, 2^32 - 1]")
+    if int(min_count) < 1:
+        raise ValueError("min_count must be at least 1")
+    if not float(max_p) >= 0.0:
+        raise ValueError("max_p must be a number >= 0")
+    o = pg_glm_opt_t()
+    lib.pg_glm_opt_init(C.byref(o))
+    o.type, o.metric, o.family, o.n_axis = DIST_TYPES.index(type), DIST_METRICS.index(metric), GLM_FAMILIES.index(family), int(n_axis)
+    o.seed, o.min_count, o.max_p = int(seed), int(min_count), float(max_p)
+    return o
+
+
+def pan_glm(lib: C.CDLL, presence, values, covariates=None, family: str = "binary", min_count: int = 1):
+    """Score statistics of every gene of a presence matrix (bool numpy array or torch tensor, shape (G, A)) against the traits `values`
+    (float64, shape (T, A), NaN = missing; 0 and 1 for the binary family) given explicit covariates (float64, shape (A, k), k <= 13, or
+    None) through pg_pan_glm: a dict of arrays a (T, G; -1 = not eligible), U, V, s_w (T, G) and N, iterations, fit, tested (T,)."""
+    import numpy as np
+    p = _presence(presence)
+    G, A = p.shape
+    if hasattr(values, "detach"):
+        values = values.detach().cpu().numpy()
+    v = np.ascontiguousarray(values, dtype=np.float64)
+    if v.ndim == 1:
+        v = v.reshape(1, -1)
+    if v.ndim != 2 or v.shape[1] != A:
+        raise ValueError("values must have one column per assembly")
+    T = v.shape[0]
+    if covariates is None:
+        cov, k = np.zeros((A, 0)), 0
+    else:
+        if hasattr(covariates, "detach"):
+            covariates = covariates.detach().cpu().numpy()
+        cov = np.ascontiguousarray(covariates, dtype=np.float64)
+        if cov.ndim == 1:
+            cov = cov.reshape(-1, 1)
+        if cov.ndim != 2 or cov.shape[0] != A:
+            raise ValueError("covariates must have one row per assembly")
+        k = cov.shape[1]
+    if family not in GLM_FAMILIES:
+        raise ValueError("family must be binary or quant")
+    o = pg_glm_opt_t()
+    lib.pg_glm_opt_init(C.byref(o))
+    o.min_count = int(min_count)
+    out, info = np.zeros((T, G, 4)), np.zeros((T, 4), dtype=np.int32)
+    rc = lib.pg_pan_glm(p.ctypes.data_as(C.POINTER(C.c_uint8)), v.ctypes.data_as(C.POINTER(C.c_double)), G, A, T,
+                        cov.ctypes.data_as(C.POINTER(C.c_double)) if k else None, k, GLM_FAMILIES.index(family), C.byref(o),
+                        out.ctypes.data_as(C.POINTER(C.c_double)), info.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc != 0:
+        raise RuntimeError("pg_pan_glm: status %d" % rc)
+    return {"a": out[:, :, 0].astype(np.int64), "U": out[:, :, 1].copy(), "V": out[:, :, 2].copy(), "s_w": out[:, :, 3].copy(), "N": info[:, 0].copy(),
+            "iterations": info[:, 1].copy(), "fit": info[:, 2].copy(), "tested": info[:, 3].copy()}
+
+
 # ---- the long options of the analyses, as run() reads them: one table, one reader -------------------------------------------------
 # A row is one --NAME-suffix=VALUE (the head row, without a suffix, is the VALUE of --NAME=VALUE): the keyword of NAME_opt() it fills,
 # the converter (its ValueError is raised where the option stands), and a test of the last value given with the words after the option's
@@ -929,6 +1003,10 @@ _ANALYSES = (
     _Analysis("pcoa", pcoa_opt, "pg_write_pcoa", "--pcoa", {}, _ints(None, "n_axis", 1, PCOA_MAX_AXIS, "must be in [1, 16]"), False,
               (_words("type", "type", DIST_TYPES, _M_TYPE, extra=True), _words("metric", "metric", TREE_METRICS, _M_METRIC, extra=True), _Row("seed", "seed", int, extra=True)),
               strict=True),
+    _Analysis("glm", glm_opt, "pg_write_glm", "--glm=FILE", None, None, True,
+              (_words("family", "family", GLM_FAMILIES, "must be binary or quant", extra=True), _ints("axes", "n_axis", 0, GLM_MAX_AXIS, "must be in [0, 13]", extra=True),
+               _words("type", "type", DIST_TYPES, _M_TYPE, extra=True), _words("metric", "metric", TREE_METRICS, _M_METRIC, extra=True), _Row("seed", "seed", int, extra=True),
+               _Row("min", "min_count", int, extra=True), _Row("max-p", "max_p", float, extra=True)), strict=True),
 )
 _HEADS = tuple("--" + a.name for a in _ANALYSES)
 
@@ -1067,6 +1145,11 @@ _API = {
                               C.POINTER(C.c_int32)]),
     "pg_pan_pcoa_presence": (C.c_int, [C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                        C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "pg_glm_opt_init": (None, [C.c_void_p]),
+    "pg_glm_file": (C.c_int, [C.c_char_p, C.c_char_p, C.c_void_p]),
+    "pg_write_glm": (None, [C.c_void_p, C.c_char_p, C.c_void_p]),
+    "pg_pan_glm": (C.c_int, [C.POINTER(C.c_uint8), C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_void_p,
+                             C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     "pg_pan_qtrait": (C.c_int, [C.POINTER(C.c_uint8), C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]),
     "pg_pan_trait": (C.c_int, [C.POINTER(C.c_uint8), C.POINTER(C.c_int8), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]),
     "pg_pan_pairs": (C.c_int, [C.POINTER(C.c_uint8), C.POINTER(C.c_int8), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int32)]),

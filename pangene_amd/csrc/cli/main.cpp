@@ -187,7 +187,7 @@ static int main_call(int argc, char *argv[])
 // memory.  Both spellings, their refusals and the dispatch come from ONE table, kAnalyses below: a record per analysis, a row per option.
 // ---------------------------------------------------------------------------------------------------------------
 union AnyOpt { pg_curves_opt_t curves; pg_dist_opt_t dist; pg_assoc_opt_t assoc; pg_trait_opt_t trait; pg_tree_opt_t tree; pg_qtrait_opt_t qtrait;
-	pg_cluster_opt_t cluster; pg_permanova_opt_t permanova; pg_mantel_opt_t mantel; pg_gainloss_opt_t gainloss; pg_coevo_opt_t coevo; pg_phylosig_opt_t phylosig; pg_pcoa_opt_t pcoa; };
+	pg_cluster_opt_t cluster; pg_permanova_opt_t permanova; pg_mantel_opt_t mantel; pg_gainloss_opt_t gainloss; pg_coevo_opt_t coevo; pg_phylosig_opt_t phylosig; pg_pcoa_opt_t pcoa; pg_glm_opt_t glm; };
 
 struct Word { const char *s; int32_t v; };
 static const Word W_TYPE[] = { { "gene", PG_DIST_GENE }, { "adj", PG_DIST_ADJ }, { nullptr, 0 } };
@@ -198,6 +198,7 @@ static const Word W_SIGN[] = { { "both", PG_ASSOC_BOTH }, { "pos", PG_ASSOC_POS 
 static const Word W_LINEAGE[] = { { "nj", PG_LINEAGE_NJ }, { "upgma", PG_LINEAGE_UPGMA }, { nullptr, 0 } };
 static const Word W_MODE[] = { { "late", PG_GAINLOSS_LATE }, { "early", PG_GAINLOSS_EARLY }, { nullptr, 0 } };
 static const Word W_OUT[] = { { "gene", PG_GAINLOSS_GENE }, { "node", PG_GAINLOSS_NODE }, { nullptr, 0 } };
+static const Word W_FAMILY[] = { { "binary", PG_GLM_BINARY }, { "quant", PG_GLM_QUANT }, { nullptr, 0 } };
 
 struct Row;
 typedef bool (*Reader)(const char *s, void *field, const Row &r); // false: not a value of this option
@@ -503,6 +504,28 @@ static const Analysis kAnalyses[] = {
 	    word('t', "type", offsetof(pg_pcoa_opt_t, type), W_TYPE, M_TYPE, true),
 	    word('m', "metric", offsetof(pg_pcoa_opt_t, metric), W_METRIC, M_METRIC, true),
 	    plain('s', "seed", rd_u32, offsetof(pg_pcoa_opt_t, seed), "must be in [0, 4294967295]", true) } },
+	// (like phylosig and pcoa: not in usage() until the transcript is recorded again)
+	{ "glm", "--glm=FILE", true, HEAD_FILE, nullptr, 't', false, calls_side<pg_glm_opt_t, pg_glm_opt_init, pg_glm_file, pg_write_glm>(),
+	  [](const AnyOpt &o) {
+		std::printf("Usage: pangene glm -t FILE [options] <in.gfa>\n       pangene --glm=FILE [--glm-NAME=VALUE ...] <in.paf> [...]   (NAME in parentheses below)\nOptions:\n"
+		            "  -t FILE   traits: a header line (any first field, one name per trait), then per line an assembly and a value or NA per trait\n"
+		            "  -y STR    (family) binary (values 1 and 0, logistic null model) or quant (numbers, least squares) [binary]\n"
+		            "  -k INT    (axes) principal coordinates used as covariates, 0 to 13; 0: intercept only [%d]\n"
+		            "  -T STR    (type) items of the distance: gene or adj [gene]; the items tested are the genes\n"
+		            "  -m STR    (metric) distance: jaccard or diff [jaccard]\n"
+		            "  -s INT    (seed) seed of the start vectors of the axes [%u]\n"
+		            "  -c INT    (min) test genes with at least INT assemblies on either side [%d]\n"
+		            "  -p FLOAT  (max-p) print genes with p <= FLOAT [%g]\n"
+		            "Score test of every gene against each trait, adjusted for the axes of pangene pcoa: T lines, one per trait (Lambda is the\n"
+		            "genomic inflation), then G lines.  A screening test: Beta is the one-step estimate for binary traits, and the axes adjust\n"
+		            "for the structure the distance shows and for no other.\n", o.glm.n_axis, o.glm.seed, o.glm.min_count, o.glm.max_p); },
+	  { word('y', "family", offsetof(pg_glm_opt_t, family), W_FAMILY, "must be binary or quant", true),
+	    i32('k', "axes", offsetof(pg_glm_opt_t, n_axis), 0, 13, "must be in [0, 13]", true),
+	    word('T', "type", offsetof(pg_glm_opt_t, type), W_TYPE, M_TYPE, true),
+	    word('m', "metric", offsetof(pg_glm_opt_t, metric), W_METRIC, M_METRIC, true),
+	    plain('s', "seed", rd_u32, offsetof(pg_glm_opt_t, seed), "must be in [0, 4294967295]", true),
+	    i32('c', "min", offsetof(pg_glm_opt_t, min_count), 1, INT31, M_MIN1, true),
+	    plain('p', "max-p", rd_nonneg, offsetof(pg_glm_opt_t, max_p), "must be a number >= 0", true) } },
 };
 enum { N_ANALYSES = sizeof(kAnalyses) / sizeof(kAnalyses[0]) };
 

@@ -249,6 +249,9 @@ int tree_joins(const std::vector<uint32_t> &bits, int32_t M, int32_t A, int32_t 
 // assemblies asm_name; 0, or -1 with a message (the line number in it) on stderr
 struct Traits { std::vector<std::string> name; std::vector<int8_t> lab; };
 int read_traits(const char *fn, const std::vector<std::string> &asm_name, Traits &tr);
+// the quantitative traits of such a file (trait.cpp; pangene qtrait and pangene glm read them): val[T][A], NaN = missing
+struct QTraits { std::vector<std::string> name; std::vector<double> val; };
+int read_qtraits(const char *fn, const std::vector<std::string> &asm_name, QTraits &tr);
 
 double now_sec();
 const char *stamp();

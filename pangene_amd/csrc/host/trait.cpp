@@ -243,8 +243,6 @@ double binom_two_sided(const std::vector<double> &lf, int32_t k, int32_t n)
 	return p < 1.0 ? p : 1.0;
 }
 
-struct QTraits { std::vector<std::string> name; std::vector<double> val; }; // val[T][A], NaN = missing
-
 std::vector<std::string> split_tab(const std::string &s)
 {
 	std::vector<std::string> f;
@@ -316,12 +314,16 @@ bool qtrait_value(const std::string &v, double &x)
 	return true;
 }
 
+} // namespace
+
 int read_qtraits(const char *fn, const std::vector<std::string> &asm_name, QTraits &tr)
 {
 	const size_t A = asm_name.size();
 	return read_trait_file(fn, asm_name, tr.name, "a finite number or NA", [&](size_t T) { tr.val.assign(T * A, std::nan("")); },
 	                       [&](size_t j, size_t c, const std::string &v) { return qtrait_value(v, tr.val[j * A + c]); });
 }
+
+namespace {
 
 // PANGENE_TRAIT_TIMING=1: one line on stderr per call
 void report_time(const char *route, int32_t G, int32_t A, size_t T, int32_t n, double t_all)

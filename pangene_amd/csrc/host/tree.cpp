@@ -9,6 +9,7 @@
 //   pan_coevo.hpp      pangene coevo (the reconstruction and the program are pan_gainloss.hpp's)
 //   pan_phylosig.hpp   pangene phylosig (the observed costs and the way up are pan_gainloss.hpp's)
 //   pan_pcoa.hpp       pangene pcoa (floating point: the exact trace uses pan_permanova.hpp's ratio)
+//   pan_glm.hpp        pangene glm (the axes are pan_pcoa.hpp's pcoa_core, the trait files trait.cpp's readers)
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -30,3 +31,4 @@ using namespace pgx;
 #include "pan_coevo.hpp"
 #include "pan_phylosig.hpp"
 #include "pan_pcoa.hpp"
+#include "pan_glm.hpp"
