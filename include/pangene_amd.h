@@ -686,6 +686,45 @@ void pg_write_glm(pg_graph_t *g, const char *trait_fn, const pg_glm_opt_t *o);
 int  pg_pan_glm(const uint8_t *presence, const double *values, int32_t n_gene, int32_t n_asm, int32_t n_trait, const double *covariates, int32_t n_cov, int32_t family,
                 const pg_glm_opt_t *o, double *out, int32_t *info);
 
+/* Gain and loss rates: `pangene rates`, `pangene --rates`.  The likelihood counterpart of pg_gainloss_*: a two-state Markov model
+ * (gain rate lambda, 0 -> 1; loss rate mu, 1 -> 0) per item on the tree of the assemblies with its branch lengths, corrected for the
+ * items nobody can observe, fitted by maximum likelihood.  DESIGN.md section 8 "Gain and loss rates" holds the definition.  Items and
+ * tree are exactly those of pg_gainloss_* (type, metric, method); the branch lengths are those `pangene tree` prints (NJ's root sits in
+ * the middle of the closing record's third branch), negative ones count as 0, and they are divided by their sum T and floored at 2^-20:
+ * the rates are per item over the whole tree.  gain = loss = 0: the rates are fitted by a deterministic lattice search in
+ * (log2 lambda, log2 mu); both > 0 (each in [1e-9, 1e9]): they are given and nothing is fitted; one without the other: PGA_ERR_ARG.
+ * At the rates every item gets its log-likelihood lnL = ln L - ln(1 - L_absent), the posterior expected Gains and Losses -- the expected
+ * numbers of branches with the item absent at the top and present at the bottom, and the reverse; NOT the expected numbers of events
+ * along the branches, which are larger -- the posterior of the root, and a screening of nine rate multipliers r = 2^-4 .. 2^4: Rate =
+ * the r with the largest lnL, LRT = 2 (lnL(Rate) - lnL(1)), p_rate = erfc(sqrt(LRT / 2)): the best of nine multipliers, not a maximum.
+ * Output, tab-separated, numbers as %.6g.  The column header first, then one line "#" with items, metric, method, A, G (the items
+ * used), gain, loss, lnL, rounds, converged and treelen (T in distance units) as NAME=VALUE fields.  out = PG_GAINLOSS_GENE:
+ * "Gene Present lnL Gains Losses Changes Root Rate LRT p_rate", one line per item present somewhere with Changes = Gains + Losses >=
+ * min_changes.  PG_GAINLOSS_NODE: "Node Child1 Child2 Leaves Length Present Gains Losses", the nodes named and ordered as
+ * pg_gainloss_* does, Length normalised, the three sums over the items, NA for the root's Gains and Losses.  Fewer than two assemblies,
+ * no items, or a tree without length: the header only, a note on stderr, status 0.
+ * pg_rates_file: 0, -1 (the GFA file cannot be opened) or -2 (bad options, or the backend's status on stderr).  pg_write_rates: the same
+ * for the graph in memory; errors go to pg_last_error.
+ * pg_pan_rates: any presence matrix [n_item][n_asm] and any tree as records, as for pg_pan_gainloss, with the same refusals; of the
+ * options gain and loss are read.  Fills fit_out[6] = lambda, mu, lnL, rounds, converged, T in record units; gene_out[n_item][7] = lnL,
+ * gains, losses, root, rate, LRT, p_rate (NaN for an item absent from every assembly, which is left out of the fit and the totals);
+ * node_out[2 n_asm - 1][4] = length (normalised), present, gains, losses in node id order.  Without a model (n_asm < 2, T = 0, no item
+ * present anywhere) it returns 0 with NaN rates.  The likelihoods and posteriors come from the backend's pga_pan_rates.
+ * sizeof(pg_rates_opt_t) is 40. */
+typedef struct {
+	int32_t type;        /* PG_DIST_GENE or PG_DIST_ADJ [gene] */
+	int32_t metric;      /* PG_DIST_JACCARD or PG_DIST_DIFF [jaccard] */
+	int32_t method;      /* PG_TREE_UPGMA or PG_TREE_NJ [upgma] */
+	int32_t out;         /* PG_GAINLOSS_GENE or PG_GAINLOSS_NODE [gene] */
+	double gain, loss;   /* the rates, both given or both 0 = fitted [0, 0] */
+	double min_changes;  /* the gene table keeps the items with Changes >= min_changes [0: all] */
+} pg_rates_opt_t;
+void pg_rates_opt_init(pg_rates_opt_t *o);
+int  pg_rates_file(const char *gfa_fn, const pg_rates_opt_t *o);
+void pg_write_rates(pg_graph_t *g, const pg_rates_opt_t *o);
+int  pg_pan_rates(const uint8_t *presence, int32_t n_item, int32_t n_asm, const int64_t *rec, int32_t method, const pg_rates_opt_t *o, double *fit_out, double *gene_out,
+                  double *node_out);
+
 /* Last error of the path (0 = none).  The reference aborts on invariant violations; this library
  * records a status instead, prints one line to stderr, and leaves the graph empty. */
 int         pg_last_error(void);

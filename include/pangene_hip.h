@@ -94,7 +94,7 @@ typedef struct {
  * Device layout limits (PGA_ERR_RANGE otherwise): coordinates inside a block < 2^31 (contigs beyond that arrive as virtual contigs,
  * see pga_genome_block_t; what remains out of reach is a single cluster of overlapping hits spanning 2^30 bp), < 2^30 hits and < 2^31
  * exons per shard, < 2^20 genes, < 2^24 genomes. */
-#define PGA_ABI_VERSION 24u /* bumped whenever a struct of this header or the order of pga_backend_t changes; pga_create refuses another */
+#define PGA_ABI_VERSION 25u /* bumped whenever a struct of this header or the order of pga_backend_t changes; pga_create refuses another */
 typedef struct {
 	uint32_t abi_version;        /* = PGA_ABI_VERSION of the header the caller was compiled against (PGA_ERR_ARG otherwise) */
 	int32_t n_genome;            /* genomes in this shard (may include genomes with 0 hits) */
@@ -699,6 +699,44 @@ typedef struct {
 typedef struct { const int32_t *a; const double *u, *v, *sw; } pga_glm_out_t;
 int pga_pan_glm(const pga_glm_in_t *in, pga_glm_out_t *out);
 
+/* Gain and loss rates (include/pangene_amd.h pg_pan_rates, pangene rates; DESIGN.md section 8 "Gain and loss rates"): the likelihood of
+ * every item under a two-state Markov model on the tree, for a batch of parameter sets, and for set 0 the posterior gains, losses and
+ * presence.  Context-free, fp64 throughout, over pan_gainloss's postfix program.  The device sees tables only: the host has turned rates
+ * and branch lengths into transition probabilities, and no kernel takes an exponential, a logarithm or divides by a rate.
+ * Up: a leaf with bit b has in = (1 - b, b); a join has in_v(a) = the product over its two children c of P^c_a0 in_c(0) + P^c_a1 in_c(1);
+ * L = pi_0 in_root(0) + pi_1 in_root(1).  After every join both values are divided by 2^e, e the binary exponent (frexp) of the larger
+ * one, which is exact, and the exponents add up: L = lik_m 2^lik_e never leaves the range of the pair.
+ * Down (post = 1, set 0): out_root = pi; for a child c of v with sibling d, O(a) = out_v(a) (P^d_a0 in_d(0) + P^d_a1 in_d(1)),
+ * J(a, b) = O(a) P^c_ab in_c(b), out_c(b) = O(0) P^c_0b + O(1) P^c_1b, Z = the sum of J; present_c = (J01 + J11) / Z, gain_c = J01 / Z,
+ * loss_c = J10 / Z (all 0 when Z = 0); at the root present = pi_1 in(1) / L.
+ * In:  op, par and bits[n_leaf][(n_gene + 31) / 32] exactly as pan_gainloss takes and checks them.  n_set in 1 .. 64.
+ *      tab[n_set][2 n_leaf - 1][4] = P00 P01 P10 P11 of the branch above the node of op k (the root's row is not read), pi[n_set][2]; an
+ *      entry that is not finite or is negative: PGA_ERR_ARG.  post 0 or 1.  n_sum in [0, n_gene]: the node totals add the items
+ *      [0, n_sum), so that a caller can append a pseudo-item and keep it out of them.  post_rows: NULL, or -- for tests only, with
+ *      post = 1 -- room for the first chunk's posterior presence, double [2 n_leaf - 1][min(n_gene, pga_rates_chunk(n_leaf))].
+ * Out: lik_m[n_set][n_gene] in [0.5, 1) or 0 and lik_e[n_set][n_gene]; with post, for set 0, gene[n_gene][3] = the sums over the
+ *      branches of gain and loss, and the root's present; node[2 n_leaf - 1][3] = in op order the sums over the items of present, gain
+ *      and loss (0 and 0 for the root); without post both are NULL.  The arrays are page-locked, belong to the backend and stay valid
+ *      until its next pan_rates.  n_leaf = 0 or n_gene = 0: nothing is launched.
+ * With post the items go through in chunks of pga_rates_chunk(n_leaf): PANGENE_RATES_CHUNK rounded up to a multiple of 256, or the
+ * largest multiple of 256 whose rows (16 bytes per item and node) fit 1 GiB, never less than 256.  No floating-point atomic and fixed
+ * reduction orders: the same call on the same build returns the same bits.  PANGENE_RATES_TIMING=1: a line with the kernels' device
+ * times on stderr.
+ * Limits (PGA_ERR_RANGE otherwise, before anything is launched): n_leaf <= 65 535, n_gene <= 16 777 215, a stack need <= 16,
+ * n_set <= 64. */
+typedef struct {
+	const uint8_t *op;
+	const uint32_t *bits;
+	const int32_t *par;
+	int32_t n_gene, n_leaf, n_set;
+	const double *tab, *pi;
+	int32_t post, n_sum;
+	double *post_rows;
+} pga_rates_in_t;
+typedef struct { const double *lik_m; const int32_t *lik_e; const double *gene, *node; } pga_rates_out_t;
+int pga_pan_rates(const pga_rates_in_t *in, pga_rates_out_t *out);
+int32_t pga_rates_chunk(int32_t n_leaf);
+
 /* the same ABI as a table, so the host driver is written once */
 struct pga_branch_par_s; struct pga_loop_xchg_s;
 typedef struct {
@@ -773,6 +811,7 @@ typedef struct {
 	int  (*pan_phylosig)(const pga_phylosig_in_t *, pga_phylosig_out_t *); /* may be NULL: the host driver then runs the same step itself */
 	int  (*pan_pcoa)(const pga_pcoa_in_t *, pga_pcoa_out_t *); /* may be NULL: the host driver then runs a second implementation (Jacobi on the dense B) */
 	int  (*pan_glm)(const pga_glm_in_t *, pga_glm_out_t *); /* may be NULL: the host driver then runs a second implementation (the set bits walked in fp64) */
+	int  (*pan_rates)(const pga_rates_in_t *, pga_rates_out_t *); /* may be NULL: the host driver then runs a second implementation (plain loops node by node in join order) */
 } pga_backend_t;
 
 const pga_backend_t *pga_backend(void);

@@ -672,6 +672,64 @@ def pan_gainloss(lib: C.CDLL, presence, rec, method: str, gain: int = 1, loss: i
     return out
 
 
+class pg_rates_opt_t(C.Structure):
+    """Gain and loss rate options (include/pangene_amd.h): the items, the tree, the table, the two rates (0 = fitted) and the table's filter."""
+    _fields_ = [("type", C.c_int32), ("metric", C.c_int32), ("method", C.c_int32), ("out", C.c_int32), ("gain", C.c_double), ("loss", C.c_double),
+                ("min_changes", C.c_double)]
+
+
+RATES_MIN, RATES_MAX = 1e-9, 1e9
+
+
+def rates_opt(lib: C.CDLL, type: str = "gene", metric: str = "jaccard", method: str = "upgma", out: str = "gene", gain: float = 0.0, loss: float = 0.0,
+              min_changes: float = 0.0) -> pg_rates_opt_t:
+    if type not in DIST_TYPES:
+        raise ValueError("type must be gene or adj")
+    if metric not in TREE_METRICS:
+        raise ValueError("metric must be jaccard or diff")
+    if method not in TREE_METHODS:
+        raise ValueError("method must be upgma or nj")
+    if out not in GAINLOSS_OUTS:
+        raise ValueError("out must be gene or node")
+    gain, loss = float(gain), float(loss)
+    if not ((gain == 0.0 and loss == 0.0) or (RATES_MIN <= gain <= RATES_MAX and RATES_MIN <= loss <= RATES_MAX)):
+        raise ValueError("gain and loss must both be in [1e-9, 1e9], or both be left out")
+    if not float(min_changes) >= 0.0:
+        raise ValueError("min_changes must be a number >= 0")
+    o = pg_rates_opt_t()
+    lib.pg_rates_opt_init(C.byref(o))
+    o.type, o.metric, o.method, o.out = DIST_TYPES.index(type), DIST_METRICS.index(metric), TREE_METHODS.index(method), GAINLOSS_OUTS.index(out)
+    o.gain, o.loss, o.min_changes = gain, loss, float(min_changes)
+    return o
+
+
+def pan_rates(lib: C.CDLL, presence, rec, method: str, gain: float = 0.0, loss: float = 0.0):
+    """Maximum-likelihood gain and loss rates of the items of an item x assembly presence matrix (bool numpy array or torch tensor, shape
+    (M, A)) on the tree of the records rec (as for pan_gainloss; their distances give the branch lengths) through pg_pan_rates.  gain and
+    loss both 0: fitted; both given: nothing is fitted.  A dict: gain, loss, lnL, T (floats), rounds, converged (ints); per item, float64
+    (M,): lnL_item, gains, losses, root, rate, lrt, p_rate (NaN for an item absent from every assembly); per node, float64 (2 A - 1,):
+    node_length, node_present, node_gains, node_losses (leaf x = x, join s = A + s)."""
+    import numpy as np
+    p = _presence(presence)
+    M, A = p.shape
+    m = TREE_METHODS.index(method)
+    rec = np.ascontiguousarray(rec if rec is not None else np.zeros((0, 6)), dtype=np.int64).reshape(-1, 6)
+    if A >= 3 and rec.shape[0] != A - 2 + m:
+        raise ValueError("rec must hold %d records for %d assemblies and %s" % (A - 2 + m, A, method))
+    o = rates_opt(lib, method=method, gain=gain, loss=loss)
+    fit = np.zeros(6, dtype=np.float64)
+    gene = np.zeros((M, 7), dtype=np.float64)
+    node = np.zeros((max(2 * A - 1, 0), 4), dtype=np.float64)
+    rc = lib.pg_pan_rates(p.ctypes.data_as(C.POINTER(C.c_uint8)), M, A, rec.ctypes.data_as(C.POINTER(C.c_int64)), m, C.byref(o),
+                          fit.ctypes.data_as(C.POINTER(C.c_double)), gene.ctypes.data_as(C.POINTER(C.c_double)), node.ctypes.data_as(C.POINTER(C.c_double)))
+    if rc != 0:
+        raise RuntimeError("pg_pan_rates: status %d" % rc)
+    out = {"gain": float(fit[0]), "loss": float(fit[1]), "lnL": float(fit[2]), "rounds": int(fit[3]), "converged": int(fit[4]), "T": float(fit[5])}
+    out.update({k: np.ascontiguousarray(gene[:, i]) for i, k in enumerate(("lnL_item", "gains", "losses", "root", "rate", "lrt", "p_rate"))})
+    out.update({"node_" + k: np.ascontiguousarray(node[:, i]) for i, k in enumerate(("length", "present", "gains", "losses"))})
+    return out
+
+
 class pg_coevo_opt_t(C.Structure):
     """Co-evolution options (include/pangene_amd.h): the items, the tree and the reconstruction as for gainloss, then the eligibility, the
     sign, the smallest |r| and the pair limit."""
@@ -1007,6 +1065,9 @@ _ANALYSES = (
               (_words("family", "family", GLM_FAMILIES, "must be binary or quant", extra=True), _ints("axes", "n_axis", 0, GLM_MAX_AXIS, "must be in [0, 13]", extra=True),
                _words("type", "type", DIST_TYPES, _M_TYPE, extra=True), _words("metric", "metric", TREE_METRICS, _M_METRIC, extra=True), _Row("seed", "seed", int, extra=True),
                _Row("min", "min_count", int, extra=True), _Row("max-p", "max_p", float, extra=True)), strict=True),
+    _Analysis("rates", rates_opt, "pg_write_rates", "--rates", {}, _Row(None, "out"), False,
+              (_Row("type", "type", extra=True), _Row("metric", "metric", extra=True), _Row("method", "method", extra=True), _Row("gain", "gain", float, extra=True),
+               _Row("loss", "loss", float, extra=True), _Row("min", "min_changes", float, extra=True)), strict=True),  # rates_opt() tests the values
 )
 _HEADS = tuple("--" + a.name for a in _ANALYSES)
 
@@ -1129,6 +1190,11 @@ _API = {
     "pg_gainloss_opt_init": (None, [C.c_void_p]),
     "pg_gainloss_file": (C.c_int, [C.c_char_p, C.c_void_p]),
     "pg_write_gainloss": (None, [C.c_void_p, C.c_void_p]),
+    "pg_rates_opt_init": (None, [C.c_void_p]),
+    "pg_rates_file": (C.c_int, [C.c_char_p, C.c_void_p]),
+    "pg_write_rates": (None, [C.c_void_p, C.c_void_p]),
+    "pg_pan_rates": (C.c_int, [C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                               C.POINTER(C.c_double)]),
     "pg_pan_gainloss": (C.c_int, [C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "pg_coevo_opt_init": (None, [C.c_void_p]),
     "pg_coevo_file": (C.c_int, [C.c_char_p, C.c_void_p]),

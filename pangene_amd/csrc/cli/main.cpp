@@ -187,7 +187,7 @@ static int main_call(int argc, char *argv[])
 // memory.  Both spellings, their refusals and the dispatch come from ONE table, kAnalyses below: a record per analysis, a row per option.
 // ---------------------------------------------------------------------------------------------------------------
 union AnyOpt { pg_curves_opt_t curves; pg_dist_opt_t dist; pg_assoc_opt_t assoc; pg_trait_opt_t trait; pg_tree_opt_t tree; pg_qtrait_opt_t qtrait;
-	pg_cluster_opt_t cluster; pg_permanova_opt_t permanova; pg_mantel_opt_t mantel; pg_gainloss_opt_t gainloss; pg_coevo_opt_t coevo; pg_phylosig_opt_t phylosig; pg_pcoa_opt_t pcoa; pg_glm_opt_t glm; };
+	pg_cluster_opt_t cluster; pg_permanova_opt_t permanova; pg_mantel_opt_t mantel; pg_gainloss_opt_t gainloss; pg_coevo_opt_t coevo; pg_phylosig_opt_t phylosig; pg_pcoa_opt_t pcoa; pg_glm_opt_t glm; pg_rates_opt_t rates; };
 
 struct Word { const char *s; int32_t v; };
 static const Word W_TYPE[] = { { "gene", PG_DIST_GENE }, { "adj", PG_DIST_ADJ }, { nullptr, 0 } };
@@ -242,6 +242,7 @@ static bool rd_atoll(const char *s, void *f, const Row &r) { return (*(int64_t *
 static bool rd_strtoul(const char *s, void *f, const Row &) { *(uint32_t *)f = (uint32_t)std::strtoul(s, nullptr, 10); return true; }
 static bool rd_unit(const char *s, void *f, const Row &) { double &x = *(double *)f; return strict_real(s, x) && x >= 0.0 && x <= 1.0; } // a number in [0, 1]
 static bool rd_nonneg(const char *s, void *f, const Row &) { double &x = *(double *)f; return strict_real(s, x) && x >= 0.0; }
+static bool rd_rate(const char *s, void *f, const Row &) { double &x = *(double *)f; return strict_real(s, x) && x >= 1e-9 && x <= 1e9; } // a rate (a NaN fails both tests)
 static bool rd_word(const char *s, void *f, const Row &r) { return (*(int32_t *)f = word_of(r.words, s)) >= 0; }
 static bool rd_flag(const char *, void *f, const Row &) { *(int32_t *)f = 1; return true; } // (an option without a value)
 // "INT" or "INT-INT": a k or a range of k, 2 <= lo <= hi; digits only.  Fills the field (k_lo) and the one after it (k_hi).
@@ -526,6 +527,30 @@ static const Analysis kAnalyses[] = {
 	    plain('s', "seed", rd_u32, offsetof(pg_glm_opt_t, seed), "must be in [0, 4294967295]", true),
 	    i32('c', "min", offsetof(pg_glm_opt_t, min_count), 1, INT31, M_MIN1, true),
 	    plain('p', "max-p", rd_nonneg, offsetof(pg_glm_opt_t, max_p), "must be a number >= 0", true) } },
+	// (like phylosig, pcoa and glm: not in usage() until the transcript is recorded again)
+	{ "rates", "--rates", false, HEAD_ROW0, nullptr, 0, true, calls<pg_rates_opt_t, pg_rates_opt_init, pg_rates_file, pg_write_rates>(),
+	  [](const AnyOpt &) {
+		std::printf("Usage: pangene rates [options] <in.gfa>\n       pangene --rates[=gene|node] [--rates-NAME=VALUE ...] <in.paf> [...]   (gene|node: -o; NAME in parentheses below)\nOptions:\n"
+		            "  -t STR    (type) items: gene (gene content) or adj (gene adjacencies of the walks) [gene]\n"
+		            "  -m STR    (metric) distance of the tree: jaccard or diff [jaccard]\n"
+		            "  -a STR    (method) tree: upgma, or nj rooted in the middle of the third branch of its closing join ((x, y), z) [upgma]\n"
+		            "  -g FLOAT  (gain) gain rate per item over the whole tree, in [1e-9, 1e9]; with -l: nothing is fitted [fitted]\n"
+		            "  -l FLOAT  (loss) loss rate, as -g; one needs the other [fitted]\n"
+		            "  -o STR    (--rates=STR) table: gene (per item: Present lnL Gains Losses Changes Root Rate LRT p_rate) or\n"
+		            "            node (per branch: Leaves Length Present Gains Losses) [gene]\n"
+		            "  -c FLOAT  (min) -o gene: print the items with Changes >= FLOAT [0]\n"
+		            "Maximum-likelihood gain and loss rates of a two-state Markov model on the tree of the assemblies with its branch lengths,\n"
+		            "corrected for the items nobody can observe.  The line after the header starts with # and holds the fit.  Gains and Losses are\n"
+		            "the expected numbers of branches absent at the top and present at the bottom, and the reverse -- not the expected numbers of\n"
+		            "events along the branches, which are larger.  Rate is the best of nine multipliers 2^-4 .. 2^4 of both rates, LRT and p_rate\n"
+		            "compare it with 1: a screening value, not a maximum-likelihood rate per item.\n"); },
+	  { word('o', nullptr, offsetof(pg_rates_opt_t, out), W_OUT, "must be gene or node"),
+	    word('t', "type", offsetof(pg_rates_opt_t, type), W_TYPE, M_TYPE, true),
+	    word('m', "metric", offsetof(pg_rates_opt_t, metric), W_METRIC, M_METRIC, true),
+	    word('a', "method", offsetof(pg_rates_opt_t, method), W_METHOD, "must be upgma or nj", true),
+	    plain('g', "gain", rd_rate, offsetof(pg_rates_opt_t, gain), "must be a number in [1e-9, 1e9]", true),
+	    plain('l', "loss", rd_rate, offsetof(pg_rates_opt_t, loss), "must be a number in [1e-9, 1e9]", true),
+	    plain('c', "min", rd_nonneg, offsetof(pg_rates_opt_t, min_changes), "must be a number >= 0", true) } },
 };
 enum { N_ANALYSES = sizeof(kAnalyses) / sizeof(kAnalyses[0]) };
 
@@ -689,7 +714,7 @@ static int run_path(pg_opt_t &opt, int n_files, char **files, const uint8_t *ids
 		else if (o.call) { pg_call_opt_t co; pg_call_opt_init(&co); pg_write_call(g, &co); if (pg_last_error()) rc = 2; }
 		else if (o.analysis) {
 			o.analysis->calls.write(g, o.side, &o.opt);
-			if (pg_last_error()) rc = o.analysis->refusal_is_1 && pg_last_error() == -3 ? 1 : 2; // (cluster's -3, PGA_ERR_ARG: a k outside [2, assemblies - 1] or fewer than 3 assemblies -- a refusal, as on `pangene cluster`)
+			if (pg_last_error()) rc = o.analysis->refusal_is_1 && pg_last_error() == -3 ? 1 : 2; // (cluster's -3, PGA_ERR_ARG: a k outside [2, assemblies - 1] or fewer than 3 assemblies; rates': one rate without the other -- a refusal, as on the subcommand)
 		}
 		else if (opt.flag & PG_F_WRITE_BED_WALK) { if (own_lines) pg_write_bed(d, 1); }
 		else if (opt.flag & PG_F_WRITE_BED_FLAG) { if (own_lines) pg_write_bed(d, 0); }

@@ -8,7 +8,7 @@
 
 constexpr int PAN_MAX_DEV = 22, PAN_MAX_HOST = 3; // buffers a pool has room for
 
-enum PanEntry { PAN_CURVES, PAN_DIST, PAN_ASSOC, PAN_TRAIT, PAN_JOIN, PAN_BOOT, PAN_PAIRS, PAN_QTRAIT, PAN_MEDOIDS, PAN_PERMANOVA, PAN_MANTEL, PAN_GAINLOSS, PAN_COEVO, PAN_PHYLOSIG, PAN_PCOA, PAN_GLM, PAN_N_ENTRY };
+enum PanEntry { PAN_CURVES, PAN_DIST, PAN_ASSOC, PAN_TRAIT, PAN_JOIN, PAN_BOOT, PAN_PAIRS, PAN_QTRAIT, PAN_MEDOIDS, PAN_PERMANOVA, PAN_MANTEL, PAN_GAINLOSS, PAN_COEVO, PAN_PHYLOSIG, PAN_PCOA, PAN_GLM, PAN_RATES, PAN_N_ENTRY };
 
 namespace {
 struct PanDev {
@@ -55,7 +55,7 @@ struct PanDev {
 	}
 };
 PanDev g_pan[PAN_N_ENTRY] = {{"pga_pan_curves"}, {"pga_pan_shared"}, {"pga_pan_assoc"}, {"pga_pan_trait"}, {"pga_pan_join"}, {"pga_pan_boot"}, {"pga_pan_pairs"},
-                            {"pga_pan_qtrait"}, {"pga_pan_medoids"}, {"pga_pan_permanova"}, {"pga_pan_mantel"}, {"pga_pan_gainloss"}, {"pga_pan_coevo"}, {"pga_pan_phylosig"}, {"pga_pan_pcoa"}, {"pga_pan_glm"}};
+                            {"pga_pan_qtrait"}, {"pga_pan_medoids"}, {"pga_pan_permanova"}, {"pga_pan_mantel"}, {"pga_pan_gainloss"}, {"pga_pan_coevo"}, {"pga_pan_phylosig"}, {"pga_pan_pcoa"}, {"pga_pan_glm"}, {"pga_pan_rates"}};
 }
 
 static void pan_release_all()

@@ -6,6 +6,7 @@
 //   pan_permanova.hpp  pangene permanova
 //   pan_mantel.hpp     pangene mantel
 //   pan_gainloss.hpp   pangene gainloss (with pan_treeprog.hpp: the records as a tree and as the backend's program, shared with trait.cpp)
+//   pan_rates.hpp      pangene rates (the program, the item counts and the limits are pan_gainloss.hpp's; floating point)
 //   pan_coevo.hpp      pangene coevo (the reconstruction and the program are pan_gainloss.hpp's)
 //   pan_phylosig.hpp   pangene phylosig (the observed costs and the way up are pan_gainloss.hpp's)
 //   pan_pcoa.hpp       pangene pcoa (floating point: the exact trace uses pan_permanova.hpp's ratio)
@@ -28,6 +29,7 @@ using namespace pgx;
 #include "pan_permanova.hpp"
 #include "pan_mantel.hpp"
 #include "pan_gainloss.hpp"
+#include "pan_rates.hpp"
 #include "pan_coevo.hpp"
 #include "pan_phylosig.hpp"
 #include "pan_pcoa.hpp"
